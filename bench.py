@@ -19,16 +19,22 @@ torchrun (RANK / LOCAL_RANK / WORLD_SIZE in the environment) or directly: `pytho
 processes itself before anything touches the GPU.  `--scaling weak` (default): every rank aligns steps x batch reads of
 its own.  `--scaling strong`: the steps x batch reads of the N=1 run are split EVENLY over the ranks (reads, not tiles:
 12 800 per rank for 102 400 on 8 GPUs), each share cut into even tiles of at most `batch` reads.  BASELINE.json's target
-is the strong one ("100k reads ... >= 6x at 8 GPUs") and the driver cannot pass flags, so a default N > 1 run times BOTH:
-`value` is the weak aggregate, `strong_100k` the 102 400-read set sharded over the N GPUs; at N = 1 `strong_proxy` times
-the share one rank would get at N = 8 (12 800 reads) against the full set on the same GPU — the ratio bounds the
-strong-scaling efficiency.
+is the strong one ("100k reads ... >= 6x at 8 GPUs"), so an N > 1 run with `--full` times BOTH: `value` is the weak
+aggregate, `strong_100k` the 102 400-read set sharded over the N GPUs; at N = 1 `strong_proxy` times the share one rank
+would get at N = 8 (12 800 reads) against the full set on the same GPU — the ratio bounds the strong-scaling efficiency.
 
-After the timed region the ranks leave the process group; rank 0 alone then measures the kernels' own durations (probe
-steps on a one-handle stream), compares the GAF text of reads of the last timed step byte for byte with the CPU
-restatement's (the in-run parity gate: exit status 3 and "parity_ok": false on any difference) and times the CPU legs of
-`cpu_baseline` on worker PROCESSES that were forked at the very top of main(), before this process touched the GPU.
-Prints ONE JSON line on rank 0.
+A plain run sets up, warms up, times the steps, writes the last timed step's outputs when `--dump-outputs DIR` is given
+and prints the result line.  Everything else runs only with `--full`: the strong_100k / strong_proxy / anchored regions,
+and, after the timed region (the ranks leave the process group first), rank 0's probe steps on a one-handle stream (the
+kernels' own durations, the roofline), the forced-i32 leg, the comparison of the GAF text of reads of the last timed step
+byte for byte with the CPU restatement's (the in-run parity gate: exit status 3 and "parity_ok": false on any difference)
+and the CPU legs of `cpu_baseline` on worker PROCESSES that were forked at the very top of main(), before this process
+touched the GPU.  Prints ONE JSON line on rank 0.
+
+`--dump-outputs DIR`: what the streams handed back for the last timed step (every rank's tile, in read order), written
+by rank 0 as DIR/<name>.npy — reads (index of each dumped read in the step), score, status and text_len (bytes of its
+GAF text) in float64, and text (those reads' GAF bytes) in float32: all reads when they fit in 64 MB, else a fixed,
+seeded sample.  The inputs are seeded: the same arguments give the same reads on every run.
 """
 import argparse
 import hashlib
@@ -72,6 +78,9 @@ def parse_args(argv=None):
     ap.add_argument("--no-strong", action="store_true", help="skip the strong_100k region (N > 1) / the strong_proxy region (N = 1)")
     ap.add_argument("--strong-ramp", type=int, default=1, help="first tiles of a share cut in two, a short one first (shard.even_tiles): the handles start out of phase, so the fill of a short tile sequence costs less (12 800 reads on one GPU: 126 ms with one ramp tile against 139 ms without, profiles/r05_notes.md)")
     ap.add_argument("--strong-tile", type=int, default=0, help="largest tile of a rank's share in the strong regions (default: see STRONG_TILE)")
+    ap.add_argument("--full", action="store_true", help="also run what the headline does not need: strong / proxy / anchored regions, probe steps "
+                    "and roofline, the i32 leg, the parity gate and the CPU legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs (every rank's tile) as DIR/<name>.npy")
     return ap.parse_args(argv)
 
 
@@ -537,6 +546,53 @@ def slice_packed(packed, lo, hi):
     return blob[int(offs[lo]):int(offs[hi])], (offs[lo:hi + 1] - offs[lo]).copy()
 
 
+DUMP_BYTES = (64 << 20) - (4 << 10)      # everything --dump-outputs writes (the .npy headers fit in the 4 KB left)
+
+
+def step_outputs(last):
+    """(GAF text, int64 offsets of each read's text, score, status) of the step `last` (run_steps' last tile; None: this rank
+    had no tile).  The stub stream (RG_BENCH_STUB=1) returns text alone, one line per read: score and status are None."""
+    import numpy as np
+    if last is None:
+        return b"", np.zeros(1, dtype=np.int64), np.zeros(0), np.zeros(0)
+    text, tile = last[2], last[3]
+    if tile is None:
+        ends = [i + 1 for i, c in enumerate(text) if c == 0x0A]
+        return text, np.asarray([0] + ends, dtype=np.int64), None, None
+    return text, np.asarray(tile.text_off, dtype=np.int64), tile.score, tile.status
+
+
+def dump_outputs(d, parts):
+    """--dump-outputs: the last timed step as the stream's callers receive it, every rank's tile in rank (= read) order;
+    `parts`: step_outputs() per rank.  Writes DIR/<name>.npy: reads (index of each dumped read in the step), score and
+    status (float64; not under the stub), text_len (bytes of each read's GAF text) and text (the GAF bytes of those reads
+    in order, float32).  All reads when that fits in DUMP_BYTES, else a fixed, seeded sample of them."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    text = b"".join(p[0] for p in parts)
+    base = np.cumsum([0] + [len(p[0]) for p in parts])
+    off = np.concatenate([np.zeros(1, dtype=np.int64)] + [p[1][1:] + base[r] for r, p in enumerate(parts)])
+    arrays = {}
+    if all(p[2] is not None for p in parts):
+        arrays = {"score": np.concatenate([np.asarray(p[2], dtype=np.float64) for p in parts]),
+                  "status": np.concatenate([np.asarray(p[3], dtype=np.float64) for p in parts])}
+    n = len(off) - 1
+    lens = np.diff(off)
+    per_read = 8 * (2 + len(arrays))                  # reads and text_len (+ score and status), float64
+    sel = np.arange(n)
+    if per_read * n + 4 * int(off[-1]) > DUMP_BYTES:
+        # a fixed, seeded sample: reads in a seeded order, taken until the next one would pass the budget
+        order = np.random.default_rng(12345).permutation(n)
+        keep = int(np.searchsorted(np.cumsum(per_read + 4 * lens[order]), DUMP_BYTES, side="right"))
+        sel = np.sort(order[:keep])
+    arrays = {k: v[sel] for k, v in arrays.items()}
+    arrays["reads"] = sel.astype(np.float64)
+    arrays["text_len"] = lens[sel].astype(np.float64)
+    arrays["text"] = np.frombuffer(b"".join(text[off[i]:off[i + 1]] for i in sel), dtype=np.uint8).astype(np.float32)
+    for k, v in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), v)
+
+
 def blocking_sync(device):
     """N > 1: host waits of THIS process on the device sleep instead of spinning (hipDeviceScheduleBlockingSync, set before
     torch creates the context).  The per-step gather calls `.item()` / `.cpu()` on device tensors while the collective waits
@@ -573,7 +629,7 @@ def main():
     cores, cores_why = cpu_limit()
     # the CPU legs' worker processes: forked NOW, before torch / HIP are imported into this process
     pool = None
-    want_cpu = rank == 0 and not args.no_cpu and not stub
+    want_cpu = rank == 0 and args.full and not args.no_cpu and not stub
     oracle_build = None
     if want_cpu:
         from oracle import oracle as O        # (ctypes only: nothing here touches the GPU)
@@ -760,11 +816,20 @@ def main():
     kstats = {k: (v[0] - k0.get(k, (0, 0))[0], v[1] - k0.get(k, (0, 0))[1]) for k, v in k1.items()}
     dt = head["dt"]
     last = head["last"]
+    if args.dump_outputs:
+        # every rank's last tile (N > 1: their text reached rank 0 in the timed region, scores and status come here)
+        parts = [step_outputs(last)]
+        if dist_on:
+            gathered = [None] * world
+            dist.all_gather_object(gathered, parts[0])
+            parts = gathered
+        if rank == 0:
+            dump_outputs(args.dump_outputs, parts)
 
     # The stated target (BASELINE.json: "100k reads sharded across the GPUs, >= 6x at 8") beside the headline, in the SAME
-    # run because the driver passes no flags: the 25 x `batch` reads of the N = 1 run, split evenly over the ranks.
+    # run with --full: the 25 x `batch` reads of the N = 1 run, split evenly over the ranks.
     strong = None
-    if args.scaling == "weak" and dist_on and not args.no_strong:
+    if args.scaling == "weak" and dist_on and args.full and not args.no_strong:
         tb = DISTINCT_BATCHES
         spans = [shard_bounds(tb * batch, r, world) for r in range(world)]
         tpr = [len(even_tiles(b - a, strong_tile, args.strong_ramp)) for a, b in spans]
@@ -780,7 +845,7 @@ def main():
     # fill / drain and tile-size effects are all of the strong-scaling loss there is (no data-path collective, graph
     # replicated), so ratio x 8 projects the 8-GPU speed-up.
     proxy = None
-    if args.scaling == "weak" and not dist_on and not stub and not args.no_strong and args.config in ("C4", "C5"):
+    if args.scaling == "weak" and not dist_on and not stub and args.full and not args.no_strong and args.config in ("C4", "C5"):
         share = DISTINCT_BATCHES * batch // 8
         p_tiles, _ = share_tiles(DISTINCT_BATCHES, 0, share, ramp=args.strong_ramp, max_tile=strong_tile)
         best = None
@@ -797,7 +862,7 @@ def main():
     # them: `band_not_enough_fraction`), so the headline times the DP but hardly ever the traceback walker and the GAF
     # formatter on a real alignment.  `anchored`: the same shape with every read starting at the graph's source.
     anchored = None
-    if mode in (0, 2) and not dist_on and not stub and not args.no_strong:
+    if mode in (0, 2) and not dist_on and not stub and args.full and not args.no_strong:
         def region(make, nt=3):
             tiles = [pack(make(k)) for k in range(nt)]
             run_steps(main_stream, tiles[:1])
@@ -827,7 +892,7 @@ def main():
     # kernel's HIP-event time in the timed region includes the other streams' kernels.  Probe steps on a ONE-handle stream
     # (after the timed region, same read sets) give the kernels' own durations.
     probe, probe_steps = {}, 0
-    if not stub and not args.no_probe and args.handles > 1 and my_tiles:
+    if not stub and args.full and not args.no_probe and args.handles > 1 and my_tiles:
         ps = HipStream(api, graph, params, dev, 1, batch, fmt_threads)
         run_steps(ps, [warm])
         p0 = ps.kernel_stats()
@@ -840,7 +905,7 @@ def main():
     # host-side range proof and hold the same integers): a few tiles on a stream of its own, after the timed region.
     int32 = None
     use16 = any(k.startswith("k_sweep16") for k in kstats)
-    if not stub and use16 and not args.sweep_i32 and not args.no_probe and mode in (4, 8) and my_tiles:
+    if not stub and args.full and use16 and not args.sweep_i32 and not args.no_probe and mode in (4, 8) and my_tiles:
         api.set_option("sweep_i32", 1)
         try:
             st32 = HipStream(api, graph, params, dev, max(1, args.handles), batch, fmt_threads)
@@ -868,7 +933,7 @@ def main():
     hbm_per_read = int(memstat[0] / memstat[1]) if memstat and memstat[1] else None
     sweeps = {k: v for k, v in kern.items() if k.startswith(("k_sweep", "k_m0", "k_m2"))}
     roof = None
-    if sweeps:
+    if sweeps and args.full:
         # dominant kernel family: the DP sweep.  One launch sweeps the whole graph once for one chunk of the batch.
         ms = sum(v[0] for v in sweeps.values())
         launches = sum(v[1] for v in sweeps.values())

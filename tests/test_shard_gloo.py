@@ -79,14 +79,14 @@ def test_bench_launcher_runs_the_world_2_path():
     real world > 1 code path of bench.py (process group, per-rank read shards, barrier + max-over-ranks timing, gather
     of every step's text to rank 0) — over gloo with the device work stubbed out (RG_BENCH_STUB=1: there is no GPU
     here), same code otherwise."""
-    weak = _run_bench(["--gpus", "2"], {})
+    weak = _run_bench(["--gpus", "2", "--full"], {})
     assert weak["n_gpus"] == 2 and weak["scaling"] == "weak" and weak["steps"] == 3 and "STUB" in weak["data"]
     assert "128 reads/step over all GPUs" in weak["config"]["workload"]
     # the stub formats 'read<i>\t<16 bases>\n' per read: all 3 steps of both ranks must arrive on rank 0
     per_rank = 3 * sum(len("read%d\t" % i) + 16 + 1 for i in range(64))
     assert weak["gaf_bytes_gathered"] == 2 * per_rank
     assert "64-read tiles" in weak["config"]["workload"]
-    # the stated target beside the headline, in the same run (the driver passes no flags): the 25 x 64 canonical reads split
+    # the stated target beside the headline, in the same --full run: the 25 x 64 canonical reads split
     # EVENLY over the ranks (reads, not tiles), even tiles of at most 64 reads
     s100 = weak["strong_100k"]
     # (13 even tiles, the first cut in two — a short one first — so that the handles start out of phase: --strong-ramp 1)
@@ -110,7 +110,7 @@ def test_bench_launcher_runs_the_world_2_path():
 def test_bench_launcher_runs_eight_ranks():
     """The driver's N = 8 shape on the CPU (device work stubbed): eight rank processes, one process group, even read shards,
     the 8-way gather of every step's text to rank 0 (VERDICT r4 #7; the modelled host budget is in profiles/r05_world8_stub.json)."""
-    d = _run_bench(["--gpus", "8", "--batch", "16", "--steps", "2"], {})
+    d = _run_bench(["--gpus", "8", "--batch", "16", "--steps", "2", "--full"], {})
     assert d["n_gpus"] == 8 and d["steps"] == 2 and "STUB" in d["data"]
     per_rank = 2 * sum(len("read%d\t" % i) + 16 + 1 for i in range(16))
     assert d["gaf_bytes_gathered"] == 8 * per_rank
