@@ -111,13 +111,22 @@ struct RowOps16 {
             m[r] = du;
             prev = old;
         }
-        // maxima of the two half chains (a tree: a serial chain of dependent packed instructions pays a wait state per link)
+        // PREFIX maxima of the two half chains, m[r] = max(du[0 .. r]), as a Brent-Kung tree: the up-sweep is the reduction the
+        // stitching needs (H - 1 instructions, m[H - 1] = the lane's maximum), the down-sweep fills the other prefixes (H - 1 -
+        // log2 H more) while the DPP scan below runs.  The left scan after the stitching is then one independent pk_max per
+        // register instead of a serial chain of H dependent ones (a wait state per link), and its last register is lmax.
+        static_assert((H & (H - 1)) == 0, "the prefix tree needs a power-of-two register count (m[H - 1] = the lane's maximum)");
 #pragma unroll
         for (int w = 1; w < H; w <<= 1) {
 #pragma unroll
-            for (int r = 0; r + w < H; r += 2 * w) m[r] = pk_max(m[r], m[r + w]);
+            for (int r = 2 * w - 1; r < H; r += 2 * w) m[r] = pk_max(m[r - w], m[r]);
         }
-        const int run = m[0];
+        const int run = m[H - 1];
+#pragma unroll
+        for (int w = H / 4; w >= 1; w >>= 1) {
+#pragma unroll
+            for (int r = 3 * w - 1; r < H; r += 2 * w) m[r] = pk_max(m[r - w], m[r]);
+        }
         // stitch: best source inside the lane = max of both chains; left scan over the lanes in z-space is a plain
         // prefix maximum
         const int TL = lo16(run), TH = hi16(run);
@@ -126,16 +135,16 @@ struct RowOps16 {
         const int ze = dpp_shr1(dpp_incl_max(max(TH, TL), INT32_MIN), INT32_MIN);   // best source of the lanes to the left
         const int bl = max(ze, NEG16);                              // carry into the lane's first column
         const int bh = max(TL, bl);                                 // carry into column H of the lane
-        int vprev = pack16(bl, bh);
-        lmax = pk_max(run, vprev);
+        const int carry = pack16(bl, bh);
+        // v[r] = max(du[r], v[r - 1]) with v[-1] = carry  ==  max(carry, max(du[0 .. r])): the same values as the serial scan
 #pragma unroll
         for (int r = 0; r < H; ++r) {
             const int du = row[r];
-            const int v = pk_max(du, vprev);
+            const int v = pk_max(m[r], carry);
             XL[r] = pk_sub(du, v);                                  // du - max(du, left) < 0 where L (left strictly better)
             row[r] = v;
-            vprev = v;
         }
+        lmax = row[H - 1];                                          // = max(run, carry)
     }
     // full masks for the members; returns `lall`: per half 0xffff iff EVERY column of that half chain took L.  It stands in for
     // the L bit mask wherever the members test "does this chain have a non-L column" (~lall & FULL is non-zero exactly then)
@@ -822,9 +831,14 @@ __global__ __launch_bounds__(64, C > 16 ? 2 : ((kColmax == 0 && !kRec) ? RG_SWEE
     // (a wave-uniform word by a wave-uniform page: selects over named scalars; the narrow variants only have word 0)
     auto word_of = [&](const PathWords& pw, int page) -> unsigned long long { return kWide ? pw.get(page) : pw.w0; };
     // (kColmax == 1, the first sweep of the three-sweep pipeline, runs without direction words at all)
-    // (the rows a sweep visits first store every word: SweepArgs::dsel_lo / dsel_hi)
+    // (the rows a sweep visits first store every word: SweepArgs::dsel_lo / dsel_hi.  Forward: row < dsel_lo, reverse: row > dsel_hi —
+    // rows are 0 .. 2^20 - 1 — as ONE unsigned range test, row - edge_base < edge_span, on two wave-uniform constants: the direction
+    // of the sweep selected per row cost three scalar compares / selects and four vector instructions in every row of the runs)
+    const unsigned edge_base = rev ? (unsigned)max(a.dsel_hi, -1) + 1u : 0u;
+    const unsigned edge_span = rev ? 0x7fffffffu : (unsigned)max(a.dsel_lo, 0);
+    auto edge_row = [&](int row) -> bool { return (unsigned)row - edge_base < edge_span; };
     auto want_dirs = [&](unsigned long long members, int page, int row) -> bool {
-        return (kColmax != 1 || dirs != nullptr) && ((members & word_of(dsel_w, page)) != 0ull || (rev ? row > a.dsel_hi : row < a.dsel_lo));
+        return (kColmax != 1 || dirs != nullptr) && ((members & word_of(dsel_w, page)) != 0ull || edge_row(row));
     };
     const int4* steps = rev ? a.rsteps : a.fsteps;
     const int nsteps = rev ? a.nrsteps : a.nfsteps;
@@ -1250,7 +1264,7 @@ __global__ __launch_bounds__(64, C > 16 ? 2 : ((kColmax == 0 && !kRec) ? RG_SWEE
                 load_steps(rli, s);
                 int lmax_unused;
                 RowOps16<C>::alpha(A, s, g_i, g0, lane, XU, XL, lmax_unused);
-                const bool gdirs = kWide ? ((kColmax != 1 || dirs != nullptr) && (wide_sel || (rev ? ri > a.dsel_hi : ri < a.dsel_lo))) : want_dirs(gmask, 0, ri);
+                const bool gdirs = kWide ? ((kColmax != 1 || dirs != nullptr) && (wide_sel || edge_row(ri))) : want_dirs(gmask, 0, ri);
                 RG_ROWSTAT((++st_grow, st_gmem += g_nme, st_dirs += gdirs ? 1 : 0));
                 if (gdirs) store_dirs(rslot, XU, XL);
                 const unsigned lmask = RowOps16<C>::masks(XU, XL, MU, ML);
@@ -1442,7 +1456,7 @@ __global__ __launch_bounds__(64, C > 16 ? 2 : ((kColmax == 0 && !kRec) ? RG_SWEE
                 int lmax;
                 RowOps16<C>::alpha(rr[0], s, g_i, g0, lane, XU, XL, lmax);
                 RG_ROWSTAT((++st_rn[RN], st_dirs += (kWide ? wide_sel : want_dirs(run_sel, run_page, ri)) ? 1 : 0, st_tail += tail ? 1 : 0));
-                if (kWide ? ((kColmax != 1 || dirs != nullptr) && (wide_sel || (rev ? ri > a.dsel_hi : ri < a.dsel_lo))) : want_dirs(run_sel, run_page, ri)) store_dirs(rslot, XU, XL);
+                if (kWide ? ((kColmax != 1 || dirs != nullptr) && (wide_sel || edge_row(ri))) : want_dirs(run_sel, run_page, ri)) store_dirs(rslot, XU, XL);
                 if constexpr (RN > 1) {
                     int MU[H], ML[H];
                     const unsigned lmask = RowOps16<C>::masks(XU, XL, MU, ML);
