@@ -477,6 +477,23 @@ int64_t rg_graph_dump(const rg_graph* g, int32_t which, char* buf, int64_t cap) 
     return (int64_t)s.size();
 }
 
+// Largest magnitude an f32 value of -m 0 SIMD (global_abpoa::exec_simd) or AVX2 -m 1 (local_poa::exec_simd) can take on a
+// graph of L rows and reads of at most `longest` bases (W = longest + 1 columns).  Every cell is the sum of the entries along
+// one alignment path — at most L + W steps of at most E = max |entry| each — started from 0, and in -m 0 possibly from
+// min_score = 2 * W * g(read[1], '-') (global_abpoa.rs:20) of a cell outside the band: |value| <= 2 W G + (L + W) E, with G
+// the largest |(b, '-')|; -m 1 starts every cell from 0 (no min_score): (L + W) E.  Below 2^24 every such sum is an integer
+// that f32 holds exactly, so the int32 kernels compute the reference's values; at or above it the reference may round (the
+// order of its additions is not the prefix scans' order) and the batch is refused.
+static long long f32_poa_bound(int mode, const int32_t* s, long long L, long long longest) {
+    long long E = 0, G = 0;
+    for (int i = 0; i < 35; ++i)
+        if (s[i] != RG_SCORE_MISSING) E = std::max<long long>(E, std::llabs((long long)s[i]));
+    for (int b = 0; b < 5; ++b)
+        if (s[b * 6 + 5] != RG_SCORE_MISSING) G = std::max<long long>(G, std::llabs((long long)s[b * 6 + 5]));
+    const long long W = longest + 1;
+    return (L + W) * E + (mode == RG_MODE_GLOBAL_POA ? 2 * W * G : 0);
+}
+
 // Reads of a batch: canonicalised (sequences.rs:13-22), coded, uploaded; every per-read buffer is (re)sized.
 // Work buffers of a previous run are kept when they are large enough, so a streaming caller re-uses one handle.
 static int load_reads(rg_batch* b, const char* reads, const int64_t* read_off, int64_t nreads) {
@@ -487,6 +504,13 @@ static int load_reads(rg_batch* b, const char* reads, const int64_t* read_off, i
     for (int64_t r = 0; r < nreads; ++r)
         if (read_off[r + 1] - read_off[r] < 1) return fail(RG_ERR_ARG, "empty read");
     if (read_off[nreads] - read_off[0] >= (1ll << 40)) return fail(RG_ERR_ARG, "read set too large");
+    if (mode == RG_MODE_GLOBAL_POA || mode == RG_MODE_LOCAL_POA) {
+        int64_t longest = 0;
+        for (int64_t r = 0; r < nreads; ++r) longest = std::max<int64_t>(longest, read_off[r + 1] - read_off[r]);
+        if (f32_poa_bound(mode, p->scores, g->h.L, longest) >= (1ll << 24))
+            return fail(RG_ERR_CAPACITY, "scores of this batch can reach 2^24 in magnitude: the reference computes -m 0 (SIMD) and "
+                                         "-m 1 (AVX2) in f32, which is not exact there, and the int32 kernels cannot round like it");
+    }
     // From here on the handle describes no read set until every buffer is sized and uploaded (`valid`): rg_batch_run and
     // rg_batch_fetch refuse it after a failed allocation instead of launching the new reads against the old buffers.
     b->valid = false;

@@ -12,6 +12,7 @@
 //   m2:         x[j] = e + max(x[j-1], m[j-1] + o),  m[j] = max(t[j], x[j]),  t = max(d, y)
 //               => x[j] - e*j = max(boundary, max_{k<j}(t[k] + o - e*k))      (needs o <= 0)
 #include "rg_device.hpp"
+#include "rg_band.hpp"
 #include "rg_poa_args.hpp"
 
 namespace rg {
@@ -22,22 +23,7 @@ constexpr int NEGB = INT32_MIN / 4;
 
 __device__ __forceinline__ int scb(const DevScores& sc, int a, int b) { return sc.t[a * 6 + b]; }
 
-// utils.rs:17-72 with simd_version = false
-__device__ void band_plain(unsigned long long ms, unsigned long long me, int r_val, unsigned long long seq_len,
-                           unsigned long long bta, int& left, int& right) {
-    int tmp_bs = min((int)ms, ((int)seq_len - r_val) - (int)bta);
-    unsigned long long band_start = tmp_bs < 0 ? 0ull : (unsigned long long)tmp_bs;
-    unsigned long long r64 = r_val < 0 ? ~0ull : (unsigned long long)r_val;
-    unsigned long long band_end;
-    if (seq_len > r64) {
-        unsigned long long a = me > seq_len - r64 ? me : seq_len - r64;
-        band_end = min(seq_len, a + bta);
-    } else {
-        band_end = min(seq_len, me + bta);
-    }
-    left = (int)band_start;
-    right = (int)band_end;
-}
+// band_plain (utils.rs:17-72, simd_version = false): rg_band.hpp
 
 // direction codes of bitfield_path.rs:3-15 that these modes use
 enum : uint32_t { PD_O = 0, PD_D = 1, PD_d = 2, PD_L = 3, PD_U = 4 };

@@ -18,7 +18,6 @@ namespace rg {
 namespace {
 
 constexpr int NEGL = INT32_MIN / 4;
-constexpr long long IDX_SPAN = 1ll << 40;   // row-major cell index < 2^40, value in the bits above
 
 __device__ __forceinline__ int scl(const DevScores& sc, int a, int b) { return sc.t[a * 6 + b]; }
 
@@ -75,8 +74,12 @@ __global__ __launch_bounds__(64) void k_poa_local(PoaArgs a) {
     __syncthreads();
 
     // best cell: kVar 0 takes the LAST maximum in row-major order ('>=', cells i,c >= 1 only, start (0,0));
-    // kVar 1/2 take the FIRST ('>', all cells, start (0,0))
-    long long best_key = kVar == 0 ? 0ll : IDX_SPAN - 1;
+    // kVar 1/2 take the FIRST ('>', all cells, start (0,0)).  Per lane (value, row-major index): a lane visits its cells in
+    // increasing index order, so '>=' / '>' keep its last / first maximum; the wave then takes the largest value and, among
+    // the lanes that hold it, the largest / smallest index.  (Value and index were packed into one 64-bit key with the
+    // index in the low 40 bits: values of 2^23 and more wrapped, and local scores are i32 up to 2^31 in the reference.)
+    int best_v = 0;
+    long long best_i = 0;
 
     // The row above travels in registers (chunk k, lane l = column 64 k + l: local rows are full width, so chunks line
     // up) when W <= 64 KC: a row whose only predecessor is the row above needs no load and no barrier.
@@ -192,8 +195,7 @@ __global__ __launch_bounds__(64) void k_poa_local(PoaArgs a) {
                     else { v = b; w = isd ? (((uint32_t)dp << 3) | LD_D) : (((uint32_t)up << 3) | LD_U); }
                     if (clamp && (simd ? v <= 0 : v < 0)) { v = 0; w = 0; }   // '<= 0' (:99) vs '< 0' (:115)
                     mval = v; w0 = w;
-                    const long long key = (long long)v * IDX_SPAN + (rowoff + c);
-                    if (key > best_key) best_key = key;
+                    if (v >= best_v) { best_v = v; best_i = rowoff + c; }
                 }
                 carry_z = max(carry_z, __builtin_amdgcn_readlane(zi, WAVE - 1));
                 carry_G = __builtin_amdgcn_readlane(G, WAVE - 1);
@@ -221,8 +223,7 @@ __global__ __launch_bounds__(64) void k_poa_local(PoaArgs a) {
                         if (dv < l) { mval = l; w0 = ((uint32_t)(i & 0xffff) << 3) | LD_L; }
                         else { mval = dv; w0 = ((uint32_t)(dp & 0xffff) << 3) | (li != rc ? LD_d : LD_D); }
                     }
-                    const long long key = (long long)mval * IDX_SPAN + (IDX_SPAN - 1 - (rowoff + c));
-                    if (key > best_key) best_key = key;
+                    if (mval > best_v) { best_v = mval; best_i = rowoff + c; }
                 }
                 carry_z = max(carry_z, __builtin_amdgcn_readlane(zi, WAVE - 1));
                 carry_G = __builtin_amdgcn_readlane(G, WAVE - 1);
@@ -266,8 +267,7 @@ __global__ __launch_bounds__(64) void k_poa_local(PoaArgs a) {
                     }
                     if (xflag) w0 |= 0x80000000u;
                     w1 = fromy ? (((uint32_t)(ypred & 0xffff) << 1) | 1u) : 0u;
-                    const long long key = (long long)mval * IDX_SPAN + (IDX_SPAN - 1 - (rowoff + c));
-                    if (key > best_key) best_key = key;
+                    if (mval > best_v) { best_v = mval; best_i = rowoff + c; }
                 }
                 if (act) ay[rowoff + c] = cell ? yval : 0;
 #pragma unroll
@@ -286,12 +286,11 @@ __global__ __launch_bounds__(64) void k_poa_local(PoaArgs a) {
         dirty = true;
     }
     __syncthreads();
-    best_key = wave_max_ll(best_key);
+    const int bestv = (int)wave_max_ll(best_v);
+    const long long held = kVar == 0 ? best_i : -best_i;          // kVar 1/2: the smallest index is the largest -index
+    const long long bsel = wave_max_ll(best_v == bestv ? held : (long long)INT64_MIN);
     if (lane != 0) return;
-
-    const int bestv = (int)(best_key >> 40);   // arithmetic shift: floor division by 2^40
-    long long bidx = best_key & (IDX_SPAN - 1);
-    if (kVar != 0) bidx = IDX_SPAN - 1 - bidx;
+    const long long bidx = kVar == 0 ? bsel : -bsel;
     const int best_row = (int)(bidx / W), best_col = (int)(bidx % W);
 
     // ---- traceback (gaf_output.rs:404-453, :527-598, :662-717), one lane ----

@@ -182,6 +182,31 @@ def test_f32_path_cell_decoding_is_exact_below_2_20(oracle):
     assert oracle.lib().orc_f32_cell_roundtrip_limit((1 << 20) + 8) == 1 << 20
 
 
+def f32_chain():
+    """A chain of 8-base segments spelling 2 476 seeded random bases: (gfa text, the whole walk).  With match 7001 / mismatch
+    -7001 the walk scores 7001 * 2476 = 17 334 476, past 2^24."""
+    rng = np.random.default_rng(3)
+    seq = "".join("ACGT"[int(x)] for x in rng.integers(0, 4, size=2476))
+    segs = [seq[i:i + 8] for i in range(0, len(seq), 8)]
+    gfa = "".join("S\t%d\t%s\n" % (i + 1, s) for i, s in enumerate(segs))
+    gfa += "".join("L\t%d\t+\t%d\t+\t0M\n" % (i + 1, i + 2) for i in range(len(segs) - 1))
+    return gfa, seq
+
+
+def test_f32_poa_scores_round_past_2_24(oracle):
+    """The fact the f32 range guard of -m 0 SIMD / AVX2 -m 1 rests on (rg_abi.hip, f32_poa_bound): the reference computes
+    those two in f32, and past 2^24 its sums round — the exact 17 334 476 comes out as 17 334 396 — while the i32 scalar
+    flavours stay exact.  At 5001 (12 382 476) all four agree."""
+    gfa, seq = f32_chain()
+    g = oracle.Graph.from_gfa_text(gfa, want_path=False)
+    got = {}
+    for x in (7001, 5001):
+        sc = oracle.scores_match_mis(x, -x, True)
+        got[x] = {m: g.align(getattr(oracle, m), seq, idx=0, scores=sc, bta=50)[1] for m in ("M0_SIMD", "M1_SIMD", "M0_SCALAR", "M1_SCALAR")}
+    assert got[7001] == {"M0_SIMD": 17334396, "M1_SIMD": 17334396, "M0_SCALAR": 17334476, "M1_SCALAR": 17334476}
+    assert set(got[5001].values()) == {12382476}
+
+
 def test_literal_and_absolute_restatements_agree(oracle):
     """Pin (ii) of the oracle header: delta-encoded transliteration (unpruned O(L^2 n) search) vs the
     absolute-score formulation, on randomised small graphs and reads."""

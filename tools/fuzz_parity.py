@@ -45,24 +45,32 @@ while time.time() < t_end and not fails:
     reads += ["ACGT"[int(x)] * int(rng.integers(1, 6)) for x in rng.integers(0, 4, size=2)]
     walk = sg.path_sequence(int(rng.integers(0, P)))
     reads.append(walk[:int(rng.integers(1, len(walk) + 1))])
-    variant = int(rng.integers(0, 4))
+    variant = int(rng.integers(0, 5))
     if variant == 0:
         sc, osc = None, None
     elif variant == 1:
         sc = api.create_score_matrix_i32(1, -1)
     elif variant == 2:
         sc = api.create_score_matrix_i32(3, -5)
-    else:
+    elif variant == 3:
         sc = {(k[0], k[1]): v for k, v in api.create_score_matrix_i32(matrix_file_path=os.path.join(ROOT, "tests", "golden", "HOXD55.mtx")).items()}
+    else:
+        # per-base, asymmetric gap entries: every (b,'-') and ('-',b) differs (the POA kernels choose between those keys)
+        sc = api.create_score_matrix_i32(int(rng.integers(1, 6)), -int(rng.integers(1, 7)))
+        for b in "ACGTN":
+            sc[(b, "-")], sc[("-", b)] = -int(rng.integers(0, 12)), -int(rng.integers(0, 12))
     osc = None if sc is None else O.scores_from_dict(sc)
+    # (the pathwise modes keep the CLI's matrices under variant 4: their long reads need one read-gap cost for every base)
+    psc, posc = (None, None) if variant == 4 else (sc, osc)
     g = api.Graph.from_gfa_text(gfa)
     og = O.Graph.from_gfa_text(gfa)
     names = ["q%d" % i for i in range(len(reads))]
     modes = list(PATH_MODES) + [POA_MODES[int(rng.integers(0, 6))], POA_MODES[int(rng.integers(0, 6))]]
     for mode, om in modes:
         kw, okw = {}, {}
-        if sc is not None:
-            kw["score_matrix"] = sc; okw["scores"] = osc
+        msc, mosc = (psc, posc) if (mode, om) in PATH_MODES else (sc, osc)
+        if msc is not None:
+            kw["score_matrix"] = msc; okw["scores"] = mosc
         if mode in (api.MODE_RECOMBINATION, api.MODE_RECOMBINATION_SEMI):
             R, r, B = int(rng.choice([0, 2, 4, 9])), float(rng.choice([0.0, 0.1, 0.5])), float(rng.choice([1.0, 0.8, 0.5]))
             kw.update(R=R, r=r, B=B); okw.update(R=R, r=r, B=B)
