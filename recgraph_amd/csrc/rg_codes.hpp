@@ -17,3 +17,10 @@ enum : uint32_t { ST_BAND_WARNING = 1u, ST_BAND_NOT_ENOUGH = 2u, ST_WOULD_PANIC 
 #ifndef RG_SWEEP16_RETIRE_SHIFT
 #define RG_SWEEP16_RETIRE_SHIFT 8
 #endif
+
+// REGISTER RUNS of k_sweep16's record variants: a run keeps the rows of at most this many paths in registers.  The builder of the
+// split step tables (rg_steps.cpp) moves a group behind a run as its TAIL only when the kernel handles that run as a register
+// run, so both sides use this constant (the kernel ties its KRUN to it with a static_assert)
+namespace rg {
+constexpr int RG_SWEEP16_RUN_PATHS = 4;
+}  // namespace rg

@@ -80,7 +80,7 @@ auto steps = [&](const std::vector<int32_t>& goff, const std::vector<GroupDesc>&
 // SPLIT TABLES (k_sweep16, record variants).  A row with several groups (the first row of a segment that several
 // segments lead into: one group per predecessor) is processed group by group, each loading and storing its members'
 // rolling rows — right after the register runs of those predecessors stored the very same rows.  Here a group whose
-// paths are exactly the paths of a register run (<= 4 paths, led by the lowest) on its predecessor row moves
+// paths are exactly the paths of a register run (<= RG_SWEEP16_RUN_PATHS paths, led by the lowest) on its predecessor row moves
 // directly behind that run as a TAIL (flag bit 4 with a zero run field): the run continues into it with the rows
 // in registers, and the row's keys fold into bkey across its groups as before (its first / last record in the NEW
 // order carry the first / last bits).  Only runs that the kernel handles as REGISTER runs may lie between the groups
@@ -106,12 +106,10 @@ auto split_tails = [&](const std::vector<StepRec>& in, std::vector<StepRec>& out
             size_t b = pos - 1;     // a run: back to its HEAD, or to the inner row that follows a general first row
             while (fl(out[b]) == 7u && b > 0 && is_run(out[b - 1]) && om[b - 1].mask == om[b].mask) --b;
             const int nm = __builtin_popcountll(om[b].mask);
-            const int len = (int)(pos - b);
-            // register runs only (<= 4 paths: rg_codes.hpp RG_SWEEP16_KRUN).  Round 4 also admitted gather runs here; since
+            // register runs only (at most RG_SWEEP16_RUN_PATHS paths: rg_codes.hpp).  Round 4 also admitted gather runs here; since
             // round 5 the keys of a row in progress wait in the LDS words of the gather table (k_sweep16: keys_ld / keys_st),
             // so a run that uses that table must not lie between the groups of one row.
-            (void)len;
-            const bool safe = nm <= 4;
+            const bool safe = nm <= RG_SWEEP16_RUN_PATHS;
             if (!safe) break;
             runs.push_back({b, pos});
             pos = b;
@@ -120,7 +118,7 @@ auto split_tails = [&](const std::vector<StepRec>& in, std::vector<StepRec>& out
         std::vector<int> tail_of(runs.size(), -1);
         std::vector<bool> taken(e - q, false);
         for (size_t j = q; j < e; ++j) {
-            if (!meta[j].low || __builtin_popcountll(meta[j].mask) > 4) continue;
+            if (!meta[j].low || __builtin_popcountll(meta[j].mask) > RG_SWEEP16_RUN_PATHS) continue;
             for (size_t u = 0; u < runs.size(); ++u) {
                 const StepMeta& last = om[runs[u].second - 1];
                 if (tail_of[u] < 0 && last.row == meta[j].pred && last.mask == meta[j].mask) { tail_of[u] = (int)j; taken[j - q] = true; break; }

@@ -250,90 +250,65 @@ __device__ __forceinline__ void run_dispatch_from(F& f, int n) {
 
 }  // namespace
 
-#ifndef RG_SWEEP16_KRUN
-#define RG_SWEEP16_KRUN 4
-#endif
-#ifndef RG_SWEEP16_GATHER
-#define RG_SWEEP16_GATHER 1          // gather runs (see k_sweep16 and gather_pays)
-#endif
-#ifndef RG_SWEEP16_GATHER_FWD
-#define RG_SWEEP16_GATHER_FWD 1      // the forward record variant spills 121 registers with them compiled in and still gains 3 ms (47.7 -> 44.7)
-#endif
-
-// when a gather run pays (instructions): member by member a row costs PER_MEMBER_ROW per member; a gather run PER_ROW per
-// row (alpha + column map + best member per column) and PER_MEMBER_RUN per member once (a pass at each end of the run)
-#ifndef RG_GATHER_PER_MEMBER_ROW
-#define RG_GATHER_PER_MEMBER_ROW 84
-#endif
-#ifndef RG_GATHER_PER_ROW
-#define RG_GATHER_PER_ROW 160
-#endif
-#ifndef RG_GATHER_PER_MEMBER_RUN
-#define RG_GATHER_PER_MEMBER_RUN 90
-#endif
-#ifndef RG_SWEEP16_GATHER32
-#define RG_SWEEP16_GATHER32 1        // gather runs in the record variants at 32 columns per lane (see kGather): round 6 — 32 spilled registers, and still 21.4 k -> 24.9 k reads/s at 1.5 kbp
-#endif
-#ifndef RG_SWEEP16_RUNWAIT
-#define RG_SWEEP16_RUNWAIT 1
-#endif
-#ifndef RG_SWEEP16_PROFILE_AHEAD
-#define RG_SWEEP16_PROFILE_AHEAD 0    // register runs: the next row's score profile is read from LDS behind this row's member steps
-#endif
-#ifndef RG_SWEEP16_CHAIN
-// chained register runs: next run's loads before this run's stores (see CHAINED RUNS).  1: in the -m 4 / -m 5 variant only
-// (config 4: 17.2 -> 14.8 ms per 4096-read sweep); 2: in the record variants of -m 8 too — measured neutral in the forward
-// sweep (37.4 vs 37.5 ms, and the variant spills 48 registers with it) and 0.7 ms SLOWER in the reverse one (34.3 vs
+// ---------------------------------------------------------------------------------------------------------------------
+// TUNING CONSTANTS of k_sweep16 and k_layer16, each with the measurement that decided it.  (They were build switches while the
+// questions were open; the timing-only builds that went with them can be rebuilt from the history of this file.)
+//
+// Register runs: rows kept in registers across the inner rows of a segment, for groups of up to KRUN paths.  Per variant:
+//   record variants (kRec), <= 16 columns per lane    4  = RG_SWEEP16_RUN_PATHS: what the split step tables are built for
+//   column-maxima variants (kColmax = 1), <= 16       4
+//   -m 4 / -m 5 (no tracking), <= 16                  3  with 4 the specialised run loops of round 6 need 178 registers; decided
+//                                                        when the variant was compiled for three waves per SIMD (config 4: 271 k
+//                                                        against 296 k reads/s) and not revisited since it is compiled for two
+//   32 columns per lane, narrow, kRec without         2  a row is 16 registers there (the -m 4 / -m 5 variant: reads of
+//   column maxima or -m 4 / -m 5                         1 024 - 2 047 bases)
+//   32 columns per lane, every other variant          0  no register runs
+constexpr int KRUN_REC = RG_SWEEP16_RUN_PATHS;
+constexpr int KRUN_M4 = 3;
+constexpr int KRUN_32 = 2;
+constexpr int sweep16_krun(int C, bool m4, bool rec_nocolmax, bool wide) {
+    if (C <= 16) return m4 ? KRUN_M4 : KRUN_REC;
+    return (!wide && (rec_nocolmax || m4)) ? KRUN_32 : 0;
+}
+// Waves per SIMD the compiler must fit every variant of k_sweep16 into (the second argument of __launch_bounds__)
+constexpr int SWEEP16_WAVES = 2;
+// Chained register runs (kChain in the kernel: the next run's loads before this run's stores, see CHAINED RUNS) in the -m 4 / -m 5
+// variant only (config 4: 17.2 -> 14.8 ms per 4096-read sweep).  In the record variants of -m 8 they measured neutral in the
+// forward sweep (37.4 vs 37.5 ms, and the variant spills 48 registers with them) and 0.7 ms SLOWER in the reverse one (34.3 vs
 // 33.6): their runs end in tails, whose epilogue separates the loads from the stores anyway (profiles/r04_notes.md)
-#define RG_SWEEP16_CHAIN 1
-#endif
-#ifndef RG_SWEEP16_M4_WAVES
-#define RG_SWEEP16_M4_WAVES 2
-#endif
-#ifndef RG_SWEEP16_KRUN_M4
-#define RG_SWEEP16_KRUN_M4 3
-#endif
-#ifndef RG_SWEEP16_KRUN32_M4
-#define RG_SWEEP16_KRUN32_M4 1       // register runs of two rows in the -m 4 / -m 5 variant at 32 columns per lane (reads of 1 024 - 2 047 bases)
-#endif
-#ifndef RG_SWEEP16_KRUN_REV
-#define RG_SWEEP16_KRUN_REV RG_SWEEP16_KRUN     // the variant without column maxima (reverse sweep of the record pipeline)
-#endif
-#ifndef RG_SWEEP16_REV_WAVES
-#define RG_SWEEP16_REV_WAVES 2                   // waves per SIMD the compiler must fit that variant into
-#endif
-#ifndef RG_SWEEP16_FWD_WAVES
-#define RG_SWEEP16_FWD_WAVES 2                   // ... and the variants that track column maxima (C <= 16)
-#endif
-// TIMING-ONLY build variants (tools/sweep_variants.sh; the results of such a build are garbage and nothing ships them):
-//   RG_SWEEP16_NOROWS   no rolling-row load / store in the main loop (rows stay whatever the registers hold)
-//   RG_SWEEP16_NOKEYS   the best-member keys are not built (row_end runs on constant keys)
-//   RG_SWEEP16_NOEMIT   row_end stops after the column maxima (no threshold tests, ballots, record / Cand stores)
-//   RG_SWEEP16_NODIRS   no direction-word stores
-//   RG_SWEEP16_KRUNNOLD / KRUNNOST   register runs without their run-start loads / run-end stores
-#ifdef RG_SWEEP16_NOROWS
-#define RG_ROW_LD(k, dst) ((void)0)
-#define RG_ROW_ST(k, src) ((void)0)
-#elif defined(RG_SWEEP16_NOROWS32)
-//   RG_SWEEP16_NOROWS32 no row traffic for the steps whose group holds 16 or more paths (the rows every path visits)
-#define RG_ROW_LD(k, dst) do { if (nm < 16) ld_row(k, dst); } while (0)
-#define RG_ROW_ST(k, src) do { if (nm < 16) st_row(k, src); } while (0)
+//
+// Register runs: the next row's score profile read from LDS a row ahead, behind this row's member steps.  Measured SLOWER (it
+// spills: 98.9 k against 114.3 k reads/s at config 5, profiles/r06_notes.md).  The code stays, switched off (kAhead in the kernel):
+// taking it out changes the capture order of the run loop's closure, and the compiler then schedules a few scalar instructions of
+// most variants differently — no longer the same kernels
+constexpr bool PROFILE_AHEAD = false;
+//
+// Gather runs (see k_sweep16 and the GATHER RUN comment) are compiled into every variant, also the record variants at 32 columns
+// per lane (round 6 — 32 spilled registers, and still 21.4 k -> 24.9 k reads/s at 1.5 kbp).
+// When a gather run pays (instructions): member by member a row costs PER_MEMBER_ROW per member; a gather run PER_ROW per
+// row (alpha + column map + best member per column) and PER_MEMBER_RUN per member once (a pass at each end of the run)
+constexpr int GATHER_PER_MEMBER_ROW = 84;
+constexpr int GATHER_PER_ROW = 160;
+constexpr int GATHER_PER_MEMBER_RUN = 90;
+// k_layer16 at <= 16 columns per lane: waves per SIMD it is compiled for, and rows fetched ahead (4 until round 6); see k_layer16
+constexpr int LAYER16_WAVES = 8;
+constexpr int LAYER16_PF = 2;
+
+// STATISTICS BUILDS of k_sweep16: the only conditional compilation in the kernel.  Their cell counters carry statistics instead
+// of cells; the alignments are the default build's.
+//   -DRG_SWEEP16_STALLSTAT[=2|3]   tools/probes/stall_stat.py: shader-clock cycles a wave spends waiting for row loads (1: at the
+//                                  start of a register run and on the general path; 2: at the start of a gather run; 3: whole
+//                                  register runs and their rows)
+//   -DRG_SWEEP16_RETSTAT           tools/probes/retire_stat.py: per evaluation point of the path retirement, the paths still needed
+// RG_STALL_BEGIN / RG_STALL_END(acc): the clock before a wait, and the wait for every load (vmcnt(0)) added to `acc`
+#ifdef RG_SWEEP16_STALLSTAT
+#define RG_STALL_BEGIN() const unsigned long long st_b = __builtin_amdgcn_s_memtime()
+#define RG_STALL_END(acc) do { __builtin_amdgcn_s_waitcnt(0x0F70); acc += __builtin_amdgcn_s_memtime() - st_b; } while (0)
 #else
-#define RG_ROW_LD(k, dst) ld_row(k, dst)
-#define RG_ROW_ST(k, src) st_row(k, src)
+#define RG_STALL_BEGIN() ((void)0)
+#define RG_STALL_END(acc) ((void)0)
 #endif
 
-// kColmax = 2: per-column maxima as packed VALUES only (8 v_perm + 8 v_pk_max per row instead of 48 compare / select
-// instructions and 24 fewer live registers): the forward sweep of the record pipeline — the other sweep's thresholds
-// need the exact maxima, while the cell k_bound pairs per column is taken from this sweep's records (k_colmax_rec)
-// kColmax = 0: no per-column maxima (the reverse sweep of the record pipeline: its maxima and their cells are
-// taken from its own records by k_colmax_rec)
-// kRec = true: emissions leave as (row, lane) records (a.frec); false: as Cand entries (a.cand) or not at all
-// kWide = true: graphs with more than 64 paths (step entries carry a 64-path page and continuation entries exist); the
-// narrow variant compiles that logic out (page 0, no continuation: it costs registers the forward sweep does not have)
-// kSemi = true: the semiglobal modes (-m 5 / -m 9: zero first column, per-path end rows).  A template flag since round 5: the
-// end-row bookkeeping (four per-lane registers of state, sixteen column-select masks in SGPRs) was carried — spilled — through
-// the record loop of every global-mode sweep
 // A path set of up to RG_PW 64-bit words as NAMED scalars: as an array (indexed by a page that is only known at run time, or
 // passed by reference) the compiler kept it in scratch — a scratch load per step record (round 6, the wide variants).
 struct PathWords {
@@ -342,40 +317,41 @@ struct PathWords {
     __device__ __forceinline__ void set(int i, unsigned long long v) { if (i == 0) w0 = v; else if (i == 1) w1 = v; else if (i == 2) w2 = v; else w3 = v; }
 };
 
-#ifdef RG_SWEEP16_VGPR_CAP
-#define RG_SWEEP16_CAP_ATTR __attribute__((amdgpu_num_vgpr(RG_SWEEP16_VGPR_CAP)))      // (experiments: a hard register budget)
-#else
-#define RG_SWEEP16_CAP_ATTR
-#endif
+// The variants launch_sweep16 instantiates, by <kColmax, kRec>:
+//   <0, true>   the record pipelines (-m 8 / -m 9), both sweeps: their column maxima and the cells attaining them are taken from
+//               the sweep's own records by k_colmax_rec
+//   <1, true>   a record sweep that is also asked for per-column maxima and their rows (a.frec and a.colmax_out both set)
+//   <1, false>  the sweeps without records: per-column maxima and their rows (ckey / crow), emissions as Cand entries
+//   <0, false>  -m 4 / -m 5: no best member, no thresholds, no emission
+// kColmax = 1: per-column maxima (best key and its row); 0: none
+// kRec = true: emissions leave as (row, lane) records (a.frec); false: as Cand entries (a.cand) or not at all
+// kWide = true: graphs with more than 64 paths (step entries carry a 64-path page and continuation entries exist); the
+// narrow variant compiles that logic out (page 0, no continuation: it costs registers the forward sweep does not have)
+// kSemi = true: the semiglobal modes (-m 5 / -m 9: zero first column, per-path end rows).  A template flag since round 5: the
+// end-row bookkeeping (four per-lane registers of state, sixteen column-select masks in SGPRs) was carried — spilled — through
+// the record loop of every global-mode sweep
+// (Every variant is compiled for two waves per SIMD.  The -m 4 / -m 5 variant at 16 columns per lane takes 196 registers with the
+// path retirement of round 6 compiled in — 148 before; compiled for three waves it spills 25 and the stream loses: 279-319 k
+// against 324-370 k reads/s at config 4, tests/test_kernel_resources.py.)
 template <int C, int kColmax, bool kRec, bool kWide, bool kSemi>
-// (the -m 4 / -m 5 variants at <= 16 columns per lane are COMPILED for three waves per SIMD: with the path retirement of round 6
-// compiled in they would otherwise take 196 registers — from 148 — and config 4 lives on the third wave)
-__global__ __launch_bounds__(64, C > 16 ? 2 : ((kColmax == 0 && !kRec) ? RG_SWEEP16_M4_WAVES : (kColmax != 0 ? RG_SWEEP16_FWD_WAVES : RG_SWEEP16_REV_WAVES))) RG_SWEEP16_CAP_ATTR void k_sweep16(SweepArgs a) {
+__global__ __launch_bounds__(64, SWEEP16_WAVES) void k_sweep16(SweepArgs a) {
+    static_assert(kColmax == 0 || kColmax == 1, "column maxima with their rows, or none");
     constexpr int H = C / 2;
-    constexpr bool kTrack = kColmax != 0 || kRec;      // <0, false>: the -m 4 / -m 5 sweep — no best member, no thresholds, no emission
-    // gather runs: not at 32 columns per lane in the record variants (a row is 16 registers there: the run's A / G / masks / steps /
-    // values / paths alone are 112, and with retirement and register runs compiled in the variant spilled 78)
-    constexpr bool kGather = C <= 16 || !kRec || RG_SWEEP16_GATHER32;
+    constexpr bool kTrack = kColmax == 1 || kRec;      // <0, false>: the -m 4 / -m 5 sweep — no best member, no thresholds, no emission
     // PATH RETIREMENT: the record pipelines of -m 8 (since round 6 also beyond 64 paths) and — round 6 — the -m 4 sweep: there a path is
     // hopeless when its final score cannot reach the bound k_verify4 checks the best final score against (see retire_eval)
-    constexpr bool kRet = ((kRec && kColmax != 1) || !kTrack) && !kSemi;
+    constexpr bool kRet = ((kRec && kColmax == 0) || !kTrack) && !kSemi;
     constexpr int NW = kWide ? RG_PW : 1;                   // 64-bit words of a path set
-    // rows kept in registers across the inner rows of a segment: groups of up to 4 paths (2 at 32 columns per lane: a row is 16 registers there)
-    // (the -m 4 / -m 5 variant: 3 — with 4 the specialised run loops of round 6 need 178 registers and the variant falls from three
-    // waves per SIMD to two: config 4 271 k against 296 k reads/s)
-    constexpr int KRUN = C <= 16 ? (!kTrack ? (RG_SWEEP16_KRUN < RG_SWEEP16_KRUN_M4 ? RG_SWEEP16_KRUN : RG_SWEEP16_KRUN_M4) : (kColmax != 0 ? RG_SWEEP16_KRUN : RG_SWEEP16_KRUN_REV)) : (((kRec && kColmax == 0 && !kWide) || (!kTrack && !kWide && RG_SWEEP16_KRUN32_M4)) ? 2 : 0);
+    constexpr bool kChain = !kTrack;                        // chained register runs (the constants block has the measurements)
+    // rows kept in registers across the inner rows of a segment (the table beside KRUN_REC)
+    constexpr int KRUN = sweep16_krun(C, !kTrack, kRec && kColmax == 0, kWide);
+    static_assert(!(kRec && C <= 16) || KRUN == RG_SWEEP16_RUN_PATHS, "the split step tables (rg_steps.cpp) are built for register runs of RG_SWEEP16_RUN_PATHS paths");
     const int rd = a.order ? a.order[blockIdx.x] : blockIdx.x;      // (launch order: see launch_order)
 #ifdef RG_SWEEP16_STALLSTAT
     // (statistics build, tools/probes/stall_stat.py: shader-clock cycles a wave spends in the waits for row loads; the cell
     // counters carry  total >> 8 | general-path waits >> 8 << 32  and  run-start waits >> 8 | run starts << 32)
     const unsigned long long st_t0 = __builtin_amdgcn_s_memtime();
     unsigned long long st_run = 0, st_nrun = 0, st_gen = 0;
-#define RG_STALL_BEGIN() const unsigned long long st_b = __builtin_amdgcn_s_memtime()
-#define RG_STALL_END(acc) do { __builtin_amdgcn_s_waitcnt(0x0F70); acc += __builtin_amdgcn_s_memtime() - st_b; } while (0)
-#define RG_STALL_END_LGKM(acc) do { __builtin_amdgcn_s_waitcnt(0xC07F); acc += __builtin_amdgcn_s_memtime() - st_b; } while (0)
-#else
-#define RG_STALL_BEGIN() ((void)0)
-#define RG_STALL_END(acc) ((void)0)
 #endif
     const int lane = threadIdx.x;
     const PathGraphDev& g = a.g;
@@ -432,7 +408,6 @@ __global__ __launch_bounds__(64, C > 16 ? 2 : ((kColmax == 0 && !kRec) ? RG_SWEE
     // (the flat form kept `rows + lane offset` and one pointer per access as VGPR pairs and rebuilt them with v_lshl_add_u64)
     const unsigned lane_row_off = (unsigned)lane * (unsigned)(H * sizeof(int));
     const __amdgpu_buffer_rsrc_t rows_rsrc = uniform_rsrc(rows, (unsigned)((P + 2) * wrow) * 4u);
-#ifndef RG_SWEEP16_FLATROWS
     auto ld_row = [&](int k, int (&dst)[H]) {
         const int so = k * (int)(wrow * sizeof(int));
         if constexpr (H >= 4) {
@@ -461,39 +436,13 @@ __global__ __launch_bounds__(64, C > 16 ? 2 : ((kColmax == 0 && !kRec) ? RG_SWEE
                 // 4096-read launch lost row words (tests/test_gpu_full_size.py::test_full_launch_every_wave_slot_vs_oracle;
                 // profiles/r05_notes.md).  The asm keeps the data registers alive up to an s_nop behind the store;
                 // tools/kernel_resources.py --hazards checks the ISA of every variant for the pattern.
-#ifndef RG_SWEEP16_NO_STORE_NOP
                 asm volatile("s_nop 1" :: "v"(v));
-#endif
             }
         } else {
             const u32x2 v = {(unsigned)src[0], (unsigned)src[1]};
             __builtin_amdgcn_raw_buffer_store_b64(v, rows_rsrc, (int)lane_row_off, so, 0);
         }
     };
-#else
-    auto ld_row = [&](int k, int (&dst)[H]) {
-        const int* p = rows + (long long)k * wrow + lane * H;
-        if constexpr (H >= 4) {
-#pragma unroll
-            for (int r4 = 0; r4 < H / 4; ++r4) {
-                const int4 v = reinterpret_cast<const int4*>(p)[r4];
-                dst[4 * r4] = v.x; dst[4 * r4 + 1] = v.y; dst[4 * r4 + 2] = v.z; dst[4 * r4 + 3] = v.w;
-            }
-        } else {
-            const int2 v = *reinterpret_cast<const int2*>(p);
-            dst[0] = v.x; dst[1] = v.y;
-        }
-    };
-    auto st_row = [&](int k, const int (&src)[H]) {
-        int* p = rows + (long long)k * wrow + lane * H;
-        if constexpr (H >= 4) {
-#pragma unroll
-            for (int r4 = 0; r4 < H / 4; ++r4) reinterpret_cast<int4*>(p)[r4] = make_int4(src[4 * r4], src[4 * r4 + 1], src[4 * r4 + 2], src[4 * r4 + 3]);
-        } else {
-            *reinterpret_cast<int2*>(p) = make_int2(src[0], src[1]);
-        }
-    };
-#endif
     // per-column constants of this lane
     unsigned long long pcode[(H + 7) / 8] = {};   // 8 bits per register: code_lo | code_hi << 3
     // emission threshold << 16 per column (INT32_MAX = never; columns that do not exist)
@@ -562,16 +511,6 @@ __global__ __launch_bounds__(64, C > 16 ? 2 : ((kColmax == 0 && !kRec) ? RG_SWEE
             for (int r = 1; r < (kRec ? H : 1); ++r) m = pk_min(m, thz[kRec ? r : 0]);
             thzmin = m;
         }
-#ifdef RG_SWEEP16_LANEMIN
-        // (experiment: one threshold per lane — the lowest of its columns — instead of one per column: how many more records?)
-        {
-            int mt = 32767;
-#pragma unroll
-            for (int r = 0; r < (kRec ? H : 0); ++r) mt = min(mt, min(lo16(thz[kRec ? r : 0]), hi16(thz[kRec ? r : 0])));
-#pragma unroll
-            for (int r = 0; r < (kRec ? H : 0); ++r) thz[kRec ? r : 0] = pack16(mt, mt);
-        }
-#endif
         int row0[H];
 #pragma unroll
         for (int r = 0; r < H; ++r) {
@@ -645,21 +584,11 @@ __global__ __launch_bounds__(64, C > 16 ? 2 : ((kColmax == 0 && !kRec) ? RG_SWEE
     int ckey[kColmax == 1 ? C : 1], crow[kColmax == 1 ? C : 1];   // best (value << 16 | path) per column and its row
 #pragma unroll
     for (int q = 0; q < (kColmax == 1 ? C : 1); ++q) { ckey[q] = INT32_MIN; crow[q] = 0; }
-    int cmv[kColmax == 2 ? H : 1];                                 // packed z-space maxima (values only)
-#pragma unroll
-    for (int r = 0; r < (kColmax == 2 ? H : 1); ++r) cmv[r] = NEGPAIR;
     unsigned ncand = 0;
     // cells: the workload's member-row updates (sum of |paths(row)| over the rows: the reference's unit of work, SURVEY
     // 8d); done: row operators actually applied — the same number except in gather runs, which do per row the alpha and
     // the column map, and per member one pass at each end of the run instead of one update per row
     unsigned long long cells = 0, done = 0;
-#ifdef RG_SWEEP16_ROWSTAT
-    // (statistics build, gpurun_tmp: rows by kind for a few reads, printed from the device)
-    unsigned st_rn[5] = {0, 0, 0, 0, 0}, st_grow = 0, st_gmem = 0, st_gen = 0, st_genmem = 0, st_dirs = 0, st_skip = 0, st_tail = 0;
-#define RG_ROWSTAT(x) x
-#else
-#define RG_ROWSTAT(x) ((void)0)
-#endif
     Cand* cand = !kRec && a.cand ? a.cand + (long long)rd * a.cand_cap : nullptr;
     uint32_t* dirs = a.dirs ? a.dirs + (long long)rd * a.dirs_stride : nullptr;
     // (the record variants always track — the driver sets track_best for every record sweep —: a compile-time constant there)
@@ -713,17 +642,6 @@ __global__ __launch_bounds__(64, C > 16 ? 2 : ((kColmax == 0 && !kRec) ? RG_SWEE
                 crow[kColmax == 1 ? q : 0] = better ? i : crow[kColmax == 1 ? q : 0];
             }
         }
-        if (kColmax == 2 && !pre_done) {
-#pragma unroll
-            for (int r = 0; r < H; ++r) {
-                // value halves of the two keys of register r: low column | high column << 16
-                const int v2 = (int)__builtin_amdgcn_perm((unsigned)bkey[r + H], (unsigned)bkey[r], 0x07060302u);
-                cmv[kColmax == 2 ? r : 0] = pk_max(cmv[kColmax == 2 ? r : 0], v2);
-            }
-        }
-#ifdef RG_SWEEP16_NOEMIT
-        return;
-#endif
         if (kRec) {
             // One fixed-size record per (row, lane) with any column whose VALUE reaches its threshold (1 + C/4 16-byte
             // stores): a saturating packed compare of the value halves against thz (the key thresholds >> 16, member rule's
@@ -735,6 +653,7 @@ __global__ __launch_bounds__(64, C > 16 ? 2 : ((kColmax == 0 && !kRec) ? RG_SWEE
                 int acc = -1;
 #pragma unroll
                 for (int r = 0; r < H; ++r) {
+                    // value halves of the two keys of register r: low column | high column << 16
                     const int v2 = (int)__builtin_amdgcn_perm((unsigned)bkey[r + H], (unsigned)bkey[r], 0x07060302u);
                     acc &= pk_sub_sat(v2, knm >= 0 ? thz[kRec ? r : 0] : minplain2);
                 }
@@ -794,16 +713,9 @@ __global__ __launch_bounds__(64, C > 16 ? 2 : ((kColmax == 0 && !kRec) ? RG_SWEE
     // direction words, format 1 (LayerArgs::dir_fmt): C <= 16: one word per lane (RowOps16::dir_word); C = 32: word 0 = U bits,
     // word 1 = L bits (bit r = column r of the lane, bit 16 + r = column H + r)
     auto store_dirs = [&](int slot, const int (&XU)[H], const int (&XL)[H]) {
-#ifdef RG_SWEEP16_NODIRS
-        return;
-#endif
         if constexpr (C <= 16) {
             const unsigned w = RowOps16<C>::dir_word(XU, XL);
-#ifndef RG_SWEEP16_FLATDIRS
             __builtin_amdgcn_raw_buffer_store_b32(w, dirs_rsrc, lane * 4, slot * (a.dir_words * 4), 0);
-#else
-            dirs[(long long)slot * a.dir_words + lane] = w;
-#endif
         } else {
             dirs[(long long)slot * a.dir_words + lane] = RowOps16<C>::sign_bits(XU);
             dirs[(long long)slot * a.dir_words + WAVE + lane] = RowOps16<C>::sign_bits(XL);
@@ -838,7 +750,7 @@ __global__ __launch_bounds__(64, C > 16 ? 2 : ((kColmax == 0 && !kRec) ? RG_SWEE
     const unsigned edge_span = rev ? 0x7fffffffu : (unsigned)max(a.dsel_lo, 0);
     auto edge_row = [&](int row) -> bool { return (unsigned)row - edge_base < edge_span; };
     auto want_dirs = [&](unsigned long long members, int page, int row) -> bool {
-        return (kColmax != 1 || dirs != nullptr) && ((members & word_of(dsel_w, page)) != 0ull || edge_row(row));
+        return (kColmax == 0 || dirs != nullptr) && ((members & word_of(dsel_w, page)) != 0ull || edge_row(row));
     };
     const int4* steps = rev ? a.rsteps : a.fsteps;
     const int nsteps = rev ? a.nrsteps : a.nfsteps;
@@ -924,9 +836,6 @@ __global__ __launch_bounds__(64, C > 16 ? 2 : ((kColmax == 0 && !kRec) ? RG_SWEE
     // The path id goes through a VGPR: a gfx9 VALU instruction takes one scalar operand, so (row & 0xffff0000) | k
     // is a single v_and_or_b32 only if the mask is the scalar and k a vector register.
     auto set_keys = [&](int (&bkey)[C], const int (&row)[H], int ks) {   // first member of a row: no reset + max
-#ifdef RG_SWEEP16_NOKEYS
-        return;
-#endif
         int k = ks;
         asm volatile("" : "+v"(k));
 #pragma unroll
@@ -936,9 +845,6 @@ __global__ __launch_bounds__(64, C > 16 ? 2 : ((kColmax == 0 && !kRec) ? RG_SWEE
         }
     };
     auto fold_keys = [&](int (&bkey)[C], const int (&row)[H], int ks) {
-#ifdef RG_SWEEP16_NOKEYS
-        return;
-#endif
         int k = ks;
         asm volatile("" : "+v"(k));
 #pragma unroll
@@ -1005,7 +911,9 @@ __global__ __launch_bounds__(64, C > 16 ? 2 : ((kColmax == 0 && !kRec) ? RG_SWEE
     auto retire_eval = [&](int e) {
         PathWords hop{0ull, 0ull, 0ull, 0ull};
         // (four rows in flight per wait: one row per wait made the evaluations ~8 % of the sweep)
-        constexpr int EB = !kTrack ? 1 : (C <= 16 ? 4 : 2);      // (the -m 4 variant: one row at a time — it has to stay under 168 registers, three waves per SIMD)
+        // (the -m 4 variant: one row at a time — chosen to keep it under 168 registers, three waves per SIMD; it is compiled for two
+        // waves now, 196 registers, and the value has not been revisited)
+        constexpr int EB = !kTrack ? 1 : (C <= 16 ? 4 : 2);
         int rvc[H];
         ld_row(PR_RVL, rvc);
 #pragma unroll
@@ -1107,8 +1015,8 @@ __global__ __launch_bounds__(64, C > 16 ? 2 : ((kColmax == 0 && !kRec) ? RG_SWEE
         const int ga = kbase + ((flags & F_INNER) ? __builtin_ctzll(gmask | (1ull << 63)) : ((w0 >> 26) & 63));
         const int nm = __popcll(gmask);
         // (inner / head records: the alpha field holds the rows left in the run, this one included, capped at 63.)  A gather
-        // run costs RG_GATHER_PER_MEMBER_RUN instructions per member once per run (two passes) + RG_GATHER_PER_ROW per row, the
-        // member-by-member form RG_GATHER_PER_MEMBER_ROW per member and row (row load + store, member operator, eager keys): it
+        // run costs GATHER_PER_MEMBER_RUN instructions per member once per run (two passes) + GATHER_PER_ROW per row, the
+        // member-by-member form GATHER_PER_MEMBER_ROW per member and row (row load + store, member operator, eager keys): it
         // pays when R * (84 (nm - 1) - 160) >= 90 (nm - 1)  (16 or 32 paths: 2 rows, 8 paths: 2, 5 paths: 3; round 4 had
         // 77 / 160 / 200: 3 / 4 / 6 rows.  Config 4's lone sweep 15.2 -> 14.8 ms, config 5 unchanged)
         const int run_left = (flags & F_INNER) ? ((w0 >> 26) & 63) : 0;
@@ -1187,8 +1095,8 @@ __global__ __launch_bounds__(64, C > 16 ? 2 : ((kColmax == 0 && !kRec) ? RG_SWEE
             }
         };
         const int g_nm = kWide ? wide_total : nm, g_nme = kWide ? wide_needed : nme;      // members of the group | the needed ones
-        if (RG_SWEEP16_GATHER && kGather && (kRec ? (kColmax == 0 || (kColmax == 2 && RG_SWEEP16_GATHER_FWD)) : !track) && a.gather_ok && !semi_end && (flags & F_INNER) && g_nm > KRUN &&
-            (!kWide || run_left > 0) && (!kRet || g_nme > KRUN) && run_left * (RG_GATHER_PER_MEMBER_ROW * (g_nm - 1) - RG_GATHER_PER_ROW) >= RG_GATHER_PER_MEMBER_RUN * (g_nm - 1)) {
+        if ((kRec ? kColmax == 0 : !track) && a.gather_ok && !semi_end && (flags & F_INNER) && g_nm > KRUN &&
+            (!kWide || run_left > 0) && (!kRet || g_nme > KRUN) && run_left * (GATHER_PER_MEMBER_ROW * (g_nm - 1) - GATHER_PER_ROW) >= GATHER_PER_MEMBER_RUN * (g_nm - 1)) {
             // ---- GATHER RUN: R consecutive inner rows of a segment that a wide group (nm paths, one group, alpha = its lowest
             // path) runs through.  Every member follows the alpha's directions, and a direction only MOVES values (D: from
             // column c - 1 of the row above, U: from column c, L: from column c - 1 of the new row) and adds a constant that
@@ -1210,7 +1118,6 @@ __global__ __launch_bounds__(64, C > 16 ? 2 : ((kColmax == 0 && !kRec) ? RG_SWEE
 #endif
             // (1) best (delta, path) per column over the members at the run start; ties -> highest path id: members in
             // ascending order, a later one replaces on >=.  Packed: delta = row_k - A0 (saturating: |delta| fits, gather_ok)
-#ifndef RG_G_NOPH1
             if (kRec && track) {         // (only the keys of the rows inside the run need it)
                 int bd[H], bk[H];
 #pragma unroll
@@ -1244,7 +1151,6 @@ __global__ __launch_bounds__(64, C > 16 ? 2 : ((kColmax == 0 && !kRec) ? RG_SWEE
                     gT[(r + H) * WAVE + lane] = (int)(((unsigned)bd[r] & 0xffff0000u) | ((unsigned)bk[r] >> 16)); // column H + r
                 }
             }
-#endif
             // (2) G: column -> code of the run-start column whose delta it carries; code = word index of the packed row
             // layout [r][lane] * 2 + half
             {
@@ -1264,15 +1170,13 @@ __global__ __launch_bounds__(64, C > 16 ? 2 : ((kColmax == 0 && !kRec) ? RG_SWEE
                 load_steps(rli, s);
                 int lmax_unused;
                 RowOps16<C>::alpha(A, s, g_i, g0, lane, XU, XL, lmax_unused);
-                const bool gdirs = kWide ? ((kColmax != 1 || dirs != nullptr) && (wide_sel || edge_row(ri))) : want_dirs(gmask, 0, ri);
-                RG_ROWSTAT((++st_grow, st_gmem += g_nme, st_dirs += gdirs ? 1 : 0));
+                const bool gdirs = kWide ? ((kColmax == 0 || dirs != nullptr) && (wide_sel || edge_row(ri))) : want_dirs(gmask, 0, ri);
                 if (gdirs) store_dirs(rslot, XU, XL);
                 const unsigned lmask = RowOps16<C>::masks(XU, XL, MU, ML);
                 const int src = RowOps16<C>::src_lane(lmask, lane);
                 RowOps16<C>::template member<true>(G, MU, lane, MU, ML, lmask, src);   // the gather follows the directions, adds nothing (SEL unused)
                 cells += (unsigned long long)g_nm;
                 done += 2ull;
-#ifndef RG_G_NOKEYS
                 if (kRec && track) {
                     // best member per column of this row: alpha value + best delta of the run-start column G points at (packed
                     // values bv + packed paths K2); the (value, path) keys only when some column can reach its threshold
@@ -1285,10 +1189,6 @@ __global__ __launch_bounds__(64, C > 16 ? 2 : ((kColmax == 0 && !kRec) ? RG_SWEE
                         const unsigned t1 = (unsigned)gT[(c1 >> 1) + ((c1 & 1) << HS)];
                         bv[r] = pk_add(A[r], (int)__builtin_amdgcn_perm(t1, t0, 0x07060302u));     // delta halves
                         K2[r] = (int)__builtin_amdgcn_perm(t1, t0, 0x05040100u);                    // path halves
-                    }
-                    if (kColmax == 2) {
-#pragma unroll
-                        for (int r = 0; r < H; ++r) cmv[kColmax == 2 ? r : 0] = pk_max(cmv[kColmax == 2 ? r : 0], bv[r]);
                     }
                     const int knm_row = ((rw1 >> 20) & 511) - 1;
                     int acc = -1;
@@ -1312,7 +1212,6 @@ __global__ __launch_bounds__(64, C > 16 ? 2 : ((kColmax == 0 && !kRec) ? RG_SWEE
                         rec_half(rp, mine, 1, hk);
                     }
                 }
-#endif
                 t += kWide ? went : 1;          // (wide: over the row's continuation entries)
                 if (step + 1 >= R || t >= nsteps) break;
                 int nw0, nw1;
@@ -1322,7 +1221,6 @@ __global__ __launch_bounds__(64, C > 16 ? 2 : ((kColmax == 0 && !kRec) ? RG_SWEE
             }
             done += (unsigned long long)(g_nme - 1) * ((kRec && track) ? 2ull : 1ull);    // passes (1) and (3)
             // (3) every member once: row_k(end)[c] = A(end)[c] - A0[G(c)] + row_k(start)[G(c)]
-#ifndef RG_G_NOPH3
             {
                 int B[H];
                 int* gS = gT;             // (the table of phase (1) is dead: its words hold one packed row at a time now)
@@ -1366,7 +1264,6 @@ __global__ __launch_bounds__(64, C > 16 ? 2 : ((kColmax == 0 && !kRec) ? RG_SWEE
                     st_row(k, outr);
                 }
             }
-#endif
             continue;
         }
         int e_i = i, e_w1 = w1, e_flags = flags;   // the row whose epilogue runs at the end of this iteration
@@ -1375,12 +1272,12 @@ __global__ __launch_bounds__(64, C > 16 ? 2 : ((kColmax == 0 && !kRec) ? RG_SWEE
         // (PATH RETIREMENT: a wide group of which <= KRUN members are left runs here too — a gather run costs two member
         // updates per row whatever is left of the group; like a gather run it leaves bkey alone, which is what the split
         // tables count on for the runs between the groups of a row)
-        if (kWide ? wide_run : (KRUN > 0 && (flags & F_INNER) && (nm <= KRUN || (kRet && nme <= KRUN && RG_SWEEP16_GATHER && kGather && a.gather_ok && !semi_end &&
-                                                             run_left * (RG_GATHER_PER_MEMBER_ROW * (nm - 1) - RG_GATHER_PER_ROW) >= RG_GATHER_PER_MEMBER_RUN * (nm - 1))) && run_left > 0)) {
+        if (kWide ? wide_run : (KRUN > 0 && (flags & F_INNER) && (nm <= KRUN || (kRet && nme <= KRUN && a.gather_ok && !semi_end &&
+                                                             run_left * (GATHER_PER_MEMBER_ROW * (nm - 1) - GATHER_PER_ROW) >= GATHER_PER_MEMBER_RUN * (nm - 1))) && run_left > 0)) {
             // ---- inner rows of a segment with a small group: the same paths, one group, predecessor = previous row.
             // Their rows stay in registers for the whole run: no row load/store latency, no HBM traffic.  The group
             // alpha of an inner row is its lowest path (alphas[row] == alphas[pred], rg_graph.cpp) = member 0.
-            // (CHAINED RUNS, RG_SWEEP16_CHAIN: when the record behind a run — behind its tail — starts another register run on
+            // (CHAINED RUNS, kChain: when the record behind a run — behind its tail — starts another register run on
             // OTHER paths, the block goes on with it instead of returning to the record loop, and it loads the next run's rows
             // BEFORE it stores this run's: gfx9 has one vmcnt for loads and stores, so a wait for freshly loaded rows also
             // drains every store issued before them — in the old order (stores, next record, loads, wait) that was the whole
@@ -1400,16 +1297,7 @@ __global__ __launch_bounds__(64, C > 16 ? 2 : ((kColmax == 0 && !kRec) ? RG_SWEE
             int rr[KRUN > 0 ? KRUN : 1][H];
 #pragma unroll
             for (int kk = 0; kk < KRUN; ++kk)
-                if (kk < rnm) {
-#if defined(RG_SWEEP16_KRUNNOLD) || defined(RG_SWEEP16_NOROWS) || defined(RG_SWEEP16_NOROWS32)
-#pragma unroll
-                    for (int r = 0; r < H; ++r) rr[kk][r] = lane ^ (kk + t);     // (what the timing-only builds without loads keep)
-#endif
-#ifndef RG_SWEEP16_KRUNNOLD
-                    RG_ROW_LD(mk[kk], rr[kk]);
-#endif
-                }
-#if RG_SWEEP16_RUNWAIT
+                if (kk < rnm) ld_row(mk[kk], rr[kk]);
             // wait for the run's rows HERE: otherwise the compiler's wait sits at the top of the row loop as vmcnt(0) (one
             // counter for loads and stores on gfx9) and every row also waits for the direction-word store of the row before
             {
@@ -1419,18 +1307,17 @@ __global__ __launch_bounds__(64, C > 16 ? 2 : ((kColmax == 0 && !kRec) ? RG_SWEE
                 RG_STALL_END(st_run); ++st_nrun;
 #endif
             }
-#endif
 #if defined(RG_SWEEP16_STALLSTAT) && RG_SWEEP16_STALLSTAT == 3
             const unsigned long long st_rb = __builtin_amdgcn_s_memtime();
 #endif
             int ri = i, rli = li, rslot = slot, rw1 = w1, rfl = 7;
             int rleft = run_left;               // rows left in the counted run, this one included (the record's run field)
             bool tail = false;
-            // The row's score profile (two 16-byte LDS reads per lane, ~100 cycles before the diagonal step can use them) is
+            // The row's score profile (two 16-byte LDS reads per lane, ~100 cycles before the diagonal step can use them) can be
             // fetched a row AHEAD: a record whose run field counts more rows than itself is followed by the next inner row of
-            // its run, so its profile row is known — and `s` is dead — as soon as the members have their steps.
-            // (not at 32 columns per lane: a row is 16 registers there and the variant is out of them)
-            constexpr bool kAhead = RG_SWEEP16_PROFILE_AHEAD && C <= 16;
+            // its run, so its profile row is known — and `s` is dead — as soon as the members have their steps.  Off: see
+            // PROFILE_AHEAD.  (not at 32 columns per lane: a row is 16 registers there and the variant is out of them)
+            constexpr bool kAhead = PROFILE_AHEAD && C <= 16;
             int s[H];
             if (kAhead) load_steps(rli, s);
             for (;;) {          // (chained runs)
@@ -1455,8 +1342,7 @@ __global__ __launch_bounds__(64, C > 16 ? 2 : ((kColmax == 0 && !kRec) ? RG_SWEE
                 if (!kAhead) load_steps(rli, s);
                 int lmax;
                 RowOps16<C>::alpha(rr[0], s, g_i, g0, lane, XU, XL, lmax);
-                RG_ROWSTAT((++st_rn[RN], st_dirs += (kWide ? wide_sel : want_dirs(run_sel, run_page, ri)) ? 1 : 0, st_tail += tail ? 1 : 0));
-                if (kWide ? ((kColmax != 1 || dirs != nullptr) && (wide_sel || edge_row(ri))) : want_dirs(run_sel, run_page, ri)) store_dirs(rslot, XU, XL);
+                if (kWide ? ((kColmax == 0 || dirs != nullptr) && (wide_sel || edge_row(ri))) : want_dirs(run_sel, run_page, ri)) store_dirs(rslot, XU, XL);
                 if constexpr (RN > 1) {
                     int MU[H], ML[H];
                     const unsigned lmask = RowOps16<C>::masks(XU, XL, MU, ML);
@@ -1480,7 +1366,7 @@ __global__ __launch_bounds__(64, C > 16 ? 2 : ((kColmax == 0 && !kRec) ? RG_SWEE
                     load_steps((__builtin_amdgcn_readlane(recs.x, tn & (WAVE - 1)) >> 20) & 7, s);
                 }
                 ++nrows;
-                if (kRec && kColmax != 1 && tail) {
+                if (kRec && kColmax == 0 && tail) {
                     if (track) {
                         if (rfl & F_FIRST) row_open = false;
                         int key[C];
@@ -1492,9 +1378,9 @@ __global__ __launch_bounds__(64, C > 16 ? 2 : ((kColmax == 0 && !kRec) ? RG_SWEE
                         if (rfl & F_LAST) { row_end(ri, ((rw1 >> 20) & 511) - 1, key); row_open = false; }
                         else keys_st(key);
                     }
-                } else if (track && kRec && kColmax != 1) {
+                } else if (track && kRec && kColmax == 0) {
                     // LAZY KEYS (rows in registers): the best VALUE per column is a packed maximum over the members (8
-                    // v_pk_max per member instead of 32 key instructions); it feeds the packed column maxima directly, and
+                    // v_pk_max per member instead of 32 key instructions), and
                     // the (value, path) keys are only built when some column of some lane can reach its threshold
                     // (saturating packed compare against thz: a superset of the exact test row_end applies)
                     int bv[H];
@@ -1506,10 +1392,6 @@ __global__ __launch_bounds__(64, C > 16 ? 2 : ((kColmax == 0 && !kRec) ? RG_SWEE
 #pragma unroll
                             for (int r = 0; r < H; ++r) bv[r] = pk_max(bv[r], rr[kk][r]);
                         }
-                    if (kColmax == 2) {
-#pragma unroll
-                        for (int r = 0; r < H; ++r) cmv[kColmax == 2 ? r : 0] = pk_max(cmv[kColmax == 2 ? r : 0], bv[r]);
-                    }
                     const int knm_row = ((rw1 >> 20) & 511) - 1;
                     int acc = -1;
                     // (a row without members besides its alpha: the lane's largest value per half chain is known from the alpha's
@@ -1583,7 +1465,7 @@ __global__ __launch_bounds__(64, C > 16 ? 2 : ((kColmax == 0 && !kRec) ? RG_SWEE
                 }
                 const int pw = peek_w0(t);
                 const int nf = (pw >> 23) & 7;
-                const bool to_tail = kRec && kColmax != 1 && (nf & F_INNER) && ((pw >> 26) & 63) == 0;
+                const bool to_tail = kRec && kColmax == 0 && (nf & F_INNER) && ((pw >> 26) & 63) == 0;
                 if (!to_tail && (nf != 7 || ((pw >> 26) & 63) == 0)) break;   // next record starts another segment (a HEAD or a general row)
                 // ... or is an inner row of ANOTHER segment: in a split table the rows of a segment whose first row had all
                 // its groups moved away as tails can follow an unrelated run (found by test_random_dag_graphs)
@@ -1608,7 +1490,7 @@ __global__ __launch_bounds__(64, C > 16 ? 2 : ((kColmax == 0 && !kRec) ? RG_SWEE
             bool chain = false;
             unsigned long long gm2 = 0;
             // (not while paths are being retired: the chained run's members would have to be masked and may all be gone)
-            if ((RG_SWEEP16_CHAIN == 2 || (RG_SWEEP16_CHAIN == 1 && !kTrack)) && !kWide && !semi_end && t < nsteps && (!kRet || next_eval == INT32_MAX)) {
+            if (kChain && !kWide && !semi_end && t < nsteps && (!kRet || next_eval == INT32_MAX)) {
                 const int pw = peek_w0(t);
                 // a HEAD (4 alone) or an inner row (7) with rows left starts a register / gather run; <= KRUN paths: a register run
                 if ((((pw >> 23) & 7) & F_INNER) && ((pw >> 26) & 63) != 0) {
@@ -1625,12 +1507,12 @@ __global__ __launch_bounds__(64, C > 16 ? 2 : ((kColmax == 0 && !kRec) ? RG_SWEE
                 for (int kk = 0; kk < KRUN; ++kk) { mk2[kk] = tm ? kbase + __builtin_ctzll(tm) : 0; tm = tm ? (tm & (tm - 1)) : 0; }
 #pragma unroll
                 for (int kk = 0; kk < KRUN; ++kk)
-                    if (kk < __popcll(gm2)) RG_ROW_LD(mk2[kk], rn[kk]);
+                    if (kk < __popcll(gm2)) ld_row(mk2[kk], rn[kk]);
             }
             __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0): the next run's rows (every older store is long done)
 #pragma unroll
             for (int kk = 0; kk < KRUN; ++kk)
-                if (kk < rnm) RG_ROW_ST(mk[kk], rr[kk]);
+                if (kk < rnm) st_row(mk[kk], rr[kk]);
             rnm = __popcll(gm2);
             rgm = gm2;
 #pragma unroll
@@ -1648,14 +1530,9 @@ __global__ __launch_bounds__(64, C > 16 ? 2 : ((kColmax == 0 && !kRec) ? RG_SWEE
                 if (kAhead) load_steps(rli, s);
             }
             }                   // (chained runs)
-#ifdef RG_SWEEP16_KRUNNOST
-#pragma unroll
-            for (int kk = 0; kk < KRUN; ++kk) if (kk < rnm) { int sink = 0; for (int r = 0; r < H; ++r) sink ^= rr[kk][r]; asm volatile("" :: "v"(sink)); }      // (timing-only: no run-end stores)
-#else
 #pragma unroll
             for (int kk = 0; kk < KRUN; ++kk)
-                if (kk < rnm) RG_ROW_ST(mk[kk], rr[kk]);
-#endif
+                if (kk < rnm) st_row(mk[kk], rr[kk]);
 #if defined(RG_SWEEP16_STALLSTAT) && RG_SWEEP16_STALLSTAT == 3
             st_gen += __builtin_amdgcn_s_memtime() - st_rb;
 #endif
@@ -1677,15 +1554,11 @@ __global__ __launch_bounds__(64, C > 16 ? 2 : ((kColmax == 0 && !kRec) ? RG_SWEE
             cells += (unsigned long long)nm;
             done += (unsigned long long)nme;
             int nxt[H];
-#if defined(RG_SWEEP16_NOROWS) || defined(RG_SWEEP16_NOROWS32)
-#pragma unroll
-            for (int r = 0; r < H; ++r) nxt[r] = s[r] ^ t;
-#endif
             int knext = -1;
             if (rest) {
                 knext = kbase + __builtin_ctzll(rest);
                 rest &= rest - 1;
-                RG_ROW_LD(knext, nxt);
+                ld_row(knext, nxt);
             }
             int key[C];           // (untracked sweeps never touch it)
             bool have = false;            // key[] holds the keys of the row's earlier records
@@ -1696,23 +1569,18 @@ __global__ __launch_bounds__(64, C > 16 ? 2 : ((kColmax == 0 && !kRec) ? RG_SWEE
             }
             if (!cont) {
                 int rowa[H];
-#if defined(RG_SWEEP16_NOROWS) || defined(RG_SWEEP16_NOROWS32)
-#pragma unroll
-                for (int r = 0; r < H; ++r) rowa[r] = s[r];
-#endif
-                RG_ROW_LD(ga, rowa);
+                ld_row(ga, rowa);
 #if defined(RG_SWEEP16_STALLSTAT) && RG_SWEEP16_STALLSTAT == 1
                 { RG_STALL_BEGIN(); RG_STALL_END(st_gen); }
 #endif
                 int XU[H], XL[H];
                 int lmax_unused;
                 RowOps16<C>::alpha(rowa, s, g_i, g0, lane, XU, XL, lmax_unused);
-                RG_ROW_ST(ga, rowa);
+                st_row(ga, rowa);
                 // (a group that spans pages — continuation entries follow — may hold a picked path in a page this entry does not
                 // see: it stores its word whatever its own members are)
                 bool wd = want_dirs(gmask, page, i);
                 if (kWide && !wd && t + 1 < nsteps) wd = peek_w1(t + 1) < 0;
-                RG_ROWSTAT((++st_gen, st_genmem += nme, st_dirs += wd ? 1 : 0));
                 if (wd) store_dirs(slot, XU, XL);
                 lmask = RowOps16<C>::masks(XU, XL, MU, ML);
                 src = RowOps16<C>::src_lane(lmask, lane);
@@ -1735,10 +1603,10 @@ __global__ __launch_bounds__(64, C > 16 ? 2 : ((kColmax == 0 && !kRec) ? RG_SWEE
                 if (rest) {
                     knext = kbase + __builtin_ctzll(rest);
                     rest &= rest - 1;
-                    RG_ROW_LD(knext, nxt);
+                    ld_row(knext, nxt);
                 } else knext = -1;
                 RowOps16<C>::member(cur, SEL, lane, MU, ML, lmask, src);
-                RG_ROW_ST(k, cur);
+                st_row(k, cur);
                 if (track) fold_keys(key, cur, k);
                 if (semi_end) end_fold(k, i, cur);
             }
@@ -1755,11 +1623,6 @@ __global__ __launch_bounds__(64, C > 16 ? 2 : ((kColmax == 0 && !kRec) ? RG_SWEE
         if (e_adv) ++t;
     }
 
-#ifdef RG_SWEEP16_ROWSTAT
-    if (lane == 0 && (rd == 0 || rd == 1 || rd == 7 || rd == 100))
-        printf("[rowstat] read %d %s: run rows by members 1:%u 2:%u 3:%u 4:%u (tails %u), gather rows %u (members %u), general records %u (members %u), direction words %u, records %d\n",
-               rd, rev ? "rev" : "fwd", st_rn[1], st_rn[2], st_rn[3], st_rn[4], st_tail, st_grow, st_gmem, st_gen, st_genmem, st_dirs, nsteps);
-#endif
     // ---- outputs ----
     if (kColmax == 1 && a.colmax_out) {
 #pragma unroll
@@ -1769,19 +1632,6 @@ __global__ __launch_bounds__(64, C > 16 ? 2 : ((kColmax == 0 && !kRec) ? RG_SWEE
                 a.colmax_out[(long long)rd * wpad + (rev ? n - c : c)] = ckey[kColmax == 1 ? q : 0] == INT32_MIN ? NEG32 : (ckey[kColmax == 1 ? q : 0] >> 16) + c * gcost;
                 if (a.colarg_out) a.colarg_out[(long long)rd * wpad + (rev ? n - c : c)] = (crow[kColmax == 1 ? q : 0] << 8) | (ckey[kColmax == 1 ? q : 0] & 255);
             }
-        }
-    }
-    if (kColmax == 2 && a.colmax_out) {
-        // (an opaque copy of the lane: the column indices and their `c < ncols` predicates are recomputed here instead of
-        // living — spilled — across the whole record loop)
-        int ol = lane;
-        asm volatile("" : "+v"(ol));
-#pragma unroll
-        for (int q = 0; q < C; ++q) {
-            const int c = ol * C + q;
-            const int pv = cmv[kColmax == 2 ? q % H : 0];
-            const int z = q >= H ? hi16(pv) : lo16(pv);
-            if (c < ncols) a.colmax_out[(long long)rd * wpad + (rev ? n - c : c)] = z <= NEG16 ? NEG32 : z + c * gcost;
         }
     }
     if (a.ncand_out && lane == 0) a.ncand_out[rd] = ncand;
@@ -1969,11 +1819,8 @@ void launch_colmax_rec(const ExpandArgs& a, int* colmax_out, int* colarg_out, in
 // its own occupancy: in the stream it runs beside the sweeps of the other handles, two sweep waves of 224 registers leave 64 of a
 // SIMD's 512, and a kernel that does not fit waits for a sweep wave to retire and then holds that wave's slot (k_layer_fwd took
 // 7-8 ms in the stream against 2.7 alone).  Config 5: 117.2 k -> 119.7 k reads/s (A/B/A/B/A/B on one box, profiles/r06_notes.md).
-#ifndef RG_LAYER16_WAVES
-#define RG_LAYER16_WAVES 8
-#endif
 template <int C>
-__global__ __launch_bounds__(64, C <= 16 ? RG_LAYER16_WAVES : 1) void k_layer16(LayerArgs a) {
+__global__ __launch_bounds__(64, C <= 16 ? LAYER16_WAVES : 1) void k_layer16(LayerArgs a) {
     constexpr int H = C / 2;
     const int rd = blockIdx.x;
     const int lane = threadIdx.x;
@@ -2023,10 +1870,7 @@ __global__ __launch_bounds__(64, C <= 16 ? RG_LAYER16_WAVES : 1) void k_layer16(
     const int start_col = recomb ? rs->rec_col : n;
     constexpr unsigned FULL = RowOps16<C>::FULL;
     constexpr unsigned LOWH = H >= 16 ? 0xffffu : ((1u << H) - 1u);
-#ifndef RG_LAYER16_PF
-#define RG_LAYER16_PF 2      // (rows fetched ahead: 4 until round 6 — see RG_LAYER16_WAVES)
-#endif
-    constexpr int PF = RG_LAYER16_PF;
+    constexpr int PF = LAYER16_PF;       // (rows fetched ahead)
     int pf_li[PF], pf_row[PF];
     uint32_t pf_w0[PF], pf_w1[PF];
     // TWO-STAGE look-ahead (round 6).  A row needs its base code and its direction word, and their addresses come from the path's
@@ -2292,10 +2136,9 @@ static void launch_sweep16_c(const SweepArgs& a, int nreads, int C, hipStream_t 
 }
 void launch_sweep16(const SweepArgs& a_, int nreads, int C, hipStream_t s) {
     SweepArgs a = a_;
-    // split step tables (TAIL records): the record variants with lazy keys, register runs of 4 and gather runs compiled in
-    constexpr bool split_built = RG_SWEEP16_KRUN == 4 && RG_SWEEP16_KRUN_REV == 4 && RG_SWEEP16_GATHER && RG_SWEEP16_GATHER_FWD;
+    // split step tables (TAIL records): for the record variants — lazy keys, register runs of RG_SWEEP16_RUN_PATHS paths, gather runs
     // (more than 64 paths: the wide-run table takes the split table's place)
-    if (split_built && a.use_split && a.fsplit && a.rsplit && a.frec && !(a.colmax_out && a.colarg_out) && C <= 16) {
+    if (a.use_split && a.fsplit && a.rsplit && a.frec && !(a.colmax_out && a.colarg_out) && C <= 16) {
         a.fsteps = a.fsplit;
         a.rsteps = a.rsplit;
         a.flead = a.fslead;
@@ -2304,8 +2147,7 @@ void launch_sweep16(const SweepArgs& a_, int nreads, int C, hipStream_t s) {
     if (!(a.rev ? a.rlead : a.flead)) a.retire = 0;
     a.table_members = a.rev ? a.rmembers : a.fmembers;
     // a sweep that writes records and is not asked for column maxima skips their tracking
-    // (kColmax = 2 — packed maxima without their cells — was the forward sweep of the record pipeline until round 5; the
-    // driver now reads both sweeps' maxima out of their records and nothing instantiates that form any more)
+    // (until round 5 the forward sweep of the record pipeline was a third form, kColmax = 2: packed maxima without their cells)
     if (a.frec && !a.colmax_out) launch_sweep16_c<0, true>(a, nreads, C, s);
     else if (a.frec) launch_sweep16_c<1, true>(a, nreads, C, s);
     // -m 4 / -m 5: no best-member tracking at all (the variant below carries the column-maxima / threshold registers it

@@ -1,4 +1,5 @@
-"""Statistics build of k_sweep16 (RG_LIB_PATH = a library built with -DRG_SWEEP16_RETSTAT): per evaluation point of the path
+"""Statistics build of k_sweep16 (RG_LIB_PATH = a library built with -DRG_SWEEP16_RETSTAT, tools/sweep_variants.sh
+RETSTAT): per evaluation point of the path
 retirement, how many paths are still needed and how many of them are not hopeless themselves (the others are kept because
 they lead a needed path).  python tools/probes/retire_stat.py [reads]"""
 import os, sys

@@ -1,6 +1,7 @@
-"""Statistics build of k_sweep16 (RG_LIB_PATH = a library built with -DRG_SWEEP16_STALLSTAT[=2], tools/sweep_variants.sh
-STALLSTAT / STALL2): shader-clock cycles the sweep waves of a config-5 batch spend waiting for row loads — at the start of
-register runs and in the general path (=1), at the start of gather runs (=2) — against their whole life.
+"""Statistics build of k_sweep16 (RG_LIB_PATH = a library built with -DRG_SWEEP16_STALLSTAT[=2|3], tools/sweep_variants.sh
+STALLSTAT / STALL2 / STALL3): shader-clock cycles the sweep waves of a config-5 batch spend waiting for row loads — at the start
+of register runs and in the general path (=1), at the start of gather runs (=2) — or inside whole register runs (=3), against
+their whole life.
 python tools/probes/stall_stat.py [reads] [config]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))

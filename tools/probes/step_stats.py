@@ -16,7 +16,7 @@ which = (31 if fwd else 33) + (1 if split else 0)
 text = gg.dump(which)
 head, recs, lead = text.split(";")[0:2], text.split(";")[2], None
 recs = [tuple(int(x, 16) for x in r.split(":")) for r in recs.split(",") if r]
-KRUN = 4
+KRUN = 4          # (RG_SWEEP16_RUN_PATHS of rg_codes.hpp: the register runs of the record variants)
 kinds = collections.Counter()
 members = collections.Counter()
 t = 0
@@ -30,7 +30,7 @@ while t < len(recs):
         R = field
         if nm <= KRUN:
             kind = "regrun_nm%d" % nm
-        elif R * (84 * (nm - 1) - 160) >= 90 * (nm - 1):          # (RG_GATHER_PER_* of rg_sweep16.hip)
+        elif R * (84 * (nm - 1) - 160) >= 90 * (nm - 1):          # (GATHER_PER_MEMBER_ROW / _PER_ROW / _PER_MEMBER_RUN of rg_sweep16.hip)
             kind = "gather"
         else:
             kind = "general_inner"
