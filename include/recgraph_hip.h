@@ -68,8 +68,33 @@ typedef struct rg_params {
     float multi_rec_cost;  /* -r                                                              */
     float rec_band_width;  /* -B                                                              */
     int32_t amb_mode;      /* POA modes, `-s true` retry (main.rs:82-106): bit 0 = node ids of the reversed handle
-                              order (utils.rs:144-165 with amb_mode), bit 1 = strand '-' (gaf_output.rs:225)       */
+                              order (utils.rs:144-165 with amb_mode), bit 1 = strand '-' (gaf_output.rs:225).
+                              Pathwise modes: bit 2 = RG_AMB_BOTH_STRANDS (below); bits 0 and 1 are refused there,
+                              bit 2 is refused in the POA modes                                                     */
 } rg_params;
+
+/*
+ * RG_AMB_BOTH_STRANDS (bit 2 of rg_params.amb_mode; modes 4, 5, 8, 9 only): both strands inside one batch.  AN
+ * EXTENSION THE REFERENCE DOES NOT HAVE: its `-s true` covers modes 0-3 (main.rs:82-106, 132-165, 188-212, 229-253) and
+ * is ignored by the pathwise modes (main.rs:254-313), as rg_stream_opts.amb_strand = 1 still is here.  Opt-in:
+ *   1. every read is aligned as given (the forward pass: the pipeline without the bit);
+ *   2. a read QUALIFIES for the reverse pass when its status has neither RG_READ_BAD_BASE nor RG_READ_WOULD_PANIC and its
+ *      forward score is < 0 (the reference's rule for the global POA modes, main.rs:82).  The score is the number the
+ *      record prints after "score: ": the integer in -m 4 / 5 and for a -m 8 / 9 record without a recombination, the f32
+ *      of a record with one; compared as f32 (every integer involved is below 2^24);
+ *   3. the reverse complement of each qualifying read (sequences.rs:65-82: reversed, A<->T, C<->G, N stays) is aligned
+ *      against the same forward graph with the same parameters, on the device, in the handle's own work buffers;
+ *   4. the reverse record replaces the forward one only when its score is STRICTLY greater; ties keep the forward one;
+ *   5. a read whose reverse record won is reported exactly as its reverse complement would be had it been submitted by
+ *      itself (path, coordinates, CIGAR, score, query length), except that the strand column is '-'.  rg_result_score,
+ *      rg_result_status, rg_result_fields().strand, rg_result_gaf, rg_batch_format_all and a stream's text / score /
+ *      status describe the record that was chosen.  Node ids are NOT relabelled (a PathGraph has no reversed handle
+ *      order: bit 0 stays POA-only).
+ * rg_batch_cell_updates and rg_batch_cell_updates_performed include the second pass (the workload grew); the kernels of
+ * the second pass add to the time and launches of their names, and k_strand_gate, k_revcomp, k_strand_merge appear
+ * under their own.  For the POA modes the way to both strands is rg_stream_opts.amb_strand (`-s true`).
+ */
+#define RG_AMB_BOTH_STRANDS 4
 
 /* Fill *p with the CLI defaults (args_parser.rs:3-147: M=2 X=4 O=4 E=2 R=4 r=0.1 B=1 b=1 f=0.01). */
 void rg_params_default(rg_params* p, int32_t mode);
@@ -272,7 +297,10 @@ typedef struct rg_stream_opts {
                                      < 0; local modes: all) are aligned again, reverse-complemented, on a second handle of
                                      the same worker (scalar exec + reversed handle labels as in the reference), the
                                      reference's per-mode comparison picks the record, and the warning lines of both
-                                     exec calls come before it.  Not together with keep_records.                */
+                                     exec calls come before it.  Not together with keep_records.
+                                     2: the same for a POA stream; for a stream of a pathwise mode it sets
+                                     RG_AMB_BOTH_STRANDS on the stream's handles (our extension, see there; the kept
+                                     record is the chosen one, so keep_records is fine)                          */
     int64_t max_undelivered_bytes;/* > 0: see "Memory" above                                                     */
 } rg_stream_opts;
 typedef struct rg_stream_result {

@@ -41,6 +41,9 @@ class Params(C.Structure):
                 ("amb_mode", C.c_int32)]
 
 
+AMB_BOTH_STRANDS = 4     # RG_AMB_BOTH_STRANDS (include/recgraph_hip.h): bit 2 of Params.amb_mode, pathwise modes
+
+
 def library_path():
     return _SO
 

@@ -46,6 +46,22 @@ MODE_GAP_LOCAL_POA = 3
 
 READ_BAND_WARNING, READ_BAND_NOT_ENOUGH, READ_WOULD_PANIC, READ_BAD_BASE = 1, 2, 4, 8
 
+# rg_params.amb_mode bit 2 (RG_AMB_BOTH_STRANDS, include/recgraph_hip.h): both strands inside a pathwise batch — an extension
+# the reference does not have (its `-s true` covers modes 0-3 only)
+AMB_BOTH_STRANDS = _lib.AMB_BOTH_STRANDS
+PATHWISE_MODES = (MODE_PATHWISE, MODE_PATHWISE_SEMI, MODE_RECOMBINATION, MODE_RECOMBINATION_SEMI)
+
+
+def _both_strands_kw(mode, both_strands, kw):
+    """``both_strands=True`` as the ``amb`` keyword of ``make_params``; refused outside the pathwise modes, where
+    ``amb_strand`` (``-s true``) is the way."""
+    if not both_strands:
+        return kw
+    if mode not in PATHWISE_MODES:
+        raise _lib.RecGraphError(-1, "both_strands applies to the pathwise modes (4, 5, 8, 9) only: the POA modes align both "
+                                     "strands with amb_strand (`-s true`)")
+    return dict(kw, amb=(kw.get("amb") or 0) | AMB_BOTH_STRANDS)
+
 
 # ----------------------------------------------------------------------------------------------
 # score matrices (HashMap<(char,char), i32|f32> of the reference as a dict)
@@ -489,8 +505,10 @@ class Stream:
 
     def __init__(self, graph, params, device_ids=None, handles_per_device=0, tile_reads=0, format_threads=0,
                  seq_index_base=1, keep_records=False, no_text=False, spin_wait=False, max_queued_tiles=0,
-                 max_undelivered_bytes=0, amb_strand=False):
-        """``amb_strand``: ``-s true`` inside the workers (POA modes).  ``max_queued_tiles`` / ``max_undelivered_bytes``:
+                 max_undelivered_bytes=0, amb_strand=False, both_strands=False):
+        """``amb_strand``: ``-s true`` inside the workers (POA modes).  ``both_strands``: rg_stream_opts.amb_strand = 2 — for
+        a pathwise mode both strands inside every tile (RG_AMB_BOTH_STRANDS, our extension), for a POA mode the same as
+        ``amb_strand``.  ``max_queued_tiles`` / ``max_undelivered_bytes``:
         bounds on what the stream holds (pushes / workers wait): the pushing and the consuming side must then be
         different threads, or one thread that drains whenever ``pending`` says so."""
         lib = _lib.load()
@@ -499,7 +517,7 @@ class Stream:
         lib.rg_stream_opts_default(C.byref(o))
         o.handles_per_device, o.tile_reads, o.format_threads = handles_per_device, tile_reads, format_threads
         o.seq_index_base, o.keep_records, o.no_text, o.spin_wait = seq_index_base, int(keep_records), int(no_text), int(spin_wait)
-        o.max_queued_tiles, o.max_undelivered_bytes, o.amb_strand = max_queued_tiles, max_undelivered_bytes, int(amb_strand)
+        o.max_queued_tiles, o.max_undelivered_bytes, o.amb_strand = max_queued_tiles, max_undelivered_bytes, 2 if both_strands else int(amb_strand)
         devs = (C.c_int32 * len(device_ids))(*device_ids) if device_ids is not None else None
         self._h = C.c_void_p()
         check(lib.rg_stream_create(graph._h, C.byref(params), devs, len(device_ids) if device_ids is not None else 0,
@@ -604,11 +622,14 @@ def set_option(name, value):
 
 
 def align_stream(graph, reads, names=None, mode=MODE_GLOBAL_POA, seq_index_base=1, device_ids=None, handles_per_device=0,
-                 tile_reads=0, amb_strand=False, **kw):
+                 tile_reads=0, amb_strand=False, both_strands=False, **kw):
     """``align_batch`` through the streaming engine (every visible GPU unless ``device_ids`` says otherwise): returns the
-    per-read texts and status bits in input order.  ``amb_strand``: the ``-s true`` retry inside the library."""
+    per-read texts and status bits in input order.  ``amb_strand``: the ``-s true`` retry inside the library.
+    ``both_strands``: pathwise modes, both strands inside every tile (RG_AMB_BOTH_STRANDS)."""
+    if both_strands and mode not in PATHWISE_MODES:
+        _both_strands_kw(mode, True, kw)
     st = Stream(graph, make_params(mode, **kw), device_ids=device_ids, handles_per_device=handles_per_device,
-                tile_reads=tile_reads, seq_index_base=seq_index_base, amb_strand=amb_strand)
+                tile_reads=tile_reads, seq_index_base=seq_index_base, amb_strand=amb_strand, both_strands=both_strands)
     st.push(reads, names)
     st.finish()
     texts, status = [], []
@@ -630,13 +651,18 @@ def rev_and_compl(read):
         raise _lib.RecGraphError(-1, "wrong char: %s, unable to rev&compl" % ex.args[0])
 
 
-def align_batch(graph, reads, names=None, mode=MODE_GLOBAL_POA, seq_index_base=1, amb_strand=False, **kw):
+def align_batch(graph, reads, names=None, mode=MODE_GLOBAL_POA, seq_index_base=1, amb_strand=False, both_strands=False, **kw):
     """The reference's per-read loop as one device batch.  Returns, per read, exactly the text the
     reference prints on stdout (warning lines + GAF line), and the per-read status bits.
 
     ``amb_strand`` is ``-s true`` (main.rs:82-106, 132-165, 188-212, 229-253; POA modes only): a second batch aligns
     the reverse complement of the reads that qualify against the same graph, labelled with the reversed handle order,
-    and the reference's per-mode comparison picks which record is written."""
+    and the reference's per-mode comparison picks which record is written.
+
+    ``both_strands`` (pathwise modes only; not in the reference): reads whose forward score is negative are aligned again as
+    their reverse complement inside the same device batch, and a reverse record that scores strictly higher replaces the
+    forward one with strand ``-`` (RG_AMB_BOTH_STRANDS in include/recgraph_hip.h)."""
+    kw = _both_strands_kw(mode, both_strands, kw)
     p = make_params(mode, **kw)
     b = Batch(graph, reads, p)
     b.run()
@@ -674,9 +700,11 @@ def align_batch(graph, reads, names=None, mode=MODE_GLOBAL_POA, seq_index_base=1
     return texts, status
 
 
-def align_batch_multi(graph, reads, names=None, mode=MODE_GLOBAL_POA, seq_index_base=1, device_ids=None, **kw):
+def align_batch_multi(graph, reads, names=None, mode=MODE_GLOBAL_POA, seq_index_base=1, device_ids=None, both_strands=False, **kw):
     """``align_batch`` over several GPUs behind one C call (``rg_align_batch_multi``: the streaming engine, one
-    results-only shard per tile; ``device_ids`` None = every visible device).  Same return value; no ``-s`` retry."""
+    results-only shard per tile; ``device_ids`` None = every visible device).  Same return value; no ``-s`` retry;
+    ``both_strands`` as in ``align_batch``."""
+    kw = _both_strands_kw(mode, both_strands, kw)
     n = len(reads)
     names = names or ["read%d" % i for i in range(n)]
     m = MultiBatch(graph, reads, make_params(mode, **kw), device_ids=device_ids)

@@ -257,6 +257,18 @@ static void fill_record(const rg_batch* b, int64_t i, ReadRecord& r) {
     r.ops = b->ops.data() + (size_t)i * b->ops_stride;
     r.rows = is_poa(b->p.mode) ? b->oprows.data() + (size_t)i * b->ops_stride : nullptr;
 }
+// RG_AMB_BOTH_STRANDS: the record of read i came from the reverse-complement pass (DevRecord.pad is written by that mode's
+// kernels only)
+static bool reverse_won(const rg_batch* b, int64_t i) {
+    return (b->p.amb_mode & RG_AMB_BOTH_STRANDS) && !is_poa(b->p.mode) && (b->rec[i].pad & REC_REVERSE_STRAND);
+}
+// ... and the base codes that record aligns: the reverse complement of the read (sequences.rs:65-82), built for the chosen reads only
+static const uint8_t* revcomp_codes(const rg_batch* b, int64_t i, std::vector<uint8_t>& buf) {
+    const size_t lo = (size_t)b->off[i], n = (size_t)(b->off[i + 1] - b->off[i]);
+    buf.resize(n);
+    for (size_t k = 0; k < n; ++k) { const uint8_t c = b->codes[lo + n - 1 - k]; buf[k] = c < 4 ? (uint8_t)(3 - c) : c; }
+    return buf.data();
+}
 bool amb_take_rev(int mode, int32_t fwd_score, int32_t rev_score) {
     if (mode == RG_MODE_LOCAL_POA || mode == RG_MODE_LOCAL_POA_SCALAR) return !(fwd_score < rev_score);   // main.rs:160-164 (sic)
     return rev_score > fwd_score;
@@ -285,7 +297,10 @@ static void append_gaf(const rg_batch* b, int64_t i, const char* name, int64_t s
         // holds the stream's text, written here, equal to rg_result_gaf's, written there)
         ReadRecord r;
         fill_record(b, i, r);
-        append_pathwise_text(b->g->h, b->codes + (size_t)b->off[i], (int)(b->off[i + 1] - b->off[i]), name ? name : "", r, b->p.mode, out);
+        static thread_local std::vector<uint8_t> rcbuf;
+        const bool rev = reverse_won(b, i);
+        append_pathwise_text(b->g->h, rev ? revcomp_codes(b, i, rcbuf) : b->codes + (size_t)b->off[i], (int)(b->off[i + 1] - b->off[i]),
+                             name ? name : "", r, b->p.mode, out, rev ? '-' : '+');
         return;
     }
     if (!score_only && build_fields(b, i, name, f)) out += f.text();
@@ -550,7 +565,16 @@ static int load_reads(rg_batch* b, const char* reads, const int64_t* read_off, i
     // half (forward to the source, reverse to the sink): <= 2 * (rows of the longest path + n)
     b->ops_stride = is_poa(mode) ? (long long)h.L + b->max_n + 8
                                  : std::min<long long>((long long)h.L + b->max_n + 8, 2ll * (h.max_path_rows + b->max_n) + 16);
+    const bool both = !is_poa(mode) && (p->amb_mode & RG_AMB_BOTH_STRANDS);
+    if (both) b->ops_stride = (b->ops_stride + 15) & ~15ll;      // k_strand_merge moves op bytes in 16-byte pieces
     if ((rc = b->d_ops.alloc((size_t)nreads * b->ops_stride))) return rc;
+    if (both) {
+        // the second pass's inputs and its record / op area: 64 B + ops_stride per read, worst case every read
+        if ((rc = b->d_sidx.alloc((size_t)nreads)) || (rc = b->d_ssum.alloc(2)) || (rc = b->d_rcoff.alloc((size_t)nreads + 1)) ||
+            (rc = b->d_rc.alloc(total + 64)) || (rc = b->d_rcbad.alloc((size_t)nreads)) || (rc = b->d_rec2.alloc((size_t)nreads)) ||
+            (rc = b->d_ops2.alloc((size_t)nreads * b->ops_stride)) || (rc = b->h_ssum.alloc(2)))
+            return rc;
+    }
     if (is_poa(mode)) {
         if ((rc = b->d_oprows.alloc((size_t)nreads * b->ops_stride))) return rc;
         long long maxbta = 0;
@@ -591,8 +615,11 @@ int32_t rg_batch_create(const rg_graph* gc, const rg_params* p, const char* read
     if ((mode == RG_MODE_GAP_POA || mode == RG_MODE_GLOBAL_POA_SCALAR || mode == RG_MODE_LOCAL_POA_SCALAR ||
          mode == RG_MODE_GAP_LOCAL_POA) && g->h.L > 65536)
         return fail(RG_ERR_GRAPH, "rows >= 65536 are truncated by the reference's u16 path cells (bitfield_path.rs:41)");
-    if (p->amb_mode & ~3) return fail(RG_ERR_ARG, "amb_mode: only bits 0 and 1 are defined");
-    if (p->amb_mode && !is_poa(mode)) return fail(RG_ERR_ARG, "amb_mode applies to the POA modes only (main.rs:82,132,188,229)");
+    if (p->amb_mode & ~7) return fail(RG_ERR_ARG, "amb_mode: only bits 0, 1 and 2 are defined");
+    if ((p->amb_mode & RG_AMB_BOTH_STRANDS) && is_poa(mode))
+        return fail(RG_ERR_ARG, "RG_AMB_BOTH_STRANDS applies to the pathwise modes only: the POA modes align both strands through "
+                                "rg_stream_opts.amb_strand (`-s true`, main.rs:82,132,188,229)");
+    if ((p->amb_mode & 3) && !is_poa(mode)) return fail(RG_ERR_ARG, "amb_mode bits 0 and 1 apply to the POA modes only (main.rs:82,132,188,229)");
     GraphTables* gt = nullptr;
     int rc = upload_graph(const_cast<rg_graph*>(g), &gt);   // per-device tables, under the graph's mutex
     if (rc) return rc;
@@ -704,7 +731,10 @@ static bool build_fields(const rg_batch* b, int64_t i, const char* name, GafFiel
     ReadRecord r;
     fill_record(b, i, r);
     std::string read((size_t)(b->off[i + 1] - b->off[i]), 'N');
-    for (size_t k = 0; k < read.size(); ++k) read[k] = "ACGTN"[b->codes[(size_t)b->off[i] + k]];
+    const bool rev = reverse_won(b, i);
+    std::vector<uint8_t> rcbuf;
+    const uint8_t* rcodes = rev ? revcomp_codes(b, i, rcbuf) : b->codes + (size_t)b->off[i];
+    for (size_t k = 0; k < read.size(); ++k) read[k] = "ACGTN"[rcodes[k]];
     std::string nm = name ? name : "";
     switch (b->p.mode) {
         case RG_MODE_GLOBAL_POA: out = fields_m0_simd(b->g->h, read, nm, r, b->p.amb_mode); break;
@@ -713,7 +743,7 @@ static bool build_fields(const rg_batch* b, int64_t i, const char* name, GafFiel
         case RG_MODE_LOCAL_POA:
         case RG_MODE_LOCAL_POA_SCALAR:
         case RG_MODE_GAP_LOCAL_POA: out = fields_poa_banded(b->g->h, read, nm, r, b->p.amb_mode); break;
-        default: out = fields_pathwise(b->g->h, read, nm, r, b->p.mode); break;
+        default: out = fields_pathwise(b->g->h, read, nm, r, b->p.mode, rev ? '-' : '+'); break;
     }
     return true;
 }
@@ -797,5 +827,35 @@ int rg_run_pathwise(rg_batch* b) {
     if (rc) return rc;
     b->cells = c[0];
     b->cells_performed = c[1];
-    return RG_OK;
+    if (!(b->p.amb_mode & RG_AMB_BOTH_STRANDS)) return RG_OK;
+    // ---- RG_AMB_BOTH_STRANDS (rg_strand.hip): the qualifying reads once more, reverse-complemented, in the same work buffers ----
+    const int n = (int)b->nreads;
+    const int recomb = b->p.mode == RG_MODE_RECOMBINATION || b->p.mode == RG_MODE_RECOMBINATION_SEMI ? 1 : 0;
+    Timed T(b);
+    StrandGateArgs ga{b->d_rec.p, b->in.off, n, recomb, b->d_sidx.p, b->d_rcoff.p, b->d_ssum.p};
+    if ((rc = T.run("k_strand_gate", [&] { launch_strand_gate(ga, b->stream); }))) return rc;
+    RevcompArgs ra{b->in.reads, b->in.off, b->d_sidx.p, b->d_rcoff.p, b->d_ssum.p, b->d_rc.p};
+    if ((rc = T.run("k_revcomp", [&] { launch_revcomp(ra, n, b->stream); }))) return rc;
+    HIPCHK(hipMemcpyAsync(b->h_ssum.p, b->d_ssum.p, 2 * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+    if ((rc = T.collect())) return rc;
+    const int count = b->h_ssum.p[0], max_len = b->h_ssum.p[1];
+    if (count <= 0) return RG_OK;
+    if (count > n || max_len < 1 || max_len > b->max_n) return fail(RG_ERR_HIP, "k_strand_gate returned an impossible read count / length");
+    HIPCHK(hipMemsetAsync(b->d_rcbad.p, 0, (size_t)count, b->stream));
+    std::vector<std::pair<std::string, std::pair<double, long long>>> st2;
+    unsigned long long c2[2] = {0, 0};
+    if ((rc = path_driver_run(h, gd, b->p, b->pw, b->d_rc.p, b->d_rcoff.p, b->d_rcbad.p, count, max_len, b->d_rec2.p, b->d_ops2.p,
+                              b->ops_stride, b->d_cells.p, b->stream, b->mem_budget, c2, st2, 0)))
+        return rc;
+    for (auto& e : st2) {
+        bool found = false;
+        for (auto& s : b->stats)
+            if (s.name == e.first) { s.ms += e.second.first; s.launches += e.second.second; found = true; break; }
+        if (!found) b->stats.push_back(KernelStat{e.first, e.second.first, e.second.second});
+    }
+    b->cells += c2[0];                  // (the workload grew: both counters include the second pass)
+    b->cells_performed += c2[1];
+    StrandMergeArgs ma{b->d_rec.p, b->d_ops.p, b->d_rec2.p, b->d_ops2.p, b->ops_stride, b->d_sidx.p, count, recomb};
+    if ((rc = T.run("k_strand_merge", [&] { launch_strand_merge(ma, b->stream); }))) return rc;
+    return T.collect();
 }

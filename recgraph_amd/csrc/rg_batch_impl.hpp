@@ -13,6 +13,7 @@
 #include "rg_host.hpp"
 #include "rg_path_args.hpp"
 #include "rg_poa_args.hpp"
+#include "rg_strand.hpp"
 
 using namespace rg;
 
@@ -210,6 +211,13 @@ struct rg_batch {
     DevBuf<unsigned long long> d_cells;
     long long cap_cells = 0, ops_stride = 0;
     PathWork pw;                       // m4/m8 buffers
+    // RG_AMB_BOTH_STRANDS (rg_strand.hip): the qualifying reads' indices, their reverse complements [offsets | codes | bad
+    // flags, all zero], {count, max_len}, and the record / op area of the second pass (sized with the batch, worst case all)
+    DevBuf<int> d_sidx, d_ssum;
+    DevBuf<long long> d_rcoff;
+    DevBuf<uint8_t> d_rc, d_rcbad, d_ops2;
+    DevBuf<DevRecord> d_rec2;
+    PinBuf<int> h_ssum;
     // host results
     std::vector<DevRecord> rec;
     std::vector<uint8_t> ops;

@@ -467,7 +467,7 @@ thread_local PathwiseScratch t_scratch;
 }  // namespace
 
 GafFields fields_pathwise(const HostGraph& g, const std::string& read, const std::string& name,
-                          const ReadRecord& r, int mode) {
+                          const ReadRecord& r, int mode, char strand) {
     const int n = (int)read.size();
     std::vector<uint8_t> codes((size_t)n);
     for (int k = 0; k < n; ++k) { const char c = read[(size_t)k]; codes[(size_t)k] = c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : 4; }
@@ -476,6 +476,7 @@ GafFields fields_pathwise(const HostGraph& g, const std::string& read, const std
     walk_pathwise(g, codes.data(), n, r, mode, sc, w);
     GafFields f;
     f.name = name; f.qlen = (size_t)n; f.qstart = 0; f.qend = (size_t)(n - 1);
+    f.strand = strand;
     f.path.assign(w.ids, w.ids + w.nids);
     f.pstart = w.pstart; f.pend = w.pend; f.plen = w.plen;
     const std::string ops(w.ops, w.nops), pseq(w.pseq, w.npseq);
@@ -495,7 +496,8 @@ GafFields fields_pathwise(const HostGraph& g, const std::string& read, const std
 
 // fields_pathwise(..).text() written straight into `out` (GAFStruct::to_string, gaf_output.rs:70-94; comments as in
 // pathwise_alignment_output.rs:161-167, recombination_output.rs:598-612, 759-765)
-void append_pathwise_text(const HostGraph& g, const uint8_t* codes, int n, const char* name, const ReadRecord& r, int mode, std::string& out) {
+void append_pathwise_text(const HostGraph& g, const uint8_t* codes, int n, const char* name, const ReadRecord& r, int mode, std::string& out,
+                          char strand) {
     PathwiseWalk w;
     walk_pathwise(g, codes, n, r, mode, t_scratch, w);
     const size_t nlen = strlen(name);
@@ -507,7 +509,7 @@ void append_pathwise_text(const HostGraph& g, const uint8_t* codes, int n, const
     c.mem(name, nlen);
     c.ch('\t'); c.num((unsigned long long)n);
     c.str("\t0\t"); c.num((unsigned long long)(n - 1));
-    c.str("\t+\t>");
+    c.ch('\t'); c.ch(strand); c.str("\t>");
     for (size_t i = 0; i < w.nids; ++i) { if (i) c.ch('>'); c.num(w.ids[i]); }
     c.ch('\t'); c.num(w.plen);
     c.ch('\t'); c.num(w.pstart);

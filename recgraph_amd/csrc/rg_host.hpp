@@ -187,9 +187,11 @@ struct GafFields {
 // amb: rg_params.amb_mode (bit 0 reversed handle ids, bit 1 strand '-')
 GafFields fields_m0_simd(const HostGraph& g, const std::string& read, const std::string& name, const ReadRecord& r, int amb = 0);
 GafFields fields_poa_banded(const HostGraph& g, const std::string& read, const std::string& name, const ReadRecord& r, int amb = 0);
-GafFields fields_pathwise(const HostGraph& g, const std::string& read, const std::string& name, const ReadRecord& r, int mode);
+// strand: '-' for a record of the reverse-complement pass of RG_AMB_BOTH_STRANDS (`read` / `codes` are the reverse complement then)
+GafFields fields_pathwise(const HostGraph& g, const std::string& read, const std::string& name, const ReadRecord& r, int mode, char strand = '+');
 // fields_pathwise(..).text() appended to `out` without the intermediate strings (codes: the read's base codes 0..4)
-void append_pathwise_text(const HostGraph& g, const uint8_t* codes, int n, const char* name, const ReadRecord& r, int mode, std::string& out);
+void append_pathwise_text(const HostGraph& g, const uint8_t* codes, int n, const char* name, const ReadRecord& r, int mode, std::string& out,
+                          char strand = '+');
 void build_rev_ids(HostGraph& g);
 void build_path_lists(HostGraph& g);
 

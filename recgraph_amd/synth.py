@@ -314,3 +314,17 @@ def make_config(name, n_reads=None, graph_seed=1234):
         g = haplotype_graph(c["rows"], c["paths"], path_len=c["n"], seed=graph_seed)
         reads = haplotype_reads(g, nr, c["n"], seed=5678 + num, mosaic_frac=0.5 if name == "C5" else 0.0)
     return g, reads, c
+
+
+_COMP = {"A": "T", "C": "G", "G": "C", "T": "A", "N": "N"}
+
+
+def reverse_complement_share(reads, share=0.5, seed=5678):
+    """A read set as a sequencer hands it over: ``share`` of the reads (chosen with ``seed``, exactly
+    ``round(share * len(reads))`` of them) replaced by their reverse complement (sequences.rs:65-82).  Returns
+    ``(reads, flipped)`` with ``flipped`` a bool array saying which."""
+    rng = np.random.default_rng(seed)
+    n = len(reads)
+    flipped = np.zeros(n, dtype=bool)
+    flipped[rng.permutation(n)[:int(round(share * n))]] = True
+    return ["".join(_COMP[c] for c in reversed(r)) if f else r for r, f in zip(reads, flipped)], flipped

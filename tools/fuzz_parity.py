@@ -1,6 +1,11 @@
 """Randomised parity campaign on the GPU: every mode vs the oracle on random graphs / reads / scores.
-   python tools/fuzz_parity.py [seconds] [seed]"""
+   python tools/fuzz_parity.py [seconds] [seed] [--both-strands]
+
+--both-strands: the pathwise modes run with RG_AMB_BOTH_STRANDS on a random mix of forward, reverse-complemented and unrelated
+reads; the expected text is built from the oracle by the rule of include/recgraph_hip.h (retry below 0, reverse wins when
+strictly greater, strand '-')."""
 import os
+import re
 import sys
 import time
 
@@ -11,8 +16,10 @@ sys.path.insert(0, ROOT)
 from oracle import oracle as O          # noqa: E402
 from recgraph_amd import api, synth      # noqa: E402
 
-budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
-seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 1
+BOTH = "--both-strands" in sys.argv
+argv = [a for a in sys.argv if not a.startswith("--")]
+budget = float(argv[1]) if len(argv) > 1 else 120.0
+seed0 = int(argv[2]) if len(argv) > 2 else 1
 t_end = time.time() + budget
 HOX = open(os.path.join(ROOT, "tests", "golden", "HOXD55.mtx")).read()
 PATH_MODES = [(api.MODE_PATHWISE, O.M4_ABS), (api.MODE_PATHWISE_SEMI, O.M5_ABS), (api.MODE_RECOMBINATION, O.M8_ABS),
@@ -45,6 +52,9 @@ while time.time() < t_end and not fails:
     reads += ["ACGT"[int(x)] * int(rng.integers(1, 6)) for x in rng.integers(0, 4, size=2)]
     walk = sg.path_sequence(int(rng.integers(0, P)))
     reads.append(walk[:int(rng.integers(1, len(walk) + 1))])
+    if BOTH:
+        reads += ["".join("ACGT"[int(x)] for x in rng.integers(0, 4, size=int(rng.integers(2, plen + 2)))) for _ in range(3)]
+        reads, _ = synth.reverse_complement_share(reads, float(rng.uniform(0.2, 0.8)), seed=int(rng.integers(1, 10**6)))
     variant = int(rng.integers(0, 5))
     if variant == 0:
         sc, osc = None, None
@@ -65,7 +75,7 @@ while time.time() < t_end and not fails:
     g = api.Graph.from_gfa_text(gfa)
     og = O.Graph.from_gfa_text(gfa)
     names = ["q%d" % i for i in range(len(reads))]
-    modes = list(PATH_MODES) + [POA_MODES[int(rng.integers(0, 6))], POA_MODES[int(rng.integers(0, 6))]]
+    modes = list(PATH_MODES) + ([] if BOTH else [POA_MODES[int(rng.integers(0, 6))], POA_MODES[int(rng.integers(0, 6))]])
     for mode, om in modes:
         kw, okw = {}, {}
         msc, mosc = (psc, posc) if (mode, om) in PATH_MODES else (sc, osc)
@@ -84,10 +94,16 @@ while time.time() < t_end and not fails:
         if os.environ.get("FUZZ_VERBOSE"):
             print("it", it, "P", P, "plen", plen, "rows", sg.rows, "mode", mode, "variant", variant, kw if sc is None else {k: v for k, v in kw.items() if k != "score_matrix"},
                   "reads", [len(q) for q in rd], file=sys.stderr, flush=True)
-        texts, status = api.align_batch(g, rd, names, mode=mode, **kw)
+        texts, status = api.align_batch(g, rd, names, mode=mode, both_strands=BOTH, **kw)
         for i, q in enumerate(rd):
             exp, _, panic, _ = og.align(om, q, name=names[i], idx=i + 1, **okw)
             checked += 1
+            if BOTH and not panic and float(re.search(r"score: (-?[0-9.]+)", exp).group(1)) < 0:
+                rexp, _, rpanic, _ = og.align(om, api.rev_and_compl(q), name=names[i], idx=i + 1, **okw)
+                if not rpanic and float(re.search(r"score: (-?[0-9.]+)", rexp).group(1)) > float(re.search(r"score: (-?[0-9.]+)", exp).group(1)):
+                    f = rexp.split("\t")
+                    f[4] = "-"
+                    exp = "\t".join(f)
             if panic:
                 if not status[i] & api.READ_WOULD_PANIC:
                     fails.append((it, mode, i, "expected panic", status[i]))

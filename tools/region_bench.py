@@ -3,7 +3,12 @@
 engine on other read lengths, score parameters and path counts, with the sweep kernel that ran and a parity check of a
 few reads against the oracle.  One JSON line per case.
 
-    python tools/region_bench.py [case ...]        cases: c5 x6 m3x5 hoxd70 len1500 p128 len600 (default: all)
+    python tools/region_bench.py [case ...]        cases: c5 x6 m3x5 hoxd70 len1500 p128 len600 (default: all but the strand cases)
+
+The strand cases (RG_AMB_BOTH_STRANDS, config-5 shape; `reads_per_s` counts SOURCE reads): `both_strands_fwd` — option on, every
+read forward (what the option costs when nothing qualifies: compare with `c5`); `both_strands` — option on, half of the reads
+reverse-complemented; `two_n` — option off, every read AND its reverse complement in the tiles, which is what a caller without
+the option has to submit (half of a tile's reads are source reads).
 
 Every case: TILES tiles of TILE reads through one rg_stream (3 handles), timed after one warm-up tile per handle."""
 import json
@@ -25,13 +30,16 @@ CASES = {
     "p128": (8, 10000, 128, 1000, {}, 2048, 6),
     "m4_len1500": (4, 15000, 32, 1500, {}, 2048, 6),
     "len5000": (8, 50000, 32, 5000, {}, 256, 4),
+    "both_strands_fwd": (8, 10000, 32, 1000, {"strands": "on_fwd"}, 4096, 6),
+    "both_strands": (8, 10000, 32, 1000, {"strands": "on_half"}, 4096, 6),
+    "two_n": (8, 10000, 32, 1000, {"strands": "two_n"}, 4096, 12),
 }
 
 
 def main():
     from recgraph_amd import api, synth
     from oracle import oracle as O
-    names = [a for a in sys.argv[1:] if not a.startswith("-")] or list(CASES)
+    names = [a for a in sys.argv[1:] if not a.startswith("-")] or [c for c in CASES if "strands" not in CASES[c][4]]
     check = 12
     handles = int(os.environ.get("RG_REGION_HANDLES", "3"))      # (1: the kernels' lone durations)
     opts = [kv.split("=") for kv in os.environ.get("RG_REGION_OPTS", "").split(",") if kv]      # e.g. sweep_i32=1,no_retire=1
@@ -39,6 +47,7 @@ def main():
         api.set_option(k, int(v))
     for name in names:
         mode, rows, paths, rlen, sk, tile, tiles = CASES[name]
+        tiles *= int(os.environ.get("RG_REGION_TILES_X", "1"))        # (longer timed windows for A/B comparisons)
         g = synth.haplotype_graph(rows, paths, path_len=rlen, seed=1234)
         gfa = g.gfa()
         sm = None
@@ -47,8 +56,20 @@ def main():
         elif "mtx" in sk:
             sm = api.create_score_matrix_i32(matrix_file_path=os.path.join(ROOT, "tests", "golden", sk["mtx"]))
         gg = api.Graph.from_gfa_text(gfa)
-        params = api.make_params(mode, score_matrix=sm)
-        sets = [api.Batch.pack_reads(synth.haplotype_reads(g, tile, length=rlen, seed=900 + k, mosaic_frac=0.5 if mode == 8 else 0.0)) for k in range(min(tiles, 3))]
+        strands = sk.get("strands")
+        params = api.make_params(mode, score_matrix=sm, amb=api.AMB_BOTH_STRANDS if strands in ("on_fwd", "on_half") else None)
+
+        def tile_reads(k):
+            """(reads of tile set k, per read: the source read the oracle aligns, whether the record must carry '-')"""
+            src = synth.haplotype_reads(g, tile // 2 if strands == "two_n" else tile, length=rlen, seed=900 + k, mosaic_frac=0.5 if mode == 8 else 0.0)
+            if strands == "on_half":
+                rd, fl = synth.reverse_complement_share(src, 0.5, seed=900 + k)
+                return rd, src, list(fl)
+            if strands == "two_n":
+                rd = [x for r in src for x in (r, api.rev_and_compl(r))]
+                return rd, [x for r in src for x in (r, None)], [False] * len(rd)
+            return src, src, [False] * len(src)
+        sets = [api.Batch.pack_reads(tile_reads(k)[0]) for k in range(min(tiles, 3))]
         st = api.Stream(gg, params, device_ids=[0], handles_per_device=handles, tile_reads=tile)
         for k in range(3):
             st.push(sets[k % len(sets)])
@@ -69,20 +90,24 @@ def main():
         osc = None if sm is None else O.scores_from_dict({k: int(v) for k, v in sm.items()})
         omode = {4: O.M4_ABS, 8: O.M8_ABS}[mode]
         last = got[-1]
-        last_reads = synth.haplotype_reads(g, tile, length=rlen, seed=900 + ((tiles - 1) % len(sets)), mosaic_frac=0.5 if mode == 8 else 0.0)
+        _, last_reads, minus = tile_reads((tiles - 1) % len(sets))
         idx = sorted(set([0, tile - 1] + [int(k * (tile - 1) / (check - 1)) for k in range(check)]))
+        idx = [i for i in idx if last_reads[i] is not None]        # (two_n: the source reads; their reverse complements are the caller's to merge)
         kw = {} if osc is None else {"scores": osc}
         _, _, exp = og.bench_text(omode, [last_reads[i] for i in idx], nthreads=min(os.cpu_count() or 1, 32), name_prefix="x", **kw)
         ok = True
         for k, i in enumerate(idx):
             e = exp[k].decode().replace("x%d\t" % k, "read%d\t" % (last.first + i), 1)
+            if minus[i]:
+                e = e.replace("\t+\t", "\t-\t", 1)
             # (bench_text numbers the reads by their position in the subset: everything but the trailing read index)
             ok = ok and last.text_of(i).decode().rsplit("\t", 1)[0] == e.rsplit("\t", 1)[0]
         sweeps = sorted(k for k in ks if k.startswith("k_sweep"))
         cu = sum(t.cell_updates for t in got)
         cp = sum(t.cell_updates_performed for t in got)
+        source = tile // 2 if strands == "two_n" else tile
         print(json.dumps({"case": name, "mode": mode, "rows": gg.rows, "paths": paths, "read_len": rlen, "scores": sk or "default",
-                          "tile_reads": tile, "tiles": tiles, "handles": handles, "options": dict((k, int(v)) for k, v in opts), "reads_per_s": round(tile * tiles / dt, 1), "ms_per_tile": round(dt / tiles * 1e3, 2),
+                          "tile_reads": tile, "tiles": tiles, "handles": handles, "options": dict((k, int(v)) for k, v in opts), "reads_per_s": round(source * tiles / dt, 1), "ms_per_tile": round(dt / tiles * 1e3, 2),
                           "cell_updates_per_s": round(cu / dt), "performed_over_counted": round(cp / cu, 3) if cu else None, "sweep_kernels": sweeps, "kernel_ms_per_tile": ks, "parity_checked": len(idx) if ok else "FAILED"}), flush=True)
 
 
