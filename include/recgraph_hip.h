@@ -360,20 +360,26 @@ int64_t rg_stream_kernel_launches(rg_stream* s, int32_t k);
 int64_t rg_stream_tiles_done(rg_stream* s);
 int32_t rg_stream_handles(rg_stream* s);      /* batch handles that aligned at least one tile */
 
-/* Process-wide diagnostic switches, also settable through the environment (read once when the library is loaded):
- * "sweep_i32" (RG_SWEEP_I32: i32 sweep kernel even when the packed 16-bit one is admissible), "three_sweeps"
- * (RG_THREE_SWEEPS), "no_frec" (RG_NO_FREC: Cand-list forward emission), "no_spec" (RG_NO_SPEC: -m 8 forward sweep
- * pruned with the provable bound instead of the speculative one), "spec_margin" (RG_SPEC_MARGIN, an integer: what the
- * speculative bound subtracts from the picked path's score; default 112), "chunk_reads" (RG_CHUNK_READS, an integer:
- * most reads one pathwise kernel launch takes), "no_gather" / "no_split" (RG_NO_GATHER / RG_NO_SPLIT: k_sweep16 without its gather runs / on the
- * plain step tables), "layer_i32" (RG_LAYER_I32: the layer rebuild in its i32 form), "no_retire" (RG_NO_RETIRE: k_sweep16 computes
- * every path to the end; 2 / 3: retirement in the forward / reverse sweep only), "no_pick2" (RG_NO_PICK2: the speculative
- * bound from one-path picks only), "no_order" (RG_NO_ORDER: the sweeps' waves in read order instead of longest first), "stripe_c" (RG_STRIPE_C: 8, 16 or 32 columns per lane for reads longer
- * than 2047 bases; 0 = 16 up to 8191 bases, 32 beyond), "spin_wait" (RG_SPIN_WAIT: hipStreamSynchronize instead of sleep-polling
- * for the long waits), "debug" (RG_DEBUG: list statistics on stderr; the packed k_opt0 is cross-checked against its i32 form),
- * "retire_shift" (RG_RETIRE_SHIFT, 2..12, default 8: the sweeps look for hopeless paths every 2^k step records; read when a
- * handle builds its step tables — the test suite runs its small graphs at 4), "lds_pad" (RG_LDS_PAD, bytes, experiments only:
- * extra dynamic LDS per k_sweep16 workgroup, which lowers the waves per CU).
+/* Process-wide diagnostic switches, also settable through the environment (read once, before the first use).  The one table
+ * they come from is RG_OPTIONS in recgraph_amd/csrc/rg_host.hpp; a switch takes 0 / 1 (any other value sets 1), an integer is
+ * clamped to its range:
+ *   "sweep_i32" (RG_SWEEP_I32: i32 sweep kernel even when the packed 16-bit one is admissible), "three_sweeps"
+ *   (RG_THREE_SWEEPS), "no_frec" (RG_NO_FREC: Cand-list forward emission), "debug" (RG_DEBUG: list statistics on stderr; the
+ *   packed k_opt0 is cross-checked against its i32 form), "spin_wait" (RG_SPIN_WAIT: hipStreamSynchronize instead of
+ *   sleep-polling for the long waits), "no_gather" / "no_split" (RG_NO_GATHER / RG_NO_SPLIT: k_sweep16 without its gather runs /
+ *   on the plain step tables), "no_spec" (RG_NO_SPEC: forward sweep pruned with the provable bound instead of the speculative
+ *   one), "spec_margin" (RG_SPEC_MARGIN, -2^24..2^24, default 112: what the speculative bound subtracts from the picked path's
+ *   score), "spec4_margin_x10" (RG_SPEC4_MARGIN_X10, 0..1000, default 25: ten times the factor -m 4 puts on that margin),
+ *   "stripe_c" (RG_STRIPE_C, 0..32: 8, 16 or 32 columns per lane for reads longer than 2047 bases; 0 = 16 up to 8191 bases, 32
+ *   beyond), "no_retire" (RG_NO_RETIRE, 0..3: 1 = k_sweep16 computes every path to the end; 2 / 3: retirement in the forward /
+ *   reverse sweep only), "retire_shift" (RG_RETIRE_SHIFT, 2..12, default 8: the sweeps look for hopeless paths every 2^k step
+ *   records; read when a handle builds its step tables — the test suite runs its small graphs at 4), "no_order" (RG_NO_ORDER:
+ *   the sweeps' waves in read order instead of longest first), "dsel_edge" (RG_DSEL_EDGE, 1..2^20, default 8: the 1 / dsel_edge
+ *   of the rows a sweep visits first always store their direction words), "no_dsel" (RG_NO_DSEL: every record of the packed
+ *   sweeps stores its direction word, not only those with a picked path), "no_pick2" (RG_NO_PICK2: the speculative bound from
+ *   one-path picks only), "layer_i32" (RG_LAYER_I32: the layer rebuild in its i32 form), "lds_pad" (RG_LDS_PAD, 0..40960 bytes,
+ *   experiments only: extra dynamic LDS per k_sweep16 workgroup, which lowers the waves per CU), "chunk_reads" (RG_CHUNK_READS,
+ *   0..2^20: most reads one pathwise kernel launch takes; 0 = what the memory budget allows).
  * The variants compute the same records byte for byte (tests/test_gpu_pathwise.py). */
 int32_t rg_set_option(const char* name, int64_t value);
 int64_t rg_get_option(const char* name);      /* -1: unknown option */

@@ -26,35 +26,6 @@ void rg_batch_destroy_impl(rg_batch* b) {
 }
 
 namespace rg {
-Options& options() {
-    static Options o;
-    static std::once_flag once;
-    std::call_once(once, [] {
-        auto env = [](const char* k) { const char* v = getenv(k); return v && *v && strcmp(v, "0") != 0 ? 1 : 0; };
-        o.sweep_i32 = env("RG_SWEEP_I32");
-        o.three_sweeps = env("RG_THREE_SWEEPS");
-        o.no_frec = env("RG_NO_FREC");
-        o.debug = env("RG_DEBUG");
-        { const char* v = getenv("RG_CHUNK_READS"); o.chunk_reads = v ? atoi(v) : 0; }
-        { const char* v = getenv("RG_STRIPE_C"); o.stripe_c = v ? atoi(v) : 0; }
-        { const char* v = getenv("RG_LB_BONUS"); o.lb_bonus = v ? atoi(v) : 0; }
-        o.no_spec = env("RG_NO_SPEC");
-        o.no_gather = env("RG_NO_GATHER");
-        o.no_split = env("RG_NO_SPLIT");
-        o.layer_i32 = env("RG_LAYER_I32");
-        { const char* v = getenv("RG_NO_RETIRE"); o.no_retire = v ? atoi(v) : 0; }
-        o.no_pick2 = env("RG_NO_PICK2");
-        o.no_dsel = env("RG_NO_DSEL");
-        o.sweep_prio = env("RG_SWEEP_PRIO");
-        if (getenv("RG_DSEL_EDGE")) o.dsel_edge = std::max(1, atoi(getenv("RG_DSEL_EDGE")));
-        o.no_order = env("RG_NO_ORDER");
-        o.spin_wait = env("RG_SPIN_WAIT");
-        { const char* v = getenv("RG_SPEC_MARGIN"); if (v) o.spec_margin = atoi(v); }
-        { const char* v = getenv("RG_LDS_PAD"); o.lds_pad = v ? atoi(v) : 0; }
-    });
-    return o;
-}
-
 int wait_stream_sleeping(void* stream, void* ev, bool spin) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (spin || options().spin_wait || !ev) return (int)hipStreamSynchronize(s);
@@ -235,14 +206,6 @@ int run_poa(rg_batch* b) {
 
 // pathwise driver lives in rg_path_driver.hip
 int rg_run_pathwise(rg_batch* b);
-namespace rg {
-int path_driver_run(const HostGraph& h, const PathGraphDev& gd, const rg_params& p, PathWork& w, const uint8_t* d_reads,
-                    const long long* d_off, const uint8_t* d_bad, int nreads, int max_n, DevRecord* d_rec, uint8_t* d_ops,
-                    long long ops_stride, unsigned long long* d_cells, hipStream_t stream, size_t mem_budget,
-                    unsigned long long* cells_out,
-                    std::vector<std::pair<std::string, std::pair<double, long long>>>& stats, int spec_level);
-}
-
 // Text of read i exactly as the reference prints it (warning lines + GAFStruct::to_string), appended to `out`.
 extern "C" {
 static bool build_fields(const rg_batch* b, int64_t i, const char* name, GafFields& out);
@@ -376,48 +339,15 @@ extern "C" {
 
 const char* rg_last_error(void) { return g_last_error.c_str(); }
 
-static std::atomic<int>* option_slot(const char* name) {
-    if (!name) return nullptr;
-    Options& o = options();
-    if (!strcmp(name, "sweep_i32")) return &o.sweep_i32;
-    if (!strcmp(name, "three_sweeps")) return &o.three_sweeps;
-    if (!strcmp(name, "no_frec")) return &o.no_frec;
-    if (!strcmp(name, "debug")) return &o.debug;
-    if (!strcmp(name, "chunk_reads")) return &o.chunk_reads;
-    if (!strcmp(name, "stripe_c")) return &o.stripe_c;
-    if (!strcmp(name, "no_spec")) return &o.no_spec;
-    if (!strcmp(name, "no_gather")) return &o.no_gather;
-    if (!strcmp(name, "no_split")) return &o.no_split;
-    if (!strcmp(name, "layer_i32")) return &o.layer_i32;
-    if (!strcmp(name, "no_retire")) return &o.no_retire;
-    if (!strcmp(name, "no_pick2")) return &o.no_pick2;
-    if (!strcmp(name, "no_dsel")) return &o.no_dsel;
-    if (!strcmp(name, "sweep_prio")) return &o.sweep_prio;
-    if (!strcmp(name, "dsel_edge")) return &o.dsel_edge;
-    if (!strcmp(name, "no_order")) return &o.no_order;
-    if (!strcmp(name, "spin_wait")) return &o.spin_wait;
-    if (!strcmp(name, "spec_margin")) return &o.spec_margin;
-    if (!strcmp(name, "lds_pad")) return &o.lds_pad;
-    if (!strcmp(name, "retire_shift")) return &retire_shift_option();
-    return nullptr;
-}
 int32_t rg_set_option(const char* name, int64_t value) {
-    std::atomic<int>* s = option_slot(name);
-    if (!s) return fail(RG_ERR_ARG, std::string("unknown option ") + (name ? name : "(null)"));
-    Options& o = options();
-    if (s == &o.stripe_c) *s = (int)std::max<int64_t>(0, std::min<int64_t>(value, 32));
-    else if (s == &o.chunk_reads) *s = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20));
-    else if (s == &retire_shift_option()) *s = (int)std::max<int64_t>(2, std::min<int64_t>(value, 12));
-    else if (s == &o.lds_pad) *s = (int)std::max<int64_t>(0, std::min<int64_t>(value, 40 << 10));
-    else if (s == &o.dsel_edge) *s = (int)std::max<int64_t>(1, std::min<int64_t>(value, 1 << 20));     // 1 / dsel_edge of the rows always store their direction words
-    else if (s == &o.spec_margin) *s = (int)std::max<int64_t>(-(1 << 24), std::min<int64_t>(value, 1 << 24));
-    else if (s == &o.no_retire) *s = (int)std::max<int64_t>(0, std::min<int64_t>(value, 3));     // 1: off, 2: forward sweep only, 3: reverse sweep only
-    else *s = value ? 1 : 0;
+    const OptionDesc* d = find_option(name);
+    if (!d) return fail(RG_ERR_ARG, std::string("unknown option ") + (name ? name : "(null)"));
+    store_option(options(), *d, value);
     return RG_OK;
 }
 int64_t rg_get_option(const char* name) {
-    std::atomic<int>* s = option_slot(name);
-    return s ? (int64_t)s->load() : -1;
+    const OptionDesc* d = find_option(name);
+    return d ? (int64_t)(options().*d->slot).load() : -1;
 }
 
 int32_t rg_device_count(void) {
@@ -816,14 +746,11 @@ int rg_run_pathwise(rg_batch* b) {
     gd.node_id = g->d_node_id.p; gd.segfirst = g->d_segfirst.p; gd.seglast = g->d_seglast.p;
     gd.eoff = g->d_eoff.p; gd.epred = g->d_epred.p; gd.emask = g->d_emask.p; gd.roff = g->d_roff.p; gd.rsucc = g->d_rsucc.p;
     gd.rmask = g->d_rmask.p; gd.pnwp = g->d_pnwp.p; gd.rnwp = g->d_rnwp.p;
-    std::vector<std::pair<std::string, std::pair<double, long long>>> st;
     // what this handle already holds counts towards its share of the device
     unsigned long long c[2] = {0, 0};
     b->pw.spin_wait = b->spin_wait;
     int rc = path_driver_run(h, gd, b->p, b->pw, b->in.reads, b->in.off, b->in.bad, (int)b->nreads, b->max_n, b->d_rec.p,
-                             b->d_ops.p, b->ops_stride, b->d_cells.p, b->stream, b->mem_budget, c, st, 0);
-    b->stats.clear();
-    for (auto& s : st) b->stats.push_back(KernelStat{s.first, s.second.first, s.second.second});
+                             b->d_ops.p, b->ops_stride, b->d_cells.p, b->stream, b->mem_budget, c, b->stats, 0);
     if (rc) return rc;
     b->cells = c[0];
     b->cells_performed = c[1];
@@ -842,17 +769,12 @@ int rg_run_pathwise(rg_batch* b) {
     if (count <= 0) return RG_OK;
     if (count > n || max_len < 1 || max_len > b->max_n) return fail(RG_ERR_HIP, "k_strand_gate returned an impossible read count / length");
     HIPCHK(hipMemsetAsync(b->d_rcbad.p, 0, (size_t)count, b->stream));
-    std::vector<std::pair<std::string, std::pair<double, long long>>> st2;
+    KernelStats st2;
     unsigned long long c2[2] = {0, 0};
     if ((rc = path_driver_run(h, gd, b->p, b->pw, b->d_rc.p, b->d_rcoff.p, b->d_rcbad.p, count, max_len, b->d_rec2.p, b->d_ops2.p,
                               b->ops_stride, b->d_cells.p, b->stream, b->mem_budget, c2, st2, 0)))
         return rc;
-    for (auto& e : st2) {
-        bool found = false;
-        for (auto& s : b->stats)
-            if (s.name == e.first) { s.ms += e.second.first; s.launches += e.second.second; found = true; break; }
-        if (!found) b->stats.push_back(KernelStat{e.first, e.second.first, e.second.second});
-    }
+    for (auto& e : st2) add_stat(b->stats, e.name, e.ms, e.launches);
     b->cells += c2[0];                  // (the workload grew: both counters include the second pass)
     b->cells_performed += c2[1];
     StrandMergeArgs ma{b->d_rec.p, b->d_ops.p, b->d_rec2.p, b->d_ops2.p, b->ops_stride, b->d_sidx.p, count, recomb};

@@ -1,5 +1,5 @@
 // Private definitions shared by rg_abi.hip (the extern "C" surface + batch driver) and rg_stream.hip (the streaming
-// engine): device / pinned buffers, the per-device graph tables and the batch handle.  Not part of the C ABI.
+// engine): pinned buffers (device buffers: DevBuf in rg_path_args.hpp), the per-device graph tables and the batch handle.  Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -26,28 +26,6 @@ using namespace rg;
                         std::string(#x) + ": " + hipGetErrorString(e_));                                \
         }                                                                                               \
     } while (0)
-
-template <typename T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t n = 0;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    size_t bytes() const { return p ? n * sizeof(T) : 0; }
-    int alloc(size_t count) {
-        if (count <= n && p) return RG_OK;
-        if (p) { (void)hipFree(p); p = nullptr; n = 0; }
-        if (count == 0) count = 1;
-        HIPCHK(hipMalloc((void**)&p, count * sizeof(T)));
-        n = count;
-        return RG_OK;
-    }
-    int upload(const std::vector<T>& v) {
-        int rc = alloc(v.size());
-        if (rc) return rc;
-        if (!v.empty()) HIPCHK(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-        return RG_OK;
-    }
-};
 
 // Device copy of the flattened graph: one per HIP device that has a batch on this graph (built on first use, under the
 // graph's mutex; the host arrays are immutable after creation, so a graph handle is shareable across threads and devices).
@@ -156,12 +134,6 @@ struct PinBuf {
     }
 };
 
-struct KernelStat {
-    std::string name;
-    double ms = 0;
-    long long launches = 0;
-};
-
 // Selects a device for the duration of an ABI entry and restores the caller's current device afterwards (a host such as
 // torch may have another device selected on the calling thread).
 struct DevGuard {
@@ -224,7 +196,7 @@ struct rg_batch {
     std::vector<int32_t> oprows;
     bool fetched = false;
     uint64_t cells = 0, cells_performed = 0;
-    std::vector<KernelStat> stats;
+    KernelStats stats;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
     hipEvent_t done_ev = nullptr;      // end-of-run marker polled by wait_stream_sleeping
     ~rg_batch() {

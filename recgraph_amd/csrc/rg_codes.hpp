@@ -10,6 +10,13 @@ enum : uint8_t { OP_D = 1, OP_U = 2, OP_L = 3, OP_CONT = 0x80 };
 // status bits mirror include/recgraph_hip.h
 enum : uint32_t { ST_BAND_WARNING = 1u, ST_BAND_NOT_ENOUGH = 2u, ST_WOULD_PANIC = 4u, ST_BAD_BASE = 8u, ST_OVERFLOW = 0x100u };
 
+constexpr int WAVE = 64;
+
+// scoring table by value in kernel arguments: t[a*6+b], alphabet "ACGTN-" -> 0..5
+struct DevScores {
+    int t[36];
+};
+
 }  // namespace rg
 
 // PATH RETIREMENT of k_sweep16: the sweeps look for hopeless paths every 2^RG_SWEEP16_RETIRE_SHIFT step records;

@@ -7,13 +7,6 @@
 
 namespace rg {
 
-constexpr int WAVE = 64;
-
-// scoring table by value in kernel arguments: t[a*6+b], alphabet "ACGTN-" -> 0..5
-struct DevScores {
-    int t[36];
-};
-
 // flattened LnzGraph in HBM (graph.rs:23-27 restated as CSR)
 struct DevLnz {
     int L;

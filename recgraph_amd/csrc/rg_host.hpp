@@ -19,31 +19,47 @@ namespace rg {
 
 extern thread_local std::string g_last_error;
 
-// Process-wide diagnostic switches (rg_set_option; defaults from the environment variables of the same meaning, read
-// once when the library is loaded): no getenv on the run path.
+// Process-wide diagnostic switches: ONE table of (name, environment variable, kind, smallest, largest, default).  From it come the
+// storage (struct Options), the environment defaults (read once, when options() is first called: no getenv on the run path),
+// rg_set_option / rg_get_option and the clamping (rg_path_plan.cpp).  Kind B: a switch (any non-zero value sets 1; the variable
+// counts unless it is empty or "0"); kind I: an integer clamped to [smallest, largest].
+#define RG_OPTIONS(X) \
+    X(sweep_i32, "RG_SWEEP_I32", B, 0, 1, 0)          /* force the i32 sweep kernel */ \
+    X(three_sweeps, "RG_THREE_SWEEPS", B, 0, 1, 0)    /* force the three-sweep -m 8 pipeline */ \
+    X(no_frec, "RG_NO_FREC", B, 0, 1, 0)              /* Cand-list forward emission instead of records */ \
+    X(debug, "RG_DEBUG", B, 0, 1, 0)                  /* candidate / record statistics on stderr; k_opt0_16 checked against k_opt0 */ \
+    X(spin_wait, "RG_SPIN_WAIT", B, 0, 1, 0)          /* long waits for the device through hipStreamSynchronize (spins a CPU) instead of hipEventQuery + usleep polling */ \
+    X(no_gather, "RG_NO_GATHER", B, 0, 1, 0)          /* k_sweep16 without its gather runs */ \
+    X(no_split, "RG_NO_SPLIT", B, 0, 1, 0)            /* k_sweep16 on the plain step tables (no TAIL records) */ \
+    X(no_spec, "RG_NO_SPEC", B, 0, 1, 0)              /* forward sweep with the provable bound (path 0) instead of the speculative one */ \
+    X(spec_margin, "RG_SPEC_MARGIN", I, -(1 << 24), 1 << 24, 112)   /* what the speculative bound subtracts from the picked path's score */ \
+    X(spec4_margin_x10, "RG_SPEC4_MARGIN_X10", I, 0, 1000, 25)      /* -m 4: ten times the factor on that margin (experiments) */ \
+    X(stripe_c, "RG_STRIPE_C", I, 0, 32, 0)           /* columns per lane of the striped long-read kernels (8, 16, 32; 0: 16 up to 8191 bases, else 32) */ \
+    X(no_retire, "RG_NO_RETIRE", I, 0, 3, 0)          /* 1: k_sweep16 computes every path to the end; 2 / 3: path retirement in the forward / reverse sweep only */ \
+    X(retire_shift, "RG_RETIRE_SHIFT", I, 2, 12, RG_SWEEP16_RETIRE_SHIFT)   /* log2 of the step records between two evaluation points of the path retirement: read when a handle builds its step tables, carried to the kernel with them (StepTables::retire_shift -> SweepArgs::retire_shift).  Small graphs only retire paths with a small period: the test suite runs its switch families at 4 */ \
+    X(no_order, "RG_NO_ORDER", B, 0, 1, 0)            /* the sweeps' waves in read order (no longest-first launch order) */ \
+    X(dsel_edge, "RG_DSEL_EDGE", I, 1, 1 << 20, 8)    /* the 1 / dsel_edge of the rows each sweep visits first always store their direction words */ \
+    X(no_dsel, "RG_NO_DSEL", B, 0, 1, 0)              /* every (row, group) record of the packed sweeps stores its direction word (otherwise: those with a picked path) */ \
+    X(no_pick2, "RG_NO_PICK2", B, 0, 1, 0)            /* the speculative bound from one-path picks only (no two-path picks) */ \
+    X(layer_i32, "RG_LAYER_I32", B, 0, 1, 0)          /* k_layer in its i32 form even when the sweep ran packed (test hook) */ \
+    X(lds_pad, "RG_LDS_PAD", I, 0, 40 << 10, 0)       /* (experiments only) extra dynamic LDS bytes per k_sweep16 workgroup: lowers the waves per CU */ \
+    X(chunk_reads, "RG_CHUNK_READS", I, 0, 1 << 20, 0)   /* most reads one pathwise kernel launch takes (0: what the HBM budget allows, <= 8192) */
 struct Options {
-    std::atomic<int> sweep_i32{0};      // RG_SWEEP_I32: force the i32 sweep kernel
-    std::atomic<int> three_sweeps{0};   // RG_THREE_SWEEPS: force the three-sweep -m 8 pipeline
-    std::atomic<int> no_frec{0};        // RG_NO_FREC: Cand-list forward emission instead of records
-    std::atomic<int> debug{0};          // RG_DEBUG: candidate / record statistics on stderr
-    std::atomic<int> spin_wait{0};      // RG_SPIN_WAIT: long waits for the device through hipStreamSynchronize (spins a CPU) instead of
-                                        // hipEventQuery + usleep polling
-    std::atomic<int> no_gather{0};      // RG_NO_GATHER: k_sweep16 without its gather runs
-    std::atomic<int> no_split{0};       // RG_NO_SPLIT: k_sweep16 on the plain step tables (no TAIL records)
-    std::atomic<int> no_spec{0};        // RG_NO_SPEC: -m 8 forward sweep with the provable bound (path 0) instead of the speculative one
-    std::atomic<int> spec_margin{112};  // RG_SPEC_MARGIN: what the speculative bound subtracts from the picked path's score
-    std::atomic<int> lb_bonus{0};       // RG_LB_BONUS (experiments only): added to the forward sweep's lower bound; > 0 may drop candidates
-    std::atomic<int> stripe_c{0};       // RG_STRIPE_C: columns per lane of the striped long-read kernels (8, 16, 32; 0: 16 up to 8191 bases, else 32)
-    std::atomic<int> no_retire{0};      // RG_NO_RETIRE: k_sweep16 computes every path to the end (no path retirement)
-    std::atomic<int> no_order{0};       // RG_NO_ORDER: the sweeps' waves in read order (no longest-first launch order)
-    std::atomic<int> dsel_edge{8};      // RG_DSEL_EDGE: the 1 / dsel_edge of the rows each sweep visits first always store their direction words
-    std::atomic<int> sweep_prio{0};     // RG_SWEEP_PRIO: the pathwise sweeps on a low-priority stream of their own (measured: -1..-3 % at config 5, +2.5 % at 1.5 kbp: off)
-    std::atomic<int> no_dsel{0};        // RG_NO_DSEL: every (row, group) record of the packed sweeps stores its direction word (round 6: only those with a picked path)
-    std::atomic<int> no_pick2{0};       // RG_NO_PICK2: the speculative bound from one-path picks only (no two-path picks)
-    std::atomic<int> layer_i32{0};      // RG_LAYER_I32: k_layer in its i32 form even when the sweep ran packed (test hook)
-    std::atomic<int> lds_pad{0};        // RG_LDS_PAD (experiments only): extra dynamic LDS bytes per k_sweep16 workgroup — lowers the waves per CU
-    std::atomic<int> chunk_reads{0};    // RG_CHUNK_READS: most reads one pathwise kernel launch takes (0: what the HBM budget allows, <= 8192)
+#define RG_OPTION_FIELD(name, env, kind, lo, hi, def) std::atomic<int> name{def};
+    RG_OPTIONS(RG_OPTION_FIELD)
+#undef RG_OPTION_FIELD
 };
+struct OptionDesc {
+    const char* name;
+    const char* env;
+    bool boolean;
+    int lo, hi, def;
+    std::atomic<int> Options::*slot;
+};
+extern const OptionDesc kOptionTable[];
+extern const int kOptionCount;
+const OptionDesc* find_option(const char* name);            // null: unknown (or null) name
+void store_option(Options& o, const OptionDesc& d, long long value);   // normalises a switch, clamps an integer
 Options& options();
 // Waits for everything enqueued on `stream` so far WITHOUT spinning: records `ev` and polls it with short sleeps.  Every HIP
 // wait spins by default (hipStreamSynchronize / hipEventSynchronize of a 0.5 s kernel = 0.5 s of CPU, hipEventBlockingSync
@@ -147,11 +163,6 @@ struct StepTables {
     int retire_shift = RG_SWEEP16_RETIRE_SHIFT;     // the period the lead tables were built for
 };
 void build_step_tables(const HostGraph& h, bool forward, bool want_split, StepTables& out);
-// log2 of the records between two evaluation points of the path retirement (rg_set_option "retire_shift" / RG_RETIRE_SHIFT,
-// 2..12, default RG_SWEEP16_RETIRE_SHIFT = 8): read when a handle builds its step tables, carried to the kernel with them
-// (StepTables::retire_shift -> SweepArgs::retire_shift).  Small graphs only retire paths with a small period: the test
-// suite runs its switch families at 4.
-std::atomic<int>& retire_shift_option();
 
 // ---- alignment records as they come back from the device ----
 struct ReadRecord {

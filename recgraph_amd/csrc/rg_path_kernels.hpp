@@ -1,28 +1,9 @@
 // Argument blocks of the pathwise kernels (rg_pathwise.hip) shared with the driver.
 #pragma once
 #include "rg_path_args.hpp"
+#include "rg_path_plan.hpp"      // ReadState, Cand
 
 namespace rg {
-
-// per-read scalar state carried between the kernels of one batch
-struct ReadState {
-    uint32_t status;
-    int s0;            // best no-recombination score (seed of the search) / m4 best score
-    int seed_path;
-    int end_row;       // sink row of the chosen path
-    int end_row_best;  // semiglobal: row of the overall best last-column value
-    int fwd_path, rev_path, fen, rsn, rec_col, displacement;
-    float fscore;
-    int bound;         // integer lower bound of the final search maximum (>= s0), tightens the pruning
-    int sink_val[RG_MAXP];  // A[sink row][n][k]; semiglobal: best last-column value of path k over its rows >= 1
-    int trace_score;        // value of the forward layer where the traceback starts (written by k_layer)
-    int path_end_row[RG_MAXP];   // semiglobal: first row attaining sink_val[k] (ending_node, pathwise_alignment_recombination.rs:885-897)
-};
-
-// one entry of the recombination candidate lists: best member of (row, col) that can still matter
-struct Cand {
-    int row, col, val, path;
-};
 
 // Direction word of k_sweep16 at C <= 16 (RowOps16::dir_word, LayerArgs::dir_fmt 1) -> U and L as bit-per-column masks in the
 // lane's column order (bit q = column q of the lane): register r of the packed row holds columns r and H + r and contributes
@@ -248,7 +229,6 @@ struct TraceArgs {
 
 void launch_sweep(const SweepArgs& a, int nreads, int C, hipStream_t s);
 void launch_sweep16(const SweepArgs& a, int nreads, int C, hipStream_t s);   // packed 16-bit rows (rg_sweep16.hip)
-bool sweep16_admissible(const DevScores& sc, int max_path_rows, int max_n, int C);
 void launch_expand(const ExpandArgs& a, int nreads, int C, hipStream_t s);
 void launch_colmax_rec(const ExpandArgs& a, int* colmax_out, int* colarg_out, int nreads, int C, hipStream_t s);
 void launch_seed(const SeedArgs& a, hipStream_t s);

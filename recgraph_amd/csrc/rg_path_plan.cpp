@@ -1,0 +1,244 @@
+// Host-only code (no HIP) of the pathwise driver: the option table, the plan of a batch (plan_pathwise) and the per-graph
+// tables the driver uploads next to the step tables of rg_steps.cpp.  Part of the sanitizer build (tests/c/host_asan.cpp);
+// tests/c/plan_check.cpp states the routes plan_pathwise takes.
+#include "rg_path_plan.hpp"
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <mutex>
+
+namespace rg {
+
+// ---- the option table (RG_OPTIONS, rg_host.hpp) ----
+#define RG_OPTION_ROW(name, env, kind, lo, hi, def) {#name, env, #kind[0] == 'B', lo, hi, def, &Options::name},
+const OptionDesc kOptionTable[] = {RG_OPTIONS(RG_OPTION_ROW)};
+#undef RG_OPTION_ROW
+const int kOptionCount = (int)(sizeof kOptionTable / sizeof kOptionTable[0]);
+
+const OptionDesc* find_option(const char* name) {
+    if (!name) return nullptr;
+    for (const OptionDesc& d : kOptionTable)
+        if (!strcmp(name, d.name)) return &d;
+    return nullptr;
+}
+void store_option(Options& o, const OptionDesc& d, long long value) {
+    o.*d.slot = d.boolean ? (value ? 1 : 0) : (int)std::max<long long>(d.lo, std::min<long long>(value, d.hi));
+}
+Options& options() {
+    static Options o;
+    static std::once_flag once;
+    std::call_once(once, [] {
+        for (const OptionDesc& d : kOptionTable) {
+            const char* v = getenv(d.env);
+            if (!v) continue;
+            store_option(o, d, d.boolean ? (*v && strcmp(v, "0") != 0) : atoi(v));
+        }
+    });
+    return o;
+}
+
+// Host-side admission test: uniform gap cost and every STORED value provably inside the 16-bit budget.
+// What the rows hold is z = A - c * g (c: column, g: the gap cost), not A.  A row starts at z = 0 and changes only through
+//   U: z + g_i (= z + g, the gap column is uniform)        D: z_diagonal + (s - g)        L: z_left (a copy)
+// — whoever chose the move (members follow their alpha), every cell is its chain's start plus one such step per move.  So after
+// at most `rows` graph rows and n read bases
+//   zlo = -(rows + 2) * |g| - (n + 2) * max(0, g - min s)   <=   z   <=   (n + 2) * max(0, max s - g) = zhi
+// (round 4 bounded |A| <= (rows + n) * max|entry| <= 24 000 instead, which refused -X 6 at 1 kbp and every read longer than
+// ~1.2 kbp: the all-gap corner of A is -(rows + n) |g|, the same corner of z only -rows |g|).  Required:
+//   * zlo above the "minus infinity" of a 16-bit lane (NEG16 = -30 000) with a step of head-room, zhi below +29 000;
+//   * zhi - zlo <= 32 000: every difference of two stored values (direction masks from the sign of d - max(d, u), the
+//     gather runs' member deltas) fits a signed half;
+//   * |A| <= (rows + n + 2) * max|entry| <= 32 000: outputs convert back (A = z + c g) inside key << 16 arithmetic;
+//   * gap entries <= 0: the border column (c = 0: z = A = i * g) then holds values <= 0, so that d - max(d, u) of lane 0's
+//     column 0 (d = NEG16 + s, u = the border value) stays above -32768 and the U mask keeps its sign.
+bool sweep16_admissible(const DevScores& sc, int max_path_rows, int max_n, int C) {
+    for (int b = 1; b < 5; ++b) if (sc.t[b * 6 + 5] != sc.t[5]) return false;
+    for (int b = 0; b < 5; ++b) if (sc.t[b * 6 + 5] > 0 || sc.t[5 * 6 + b] > 0) return false;
+    long long maxabs = 0, smin = INT32_MAX, smax = INT32_MIN;
+    for (int x = 0; x < 6; ++x)
+        for (int y = 0; y < 6; ++y) {
+            if (x == 5 && y == 5) continue;
+            const long long v = sc.t[x * 6 + y];
+            maxabs = std::max(maxabs, v < 0 ? -v : v);
+            if (x < 5 && y < 5) { smin = std::min(smin, v); smax = std::max(smax, v); }
+        }
+    if (maxabs > 1000) return false;
+    const long long g = sc.t[5];                 // <= 0
+    const long long rows = max_path_rows + 2, n = max_n + 2;
+    const long long zlo = rows * g - n * std::max(0ll, g - smin);
+    const long long zhi = n * std::max(0ll, smax - g);
+    if (zlo < -29000 || zhi > 29000 || zhi - zlo > 32000) return false;
+    if ((rows + n) * maxabs > 32000) return false;                 // |A| of every cell
+    if ((long long)(C / 2 + 2) * maxabs > 2000) return false;
+    return true;
+}
+
+int plan_pathwise(const rg_params& p, const PathPlanInput& in, const Options& opt, int spec_level, PathPlan& o) {
+    o = PathPlan{};
+    const int P = in.P, L = in.L, max_n = in.max_n;
+    o.semi = p.mode == RG_MODE_PATHWISE_SEMI || p.mode == RG_MODE_RECOMBINATION_SEMI;
+    o.mode = p.mode == RG_MODE_PATHWISE_SEMI ? RG_MODE_PATHWISE : p.mode == RG_MODE_RECOMBINATION_SEMI ? RG_MODE_RECOMBINATION : p.mode;
+    const bool recomb = o.mode == RG_MODE_RECOMBINATION, semi = o.semi;
+    int C = 4;
+    while (C * WAVE < max_n + 1 && C < 32) C *= 2;
+    // Reads longer than 2047 bases: column stripes, one wave per stripe in one workgroup of at most 8 waves (k_sweep /
+    // k_layer <C, true>): i32 rows, Cand lists; needs a uniform read-gap cost (every matrix the reference's CLI builds).
+    // Stripes of 1024 columns (C = 16: rows, keys and thresholds fit the 256 registers) up to 8191 bases; 2048 (C = 32,
+    // which spills 800 registers) beyond; RG_STRIPE_C / rg_set_option("stripe_c") overrides (8, 16, 32).
+    if (max_n + 1 > 32 * WAVE) {
+        C = max_n + 1 <= 8 * 16 * WAVE ? 16 : 32;
+        if ((opt.stripe_c == 8 || opt.stripe_c == 16 || opt.stripe_c == 32) && max_n + 1 <= 8 * opt.stripe_c * WAVE) C = opt.stripe_c;
+    }
+    const int nwv = (max_n + 1 + C * WAVE - 1) / (C * WAVE);
+    if (nwv > 8) return fail(RG_ERR_ARG, "reads longer than 16383 bases are not supported by the pathwise kernels");
+    if (nwv > 1)
+        for (int b = 1; b < 5; ++b)
+            if (p.scores[b * 6 + 5] != p.scores[5]) return fail(RG_ERR_ARG, "reads longer than 2047 bases need a uniform read-gap cost");
+    o.C = C;
+    o.nwv = nwv;
+    o.wpad = nwv * C * WAVE;
+    o.dir_words = nwv * WAVE * (C <= 16 ? 1 : 2);
+    o.recw = 4 + C;
+    // packed 16-bit rows (rg_sweep16.hip) whenever the scores of this batch provably fit; RG_SWEEP_I32=1 forces the i32
+    // kernel (test hook: the two must agree byte for byte).  One wave per read only: `use16` says both from here on.
+    DevScores dsc;
+    for (int i = 0; i < 36; ++i) dsc.t[i] = p.scores[i];
+    o.use16 = nwv == 1 && !opt.sweep_i32 && sweep16_admissible(dsc, in.max_path_rows, max_n, C);
+    if (!o.use16) {
+        // the i32 sweep packs (value, path) keys as value * 256 + path in 32 bits: |value| must stay below 2^23
+        long long maxabs = 0;
+        for (int i = 0; i < 36; ++i) if (i != 35 && p.scores[i] != RG_SCORE_MISSING) maxabs = std::max<long long>(maxabs, std::llabs((long long)p.scores[i]));
+        if ((long long)(in.max_path_rows + max_n + 2) * maxabs >= (1ll << 23))
+            return fail(RG_ERR_CAPACITY, "scores of this batch can reach 2^23 in magnitude: outside the 32-bit (value, path) keys of the pathwise kernels");
+    }
+    const bool use16 = o.use16;
+    o.layer_stride = (long long)(in.max_path_rows + 2) * o.dir_words;   // traceback decisions: 2 bits per cell
+    o.fdirs_stride = (long long)in.fslots * o.dir_words;
+    o.rdirs_stride = (long long)in.rslots * o.dir_words;
+    // (k_sweep16: P + 2 packed rows per read — two pseudo-rows behind the rolling rows — of wpad / 2 words)
+    o.per_read = (size_t)(o.fdirs_stride + (recomb ? o.rdirs_stride : 0)) * 4 + (size_t)o.layer_stride * 4 * (recomb ? 2 : 1) +
+                 (size_t)(P + 2) * o.wpad * 4 + (size_t)o.wpad * 20 + sizeof(ReadState);
+    // -m 8 pipeline: two sweeps (forward with a loose threshold from the exact path-0 score, then reverse) when
+    // every gap entry is <= 0 (then w[.][j] <= (n - j) * max match); three sweeps otherwise / on request
+    o.gaps_nonpos = o.gaps_agree = true;
+    for (int x = 0; x < 5; ++x) {
+        o.gaps_nonpos = o.gaps_nonpos && p.scores[x * 6 + 5] <= 0 && p.scores[5 * 6 + x] <= 0;
+        o.gaps_agree = o.gaps_agree && p.scores[5 * 6 + x] == p.scores[x * 6 + 5];
+        for (int y = 0; y < 5; ++y) o.maxmatch = std::max(o.maxmatch, p.scores[x * 6 + y]);
+    }
+    // (striped long reads, nwv > 1, take it too since round 4: k_opt0_striped gives them the forward bound)
+    o.two_sweep = recomb && o.gaps_nonpos && !opt.three_sweeps;
+    // forward emissions of the two-sweep pipeline are loose (threshold from the path-0 score): k_sweep16 writes them as
+    // (row, lane) records that k_expand filters with the final bound; k_sweep writes plain Cand entries
+    o.use_rec = o.two_sweep && use16 && !opt.no_frec;
+    // more than 64 paths only on packed rows: k_pick votes over up to 256 paths, k_sweep16 retires over several words
+    const bool paths_ok = P <= 64 || use16;
+    // speculative forward bound (PickArgs in rg_path_kernels.hpp): checked by k_verify, failed reads aligned again by the driver
+    // (long reads emit Cand entries, not records: without the speculation their forward lists would hold every cell within
+    // ~(seed - path-0 score) / 10 columns of a diagonal — millions per read at 5 kbp)
+    // spec_level 1: the sweeps of the failed reads still retire paths and emit few records (a second pass on the provable bound
+    // keeps one wave per read busy for two full sweeps and a search over ~40 000 records)
+    // (round 5: the i32 sweep of reads that fit one wave takes it as well — score matrices outside the 16-bit budget, HOXD70 /
+    // HOXD55 with their -200 gaps, emitted every forward cell within (seed - path-0 score) of a diagonal as a Cand)
+    o.spec = o.two_sweep && spec_level < 2 && !semi && paths_ok && !opt.no_spec;
+    // (a follower path's sink value lies below its own NW optimum — measured up to 72 at 1 kbp — and the gap grows with the
+    // read: long reads scale the margin with their length, or every read would fail the check and run again)
+    // The margin is in units of the default scores (match 2): other matrices scale it with their best match (HOXD70: 100 -> x50).
+    o.score_scale = std::max(1, o.maxmatch / 2);
+    const int per_kbp = (max_n + 999) / 1000;
+    o.spec_margin = ((nwv > 1 ? opt.spec_margin * per_kbp : (int)opt.spec_margin) + (spec_level == 1 ? 320 * per_kbp : 0)) *
+                    (opt.spec_margin > 0 ? o.score_scale : 1);
+    o.pick_two = o.spec && !opt.no_pick2;      // (two-path picks: global mode, which `spec` implies)
+    // direction words on demand (k_sweep16, DIRECTION WORDS ON DEMAND): the record variants, first pass
+    // only — a read that comes back because its final paths were not the picked ones stores every word the second time
+    o.dsel = o.spec && o.use_rec && spec_level == 0 && !opt.no_dsel;
+    { const int e = L / std::max(1, (int)opt.dsel_edge); o.dsel_lo = e; o.dsel_hi = L - 1 - e; }      // (an eighth of the rows at the end each sweep starts from)
+    o.rec_pen = p.base_rec_cost + (int)std::ceil(p.multi_rec_cost * 8.0f);
+    // -m 4 on a speculative bound (round 6): k_pick's path, k_opt0's score against it minus the margin as the bound the sweep retires
+    // paths against, direction words for the picked path only; k_verify4 sends a read whose best final score does not reach the bound
+    // (or whose best path is not the pick) to a second pass without any of it.  Packed rows, one wave per read, the default scores' sign
+    // conditions (gap entries <= 0: the hopeless bound counts on them).
+    o.spec4 = o.mode == RG_MODE_PATHWISE && !semi && use16 && o.gaps_nonpos && spec_level == 0 && !opt.no_spec;
+    // (the margin: a follower path's final score lies below its own alignment optimum — up to 180 at 1 kbp in config 4, where
+    // -m 8's search maximum rarely does: 2.5 x the -m 8 margin; RG_SPEC4_MARGIN_X10 scales it for experiments)
+    o.spec4_margin = o.spec_margin * opt.spec4_margin_x10 / 10;
+    o.retire4 = o.spec4 && opt.no_retire != 1;
+    o.dsel4 = o.spec4 && !opt.no_dsel;
+    o.order = !opt.no_order;
+    // (packed rows whenever the sweep runs packed: a third of the i32 form's instructions)
+    o.opt16 = use16;
+    // (packed 16-bit rows whenever the sweep ran packed: the same decisions, ~40 % fewer instructions; `layer_i32` keeps the
+    // i32 form for the tests)
+    o.layer16 = use16 && o.gaps_agree && !opt.layer_i32;
+    // (gather runs carry differences of two members' stored values: sweep16_admissible bounds every such difference)
+    o.gather_ok = use16 && !opt.no_gather;
+    // split tables: only where every run between the groups of a row is a register or a gather run of k_sweep16
+    o.use_split = o.gather_ok && !semi && C <= 16 && !opt.no_split;
+    // path retirement: the record pipelines of -m 8 (global) (round 5: the i32 sweep too — one wave, or stripes of <= 16 columns per lane)
+    o.retire = (use16 || nwv == 1 || C <= 16) && paths_ok && !semi && recomb && o.gaps_nonpos && opt.no_retire != 1;
+    o.retire_fwd = o.retire && opt.no_retire != 3;
+    o.retire_rev = o.retire && opt.no_retire != 2;
+    // (round 6: 16 Ki / 8 Ki records of 80 B to start with instead of 64 Ki / 32 Ki — 2 MB per read instead of 7.9; a read that needs
+    // more regrows the lists and the chunk runs again, once per handle; batches WITHOUT a speculative bound keep the old sizes: their
+    // forward lists hold tens of thousands of records per read, and 128-path tiles ran twice every time a tile's largest read outgrew
+    // the last one's.  Config 5 with the two-path pick: forward mean ~11 k)
+    o.fcap = (o.two_sweep && !o.use_rec) ? 1u << 20 : 1u << 15;
+    o.rcap = o.use_rec ? 1u << 16 : 1u << 19;
+    o.frec_cap = o.spec ? 1u << 14 : 1u << 16;
+    o.rrec_cap = o.spec ? 1u << 13 : 1u << 15;
+    return RG_OK;
+}
+
+void build_path_rows(const HostGraph& h, bool fwd, std::vector<int>& poff, std::vector<int>& prow, std::vector<int>& pslot) {
+    const std::vector<int32_t>& goff = fwd ? h.fgoff : h.rgoff;
+    const std::vector<GroupDesc>& groups = fwd ? h.fgroups : h.rgroups;
+    const int P = h.P, L = h.L;
+    std::vector<std::vector<std::pair<int, int>>> per(P);
+    for (int step = 1; step + 1 < L; ++step) {
+        const int i = fwd ? step : L - 1 - step;
+        for (int gi = goff[i]; gi < goff[i + 1]; ++gi)
+            for (int b = 0; b < 64; ++b)
+                if ((groups[gi].mask >> b) & 1) per[groups[gi].page * 64 + b].push_back({i, groups[gi].slot});
+    }
+    poff.assign(P + 1, 0);
+    prow.clear();
+    pslot.clear();
+    for (int k = 0; k < P; ++k) {
+        for (auto& e : per[k]) { prow.push_back(e.first); pslot.push_back(e.second); }
+        poff[k + 1] = (int)prow.size();
+    }
+}
+
+void build_kmer_table(const HostGraph& h, const std::vector<int>& po, const std::vector<int>& pr, std::vector<uint32_t>& keys,
+                      std::vector<unsigned long long>& masks) {
+    const int P = h.P;
+    const size_t NW = (size_t)((P + 63) / 64);
+    constexpr int K = 12;
+    size_t total = 0;
+    for (int k = 0; k < P; ++k) total += (size_t)std::max(0, po[k + 1] - po[k] - K + 1);
+    size_t size = 64;
+    while (size < 2 * total + 2) size <<= 1;
+    keys.assign(size, 0xffffffffu);
+    masks.assign(size * NW, 0ull);
+    for (int k = 0; k < P; ++k) {
+        unsigned key = 0;
+        int valid = 0;
+        for (int t = po[k]; t < po[k + 1]; ++t) {
+            const size_t c = std::string("ACGT").find(h.lnz[pr[t]]);
+            if (c == std::string::npos) { valid = 0; key = 0; continue; }
+            key = ((key << 2) | (unsigned)c) & 0xffffffu;
+            if (++valid < K) continue;
+            unsigned hsh = (key * 2654435761u) >> 8;
+            for (unsigned probe = 0;; ++probe) {
+                const size_t slot = (hsh + probe) & (size - 1);
+                if (keys[slot] == 0xffffffffu) keys[slot] = key;
+                if (keys[slot] == key) { masks[slot * NW + (size_t)(k >> 6)] |= 1ull << (k & 63); break; }
+            }
+        }
+    }
+}
+
+}  // namespace rg

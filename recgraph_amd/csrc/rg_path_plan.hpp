@@ -1,0 +1,80 @@
+// The decisions of the pathwise driver (rg_path_driver.hip) as data: which kernels a batch runs, on what geometry, with which
+// margins and list sizes.  Plain host arithmetic on (rg_params, graph sizes, longest read, Options, spec_level) — no HIP here, so
+// tests/c/plan_check.cpp states the routes without a GPU.  Also the per-graph host tables the driver uploads (rows of every
+// path, the 12-mer vote table) and the structs whose sizes the plan counts.
+#pragma once
+#include <cstddef>
+#include <vector>
+
+#include "rg_host.hpp"
+
+namespace rg {
+
+// per-read scalar state carried between the kernels of one batch
+struct ReadState {
+    uint32_t status;
+    int s0;            // best no-recombination score (seed of the search) / m4 best score
+    int seed_path;
+    int end_row;       // sink row of the chosen path
+    int end_row_best;  // semiglobal: row of the overall best last-column value
+    int fwd_path, rev_path, fen, rsn, rec_col, displacement;
+    float fscore;
+    int bound;         // integer lower bound of the final search maximum (>= s0), tightens the pruning
+    int sink_val[RG_MAXP];  // A[sink row][n][k]; semiglobal: best last-column value of path k over its rows >= 1
+    int trace_score;        // value of the forward layer where the traceback starts (written by k_layer)
+    int path_end_row[RG_MAXP];   // semiglobal: first row attaining sink_val[k] (ending_node, pathwise_alignment_recombination.rs:885-897)
+};
+
+// one entry of the recombination candidate lists: best member of (row, col) that can still matter
+struct Cand {
+    int row, col, val, path;
+};
+
+// the only HostGraph fields (and the longest read of the batch) the decisions read
+struct PathPlanInput {
+    int P, L, fslots, rslots, max_path_rows, max_n;
+};
+
+struct PathPlan {
+    // geometry: columns per lane, waves (column stripes) per read, padded columns, u32 words per (row, group) slot, ints per record
+    int C, nwv, wpad, dir_words, recw;
+    long long layer_stride, fdirs_stride, rdirs_stride;   // words per read: traceback decisions (2 bits per cell), direction words
+    size_t per_read;              // bytes of HBM work buffers per read without the candidate / record lists
+    int mode;                     // pipeline selector: the semiglobal modes run the kernels of -m 4 / -m 8 with the `semi` switches
+    bool semi;
+    int maxmatch;
+    bool gaps_nonpos;             // every gap entry <= 0 (then w[.][j] <= (n - j) * max match)
+    bool gaps_agree;              // ('-', b) == (b, '-') for every base: the walkers' L key vs the sweep's
+    int score_scale;
+    bool use16;                   // packed 16-bit rows (rg_sweep16.hip); implies one wave per read
+    bool two_sweep, use_rec, spec, pick_two, dsel, spec4, opt16, layer16;
+    bool retire, use_split, gather_ok;
+    bool retire_fwd, retire_rev;  // `retire` in the forward / reverse sweep of -m 8 (no_retire 3 / 2 keep one of them)
+    bool retire4, dsel4;          // -m 4 on its speculative bound: path retirement, direction words of the picked path only
+    bool order;                   // longest-first launch order of the sweeps' waves wherever paths retire
+    int spec_margin, spec4_margin, dsel_lo, dsel_hi, rec_pen;
+    unsigned fcap, rcap, frec_cap, rrec_cap;    // what the lists of a handle start with (regrown on overflow)
+
+    // ... with candidate lists of fcap / rcap entries and record lists of frec_cap / rrec_cap records
+    size_t per_read_all(unsigned fcap_, unsigned rcap_, unsigned frec_cap_, unsigned rrec_cap_) const {
+        if (mode != RG_MODE_RECOMBINATION) return per_read;
+        return per_read + (size_t)fcap_ * sizeof(Cand) + (size_t)rcap_ * (sizeof(Cand) + 4) +
+               (use_rec ? (size_t)(frec_cap_ + rrec_cap_) * recw * 4 : 0);
+    }
+};
+
+// spec_level: 0 = the batch itself; 1 = the reads whose speculation failed, once more with a generous margin; 2 = what fails
+// even that, with the provable bound.  RG_ERR_ARG / RG_ERR_CAPACITY (through fail()) for batches the kernels cannot take.
+int plan_pathwise(const rg_params& p, const PathPlanInput& in, const Options& opt, int spec_level, PathPlan& out);
+
+bool sweep16_admissible(const DevScores& sc, int max_path_rows, int max_n, int C);
+
+// rows of every path in program order (rows of path k: prow[poff[k] .. poff[k + 1])), with the direction-word slot of the
+// group holding the path
+void build_path_rows(const HostGraph& h, bool fwd, std::vector<int>& poff, std::vector<int>& prow, std::vector<int>& pslot);
+// 12-mers of every path -> paths that contain them (k_pick votes with it): open addressing, 24-bit keys or 0xffffffff; (P + 63) / 64
+// words of path bits per entry; keys.size() is a power of two.  poff / prow: the FORWARD lists of build_path_rows.
+void build_kmer_table(const HostGraph& h, const std::vector<int>& poff, const std::vector<int>& prow, std::vector<uint32_t>& keys,
+                      std::vector<unsigned long long>& masks);
+
+}  // namespace rg

@@ -11,18 +11,7 @@
 #include <utility>
 #include <vector>
 
-#include <cstdlib>
-
 namespace rg {
-
-std::atomic<int>& retire_shift_option() {
-    static std::atomic<int> v{[] {
-        const char* e = getenv("RG_RETIRE_SHIFT");
-        const int k = e ? atoi(e) : RG_SWEEP16_RETIRE_SHIFT;
-        return k < 2 ? 2 : (k > 12 ? 12 : k);
-    }()};
-    return v;
-}
 
 void build_step_tables(const HostGraph& h, bool forward, bool want_split, StepTables& T) {
     const int L = h.L;
@@ -223,7 +212,7 @@ auto lead_table = [&](const std::vector<StepRec>& recs) {
 };
 
     steps(goff_, groups_, forward, T.plain);
-    T.retire_shift = retire_shift_option().load();
+    T.retire_shift = options().retire_shift;
     T.members = 0;
     for (const StepRec& r : T.plain) T.members += (unsigned long long)(__builtin_popcount((unsigned)r.z) + __builtin_popcount((unsigned)r.w));
     T.lead_plain.clear();

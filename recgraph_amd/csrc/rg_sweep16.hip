@@ -393,7 +393,7 @@ __global__ __launch_bounds__(64, SWEEP16_WAVES) void k_sweep16(SweepArgs a) {
     const int PR_RVL = P, PR_NPROF = P + 1;     // pseudo-rows behind the P rolling rows (same [lane][r] layout)
     if (lane < 36) sct[lane] = a.sc.t[lane];
     __syncthreads();
-    // uniform gap cost (checked by the launcher, sweep16_admissible: score(b, '-') is the same for b = A, C, G, T, N): the
+    // uniform gap cost (checked by the driver's plan, sweep16_admissible in rg_path_plan.cpp: score(b, '-') is the same for b = A, C, G, T, N): the
     // z-space slope — and, being the same table column, what a U move adds in EVERY row (g_i below): no per-row lookup
     const int gcost = __builtin_amdgcn_readfirstlane(sct[GAP]);
     for (int e = lane; e < 5 * 64; e += WAVE) {
@@ -1668,42 +1668,6 @@ __global__ __launch_bounds__(64, SWEEP16_WAVES) void k_sweep16(SweepArgs a) {
     }
 }
 
-// Host-side admission test: uniform gap cost and every STORED value provably inside the 16-bit budget.
-// What the rows hold is z = A - c * g (c: column, g: the gap cost), not A.  A row starts at z = 0 and changes only through
-//   U: z + g_i (= z + g, the gap column is uniform)        D: z_diagonal + (s - g)        L: z_left (a copy)
-// — whoever chose the move (members follow their alpha), every cell is its chain's start plus one such step per move.  So after
-// at most `rows` graph rows and n read bases
-//   zlo = -(rows + 2) * |g| - (n + 2) * max(0, g - min s)   <=   z   <=   (n + 2) * max(0, max s - g) = zhi
-// (round 4 bounded |A| <= (rows + n) * max|entry| <= 24 000 instead, which refused -X 6 at 1 kbp and every read longer than
-// ~1.2 kbp: the all-gap corner of A is -(rows + n) |g|, the same corner of z only -rows |g|).  Required:
-//   * zlo above the "minus infinity" of a 16-bit lane (NEG16 = -30 000) with a step of head-room, zhi below +29 000;
-//   * zhi - zlo <= 32 000: every difference of two stored values (direction masks from the sign of d - max(d, u), the
-//     gather runs' member deltas) fits a signed half;
-//   * |A| <= (rows + n + 2) * max|entry| <= 32 000: outputs convert back (A = z + c g) inside key << 16 arithmetic;
-//   * gap entries <= 0: the border column (c = 0: z = A = i * g) then holds values <= 0, so that d - max(d, u) of lane 0's
-//     column 0 (d = NEG16 + s, u = the border value) stays above -32768 and the U mask keeps its sign.
-bool sweep16_admissible(const DevScores& sc, int max_path_rows, int max_n, int C) {
-    for (int b = 1; b < 5; ++b) if (sc.t[b * 6 + 5] != sc.t[5]) return false;
-    for (int b = 0; b < 5; ++b) if (sc.t[b * 6 + 5] > 0 || sc.t[5 * 6 + b] > 0) return false;
-    long long maxabs = 0, smin = INT32_MAX, smax = INT32_MIN;
-    for (int x = 0; x < 6; ++x)
-        for (int y = 0; y < 6; ++y) {
-            if (x == 5 && y == 5) continue;
-            const long long v = sc.t[x * 6 + y];
-            maxabs = std::max(maxabs, v < 0 ? -v : v);
-            if (x < 5 && y < 5) { smin = std::min(smin, v); smax = std::max(smax, v); }
-        }
-    if (maxabs > 1000) return false;
-    const long long g = sc.t[5];                 // <= 0
-    const long long rows = max_path_rows + 2, n = max_n + 2;
-    const long long zlo = rows * g - n * std::max(0ll, g - smin);
-    const long long zhi = n * std::max(0ll, smax - g);
-    if (zlo < -29000 || zhi > 29000 || zhi - zlo > 32000) return false;
-    if ((rows + n) * maxabs > 32000) return false;                 // |A| of every cell
-    if ((long long)(C / 2 + 2) * maxabs > 2000) return false;
-    return true;
-}
-
 // Forward (row, lane) records -> Cand list, filtered with the final bound (the same test k_search applies).
 template <int C>
 __global__ __launch_bounds__(256) void k_expand(ExpandArgs a) {
@@ -1998,7 +1962,7 @@ void launch_layer16(const LayerArgs& a, int nreads, int C, hipStream_t s) {
 // column, ~170 wave-instructions per row; this one ~55).  Same job: the plain NW score of the read against the rows of one
 // path — path 0 (the provable bound), the picked path, or p1's rows up to X followed by p2's (two-path picks) — in the
 // sweep's z-space with the sweep's score profile.  Only the final value leaves the kernel; no masks, no direction words.
-// Batches the packed sweep admits (sweep16_admissible: every stored value fits; the driver sends the others to k_opt0).
+// Batches the packed sweep admits (sweep16_admissible, rg_path_plan.cpp: every stored value fits; the driver sends the others to k_opt0).
 template <int C>
 __global__ __launch_bounds__(64) void k_opt0_16(Opt0Args a) {
     constexpr int H = C / 2;

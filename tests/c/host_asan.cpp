@@ -1,5 +1,5 @@
 // Sanitizer harness for the host-only, text-eating code of librecgraph_hip (`make -C recgraph_amd/csrc asan`: g++
-// -fsanitize=address,undefined over rg_graph.cpp, rg_gaf.cpp, rg_reads.cpp — no HIP, no GPU).  Feeds it hand-made
+// -fsanitize=address,undefined over rg_graph.cpp, rg_gaf.cpp, rg_reads.cpp, rg_steps.cpp, rg_path_plan.cpp — no HIP, no GPU).  Feeds it hand-made
 // malformed inputs and seeded byte / line mutations of valid GFA and FASTA text: every call must come back with a
 // status code (never crash, never trip ASan / UBSan).  Usage: host_asan graph.gfa reads.fa [iterations] [seed]
 #include <cstdio>
@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "rg_host.hpp"
+#include "rg_path_plan.hpp"
 
 using namespace rg;
 
@@ -33,6 +34,16 @@ static void try_gfa(const std::string& t) {
         for (int which = 0; which < 8; ++which) (void)dump_graph(g, which);     // walks every flattened array
         // the step tables of the pathwise sweeps, their split form and the path-retirement tables (rg_steps.cpp)
         for (int which = 30; which <= 34; ++which) (void)dump_graph(g, which);
+        // what the pathwise driver uploads besides: the rows of every path and the 12-mer vote table (rg_path_plan.cpp)
+        if (g.has_path) {
+            std::vector<int> po, pr, ps;
+            std::vector<uint32_t> keys;
+            std::vector<unsigned long long> masks;
+            build_path_rows(g, false, po, pr, ps);
+            build_path_rows(g, true, po, pr, ps);
+            build_kmer_table(g, po, pr, keys, masks);
+            if (keys.empty() || (keys.size() & (keys.size() - 1)) || masks.size() != keys.size() * (size_t)((g.P + 63) / 64)) { fprintf(stderr, "12-mer table shape\n"); abort(); }
+        }
     } else {
         ++bad_gfa;
     }

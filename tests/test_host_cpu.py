@@ -109,8 +109,19 @@ def test_duplicate_segment_ids_are_rejected(rg):
         api.Graph.from_gfa_text("S\t1\tA\nS\t2\tC\nS\t3\tG\nS\t2\tT\nL\t1\t+\t2\t+\t0M\nL\t2\t+\t3\t+\t0M\n")
 
 
+def _option_table():
+    """(name, env, kind, lo, hi, default) rows of RG_OPTIONS (recgraph_amd/csrc/rg_host.hpp), the one table of the switches."""
+    hpp = open(os.path.join(ROOT, "recgraph_amd", "csrc", "rg_host.hpp")).read()
+    consts = {"RG_SWEEP16_RETIRE_SHIFT": 8, "__builtins__": {}}
+    rows = []
+    for name, env, kind, lo, hi, default in re.findall(r'^\s*X\((\w+), "(\w+)", ([BI]), ([^,]+), ([^,]+), ([^,)]+)\)', hpp, re.M):
+        rows.append((name, env, kind, eval(lo, consts), eval(hi, consts), eval(default, consts)))
+    return rows
+
+
 def test_option_switches(rg):
-    """rg_set_option / rg_get_option: the diagnostic switches the GPU tests flip (no getenv on the run path)."""
+    """rg_set_option / rg_get_option: the diagnostic switches the GPU tests flip (no getenv on the run path).  Every row of the
+    option table round-trips, a switch normalises to 0 / 1, an integer is clamped at both ends of its range."""
     from recgraph_amd import _lib, api
     lib = _lib.load()
     for name in ("sweep_i32", "three_sweeps", "no_frec", "debug"):
@@ -121,9 +132,42 @@ def test_option_switches(rg):
     api.set_option("chunk_reads", 2048)
     assert lib.rg_get_option(b"chunk_reads") == 2048
     api.set_option("chunk_reads", 0)
-    assert lib.rg_get_option(b"nope") == -1
-    with pytest.raises(_lib.RecGraphError):
-        api.set_option("nope", 1)
+    table = _option_table()
+    assert len(table) == 20 and {"spec4_margin_x10", "retire_shift", "dsel_edge", "no_dsel"} <= {r[0] for r in table}
+    get = lambda n: lib.rg_get_option(n.encode())                      # noqa: E731
+    for name, env, kind, lo, hi, default in table:
+        assert env == "RG_" + name.upper() and lo <= default <= hi
+        assert get(name) == default, name
+        if kind == "B":
+            assert (lo, hi) == (0, 1)
+            for v, exp in ((1, 1), (7, 1), (-3, 1), (0, 0)):
+                api.set_option(name, v)
+                assert get(name) == exp, (name, v)
+        else:
+            for v, exp in ((lo, lo), (lo - 1, lo), (-2 ** 40, lo), (hi, hi), (hi + 1, hi), (2 ** 40, hi), ((lo + hi) // 2, (lo + hi) // 2)):
+                api.set_option(name, v)
+                assert get(name) == exp, (name, v)
+        api.set_option(name, default)
+        assert get(name) == default
+    for gone in ("nope", "sweep_prio", "lb_bonus"):
+        assert get(gone) == -1
+        with pytest.raises(_lib.RecGraphError) as e:
+            api.set_option(gone, 1)
+        assert e.value.code == -1 and "unknown option " + gone in str(e.value)
+
+
+def test_option_defaults_from_the_environment(rg):
+    """The environment variables of the table are read once, in a fresh process: a switch counts unless empty or "0", an integer
+    goes through the clamp of its row."""
+    import subprocess
+    import sys
+    code = ("import json; from recgraph_amd import _lib; lib = _lib.load();"
+            "print(json.dumps({n: lib.rg_get_option(n.encode()) for n in ('no_spec', 'debug', 'no_frec', 'spec_margin', 'retire_shift', 'spec4_margin_x10', 'chunk_reads')}))")
+    env = dict(os.environ, RG_NO_SPEC="1", RG_DEBUG="0", RG_NO_FREC="", RG_SPEC_MARGIN="77", RG_RETIRE_SHIFT="99", RG_SPEC4_MARGIN_X10="30",
+               PYTHONPATH=ROOT)
+    env.pop("RG_CHUNK_READS", None)
+    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, check=True, cwd=ROOT).stdout
+    assert json.loads(out) == {"no_spec": 1, "debug": 0, "no_frec": 0, "spec_margin": 77, "retire_shift": 12, "spec4_margin_x10": 30, "chunk_reads": 0}
 
 
 def test_graphs_that_are_not_topological_are_rejected(rg):
