@@ -69,8 +69,8 @@ typedef struct rg_params {
     float rec_band_width;  /* -B                                                              */
     int32_t amb_mode;      /* POA modes, `-s true` retry (main.rs:82-106): bit 0 = node ids of the reversed handle
                               order (utils.rs:144-165 with amb_mode), bit 1 = strand '-' (gaf_output.rs:225).
-                              Pathwise modes: bit 2 = RG_AMB_BOTH_STRANDS (below); bits 0 and 1 are refused there,
-                              bit 2 is refused in the POA modes                                                     */
+                              Pathwise modes: bit 2 = RG_AMB_BOTH_STRANDS, bit 3 = RG_AMB_STRAND_VOTE (below; bit 3 only
+                              together with bit 2); bits 0 and 1 are refused there, bits 2 and 3 in the POA modes    */
 } rg_params;
 
 /*
@@ -95,6 +95,32 @@ typedef struct rg_params {
  * under their own.  For the POA modes the way to both strands is rg_stream_opts.amb_strand (`-s true`).
  */
 #define RG_AMB_BOTH_STRANDS 4
+
+/*
+ * RG_AMB_STRAND_VOTE (bit 3 of rg_params.amb_mode; valid only together with bit 2, so amb_mode = 12, and only in modes
+ * 4, 5, 8, 9): RG_AMB_BOTH_STRANDS with the FIRST strand picked per read by a 12-mer vote, so that a read of the other
+ * strand is not first aligned as a hopeless forward read.  The vote is a pure function of (graph, read); the rule, a
+ * second one beside the exact rule above:
+ *   1. VOTES.  K = 12; for a read of n bases npos = n - 11.  npos < 1: both votes are 0.  Otherwise step =
+ *      ceil(npos / 256) and the samples are the windows that start at t * step for t * step < npos (at most 256).  V_f =
+ *      the number of sampled windows of the read that consist of A/C/G/T only and occur as a 12-mer of some path of the
+ *      graph (exact set membership).  V_r = the same count for the reverse complement of the read, sampled in the
+ *      reverse complement's own coordinates.  A read with RG_READ_BAD_BASE votes 0 / 0.
+ *   2. FIRST STRAND.  '-' iff V_r > V_f; ties go to '+'.
+ *   3. PASS A aligns every read on its first strand (one pass of the pipeline).
+ *   4. PASS B.  A read goes to pass B iff its pass-A status has neither RG_READ_BAD_BASE nor RG_READ_WOULD_PANIC and its
+ *      pass-A score (the printed score of rule 2 above) is < 0.  Pass B aligns the other strand.
+ *   5. CHOICE.  One strand aligned: that record.  Both aligned: the reverse record only if its score is STRICTLY greater;
+ *      ties keep forward, whichever strand went first.  A pass that yields no record never wins.
+ *   6. REPORTING as rule 5 above: strand column '-' for a chosen reverse record, and every accessor and a stream's text,
+ *      score and status describe the chosen record.
+ *   7. WHERE IT DIFFERS FROM THE EXACT RULE: only for a read that goes reverse first and whose reverse score is >= 0.  Its
+ *      forward strand is then never looked at, while RG_AMB_BOTH_STRANDS alone would have kept the forward record
+ *      whenever forward >= 0 or forward >= reverse.
+ * k_strand_vote and k_strand_orient appear in the kernel statistics under their own names; both cell counters include
+ * pass B.  Bit 3 alone, and bit 3 in a POA mode, are RG_ERR_ARG.
+ */
+#define RG_AMB_STRAND_VOTE 8
 
 /* Fill *p with the CLI defaults (args_parser.rs:3-147: M=2 X=4 O=4 E=2 R=4 r=0.1 B=1 b=1 f=0.01). */
 void rg_params_default(rg_params* p, int32_t mode);
@@ -300,7 +326,8 @@ typedef struct rg_stream_opts {
                                      exec calls come before it.  Not together with keep_records.
                                      2: the same for a POA stream; for a stream of a pathwise mode it sets
                                      RG_AMB_BOTH_STRANDS on the stream's handles (our extension, see there; the kept
-                                     record is the chosen one, so keep_records is fine)                          */
+                                     record is the chosen one, so keep_records is fine)
+                                     3: as 2, and on a pathwise stream RG_AMB_STRAND_VOTE as well                */
     int64_t max_undelivered_bytes;/* > 0: see "Memory" above                                                     */
 } rg_stream_opts;
 typedef struct rg_stream_result {

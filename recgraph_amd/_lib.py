@@ -42,6 +42,7 @@ class Params(C.Structure):
 
 
 AMB_BOTH_STRANDS = 4     # RG_AMB_BOTH_STRANDS (include/recgraph_hip.h): bit 2 of Params.amb_mode, pathwise modes
+AMB_STRAND_VOTE = 8      # RG_AMB_STRAND_VOTE: bit 3, only together with bit 2 — the first strand by a 12-mer vote
 
 
 def library_path():

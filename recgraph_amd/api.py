@@ -49,18 +49,20 @@ READ_BAND_WARNING, READ_BAND_NOT_ENOUGH, READ_WOULD_PANIC, READ_BAD_BASE = 1, 2,
 # rg_params.amb_mode bit 2 (RG_AMB_BOTH_STRANDS, include/recgraph_hip.h): both strands inside a pathwise batch — an extension
 # the reference does not have (its `-s true` covers modes 0-3 only)
 AMB_BOTH_STRANDS = _lib.AMB_BOTH_STRANDS
+# bit 3 (RG_AMB_STRAND_VOTE), only together with bit 2: the strand that is aligned first is picked per read by a 12-mer vote
+AMB_STRAND_VOTE = _lib.AMB_STRAND_VOTE
 PATHWISE_MODES = (MODE_PATHWISE, MODE_PATHWISE_SEMI, MODE_RECOMBINATION, MODE_RECOMBINATION_SEMI)
 
 
-def _both_strands_kw(mode, both_strands, kw):
-    """``both_strands=True`` as the ``amb`` keyword of ``make_params``; refused outside the pathwise modes, where
-    ``amb_strand`` (``-s true``) is the way."""
-    if not both_strands:
+def _both_strands_kw(mode, both_strands, kw, strand_vote=False):
+    """``both_strands=True`` / ``strand_vote=True`` (which implies it) as the ``amb`` keyword of ``make_params``; refused
+    outside the pathwise modes, where ``amb_strand`` (``-s true``) is the way."""
+    if not both_strands and not strand_vote:
         return kw
     if mode not in PATHWISE_MODES:
-        raise _lib.RecGraphError(-1, "both_strands applies to the pathwise modes (4, 5, 8, 9) only: the POA modes align both "
-                                     "strands with amb_strand (`-s true`)")
-    return dict(kw, amb=(kw.get("amb") or 0) | AMB_BOTH_STRANDS)
+        raise _lib.RecGraphError(-1, "%s applies to the pathwise modes (4, 5, 8, 9) only: the POA modes align both "
+                                     "strands with amb_strand (`-s true`)" % ("strand_vote" if strand_vote else "both_strands"))
+    return dict(kw, amb=(kw.get("amb") or 0) | AMB_BOTH_STRANDS | (AMB_STRAND_VOTE if strand_vote else 0))
 
 
 # ----------------------------------------------------------------------------------------------
@@ -505,10 +507,11 @@ class Stream:
 
     def __init__(self, graph, params, device_ids=None, handles_per_device=0, tile_reads=0, format_threads=0,
                  seq_index_base=1, keep_records=False, no_text=False, spin_wait=False, max_queued_tiles=0,
-                 max_undelivered_bytes=0, amb_strand=False, both_strands=False):
+                 max_undelivered_bytes=0, amb_strand=False, both_strands=False, strand_vote=False):
         """``amb_strand``: ``-s true`` inside the workers (POA modes).  ``both_strands``: rg_stream_opts.amb_strand = 2 — for
         a pathwise mode both strands inside every tile (RG_AMB_BOTH_STRANDS, our extension), for a POA mode the same as
-        ``amb_strand``.  ``max_queued_tiles`` / ``max_undelivered_bytes``:
+        ``amb_strand``.  ``strand_vote``: rg_stream_opts.amb_strand = 3 — ``both_strands`` with the first strand of every
+        read picked by a 12-mer vote (RG_AMB_STRAND_VOTE).  ``max_queued_tiles`` / ``max_undelivered_bytes``:
         bounds on what the stream holds (pushes / workers wait): the pushing and the consuming side must then be
         different threads, or one thread that drains whenever ``pending`` says so."""
         lib = _lib.load()
@@ -517,7 +520,7 @@ class Stream:
         lib.rg_stream_opts_default(C.byref(o))
         o.handles_per_device, o.tile_reads, o.format_threads = handles_per_device, tile_reads, format_threads
         o.seq_index_base, o.keep_records, o.no_text, o.spin_wait = seq_index_base, int(keep_records), int(no_text), int(spin_wait)
-        o.max_queued_tiles, o.max_undelivered_bytes, o.amb_strand = max_queued_tiles, max_undelivered_bytes, 2 if both_strands else int(amb_strand)
+        o.max_queued_tiles, o.max_undelivered_bytes, o.amb_strand = max_queued_tiles, max_undelivered_bytes, 3 if strand_vote else 2 if both_strands else int(amb_strand)
         devs = (C.c_int32 * len(device_ids))(*device_ids) if device_ids is not None else None
         self._h = C.c_void_p()
         check(lib.rg_stream_create(graph._h, C.byref(params), devs, len(device_ids) if device_ids is not None else 0,
@@ -625,14 +628,16 @@ def set_option(name, value):
 
 
 def align_stream(graph, reads, names=None, mode=MODE_GLOBAL_POA, seq_index_base=1, device_ids=None, handles_per_device=0,
-                 tile_reads=0, amb_strand=False, both_strands=False, **kw):
+                 tile_reads=0, amb_strand=False, both_strands=False, strand_vote=False, **kw):
     """``align_batch`` through the streaming engine (every visible GPU unless ``device_ids`` says otherwise): returns the
     per-read texts and status bits in input order.  ``amb_strand``: the ``-s true`` retry inside the library.
-    ``both_strands``: pathwise modes, both strands inside every tile (RG_AMB_BOTH_STRANDS)."""
-    if both_strands and mode not in PATHWISE_MODES:
-        _both_strands_kw(mode, True, kw)
+    ``both_strands``: pathwise modes, both strands inside every tile (RG_AMB_BOTH_STRANDS); ``strand_vote``: the same with
+    the first strand picked by a 12-mer vote (RG_AMB_STRAND_VOTE)."""
+    if (both_strands or strand_vote) and mode not in PATHWISE_MODES:
+        _both_strands_kw(mode, both_strands, kw, strand_vote)
     st = Stream(graph, make_params(mode, **kw), device_ids=device_ids, handles_per_device=handles_per_device,
-                tile_reads=tile_reads, seq_index_base=seq_index_base, amb_strand=amb_strand, both_strands=both_strands)
+                tile_reads=tile_reads, seq_index_base=seq_index_base, amb_strand=amb_strand, both_strands=both_strands,
+                strand_vote=strand_vote)
     st.push(reads, names)
     st.finish()
     texts, status = [], []
@@ -654,7 +659,8 @@ def rev_and_compl(read):
         raise _lib.RecGraphError(-1, "wrong char: %s, unable to rev&compl" % ex.args[0])
 
 
-def align_batch(graph, reads, names=None, mode=MODE_GLOBAL_POA, seq_index_base=1, amb_strand=False, both_strands=False, **kw):
+def align_batch(graph, reads, names=None, mode=MODE_GLOBAL_POA, seq_index_base=1, amb_strand=False, both_strands=False,
+                strand_vote=False, **kw):
     """The reference's per-read loop as one device batch.  Returns, per read, exactly the text the
     reference prints on stdout (warning lines + GAF line), and the per-read status bits.
 
@@ -664,8 +670,12 @@ def align_batch(graph, reads, names=None, mode=MODE_GLOBAL_POA, seq_index_base=1
 
     ``both_strands`` (pathwise modes only; not in the reference): reads whose forward score is negative are aligned again as
     their reverse complement inside the same device batch, and a reverse record that scores strictly higher replaces the
-    forward one with strand ``-`` (RG_AMB_BOTH_STRANDS in include/recgraph_hip.h)."""
-    kw = _both_strands_kw(mode, both_strands, kw)
+    forward one with strand ``-`` (RG_AMB_BOTH_STRANDS in include/recgraph_hip.h).
+
+    ``strand_vote`` (implies ``both_strands``): the strand that is aligned first is picked per read by a vote of its 12-mers
+    against the paths', so a read of the other strand is not aligned forward first; a read that goes reverse first and
+    scores >= 0 there never has its forward strand looked at (RG_AMB_STRAND_VOTE, the rule in include/recgraph_hip.h)."""
+    kw = _both_strands_kw(mode, both_strands, kw, strand_vote)
     p = make_params(mode, **kw)
     b = Batch(graph, reads, p)
     b.run()
@@ -703,11 +713,12 @@ def align_batch(graph, reads, names=None, mode=MODE_GLOBAL_POA, seq_index_base=1
     return texts, status
 
 
-def align_batch_multi(graph, reads, names=None, mode=MODE_GLOBAL_POA, seq_index_base=1, device_ids=None, both_strands=False, **kw):
+def align_batch_multi(graph, reads, names=None, mode=MODE_GLOBAL_POA, seq_index_base=1, device_ids=None, both_strands=False,
+                      strand_vote=False, **kw):
     """``align_batch`` over several GPUs behind one C call (``rg_align_batch_multi``: the streaming engine, one
     results-only shard per tile; ``device_ids`` None = every visible device).  Same return value; no ``-s`` retry;
-    ``both_strands`` as in ``align_batch``."""
-    kw = _both_strands_kw(mode, both_strands, kw)
+    ``both_strands`` and ``strand_vote`` as in ``align_batch``."""
+    kw = _both_strands_kw(mode, both_strands, kw, strand_vote)
     n = len(reads)
     names = names or ["read%d" % i for i in range(n)]
     m = MultiBatch(graph, reads, make_params(mode, **kw), device_ids=device_ids)

@@ -59,6 +59,9 @@ def build_parser():
     p.add_argument("--both-strands", action="store_true", dest="both_strands",
                    help="modes 4, 5, 8, 9 (not a flag of the reference): reads that score below 0 are aligned again as their reverse "
                         "complement; a strictly better reverse record is written with strand '-'")
+    p.add_argument("--strand-vote", action="store_true", dest="strand_vote",
+                   help="modes 4, 5, 8, 9 (not a flag of the reference; implies --both-strands): the strand that is aligned first is "
+                        "picked per read by a vote of its 12-mers against the paths'")
     p.add_argument("--scalar", action="store_true", help="-m 0 / -m 1 with the non-AVX2 path of the reference")
     p.add_argument("--devices", default="", help="comma-separated HIP device ids (default: every visible device)")
     p.add_argument("--handles", type=int, default=0, help="batch handles per device (default 3)")
@@ -82,8 +85,11 @@ def main(argv=None):
     if a.alignment_mode not in (0, 1, 2, 3, 4, 5, 8, 9):
         raise SystemExit("Alignment mode must be in [0..5] or [8, 9]")   # main.rs:315-317
     amb = a.amb_strand == "true" and a.alignment_mode in (0, 1, 2, 3)     # modes 4+ ignore -s (main.rs:254-313)
+    if a.strand_vote and a.alignment_mode in (0, 1, 2, 3):
+        raise SystemExit("--strand-vote applies to modes 4, 5, 8 and 9: for modes 0-3 use `-s true`")
     if a.both_strands and a.alignment_mode in (0, 1, 2, 3):
         raise SystemExit("--both-strands applies to modes 4, 5, 8 and 9: for modes 0-3 use `-s true`")
+    a.both_strands = a.both_strands or a.strand_vote
     if a.matrix in ("none",):
         scores = api.create_score_matrix_i32(a.match_score, -a.mismatch_score)   # args_parser.rs:155
     else:
@@ -124,7 +130,7 @@ def main(argv=None):
     import threading
     devs = [int(x) for x in a.devices.split(",")] if a.devices else None
     st = api.Stream(g, api.make_params(mode, **kw), device_ids=devs, handles_per_device=a.handles, tile_reads=a.tile,
-                    amb_strand=amb, both_strands=a.both_strands, max_queued_tiles=a.queue, max_undelivered_bytes=a.hold_mb << 20)
+                    amb_strand=amb, both_strands=a.both_strands, strand_vote=a.strand_vote, max_queued_tiles=a.queue, max_undelivered_bytes=a.hold_mb << 20)
     tp = mark("stream_create", tp)
     feed_err = []
 

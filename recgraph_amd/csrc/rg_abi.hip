@@ -504,6 +504,8 @@ static int load_reads(rg_batch* b, const char* reads, const int64_t* read_off, i
             (rc = b->d_rc.alloc(total + 64)) || (rc = b->d_rcbad.alloc((size_t)nreads)) || (rc = b->d_rec2.alloc((size_t)nreads)) ||
             (rc = b->d_ops2.alloc((size_t)nreads * b->ops_stride)) || (rc = b->h_ssum.alloc(2)))
             return rc;
+        if ((p->amb_mode & RG_AMB_STRAND_VOTE) && ((rc = b->d_first_rev.alloc((size_t)nreads)) || (rc = b->d_pa.alloc(total + 64))))
+            return rc;
     }
     if (is_poa(mode)) {
         if ((rc = b->d_oprows.alloc((size_t)nreads * b->ops_stride))) return rc;
@@ -545,7 +547,10 @@ int32_t rg_batch_create(const rg_graph* gc, const rg_params* p, const char* read
     if ((mode == RG_MODE_GAP_POA || mode == RG_MODE_GLOBAL_POA_SCALAR || mode == RG_MODE_LOCAL_POA_SCALAR ||
          mode == RG_MODE_GAP_LOCAL_POA) && g->h.L > 65536)
         return fail(RG_ERR_GRAPH, "rows >= 65536 are truncated by the reference's u16 path cells (bitfield_path.rs:41)");
-    if (p->amb_mode & ~7) return fail(RG_ERR_ARG, "amb_mode: only bits 0, 1 and 2 are defined");
+    if (p->amb_mode & ~15) return fail(RG_ERR_ARG, "amb_mode: only bits 0 to 3 are defined");
+    if ((p->amb_mode & RG_AMB_STRAND_VOTE) && (is_poa(mode) || !(p->amb_mode & RG_AMB_BOTH_STRANDS)))
+        return fail(RG_ERR_ARG, "RG_AMB_STRAND_VOTE picks the first strand of RG_AMB_BOTH_STRANDS: it is valid only together with that "
+                                "bit (amb_mode = 12), in the pathwise modes");
     if ((p->amb_mode & RG_AMB_BOTH_STRANDS) && is_poa(mode))
         return fail(RG_ERR_ARG, "RG_AMB_BOTH_STRANDS applies to the pathwise modes only: the POA modes align both strands through "
                                 "rg_stream_opts.amb_strand (`-s true`, main.rs:82,132,188,229)");
@@ -749,19 +754,39 @@ int rg_run_pathwise(rg_batch* b) {
     // what this handle already holds counts towards its share of the device
     unsigned long long c[2] = {0, 0};
     b->pw.spin_wait = b->spin_wait;
-    int rc = path_driver_run(h, gd, b->p, b->pw, b->in.reads, b->in.off, b->in.bad, (int)b->nreads, b->max_n, b->d_rec.p,
-                             b->d_ops.p, b->ops_stride, b->d_cells.p, b->stream, b->mem_budget, c, b->stats, 0);
-    if (rc) return rc;
+    const int n = (int)b->nreads;
+    const bool vote = (b->p.amb_mode & RG_AMB_STRAND_VOTE) != 0;
+    Timed T(b);
+    int rc;
+    // the reads of the first pass: as given, or (RG_AMB_STRAND_VOTE, rg_strand_vote.hip) each on the strand its 12-mers vote
+    // for, at the same offsets; no host synchronisation in front of the pass
+    const uint8_t* reads_a = b->in.reads;
+    if (vote) {
+        const uint32_t* keys = nullptr;
+        unsigned table_mask = 0;
+        if ((rc = path_driver_vote_table(h, b->pw, &keys, &table_mask))) return rc;
+        b->stats.clear();
+        StrandVoteArgs va{b->in.reads, b->in.off, b->in.bad, keys, table_mask, b->d_first_rev.p};
+        if ((rc = T.run("k_strand_vote", [&] { launch_strand_vote(va, n, b->stream); }))) return rc;
+        StrandOrientArgs oa{b->in.reads, b->in.off, b->d_first_rev.p, b->d_pa.p};
+        if ((rc = T.run("k_strand_orient", [&] { launch_strand_orient(oa, n, b->stream); }))) return rc;
+        reads_a = b->d_pa.p;
+        KernelStats st1;
+        if ((rc = path_driver_run(h, gd, b->p, b->pw, reads_a, b->in.off, b->in.bad, n, b->max_n, b->d_rec.p, b->d_ops.p, b->ops_stride,
+                                  b->d_cells.p, b->stream, b->mem_budget, c, st1, 0)))
+            return rc;
+        for (auto& e : st1) add_stat(b->stats, e.name, e.ms, e.launches);
+    } else if ((rc = path_driver_run(h, gd, b->p, b->pw, b->in.reads, b->in.off, b->in.bad, n, b->max_n, b->d_rec.p, b->d_ops.p,
+                                     b->ops_stride, b->d_cells.p, b->stream, b->mem_budget, c, b->stats, 0)))
+        return rc;
     b->cells = c[0];
     b->cells_performed = c[1];
     if (!(b->p.amb_mode & RG_AMB_BOTH_STRANDS)) return RG_OK;
-    // ---- RG_AMB_BOTH_STRANDS (rg_strand.hip): the qualifying reads once more, reverse-complemented, in the same work buffers ----
-    const int n = (int)b->nreads;
+    // ---- RG_AMB_BOTH_STRANDS (rg_strand.hip): the qualifying reads once more, on the other strand, in the same work buffers ----
     const int recomb = b->p.mode == RG_MODE_RECOMBINATION || b->p.mode == RG_MODE_RECOMBINATION_SEMI ? 1 : 0;
-    Timed T(b);
-    StrandGateArgs ga{b->d_rec.p, b->in.off, n, recomb, b->d_sidx.p, b->d_rcoff.p, b->d_ssum.p};
+    StrandGateArgs ga{b->d_rec.p, b->in.off, n, recomb, b->d_sidx.p, b->d_rcoff.p, b->d_ssum.p, vote ? b->d_first_rev.p : nullptr};
     if ((rc = T.run("k_strand_gate", [&] { launch_strand_gate(ga, b->stream); }))) return rc;
-    RevcompArgs ra{b->in.reads, b->in.off, b->d_sidx.p, b->d_rcoff.p, b->d_ssum.p, b->d_rc.p};
+    RevcompArgs ra{reads_a, b->in.off, b->d_sidx.p, b->d_rcoff.p, b->d_ssum.p, b->d_rc.p};
     if ((rc = T.run("k_revcomp", [&] { launch_revcomp(ra, n, b->stream); }))) return rc;
     HIPCHK(hipMemcpyAsync(b->h_ssum.p, b->d_ssum.p, 2 * sizeof(int), hipMemcpyDeviceToHost, b->stream));
     if ((rc = T.collect())) return rc;

@@ -190,6 +190,9 @@ struct rg_batch {
     DevBuf<uint8_t> d_rc, d_rcbad, d_ops2;
     DevBuf<DevRecord> d_rec2;
     PinBuf<int> h_ssum;
+    // RG_AMB_STRAND_VOTE (rg_strand_vote.hip): per read, 1 = the first pass aligns the reverse complement; the first pass's
+    // read buffer (the reads at their own offsets, each as given or reverse-complemented)
+    DevBuf<uint8_t> d_first_rev, d_pa;
     // host results
     std::vector<DevRecord> rec;
     std::vector<uint8_t> ops;

@@ -103,4 +103,8 @@ int path_driver_run(const HostGraph& h, const PathGraphDev& gd, const rg_params&
                     long long ops_stride, unsigned long long* d_cells, hipStream_t stream, size_t mem_budget,
                     unsigned long long* cells_out, KernelStats& stats, int spec_level);
 
+// The 12-mer table of the paths that `w` holds for k_pick (built with the handle's other per-graph tables on first use):
+// its keys and slot mask, for a vote that runs before the first path_driver_run (RG_AMB_STRAND_VOTE, rg_strand_vote.hip).
+int path_driver_vote_table(const HostGraph& h, PathWork& w, const uint32_t** keys, unsigned* table_mask);
+
 }  // namespace rg

@@ -142,7 +142,6 @@ struct Run {
     const unsigned* need() const { return reinterpret_cast<const unsigned*>(w.h_sum + 1); }
     unsigned nretry() const { return (plan.spec || plan.spec4) ? need()[4] : 0u; }
 
-    int ensure_tables();
     int alloc_chunk(bool* oom);
     int enqueue_chunk();
     SweepArgs sweep_args() const;
@@ -160,7 +159,7 @@ struct Run {
 };
 
 // per-graph tables of a handle, uploaded once: rows of every path, the 12-mer vote table, the step tables of the sweeps
-int Run::ensure_tables() {
+int ensure_tables(const HostGraph& h, PathWorkImpl& w) {
     if (w.tables) return RG_OK;
     int rc;
     std::vector<int> po, pr, ps;
@@ -561,6 +560,15 @@ int Run::second_pass(unsigned long long& cells_perf) {
 
 }  // namespace
 
+int path_driver_vote_table(const HostGraph& h, PathWork& pw, const uint32_t** keys, unsigned* table_mask) {
+    if (!pw.impl) pw.impl = new PathWorkImpl();
+    const int rc = ensure_tables(h, *pw.impl);
+    if (rc) return rc;
+    *keys = pw.impl->kmer_keys.p;
+    *table_mask = pw.impl->kmer_mask;
+    return RG_OK;
+}
+
 int path_driver_run(const HostGraph& h, const PathGraphDev& gd, const rg_params& p, PathWork& pw, const uint8_t* d_reads,
                     const long long* d_off, const uint8_t* d_bad, int nreads, int max_n, DevRecord* d_rec, uint8_t* d_ops,
                     long long ops_stride, unsigned long long* d_cells, hipStream_t stream, size_t mem_budget,
@@ -576,7 +584,7 @@ int path_driver_run(const HostGraph& h, const PathGraphDev& gd, const rg_params&
           Timer{&w, stream, pw.spin_wait}, opt.debug != 0};
     for (int i = 0; i < 36; ++i) r.sc.t[i] = p.scores[i];
     if (!w.h_sum) HIPCHK(hipHostMalloc((void**)&w.h_sum, 8 * sizeof(unsigned long long), hipHostMallocDefault));
-    if ((rc = w.need.alloc(8)) || (rc = r.ensure_tables())) return rc;
+    if ((rc = w.need.alloc(8)) || (rc = ensure_tables(h, w))) return rc;
     if (w.fcap == 0) { w.fcap = plan.fcap; w.rcap = plan.rcap; w.frec_cap = plan.frec_cap; w.rrec_cap = plan.rrec_cap; }
     // reads per chunk: bounded by a memory budget for the per-read work buffers
     size_t budget = (size_t)96 << 30;

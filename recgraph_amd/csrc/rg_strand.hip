@@ -8,7 +8,9 @@
 // prints is < 0 (the reference's rule for the global POA modes, main.rs:82).  The printed score (rg_gaf.cpp) is the integer
 // `score`, or the f32 `fscore` of a record with a recombination (two different paths, -m 8 / -m 9): compared as f32, every
 // integer involved is below 2^24.  The reverse record replaces the forward one only when its printed score is STRICTLY
-// greater; ties keep the forward record.
+// greater; ties keep the forward record.  With RG_AMB_STRAND_VOTE (rg_strand_vote.hip) the first pass aligned each read on
+// the strand its 12-mers vote for: the gate presets the strand flag from `first_rev`, and the merge keeps the reverse record
+// only when it is strictly greater, whichever pass produced it.
 //
 // The kernels are memory-shaped and small on purpose: they run beside the sweeps of other handles, which leave 64 VGPRs
 // per SIMD (tests/test_both_strands_cpu.py holds them to that, without scratch).  Plain vector stores only.
@@ -47,7 +49,7 @@ __global__ __launch_bounds__(GATE_THREADS) void k_strand_gate(StrandGateArgs a) 
             const DevRecord r = a.rec[i];
             q = !no_record(r.status) && printed_score(r, a.recomb) < 0.0f;
             if (q) len = (int)(a.off[i + 1] - a.off[i]);
-            a.rec[i].pad = 0;
+            a.rec[i].pad = a.first_rev ? (int32_t)a.first_rev[i] : 0;      // (REC_REVERSE_STRAND: the strand of the record so far)
         }
         const unsigned long long bal = __ballot(q);
         const int rank = __popcll(bal & ((1ull << lane) - 1ull));
@@ -119,11 +121,15 @@ __global__ __launch_bounds__(WAVE) void k_strand_merge(StrandMergeArgs a) {
     const DevRecord r = a.rec2[k];
     if (no_record(r.status)) return;
     const DevRecord f = a.rec[rd];
-    if (!(printed_score(r, a.recomb) > printed_score(f, a.recomb))) return;
+    // (RG_AMB_STRAND_VOTE: a read whose first pass was the reverse one, `pad` preset by the gate, has its FORWARD record
+    // here: it replaces the reverse one unless that is strictly greater.  Without the vote `pad` is 0 on every read.)
+    const bool first_rev = (f.pad & REC_REVERSE_STRAND) != 0;
+    const float sf = printed_score(f, a.recomb), sr = printed_score(r, a.recomb);
+    if (first_rev ? sf > sr : !(sr > sf)) return;
     static_assert(sizeof(DevRecord) == 4 * sizeof(int4), "a record is four 16-byte pieces");
     if (lane < 4) {
         int4 v = reinterpret_cast<const int4*>(a.rec2 + k)[lane];
-        if (lane == 3) v.w = REC_REVERSE_STRAND;       // DevRecord::pad
+        if (lane == 3) v.w = first_rev ? 0 : REC_REVERSE_STRAND;       // DevRecord::pad
         reinterpret_cast<int4*>(a.rec + rd)[lane] = v;
     }
     const int4* so = reinterpret_cast<const int4*>(a.ops2 + (long long)k * a.ops_stride);

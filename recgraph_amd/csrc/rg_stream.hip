@@ -397,7 +397,8 @@ int32_t rg_stream_create(const rg_graph* g, const rg_params* p, const int32_t* d
     s->amb = s->o.amb_strand != 0 && !mode_is_pathwise(p->mode);      // modes 4+ ignore -s (main.rs:254-313)
     // amb_strand = 2 on a pathwise stream: both strands inside every tile, on the tile's own handle (RG_AMB_BOTH_STRANDS: our
     // extension; no second handle, and the kept record is the chosen one)
-    if (s->o.amb_strand == 2 && mode_is_pathwise(p->mode)) s->p.amb_mode |= RG_AMB_BOTH_STRANDS;
+    if ((s->o.amb_strand == 2 || s->o.amb_strand == 3) && mode_is_pathwise(p->mode)) s->p.amb_mode |= RG_AMB_BOTH_STRANDS;
+    if (s->o.amb_strand == 3 && mode_is_pathwise(p->mode)) s->p.amb_mode |= RG_AMB_STRAND_VOTE;      // (the first strand by a 12-mer vote)
     if (s->amb && s->o.keep_records) return fail(RG_ERR_ARG, "amb_strand and keep_records exclude each other (the kept record would be the forward one)");
     if (s->amb && p->amb_mode) return fail(RG_ERR_ARG, "amb_strand runs the retry itself: rg_params.amb_mode must be 0");
     const int visible = rg_device_count();

@@ -8,11 +8,14 @@ few reads against the oracle.  One JSON line per case.
 The strand cases (RG_AMB_BOTH_STRANDS, config-5 shape; `reads_per_s` counts SOURCE reads): `both_strands_fwd` — option on, every
 read forward (what the option costs when nothing qualifies: compare with `c5`); `both_strands` — option on, half of the reads
 reverse-complemented; `two_n` — option off, every read AND its reverse complement in the tiles, which is what a caller without
-the option has to submit (half of a tile's reads are source reads).
+the option has to submit (half of a tile's reads are source reads).  `strand_vote_fwd` / `strand_vote` — the same two read sets
+(the same seeds) with RG_AMB_STRAND_VOTE on top: the first strand by a 12-mer vote; their parity check builds the expected
+text by that option's rule (include/recgraph_hip.h) from the oracle and the vote stated below.
 
 Every case: TILES tiles of TILE reads through one rg_stream (3 handles), timed after one warm-up tile per handle."""
 import json
 import os
+import re
 import sys
 import time
 
@@ -33,7 +36,19 @@ CASES = {
     "both_strands_fwd": (8, 10000, 32, 1000, {"strands": "on_fwd"}, 4096, 6),
     "both_strands": (8, 10000, 32, 1000, {"strands": "on_half"}, 4096, 6),
     "two_n": (8, 10000, 32, 1000, {"strands": "two_n"}, 4096, 12),
+    "strand_vote_fwd": (8, 10000, 32, 1000, {"strands": "on_fwd", "vote": True}, 4096, 6),
+    "strand_vote": (8, 10000, 32, 1000, {"strands": "on_half", "vote": True}, 4096, 6),
 }
+
+
+def vote_first_reverse(kmers, read):
+    """RG_AMB_STRAND_VOTE, rule 1 and 2: up to 256 sampled 12-mers of the read and of its reverse complement against the paths'."""
+    def count(s):
+        npos = len(s) - 11
+        step = -(-npos // 256) if npos > 0 else 1
+        return sum(1 for q in range(0, max(npos, 0), step) if s[q:q + 12] in kmers)
+    comp = {"A": "T", "C": "G", "G": "C", "T": "A", "N": "N"}
+    return count("".join(comp[c] for c in reversed(read))) > count(read)
 
 
 def main():
@@ -57,7 +72,8 @@ def main():
             sm = api.create_score_matrix_i32(matrix_file_path=os.path.join(ROOT, "tests", "golden", sk["mtx"]))
         gg = api.Graph.from_gfa_text(gfa)
         strands = sk.get("strands")
-        params = api.make_params(mode, score_matrix=sm, amb=api.AMB_BOTH_STRANDS if strands in ("on_fwd", "on_half") else None)
+        vote = bool(sk.get("vote"))
+        params = api.make_params(mode, score_matrix=sm, amb=(api.AMB_BOTH_STRANDS | (api.AMB_STRAND_VOTE if vote else 0)) if strands in ("on_fwd", "on_half") else None)
 
         def tile_reads(k):
             """(reads of tile set k, per read: the source read the oracle aligns, whether the record must carry '-')"""
@@ -90,12 +106,18 @@ def main():
         osc = None if sm is None else O.scores_from_dict({k: int(v) for k, v in sm.items()})
         omode = {4: O.M4_ABS, 8: O.M8_ABS}[mode]
         last = got[-1]
-        _, last_reads, minus = tile_reads((tiles - 1) % len(sets))
+        given, last_reads, minus = tile_reads((tiles - 1) % len(sets))
         idx = sorted(set([0, tile - 1] + [int(k * (tile - 1) / (check - 1)) for k in range(check)]))
         idx = [i for i in idx if last_reads[i] is not None]        # (two_n: the source reads; their reverse complements are the caller's to merge)
         kw = {} if osc is None else {"scores": osc}
         _, _, exp = og.bench_text(omode, [last_reads[i] for i in idx], nthreads=min(os.cpu_count() or 1, 32), name_prefix="x", **kw)
         ok = True
+        if vote:
+            # the vote must send every checked read to the strand it was drawn from, and that strand must be accepted (score >= 0):
+            # then the rule's expected record is the source read's, '-' where the read was given reverse-complemented
+            kmers = {p[q:q + 12] for p in (g.path_sequence(k) for k in range(paths)) for q in range(len(p) - 11)}
+            ok = all(vote_first_reverse(kmers, given[i]) == bool(minus[i]) for i in idx) and \
+                all(float(re.search(r"score: (-?[0-9.]+)", t.decode()).group(1)) >= 0 for t in exp)
         for k, i in enumerate(idx):
             e = exp[k].decode().replace("x%d\t" % k, "read%d\t" % (last.first + i), 1)
             if minus[i]:
