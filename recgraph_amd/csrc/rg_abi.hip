@@ -47,7 +47,9 @@ struct Timed {
     rg_batch* b;
     std::vector<std::pair<int, int>> pending;  // (stat index, event index)
     size_t used = 0;
-    explicit Timed(rg_batch* b_) : b(b_) {}
+    const bool log;                            // the launch log is on: "inst:" pseudo-entries, counted in collect()
+    std::vector<const char*> insts;
+    explicit Timed(rg_batch* b_) : b(b_), log(options().launch_log != 0) {}
     int stat(const char* name) {
         for (size_t i = 0; i < b->stats.size(); ++i) if (b->stats[i].name == name) return (int)i;
         b->stats.push_back(KernelStat{name, 0, 0});
@@ -63,7 +65,8 @@ struct Timed {
         }
         auto& ev = b->ev_pool[used];
         HIPCHK(hipEventRecord(ev.first, b->stream));
-        launch();
+        const char* label = launch();      // what the launcher dispatched (rg_launch_log.hpp)
+        if (log && label) insts.push_back(label);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(ev.second, b->stream));
         pending.emplace_back(stat(name), (int)used);
@@ -81,9 +84,17 @@ struct Timed {
         }
         pending.clear();
         used = 0;
+        for (const char* l : insts) add_stat(b->stats, std::string("inst:") + l, 0, 1);
+        insts.clear();
         return RG_OK;
     }
 };
+
+// a new run of a handle: the kernels keep their slots, the launch log's entries go (a run with the log off shows none)
+void reset_stats(KernelStats& stats) {
+    stats.erase(std::remove_if(stats.begin(), stats.end(), [](const KernelStat& s) { return s.name.compare(0, 5, "inst:") == 0; }), stats.end());
+    for (auto& s : stats) { s.ms = 0; s.launches = 0; }
+}
 
 bool is_local(int mode) { return mode == RG_MODE_LOCAL_POA || mode == RG_MODE_LOCAL_POA_SCALAR || mode == RG_MODE_GAP_LOCAL_POA; }
 bool is_poa(int mode) {
@@ -99,7 +110,7 @@ int run_local(rg_batch* b) {
     const int variant = mode == RG_MODE_LOCAL_POA ? 0 : mode == RG_MODE_LOCAL_POA_SCALAR ? 1 : 2;
     const char* kname = variant == 0 ? "k_m1_local_simd" : variant == 1 ? "k_m1_local_scalar" : "k_m3_gap_local";
     Timed T(b);
-    for (auto& s : b->stats) { s.ms = 0; s.launches = 0; }
+    reset_stats(b->stats);
     b->cap_cells = (long long)(h.L - 1) * (b->max_n + 1);
     const size_t per_read = (size_t)b->cap_cells * planes * (sizeof(int) + sizeof(uint32_t));
     size_t free_b = 0, total_b = 0;
@@ -124,7 +135,7 @@ int run_local(rg_batch* b) {
     for (long long base = 0; base < b->nreads; base += chunk) {
         a.read_base = (int)base;
         a.nreads = (int)std::min<long long>(chunk, b->nreads - base);
-        if ((rc = T.run(kname, [&] { launch_local(a, variant, b->stream); }))) return rc;
+        if ((rc = T.run(kname, [&] { return launch_local(a, variant, b->stream); }))) return rc;
     }
     if ((rc = T.collect())) return rc;
     unsigned long long c = 0;
@@ -142,7 +153,7 @@ int run_poa(rg_batch* b) {
     if (is_local(mode)) return run_local(b);
     const int planes = mode == RG_MODE_GAP_POA ? 2 : 1;   // m2: m | y score planes, w0 | w1 path planes
     Timed T(b);
-    for (auto& s : b->stats) { s.ms = 0; s.launches = 0; }
+    reset_stats(b->stats);
     int oom_shift = 0;      // the budget is halved every time an arena allocation fails (other handles / threads took the memory)
     for (int attempt = 0; attempt < 24; ++attempt) {
         int rc;
@@ -177,9 +188,9 @@ int run_poa(rg_batch* b) {
         for (long long base = 0; base < b->nreads; base += chunk) {
             a.read_base = (int)base;
             a.nreads = (int)std::min<long long>(chunk, b->nreads - base);
-            if (mode == RG_MODE_GLOBAL_POA) { if ((rc = T.run("k_m0_simd", [&] { launch_m0_simd(a, b->stream); }))) return rc; }
-            else if (mode == RG_MODE_GAP_POA) { if ((rc = T.run("k_m2_gap", [&] { launch_m2(a, b->stream); }))) return rc; }
-            else { if ((rc = T.run("k_m0_scalar", [&] { launch_m0_scalar(a, b->stream); }))) return rc; }
+            if (mode == RG_MODE_GLOBAL_POA) { if ((rc = T.run("k_m0_simd", [&] { return launch_m0_simd(a, b->stream); }))) return rc; }
+            else if (mode == RG_MODE_GAP_POA) { if ((rc = T.run("k_m2_gap", [&] { return launch_m2(a, b->stream); }))) return rc; }
+            else { if ((rc = T.run("k_m0_scalar", [&] { return launch_m0_scalar(a, b->stream); }))) return rc; }
         }
         if ((rc = T.collect())) return rc;
         // overflow check: a read whose band cells did not fit asks for a bigger arena
@@ -197,7 +208,7 @@ int run_poa(rg_batch* b) {
         const long long full = (long long)h.L * (b->max_n + 1);
         if (b->cap_cells >= full) return fail(RG_ERR_CAPACITY, "band arena overflow at full size");
         b->cap_cells = std::min(full, b->cap_cells * 2);
-        for (auto& s : b->stats) { s.ms = 0; s.launches = 0; }
+        reset_stats(b->stats);
     }
     return fail(RG_ERR_CAPACITY, "band arena overflow");
 }
@@ -767,9 +778,9 @@ int rg_run_pathwise(rg_batch* b) {
         if ((rc = path_driver_vote_table(h, b->pw, &keys, &table_mask))) return rc;
         b->stats.clear();
         StrandVoteArgs va{b->in.reads, b->in.off, b->in.bad, keys, table_mask, b->d_first_rev.p};
-        if ((rc = T.run("k_strand_vote", [&] { launch_strand_vote(va, n, b->stream); }))) return rc;
+        if ((rc = T.run("k_strand_vote", [&] { return launch_strand_vote(va, n, b->stream); }))) return rc;
         StrandOrientArgs oa{b->in.reads, b->in.off, b->d_first_rev.p, b->d_pa.p};
-        if ((rc = T.run("k_strand_orient", [&] { launch_strand_orient(oa, n, b->stream); }))) return rc;
+        if ((rc = T.run("k_strand_orient", [&] { return launch_strand_orient(oa, n, b->stream); }))) return rc;
         reads_a = b->d_pa.p;
         KernelStats st1;
         if ((rc = path_driver_run(h, gd, b->p, b->pw, reads_a, b->in.off, b->in.bad, n, b->max_n, b->d_rec.p, b->d_ops.p, b->ops_stride,
@@ -785,9 +796,9 @@ int rg_run_pathwise(rg_batch* b) {
     // ---- RG_AMB_BOTH_STRANDS (rg_strand.hip): the qualifying reads once more, on the other strand, in the same work buffers ----
     const int recomb = b->p.mode == RG_MODE_RECOMBINATION || b->p.mode == RG_MODE_RECOMBINATION_SEMI ? 1 : 0;
     StrandGateArgs ga{b->d_rec.p, b->in.off, n, recomb, b->d_sidx.p, b->d_rcoff.p, b->d_ssum.p, vote ? b->d_first_rev.p : nullptr};
-    if ((rc = T.run("k_strand_gate", [&] { launch_strand_gate(ga, b->stream); }))) return rc;
+    if ((rc = T.run("k_strand_gate", [&] { return launch_strand_gate(ga, b->stream); }))) return rc;
     RevcompArgs ra{reads_a, b->in.off, b->d_sidx.p, b->d_rcoff.p, b->d_ssum.p, b->d_rc.p};
-    if ((rc = T.run("k_revcomp", [&] { launch_revcomp(ra, n, b->stream); }))) return rc;
+    if ((rc = T.run("k_revcomp", [&] { return launch_revcomp(ra, n, b->stream); }))) return rc;
     HIPCHK(hipMemcpyAsync(b->h_ssum.p, b->d_ssum.p, 2 * sizeof(int), hipMemcpyDeviceToHost, b->stream));
     if ((rc = T.collect())) return rc;
     const int count = b->h_ssum.p[0], max_len = b->h_ssum.p[1];
@@ -803,6 +814,6 @@ int rg_run_pathwise(rg_batch* b) {
     b->cells += c2[0];                  // (the workload grew: both counters include the second pass)
     b->cells_performed += c2[1];
     StrandMergeArgs ma{b->d_rec.p, b->d_ops.p, b->d_rec2.p, b->d_ops2.p, b->ops_stride, b->d_sidx.p, count, recomb};
-    if ((rc = T.run("k_strand_merge", [&] { launch_strand_merge(ma, b->stream); }))) return rc;
+    if ((rc = T.run("k_strand_merge", [&] { return launch_strand_merge(ma, b->stream); }))) return rc;
     return T.collect();
 }

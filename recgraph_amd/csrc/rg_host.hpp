@@ -43,7 +43,8 @@ extern thread_local std::string g_last_error;
     X(no_pick2, "RG_NO_PICK2", B, 0, 1, 0)            /* the speculative bound from one-path picks only (no two-path picks) */ \
     X(layer_i32, "RG_LAYER_I32", B, 0, 1, 0)          /* k_layer in its i32 form even when the sweep ran packed (test hook) */ \
     X(lds_pad, "RG_LDS_PAD", I, 0, 40 << 10, 0)       /* (experiments only) extra dynamic LDS bytes per k_sweep16 workgroup: lowers the waves per CU */ \
-    X(chunk_reads, "RG_CHUNK_READS", I, 0, 1 << 20, 0)   /* most reads one pathwise kernel launch takes (0: what the HBM budget allows, <= 8192) */
+    X(chunk_reads, "RG_CHUNK_READS", I, 0, 1 << 20, 0)   /* most reads one pathwise kernel launch takes (0: what the HBM budget allows, <= 8192) */ \
+    X(launch_log, "RG_LAUNCH_LOG", B, 0, 1, 0)        /* every kernel launch leaves an "inst:<instantiation>" pseudo-entry in the batch's kernel statistics (rg_launch_log.hpp: ms 0, launches counted) */
 struct Options {
 #define RG_OPTION_FIELD(name, env, kind, lo, hi, def) std::atomic<int> name{def};
     RG_OPTIONS(RG_OPTION_FIELD)

@@ -68,9 +68,17 @@ struct Timer {
     PathWorkImpl* w;
     hipStream_t s;
     bool spin = false;
+    bool log = false;                  // the launch log (rg_launch_log.hpp) is on
     size_t used = 0;
     struct Pend { std::string name; size_t e0, e1; };
     std::vector<Pend> pend;
+    std::vector<const char*> insts;    // what the launchers of this chunk said they launched
+    // takes a launcher's result: the instantiation it dispatched (null: it launched nothing — an argument block no kernel is compiled for)
+    void inst(const char* label) {
+        if (!label) bad_launch = true;
+        else if (log) insts.push_back(label);
+    }
+    bool bad_launch = false;
     int begin(const char* name) {
         while (w->ev.size() < used + 2) {
             hipEvent_t e;
@@ -85,6 +93,7 @@ struct Timer {
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(w->ev[used + 1], s));
         used += 2;
+        if (bad_launch) return fail(RG_ERR_ARG, "no kernel is compiled for this launch: " + pend.back().name);
         return RG_OK;
     }
     int collect(KernelStats& stats) {
@@ -97,7 +106,12 @@ struct Timer {
         }
         pend.clear();
         used = 0;
+        flush(stats);
         return RG_OK;
+    }
+    void flush(KernelStats& stats) {
+        for (const char* l : insts) add_stat(stats, std::string("inst:") + l, 0, 1);
+        insts.clear();
     }
 };
 
@@ -105,7 +119,7 @@ struct Timer {
     do {                                        \
         int rc_ = (T).begin(name);              \
         if (rc_) return rc_;                    \
-        call;                                   \
+        (T).inst(call);                         \
         rc_ = (T).end();                        \
         if (rc_) return rc_;                    \
     } while (0)
@@ -145,7 +159,7 @@ struct Run {
     int alloc_chunk(bool* oom);
     int enqueue_chunk();
     SweepArgs sweep_args() const;
-    void sweep(const SweepArgs& sa);
+    const char* sweep(const SweepArgs& sa);     // (what it launched, like the launchers: rg_launch_log.hpp)
     int enqueue_pathwise(const SweepArgs& sa, const SeedArgs& se);
     int enqueue_recombination(SweepArgs& sa, const SeedArgs& se);
     int enqueue_forward_bounded(SweepArgs& sa, const SeedArgs& se);
@@ -245,14 +259,13 @@ SweepArgs Run::sweep_args() const {
     return sa;
 }
 
-void Run::sweep(const SweepArgs& sa) {
+const char* Run::sweep(const SweepArgs& sa) {
     // (striped sweeps advance the candidate counter of a read atomically from several waves: start it at zero)
     if (plan.nwv > 1 && sa.cand && sa.ncand_out) {
         const hipError_t e = hipMemsetAsync(sa.ncand_out, 0, sizeof(unsigned) * chunk, stream);
         if (e != hipSuccess) async_err = e;
     }
-    if (plan.use16) launch_sweep16(sa, chunk, plan.C, stream);
-    else launch_sweep(sa, chunk, plan.C, stream);
+    return plan.use16 ? launch_sweep16(sa, chunk, plan.C, stream) : launch_sweep(sa, chunk, plan.C, stream);
 }
 
 // -m 4 / -m 5:  [pick -> opt0 ->] sweep(F, dirs) -> seed [-> verify4]
@@ -267,13 +280,13 @@ int Run::enqueue_pathwise(const SweepArgs& sa, const SeedArgs& se) {
         TIMED(T, "k_opt0", launch_opt0_16(oa, chunk, plan.C, stream));
         if (plan.retire4) {
             f.retire = 1; f.lb = w.lb.p; f.maxmatch = plan.maxmatch;
-            if (plan.order) { launch_order(w.pick.p, nullptr, w.order.p, chunk, stream); f.order = w.order.p; }
+            if (plan.order) { T.inst(launch_order(w.pick.p, nullptr, w.order.p, chunk, stream)); f.order = w.order.p; }
         }
         if (plan.dsel4) { f.dsel_pick = w.pick.p; f.dsel_pick2 = nullptr; f.dsel_lo = 0; f.dsel_hi = h.L; }     // (no recombination: no edge rows)
     }
     TIMED(T, plan.use16 ? "k_sweep16_fwd" : "k_sweep_fwd", sweep(f));
     TIMED(T, "k_seed", launch_seed(se, stream));
-    if (plan.spec4) launch_verify4(w.state.p, w.lb.p, w.need.p + 4, w.rt_flags.p, chunk, f.dsel_pick, stream);
+    if (plan.spec4) T.inst(launch_verify4(w.state.p, w.lb.p, w.need.p + 4, w.rt_flags.p, chunk, f.dsel_pick, stream));
     return RG_OK;
 }
 
@@ -283,7 +296,7 @@ int Run::check_opt0_16(const Opt0Args& oa) {
     std::vector<int> h16(chunk), h32(chunk);
     HIPCHK(hipMemcpyAsync(h16.data(), w.lb.p, sizeof(int) * chunk, hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
-    launch_opt0(oa, chunk, plan.C, stream);
+    T.inst(launch_opt0(oa, chunk, plan.C, stream));
     HIPCHK(hipMemcpyAsync(h32.data(), w.lb.p, sizeof(int) * chunk, hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
     for (int k = 0; k < chunk; ++k)
@@ -302,7 +315,7 @@ int Run::enqueue_forward_bounded(SweepArgs& sa, const SeedArgs& se) {
         oa.rec_pen = plan.rec_pen;
         TIMED(T, "k_pick", launch_pick(pa, chunk, stream));
         if (plan.retire && plan.order) {
-            launch_order(w.pick.p, pa.pick2, w.order.p, chunk, stream);
+            T.inst(launch_order(w.pick.p, pa.pick2, w.order.p, chunk, stream));
             sa.order = w.order.p;
         }
         oa.pick = w.pick.p;
@@ -390,8 +403,8 @@ int Run::enqueue_recombination(SweepArgs& sa, const SeedArgs& se) {
     SearchArgs sr{gd, w.state.p, w.fcand.p, w.rcand.p, w.nf.p, w.nr.p, w.ridx.p, w.fcap, w.rcap, w.wr.p, wpad, p.base_rec_cost, p.multi_rec_cost};
     TIMED(T, "k_search", launch_search(sr, chunk, stream));
     // largest list / record counts of the chunk, read back once after the traceback (no host round trip here)
-    launch_need(w.state.p, w.nf.p, w.nr.p, plan.use_rec ? w.nrec.p : nullptr, plan.use_rec ? w.nrrec.p : nullptr, w.need.p, chunk, stream);
-    if (plan.spec) launch_verify(w.state.p, w.lb.p, w.need.p + 4, w.rt_flags.p, chunk, sa.dsel_pick, sa.dsel_pick2, sa.dsel_lo, sa.dsel_hi, stream);
+    T.inst(launch_need(w.state.p, w.nf.p, w.nr.p, plan.use_rec ? w.nrec.p : nullptr, plan.use_rec ? w.nrrec.p : nullptr, w.need.p, chunk, stream));
+    if (plan.spec) T.inst(launch_verify(w.state.p, w.lb.p, w.need.p + 4, w.rt_flags.p, chunk, sa.dsel_pick, sa.dsel_pick2, sa.dsel_lo, sa.dsel_hi, stream));
     return RG_OK;
 }
 
@@ -406,7 +419,7 @@ int Run::enqueue_tail() {
     la.layer_stride = plan.layer_stride; la.fpoff = w.fpoff.p; la.fprow = w.fprow.p; la.fpslot = w.fpslot.p;
     la.rpoff = w.rpoff.p; la.rprow = w.rprow.p; la.rpslot = w.rpslot.p;
     la.rev = 0; la.dirs = w.fdirs.p; la.dirs_stride = plan.fdirs_stride; la.layer = w.flayer.p;
-    auto layer = [&]() { if (plan.layer16) launch_layer16(la, chunk, C, stream); else launch_layer(la, chunk, C, stream); };
+    auto layer = [&]() { return plan.layer16 ? launch_layer16(la, chunk, C, stream) : launch_layer(la, chunk, C, stream); };
     TIMED(T, "k_layer_fwd", layer());
     if (plan.mode == RG_MODE_RECOMBINATION) {
         la.rev = 1; la.dirs = w.rdirs.p; la.dirs_stride = plan.rdirs_stride; la.layer = w.rlayer.p;
@@ -545,16 +558,17 @@ int Run::second_pass(unsigned long long& cells_perf) {
         (rc = w.rt_cells.alloc(2)))
         return rc;
     HIPCHK(hipMemsetAsync(w.rt_bad.p, 0, (size_t)nr, stream));
-    launch_gather_reads(d_reads, off(), w.rt_idx.p, w.rt_off.p, w.rt_reads.p, nr, stream);
+    T.inst(launch_gather_reads(d_reads, off(), w.rt_idx.p, w.rt_off.p, w.rt_reads.p, nr, stream));
     KernelStats st2;
     unsigned long long c2[2] = {0, 0};
     if ((rc = path_driver_run(h, gd, p, w.retry, w.rt_reads.p, w.rt_off.p, w.rt_bad.p, nr, max_n, w.rt_rec.p, w.rt_ops.p, ops_stride,
                               w.rt_cells.p, stream, 0, c2, st2, spec_level + 1)))
         return rc;
-    launch_scatter_results(w.rt_idx.p, w.rt_rec.p, w.rt_ops.p, d_rec + done, d_ops + (long long)done * ops_stride, ops_stride, nr, stream);
+    T.inst(launch_scatter_results(w.rt_idx.p, w.rt_rec.p, w.rt_ops.p, d_rec + done, d_ops + (long long)done * ops_stride, ops_stride, nr, stream));
     HIPCHK(hipStreamSynchronize(stream));
     cells_perf += c2[1];             // the second pass is work the sweeps performed too (the counted figure stays the workload's)
     for (auto& e : st2) add_stat(stats, e.name, e.ms, e.launches);
+    T.flush(stats);                  // (the gather / scatter pair was launched behind the chunk's collect)
     return RG_OK;
 }
 
@@ -581,7 +595,7 @@ int path_driver_run(const HostGraph& h, const PathGraphDev& gd, const rg_params&
     int rc = plan_pathwise(p, PathPlanInput{h.P, h.L, h.fslots, h.rslots, h.max_path_rows, max_n}, opt, spec_level, plan);
     if (rc) return rc;
     Run r{h, gd, p, w, plan, d_reads, d_off, d_bad, max_n, d_rec, d_ops, ops_stride, d_cells, stream, stats, spec_level,
-          Timer{&w, stream, pw.spin_wait}, opt.debug != 0};
+          Timer{&w, stream, pw.spin_wait, opt.launch_log != 0}, opt.debug != 0};
     for (int i = 0; i < 36; ++i) r.sc.t[i] = p.scores[i];
     if (!w.h_sum) HIPCHK(hipHostMalloc((void**)&w.h_sum, 8 * sizeof(unsigned long long), hipHostMallocDefault));
     if ((rc = w.need.alloc(8)) || (rc = ensure_tables(h, w))) return rc;

@@ -2,6 +2,7 @@
 #pragma once
 #include "rg_path_args.hpp"
 #include "rg_path_plan.hpp"      // ReadState, Cand
+#include "rg_launch_log.hpp"
 
 namespace rg {
 
@@ -227,29 +228,29 @@ struct TraceArgs {
     int nwv;                   // column stripes per read (see SweepArgs)
 };
 
-void launch_sweep(const SweepArgs& a, int nreads, int C, hipStream_t s);
-void launch_sweep16(const SweepArgs& a, int nreads, int C, hipStream_t s);   // packed 16-bit rows (rg_sweep16.hip)
-void launch_expand(const ExpandArgs& a, int nreads, int C, hipStream_t s);
-void launch_colmax_rec(const ExpandArgs& a, int* colmax_out, int* colarg_out, int nreads, int C, hipStream_t s);
-void launch_seed(const SeedArgs& a, hipStream_t s);
-void launch_opt0(const Opt0Args& a, int nreads, int C, hipStream_t s);
-void launch_opt0_16(const Opt0Args& a, int nreads, int C, hipStream_t s);   // packed rows (rg_sweep16.hip): batches the packed sweep admits
-void launch_pick(const PickArgs& a, int nreads, hipStream_t s);
+const char* launch_sweep(const SweepArgs& a, int nreads, int C, hipStream_t s);
+const char* launch_sweep16(const SweepArgs& a, int nreads, int C, hipStream_t s);   // packed 16-bit rows (rg_sweep16.hip)
+const char* launch_expand(const ExpandArgs& a, int nreads, int C, hipStream_t s);
+const char* launch_colmax_rec(const ExpandArgs& a, int* colmax_out, int* colarg_out, int nreads, int C, hipStream_t s);
+const char* launch_seed(const SeedArgs& a, hipStream_t s);
+const char* launch_opt0(const Opt0Args& a, int nreads, int C, hipStream_t s);
+const char* launch_opt0_16(const Opt0Args& a, int nreads, int C, hipStream_t s);   // packed rows (rg_sweep16.hip): batches the packed sweep admits
+const char* launch_pick(const PickArgs& a, int nreads, hipStream_t s);
 // Launch order of the sweeps' waves under path retirement: the work of a read grows with the highest id among its picked
 // paths (every lower path leads it somewhere), from a few percent of a full sweep to all of it — longest first,
 // so that the launch does not end on a few full-length waves (one block: counting sort by that id, descending).
-void launch_order(const int* pick, const int* pick2, int* order, int nreads, hipStream_t s);
-void launch_verify4(ReadState* st, const int* lb, unsigned* nretry, uint8_t* flags, int nreads, const int* dsel_pick, hipStream_t s);
-void launch_verify(ReadState* st, const int* lb, unsigned* nretry, uint8_t* flags, int nreads, const int* dsel_pick, const int* dsel_pick2, int dsel_lo, int dsel_hi, hipStream_t s);
-void launch_gather_reads(const uint8_t* reads, const long long* off, const int* idx, const long long* sub_off, uint8_t* out, int n, hipStream_t s);
-void launch_scatter_results(const int* idx, const DevRecord* sub_rec, const uint8_t* sub_ops, DevRecord* rec, uint8_t* ops, long long ops_stride, int n, hipStream_t s);
-void launch_threshold(const ThrArgs& a, int nreads, hipStream_t s);
-void launch_bound(const BoundArgs& a, int nreads, hipStream_t s);
-void launch_search(const SearchArgs& a, int nreads, hipStream_t s);
-void launch_need(const ReadState* st, const unsigned* nf, const unsigned* nr, const unsigned* nrec, const unsigned* nrrec,
+const char* launch_order(const int* pick, const int* pick2, int* order, int nreads, hipStream_t s);
+const char* launch_verify4(ReadState* st, const int* lb, unsigned* nretry, uint8_t* flags, int nreads, const int* dsel_pick, hipStream_t s);
+const char* launch_verify(ReadState* st, const int* lb, unsigned* nretry, uint8_t* flags, int nreads, const int* dsel_pick, const int* dsel_pick2, int dsel_lo, int dsel_hi, hipStream_t s);
+const char* launch_gather_reads(const uint8_t* reads, const long long* off, const int* idx, const long long* sub_off, uint8_t* out, int n, hipStream_t s);
+const char* launch_scatter_results(const int* idx, const DevRecord* sub_rec, const uint8_t* sub_ops, DevRecord* rec, uint8_t* ops, long long ops_stride, int n, hipStream_t s);
+const char* launch_threshold(const ThrArgs& a, int nreads, hipStream_t s);
+const char* launch_bound(const BoundArgs& a, int nreads, hipStream_t s);
+const char* launch_search(const SearchArgs& a, int nreads, hipStream_t s);
+const char* launch_need(const ReadState* st, const unsigned* nf, const unsigned* nr, const unsigned* nrec, const unsigned* nrrec,
                  unsigned* need, int nreads, hipStream_t s);
-void launch_layer(const LayerArgs& a, int nreads, int C, hipStream_t s);
-void launch_layer16(const LayerArgs& a, int nreads, int C, hipStream_t s);   // packed rows (dir_fmt 1, one wave per read)
-void launch_trace(const TraceArgs& a, int C, hipStream_t s);
+const char* launch_layer(const LayerArgs& a, int nreads, int C, hipStream_t s);
+const char* launch_layer16(const LayerArgs& a, int nreads, int C, hipStream_t s);   // packed rows (dir_fmt 1, one wave per read)
+const char* launch_trace(const TraceArgs& a, int C, hipStream_t s);
 
 }  // namespace rg

@@ -1479,23 +1479,23 @@ __global__ __launch_bounds__(256) void k_need(const ReadState* st, const unsigne
         if ((threadIdx.x & (WAVE - 1)) == 0 && v[e]) atomicMax(&need[e], v[e]);
     }
 }
-void launch_need(const ReadState* st, const unsigned* nf, const unsigned* nr, const unsigned* nrec, const unsigned* nrrec,
-                 unsigned* need, int nreads, hipStream_t s) {
-    hipLaunchKernelGGL(k_need, dim3((nreads + 255) / 256), dim3(256), 0, s, st, nf, nr, nrec, nrrec, need, nreads);
+const char* launch_need(const ReadState* st, const unsigned* nf, const unsigned* nr, const unsigned* nrec, const unsigned* nrrec,
+                        unsigned* need, int nreads, hipStream_t s) {
+    RG_LAUNCH0(k_need, dim3((nreads + 255) / 256), dim3(256), 0, s, st, nf, nr, nrec, nrrec, need, nreads);
 }
 
 // ---------------------------------------------------------------------------------
 // launchers
 template <int C>
-static void launch_sweep_c(const SweepArgs& a, int nreads, hipStream_t s) {
+static const char* launch_sweep_c(const SweepArgs& a, int nreads, hipStream_t s) {
     // uniform read-gap cost: every (base, '-') entry equal (reads hold ACGTN only)
     bool uni = true;
     for (int b = 1; b < 5; ++b) uni = uni && a.sc.t[b * 6 + 5] == a.sc.t[5];
     const size_t sct_bytes = (64 + 2 * RG_MAXP + C * WAVE) * sizeof(int);       // (+ the path-retirement constants)
-    if (uni) hipLaunchKernelGGL((k_sweep<C, true>), dim3(nreads), dim3(64), sct_bytes, s, a);
-    else hipLaunchKernelGGL((k_sweep<C, false>), dim3(nreads), dim3(64), sct_bytes, s, a);
+    if (uni) RG_LAUNCH(k_sweep, (C, true, false), dim3(nreads), dim3(64), sct_bytes, s, a);
+    else RG_LAUNCH(k_sweep, (C, false, false), dim3(nreads), dim3(64), sct_bytes, s, a);
 }
-void launch_sweep(const SweepArgs& a, int nreads, int C, hipStream_t s) {
+const char* launch_sweep(const SweepArgs& a, int nreads, int C, hipStream_t s) {
     if (a.nwv > 1) {
         // striped long reads: a.nwv waves per read, C columns per lane (16: the rows and keys fit the registers; 32 spills
         // 800 of them and only serves reads beyond 8 x 1024 columns), uniform read-gap cost (checked by the driver)
@@ -1504,39 +1504,37 @@ void launch_sweep(const SweepArgs& a, int nreads, int C, hipStream_t s) {
         // (the 32-column stripes do not retire paths and get no constants: eight of them would pass the 64 KB a launch may ask for)
         const size_t bytes = (64 + 2 * RG_MAXP + 8 * (FIFO_WORDS + 2) + 16 + 4 * 8 * WAVE + (C <= 16 ? (size_t)a.nwv * C * WAVE : 0)) * sizeof(int);
         switch (C) {
-            case 8: hipLaunchKernelGGL((k_sweep<8, true, true>), dim3(nreads), dim3(64 * a.nwv), bytes, s, a); break;
-            case 16: hipLaunchKernelGGL((k_sweep<16, true, true>), dim3(nreads), dim3(64 * a.nwv), bytes, s, a); break;
-            default: hipLaunchKernelGGL((k_sweep<32, true, true>), dim3(nreads), dim3(64 * a.nwv), bytes, s, a); break;
+            case 8: RG_LAUNCH(k_sweep, (8, true, true), dim3(nreads), dim3(64 * a.nwv), bytes, s, a);
+            case 16: RG_LAUNCH(k_sweep, (16, true, true), dim3(nreads), dim3(64 * a.nwv), bytes, s, a);
+            default: RG_LAUNCH(k_sweep, (32, true, true), dim3(nreads), dim3(64 * a.nwv), bytes, s, a);
         }
-        return;
     }
     switch (C) {
-        case 4: launch_sweep_c<4>(a, nreads, s); break;
-        case 8: launch_sweep_c<8>(a, nreads, s); break;
-        case 16: launch_sweep_c<16>(a, nreads, s); break;
-        default: launch_sweep_c<32>(a, nreads, s); break;
+        case 4: return launch_sweep_c<4>(a, nreads, s);
+        case 8: return launch_sweep_c<8>(a, nreads, s);
+        case 16: return launch_sweep_c<16>(a, nreads, s);
+        default: return launch_sweep_c<32>(a, nreads, s);
     }
 }
-void launch_seed(const SeedArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(k_seed, dim3((a.nreads + 63) / 64), dim3(64), 0, s, a);
+const char* launch_seed(const SeedArgs& a, hipStream_t s) {
+    RG_LAUNCH0(k_seed, dim3((a.nreads + 63) / 64), dim3(64), 0, s, a);
 }
-void launch_opt0(const Opt0Args& a, int nreads, int C, hipStream_t s) {
+const char* launch_opt0(const Opt0Args& a, int nreads, int C, hipStream_t s) {
     if (a.nwv > 1) {
         switch (C) {
-            case 8: hipLaunchKernelGGL((k_opt0_striped<8>), dim3(nreads), dim3(64 * a.nwv), 0, s, a); break;
-            case 16: hipLaunchKernelGGL((k_opt0_striped<16>), dim3(nreads), dim3(64 * a.nwv), 0, s, a); break;
-            default: hipLaunchKernelGGL((k_opt0_striped<32>), dim3(nreads), dim3(64 * a.nwv), 0, s, a); break;
+            case 8: RG_LAUNCH(k_opt0_striped, (8), dim3(nreads), dim3(64 * a.nwv), 0, s, a);
+            case 16: RG_LAUNCH(k_opt0_striped, (16), dim3(nreads), dim3(64 * a.nwv), 0, s, a);
+            default: RG_LAUNCH(k_opt0_striped, (32), dim3(nreads), dim3(64 * a.nwv), 0, s, a);
         }
-        return;
     }
     switch (C) {
-        case 4: hipLaunchKernelGGL((k_opt0<4>), dim3(nreads), dim3(64), 0, s, a); break;
-        case 8: hipLaunchKernelGGL((k_opt0<8>), dim3(nreads), dim3(64), 0, s, a); break;
-        case 16: hipLaunchKernelGGL((k_opt0<16>), dim3(nreads), dim3(64), 0, s, a); break;
-        default: hipLaunchKernelGGL((k_opt0<32>), dim3(nreads), dim3(64), 0, s, a); break;
+        case 4: RG_LAUNCH(k_opt0, (4), dim3(nreads), dim3(64), 0, s, a);
+        case 8: RG_LAUNCH(k_opt0, (8), dim3(nreads), dim3(64), 0, s, a);
+        case 16: RG_LAUNCH(k_opt0, (16), dim3(nreads), dim3(64), 0, s, a);
+        default: RG_LAUNCH(k_opt0, (32), dim3(nreads), dim3(64), 0, s, a);
     }
 }
-void launch_pick(const PickArgs& a, int nreads, hipStream_t s) { hipLaunchKernelGGL(k_pick, dim3(nreads), dim3(64), 0, s, a); }
+const char* launch_pick(const PickArgs& a, int nreads, hipStream_t s) { RG_LAUNCH0(k_pick, dim3(nreads), dim3(64), 0, s, a); }
 __global__ __launch_bounds__(1024) void k_order(const int* pick, const int* pick2, int* order, int nreads) {
     __shared__ unsigned cnt[256], base[256];
     const int tid = threadIdx.x;
@@ -1553,55 +1551,54 @@ __global__ __launch_bounds__(1024) void k_order(const int* pick, const int* pick
     __syncthreads();
     for (int rd = tid; rd < nreads; rd += blockDim.x) order[atomicAdd(&base[key(rd)], 1u)] = rd;
 }
-void launch_order(const int* pick, const int* pick2, int* order, int nreads, hipStream_t s) {
-    hipLaunchKernelGGL(k_order, dim3(1), dim3(1024), 0, s, pick, pick2, order, nreads);
+const char* launch_order(const int* pick, const int* pick2, int* order, int nreads, hipStream_t s) {
+    RG_LAUNCH0(k_order, dim3(1), dim3(1024), 0, s, pick, pick2, order, nreads);
 }
-void launch_verify(ReadState* st, const int* lb, unsigned* nretry, uint8_t* flags, int nreads, const int* dsel_pick, const int* dsel_pick2, int dsel_lo, int dsel_hi, hipStream_t s) {
-    hipLaunchKernelGGL(k_verify, dim3((nreads + 255) / 256), dim3(256), 0, s, st, lb, nretry, flags, nreads, dsel_pick, dsel_pick2, dsel_lo, dsel_hi);
+const char* launch_verify(ReadState* st, const int* lb, unsigned* nretry, uint8_t* flags, int nreads, const int* dsel_pick, const int* dsel_pick2, int dsel_lo, int dsel_hi, hipStream_t s) {
+    RG_LAUNCH0(k_verify, dim3((nreads + 255) / 256), dim3(256), 0, s, st, lb, nretry, flags, nreads, dsel_pick, dsel_pick2, dsel_lo, dsel_hi);
 }
-void launch_verify4(ReadState* st, const int* lb, unsigned* nretry, uint8_t* flags, int nreads, const int* dsel_pick, hipStream_t s) {
-    hipLaunchKernelGGL(k_verify4, dim3((nreads + 255) / 256), dim3(256), 0, s, st, lb, nretry, flags, nreads, dsel_pick);
+const char* launch_verify4(ReadState* st, const int* lb, unsigned* nretry, uint8_t* flags, int nreads, const int* dsel_pick, hipStream_t s) {
+    RG_LAUNCH0(k_verify4, dim3((nreads + 255) / 256), dim3(256), 0, s, st, lb, nretry, flags, nreads, dsel_pick);
 }
-void launch_gather_reads(const uint8_t* reads, const long long* off, const int* idx, const long long* sub_off, uint8_t* out, int n, hipStream_t s) {
-    hipLaunchKernelGGL(k_gather_reads, dim3(n), dim3(256), 0, s, reads, off, idx, sub_off, out);
+const char* launch_gather_reads(const uint8_t* reads, const long long* off, const int* idx, const long long* sub_off, uint8_t* out, int n, hipStream_t s) {
+    RG_LAUNCH0(k_gather_reads, dim3(n), dim3(256), 0, s, reads, off, idx, sub_off, out);
 }
-void launch_scatter_results(const int* idx, const DevRecord* sub_rec, const uint8_t* sub_ops, DevRecord* rec, uint8_t* ops, long long ops_stride,
+const char* launch_scatter_results(const int* idx, const DevRecord* sub_rec, const uint8_t* sub_ops, DevRecord* rec, uint8_t* ops, long long ops_stride,
                             int n, hipStream_t s) {
-    hipLaunchKernelGGL(k_scatter_results, dim3(n), dim3(256), 0, s, idx, sub_rec, sub_ops, rec, ops, ops_stride);
+    RG_LAUNCH0(k_scatter_results, dim3(n), dim3(256), 0, s, idx, sub_rec, sub_ops, rec, ops, ops_stride);
 }
-void launch_threshold(const ThrArgs& a, int nreads, hipStream_t s) {
-    hipLaunchKernelGGL(k_threshold, dim3((a.wpad + 255) / 256, nreads), dim3(256), 0, s, a);
+const char* launch_threshold(const ThrArgs& a, int nreads, hipStream_t s) {
+    RG_LAUNCH0(k_threshold, dim3((a.wpad + 255) / 256, nreads), dim3(256), 0, s, a);
 }
-void launch_bound(const BoundArgs& a, int nreads, hipStream_t s) {
-    hipLaunchKernelGGL(k_bound, dim3(nreads), dim3(64), 0, s, a);
+const char* launch_bound(const BoundArgs& a, int nreads, hipStream_t s) {
+    RG_LAUNCH0(k_bound, dim3(nreads), dim3(64), 0, s, a);
 }
-void launch_search(const SearchArgs& a, int nreads, hipStream_t s) {
+const char* launch_search(const SearchArgs& a, int nreads, hipStream_t s) {
     const size_t bytes = (size_t)(2 * (a.wpad + 1)) * sizeof(int);
-    hipLaunchKernelGGL(k_search, dim3(nreads), dim3(64), bytes, s, a);
+    RG_LAUNCH0(k_search, dim3(nreads), dim3(64), bytes, s, a);
 }
-void launch_layer(const LayerArgs& a, int nreads, int C, hipStream_t s) {
+const char* launch_layer(const LayerArgs& a, int nreads, int C, hipStream_t s) {
     if (a.nwv > 1) {
         switch (C) {
-            case 8: hipLaunchKernelGGL((k_layer<8, true>), dim3(nreads), dim3(64 * a.nwv), 0, s, a); break;
-            case 16: hipLaunchKernelGGL((k_layer<16, true>), dim3(nreads), dim3(64 * a.nwv), 0, s, a); break;
-            default: hipLaunchKernelGGL((k_layer<32, true>), dim3(nreads), dim3(64 * a.nwv), 0, s, a); break;
+            case 8: RG_LAUNCH(k_layer, (8, true), dim3(nreads), dim3(64 * a.nwv), 0, s, a);
+            case 16: RG_LAUNCH(k_layer, (16, true), dim3(nreads), dim3(64 * a.nwv), 0, s, a);
+            default: RG_LAUNCH(k_layer, (32, true), dim3(nreads), dim3(64 * a.nwv), 0, s, a);
         }
-        return;
     }
     switch (C) {
-        case 4: hipLaunchKernelGGL((k_layer<4>), dim3(nreads), dim3(64), 0, s, a); break;
-        case 8: hipLaunchKernelGGL((k_layer<8>), dim3(nreads), dim3(64), 0, s, a); break;
-        case 16: hipLaunchKernelGGL((k_layer<16>), dim3(nreads), dim3(64), 0, s, a); break;
-        default: hipLaunchKernelGGL((k_layer<32>), dim3(nreads), dim3(64), 0, s, a); break;
+        case 4: RG_LAUNCH(k_layer, (4, false), dim3(nreads), dim3(64), 0, s, a);
+        case 8: RG_LAUNCH(k_layer, (8, false), dim3(nreads), dim3(64), 0, s, a);
+        case 16: RG_LAUNCH(k_layer, (16, false), dim3(nreads), dim3(64), 0, s, a);
+        default: RG_LAUNCH(k_layer, (32, false), dim3(nreads), dim3(64), 0, s, a);
     }
 }
-void launch_trace(const TraceArgs& a, int C, hipStream_t s) {
+const char* launch_trace(const TraceArgs& a, int C, hipStream_t s) {
     const dim3 grid((a.nreads + 63) / 64), blk(64);
     switch (C) {
-        case 4: hipLaunchKernelGGL((k_trace<4>), grid, blk, 0, s, a); break;
-        case 8: hipLaunchKernelGGL((k_trace<8>), grid, blk, 0, s, a); break;
-        case 16: hipLaunchKernelGGL((k_trace<16>), grid, blk, 0, s, a); break;
-        default: hipLaunchKernelGGL((k_trace<32>), grid, blk, 0, s, a); break;
+        case 4: RG_LAUNCH(k_trace, (4), grid, blk, 0, s, a);
+        case 8: RG_LAUNCH(k_trace, (8), grid, blk, 0, s, a);
+        case 16: RG_LAUNCH(k_trace, (16), grid, blk, 0, s, a);
+        default: RG_LAUNCH(k_trace, (32), grid, blk, 0, s, a);
     }
 }
 

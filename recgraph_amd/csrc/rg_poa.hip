@@ -355,14 +355,14 @@ __global__ __launch_bounds__(64) void k_m0_simd(PoaArgs a) {
     }
 }
 
-void launch_m0_simd(const PoaArgs& a, hipStream_t s) {
+const char* launch_m0_simd(const PoaArgs& a, hipStream_t s) {
     const size_t bytes = 36 * sizeof(int) + (a.lds_read ? (((size_t)a.max_n + 2 + 3) & ~(size_t)3) : 0);
     bool uni = true;                     // one gap cost for every read base (ACGTN)
     for (int b = 1; b < 5; ++b) uni = uni && a.sc.t[b * 6 + 5] == a.sc.t[5];
-    if (a.lds_read && uni) hipLaunchKernelGGL((k_m0_simd<true, true>), dim3(a.nreads), dim3(64), bytes, s, a);
-    else if (a.lds_read) hipLaunchKernelGGL((k_m0_simd<true, false>), dim3(a.nreads), dim3(64), bytes, s, a);
-    else if (uni) hipLaunchKernelGGL((k_m0_simd<false, true>), dim3(a.nreads), dim3(64), bytes, s, a);
-    else hipLaunchKernelGGL((k_m0_simd<false, false>), dim3(a.nreads), dim3(64), bytes, s, a);
+    if (a.lds_read && uni) RG_LAUNCH(k_m0_simd, (true, true), dim3(a.nreads), dim3(64), bytes, s, a);
+    else if (a.lds_read) RG_LAUNCH(k_m0_simd, (true, false), dim3(a.nreads), dim3(64), bytes, s, a);
+    else if (uni) RG_LAUNCH(k_m0_simd, (false, true), dim3(a.nreads), dim3(64), bytes, s, a);
+    else RG_LAUNCH(k_m0_simd, (false, false), dim3(a.nreads), dim3(64), bytes, s, a);
 }
 
 }  // namespace rg

@@ -1,6 +1,7 @@
 // Kernel argument blocks shared between the launchers (.hip) and the batch driver.
 #pragma once
 #include "rg_device.hpp"
+#include "rg_launch_log.hpp"
 
 namespace rg {
 
@@ -35,9 +36,9 @@ struct PoaArgs {
     unsigned long long* cells; // DP cell-update counter
 };
 
-void launch_m0_simd(const PoaArgs& a, hipStream_t s);
-void launch_m2(const PoaArgs& a, hipStream_t s);
-void launch_m0_scalar(const PoaArgs& a, hipStream_t s);
-void launch_local(const PoaArgs& a, int variant, hipStream_t s);   // 0: -m 1 AVX2 semantics, 1: -m 1 scalar, 2: -m 3
+const char* launch_m0_simd(const PoaArgs& a, hipStream_t s);
+const char* launch_m2(const PoaArgs& a, hipStream_t s);
+const char* launch_m0_scalar(const PoaArgs& a, hipStream_t s);
+const char* launch_local(const PoaArgs& a, int variant, hipStream_t s);   // 0: -m 1 AVX2 semantics, 1: -m 1 scalar, 2: -m 3
 
 }  // namespace rg

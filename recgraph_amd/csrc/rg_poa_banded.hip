@@ -516,12 +516,12 @@ __global__ __launch_bounds__(64) void k_poa_banded(PoaArgs a) {
 }
 
 template <bool kGap>
-static void launch_banded(const PoaArgs& a, hipStream_t s) {
+static const char* launch_banded(const PoaArgs& a, hipStream_t s) {
     const size_t bytes = 36 * sizeof(int) + (a.lds_read ? (((size_t)a.max_n + 2 + 3) & ~(size_t)3) : 0);
-    if (a.lds_read) hipLaunchKernelGGL((k_poa_banded<kGap, true>), dim3(a.nreads), dim3(64), bytes, s, a);
-    else hipLaunchKernelGGL((k_poa_banded<kGap, false>), dim3(a.nreads), dim3(64), bytes, s, a);
+    if (a.lds_read) RG_LAUNCH(k_poa_banded, (kGap, true), dim3(a.nreads), dim3(64), bytes, s, a);
+    else RG_LAUNCH(k_poa_banded, (kGap, false), dim3(a.nreads), dim3(64), bytes, s, a);
 }
-void launch_m2(const PoaArgs& a, hipStream_t s) { launch_banded<true>(a, s); }
-void launch_m0_scalar(const PoaArgs& a, hipStream_t s) { launch_banded<false>(a, s); }
+const char* launch_m2(const PoaArgs& a, hipStream_t s) { return launch_banded<true>(a, s); }
+const char* launch_m0_scalar(const PoaArgs& a, hipStream_t s) { return launch_banded<false>(a, s); }
 
 }  // namespace rg

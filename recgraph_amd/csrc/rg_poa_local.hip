@@ -354,15 +354,15 @@ __global__ __launch_bounds__(64) void k_poa_local(PoaArgs a) {
 }
 
 template <int kVar>
-static void launch_local_v(const PoaArgs& a, hipStream_t s) {
+static const char* launch_local_v(const PoaArgs& a, hipStream_t s) {
     const size_t bytes = 36 * sizeof(int) + (a.lds_read ? (((size_t)a.max_n + 2 + 3) & ~(size_t)3) : 0);
-    if (a.lds_read) hipLaunchKernelGGL((k_poa_local<kVar, true>), dim3(a.nreads), dim3(64), bytes, s, a);
-    else hipLaunchKernelGGL((k_poa_local<kVar, false>), dim3(a.nreads), dim3(64), bytes, s, a);
+    if (a.lds_read) RG_LAUNCH(k_poa_local, (kVar, true), dim3(a.nreads), dim3(64), bytes, s, a);
+    else RG_LAUNCH(k_poa_local, (kVar, false), dim3(a.nreads), dim3(64), bytes, s, a);
 }
-void launch_local(const PoaArgs& a, int variant, hipStream_t s) {
-    if (variant == 0) launch_local_v<0>(a, s);
-    else if (variant == 1) launch_local_v<1>(a, s);
-    else launch_local_v<2>(a, s);
+const char* launch_local(const PoaArgs& a, int variant, hipStream_t s) {
+    if (variant == 0) return launch_local_v<0>(a, s);
+    if (variant == 1) return launch_local_v<1>(a, s);
+    return launch_local_v<2>(a, s);
 }
 
 }  // namespace rg

@@ -138,14 +138,14 @@ __global__ __launch_bounds__(WAVE) void k_strand_merge(StrandMergeArgs a) {
     for (int t = lane; t < pieces; t += WAVE) dn[t] = so[t];
 }
 
-void launch_strand_gate(const StrandGateArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(k_strand_gate, dim3(1), dim3(GATE_THREADS), 0, s, a);
+const char* launch_strand_gate(const StrandGateArgs& a, hipStream_t s) {
+    RG_LAUNCH0(k_strand_gate, dim3(1), dim3(GATE_THREADS), 0, s, a);
 }
-void launch_revcomp(const RevcompArgs& a, int nreads, hipStream_t s) {
-    hipLaunchKernelGGL(k_revcomp, dim3(nreads), dim3(WAVE), 0, s, a);
+const char* launch_revcomp(const RevcompArgs& a, int nreads, hipStream_t s) {
+    RG_LAUNCH0(k_revcomp, dim3(nreads), dim3(WAVE), 0, s, a);
 }
-void launch_strand_merge(const StrandMergeArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(k_strand_merge, dim3(a.count), dim3(WAVE), 0, s, a);
+const char* launch_strand_merge(const StrandMergeArgs& a, hipStream_t s) {
+    RG_LAUNCH0(k_strand_merge, dim3(a.count), dim3(WAVE), 0, s, a);
 }
 
 }  // namespace rg

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "rg_device.hpp"
+#include "rg_launch_log.hpp"
 
 namespace rg {
 
@@ -54,10 +55,10 @@ struct StrandOrientArgs {
     uint8_t* out;              // the read, or its reverse complement, at the SAME offset (3 bytes of slack behind the last read)
 };
 
-void launch_strand_vote(const StrandVoteArgs& a, int nreads, hipStream_t s);        // one wave per read
-void launch_strand_orient(const StrandOrientArgs& a, int nreads, hipStream_t s);    // one wave per read
-void launch_strand_gate(const StrandGateArgs& a, hipStream_t s);
-void launch_revcomp(const RevcompArgs& a, int nreads, hipStream_t s);      // one wave per read slot; slots >= summary[0] leave
-void launch_strand_merge(const StrandMergeArgs& a, hipStream_t s);
+const char* launch_strand_vote(const StrandVoteArgs& a, int nreads, hipStream_t s);        // one wave per read
+const char* launch_strand_orient(const StrandOrientArgs& a, int nreads, hipStream_t s);    // one wave per read
+const char* launch_strand_gate(const StrandGateArgs& a, hipStream_t s);
+const char* launch_revcomp(const RevcompArgs& a, int nreads, hipStream_t s);      // one wave per read slot; slots >= summary[0] leave
+const char* launch_strand_merge(const StrandMergeArgs& a, hipStream_t s);
 
 }  // namespace rg

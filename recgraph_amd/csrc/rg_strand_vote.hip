@@ -110,11 +110,11 @@ __global__ __launch_bounds__(WAVE) void k_strand_orient(StrandOrientArgs a) {
     if (lane < n - tail0) dst[tail0 + lane] = pick(tail0 + lane);
 }
 
-void launch_strand_vote(const StrandVoteArgs& a, int nreads, hipStream_t s) {
-    hipLaunchKernelGGL(k_strand_vote, dim3(nreads), dim3(WAVE), 0, s, a);
+const char* launch_strand_vote(const StrandVoteArgs& a, int nreads, hipStream_t s) {
+    RG_LAUNCH0(k_strand_vote, dim3(nreads), dim3(WAVE), 0, s, a);
 }
-void launch_strand_orient(const StrandOrientArgs& a, int nreads, hipStream_t s) {
-    hipLaunchKernelGGL(k_strand_orient, dim3(nreads), dim3(WAVE), 0, s, a);
+const char* launch_strand_orient(const StrandOrientArgs& a, int nreads, hipStream_t s) {
+    RG_LAUNCH0(k_strand_orient, dim3(nreads), dim3(WAVE), 0, s, a);
 }
 
 }  // namespace rg

@@ -336,6 +336,7 @@ struct PathWords {
 template <int C, int kColmax, bool kRec, bool kWide, bool kSemi>
 __global__ __launch_bounds__(64, SWEEP16_WAVES) void k_sweep16(SweepArgs a) {
     static_assert(kColmax == 0 || kColmax == 1, "column maxima with their rows, or none");
+    static_assert(!(kColmax == 1 && kRec), "a record sweep tracks no column maxima (k_colmax_rec reads them out of the records): launch_sweep16");
     constexpr int H = C / 2;
     constexpr bool kTrack = kColmax == 1 || kRec;      // <0, false>: the -m 4 / -m 5 sweep — no best member, no thresholds, no emission
     // PATH RETIREMENT: the record pipelines of -m 8 (since round 6 also beyond 64 paths) and — round 6 — the -m 4 sweep: there a path is
@@ -1710,12 +1711,12 @@ __global__ __launch_bounds__(256) void k_expand(ExpandArgs a) {
     }
 }
 
-void launch_expand(const ExpandArgs& a, int nreads, int C, hipStream_t s) {
+const char* launch_expand(const ExpandArgs& a, int nreads, int C, hipStream_t s) {
     switch (C) {
-        case 4: hipLaunchKernelGGL((k_expand<4>), dim3(nreads), dim3(256), 0, s, a); break;
-        case 8: hipLaunchKernelGGL((k_expand<8>), dim3(nreads), dim3(256), 0, s, a); break;
-        case 16: hipLaunchKernelGGL((k_expand<16>), dim3(nreads), dim3(256), 0, s, a); break;
-        default: hipLaunchKernelGGL((k_expand<32>), dim3(nreads), dim3(256), 0, s, a); break;
+        case 4: RG_LAUNCH(k_expand, (4), dim3(nreads), dim3(256), 0, s, a);
+        case 8: RG_LAUNCH(k_expand, (8), dim3(nreads), dim3(256), 0, s, a);
+        case 16: RG_LAUNCH(k_expand, (16), dim3(nreads), dim3(256), 0, s, a);
+        default: RG_LAUNCH(k_expand, (32), dim3(nreads), dim3(256), 0, s, a);
     }
 }
 
@@ -1760,13 +1761,13 @@ __global__ __launch_bounds__(256) void k_colmax_rec(ExpandArgs a, int* colmax_ou
     }
 }
 
-void launch_colmax_rec(const ExpandArgs& a, int* colmax_out, int* colarg_out, int nreads, int C, hipStream_t s) {
+const char* launch_colmax_rec(const ExpandArgs& a, int* colmax_out, int* colarg_out, int nreads, int C, hipStream_t s) {
     const size_t bytes = (size_t)a.wpad * sizeof(unsigned long long);
     switch (C) {
-        case 4: hipLaunchKernelGGL((k_colmax_rec<4>), dim3(nreads), dim3(256), bytes, s, a, colmax_out, colarg_out); break;
-        case 8: hipLaunchKernelGGL((k_colmax_rec<8>), dim3(nreads), dim3(256), bytes, s, a, colmax_out, colarg_out); break;
-        case 16: hipLaunchKernelGGL((k_colmax_rec<16>), dim3(nreads), dim3(256), bytes, s, a, colmax_out, colarg_out); break;
-        default: hipLaunchKernelGGL((k_colmax_rec<32>), dim3(nreads), dim3(256), bytes, s, a, colmax_out, colarg_out); break;
+        case 4: RG_LAUNCH(k_colmax_rec, (4), dim3(nreads), dim3(256), bytes, s, a, colmax_out, colarg_out);
+        case 8: RG_LAUNCH(k_colmax_rec, (8), dim3(nreads), dim3(256), bytes, s, a, colmax_out, colarg_out);
+        case 16: RG_LAUNCH(k_colmax_rec, (16), dim3(nreads), dim3(256), bytes, s, a, colmax_out, colarg_out);
+        default: RG_LAUNCH(k_colmax_rec, (32), dim3(nreads), dim3(256), bytes, s, a, colmax_out, colarg_out);
     }
 }
 
@@ -1947,13 +1948,13 @@ __global__ __launch_bounds__(64, C <= 16 ? LAYER16_WAVES : 1) void k_layer16(Lay
     }
 }
 
-void launch_layer16(const LayerArgs& a, int nreads, int C, hipStream_t s) {
+const char* launch_layer16(const LayerArgs& a, int nreads, int C, hipStream_t s) {
     const size_t bytes = (size_t)(64 + 5 * 64 + 5 * WAVE * (C / 2)) * sizeof(int);
     switch (C) {
-        case 4: hipLaunchKernelGGL((k_layer16<4>), dim3(nreads), dim3(64), bytes, s, a); break;
-        case 8: hipLaunchKernelGGL((k_layer16<8>), dim3(nreads), dim3(64), bytes, s, a); break;
-        case 16: hipLaunchKernelGGL((k_layer16<16>), dim3(nreads), dim3(64), bytes, s, a); break;
-        default: hipLaunchKernelGGL((k_layer16<32>), dim3(nreads), dim3(64), bytes, s, a); break;
+        case 4: RG_LAUNCH(k_layer16, (4), dim3(nreads), dim3(64), bytes, s, a);
+        case 8: RG_LAUNCH(k_layer16, (8), dim3(nreads), dim3(64), bytes, s, a);
+        case 16: RG_LAUNCH(k_layer16, (16), dim3(nreads), dim3(64), bytes, s, a);
+        default: RG_LAUNCH(k_layer16, (32), dim3(nreads), dim3(64), bytes, s, a);
     }
 }
 
@@ -2068,37 +2069,37 @@ __global__ __launch_bounds__(64) void k_opt0_16(Opt0Args a) {
     if (lane == ln) a.lb[rd] = (a.semi ? semibest : v) - (a.pick ? a.margin : 0) - (pk2 >= 0 ? a.rec_pen : 0);
 }
 
-void launch_opt0_16(const Opt0Args& a, int nreads, int C, hipStream_t s) {
+const char* launch_opt0_16(const Opt0Args& a, int nreads, int C, hipStream_t s) {
     const size_t bytes = (size_t)(64 + 5 * 64 + 5 * WAVE * (C / 2)) * sizeof(int);
     switch (C) {
-        case 4: hipLaunchKernelGGL((k_opt0_16<4>), dim3(nreads), dim3(64), bytes, s, a); break;
-        case 8: hipLaunchKernelGGL((k_opt0_16<8>), dim3(nreads), dim3(64), bytes, s, a); break;
-        case 16: hipLaunchKernelGGL((k_opt0_16<16>), dim3(nreads), dim3(64), bytes, s, a); break;
-        default: hipLaunchKernelGGL((k_opt0_16<32>), dim3(nreads), dim3(64), bytes, s, a); break;
+        case 4: RG_LAUNCH(k_opt0_16, (4), dim3(nreads), dim3(64), bytes, s, a);
+        case 8: RG_LAUNCH(k_opt0_16, (8), dim3(nreads), dim3(64), bytes, s, a);
+        case 16: RG_LAUNCH(k_opt0_16, (16), dim3(nreads), dim3(64), bytes, s, a);
+        default: RG_LAUNCH(k_opt0_16, (32), dim3(nreads), dim3(64), bytes, s, a);
     }
 }
 
 template <int kColmax, bool kRec, bool kWide, bool kSemi>
-static void launch_sweep16_s(const SweepArgs& a, int nreads, int C, hipStream_t s) {
+static const char* launch_sweep16_s(const SweepArgs& a, int nreads, int C, hipStream_t s) {
     const size_t bytes = (size_t)(64 + 2 * (kWide ? RG_MAXP : 64) + std::max(C * WAVE, 5 * 64) + 4 * WAVE * (C / 2)) * sizeof(int) + (size_t)options().lds_pad;
     switch (C) {
-        case 4: hipLaunchKernelGGL((k_sweep16<4, kColmax, kRec, kWide, kSemi>), dim3(nreads), dim3(64), bytes, s, a); break;
-        case 8: hipLaunchKernelGGL((k_sweep16<8, kColmax, kRec, kWide, kSemi>), dim3(nreads), dim3(64), bytes, s, a); break;
-        case 16: hipLaunchKernelGGL((k_sweep16<16, kColmax, kRec, kWide, kSemi>), dim3(nreads), dim3(64), bytes, s, a); break;
-        default: hipLaunchKernelGGL((k_sweep16<32, kColmax, kRec, kWide, kSemi>), dim3(nreads), dim3(64), bytes, s, a); break;
+        case 4: RG_LAUNCH(k_sweep16, (4, kColmax, kRec, kWide, kSemi), dim3(nreads), dim3(64), bytes, s, a);
+        case 8: RG_LAUNCH(k_sweep16, (8, kColmax, kRec, kWide, kSemi), dim3(nreads), dim3(64), bytes, s, a);
+        case 16: RG_LAUNCH(k_sweep16, (16, kColmax, kRec, kWide, kSemi), dim3(nreads), dim3(64), bytes, s, a);
+        default: RG_LAUNCH(k_sweep16, (32, kColmax, kRec, kWide, kSemi), dim3(nreads), dim3(64), bytes, s, a);
     }
 }
 template <int kColmax, bool kRec, bool kWide>
-static void launch_sweep16_w(const SweepArgs& a, int nreads, int C, hipStream_t s) {
-    if (a.semi) launch_sweep16_s<kColmax, kRec, kWide, true>(a, nreads, C, s);
-    else launch_sweep16_s<kColmax, kRec, kWide, false>(a, nreads, C, s);
+static const char* launch_sweep16_w(const SweepArgs& a, int nreads, int C, hipStream_t s) {
+    if (a.semi) return launch_sweep16_s<kColmax, kRec, kWide, true>(a, nreads, C, s);
+    return launch_sweep16_s<kColmax, kRec, kWide, false>(a, nreads, C, s);
 }
 template <int kColmax, bool kRec>
-static void launch_sweep16_c(const SweepArgs& a, int nreads, int C, hipStream_t s) {
-    if (a.g.P > 64) launch_sweep16_w<kColmax, kRec, true>(a, nreads, C, s);
-    else launch_sweep16_w<kColmax, kRec, false>(a, nreads, C, s);
+static const char* launch_sweep16_c(const SweepArgs& a, int nreads, int C, hipStream_t s) {
+    if (a.g.P > 64) return launch_sweep16_w<kColmax, kRec, true>(a, nreads, C, s);
+    return launch_sweep16_w<kColmax, kRec, false>(a, nreads, C, s);
 }
-void launch_sweep16(const SweepArgs& a_, int nreads, int C, hipStream_t s) {
+const char* launch_sweep16(const SweepArgs& a_, int nreads, int C, hipStream_t s) {
     SweepArgs a = a_;
     // split step tables (TAIL records): for the record variants — lazy keys, register runs of RG_SWEEP16_RUN_PATHS paths, gather runs
     // (more than 64 paths: the wide-run table takes the split table's place)
@@ -2112,12 +2113,14 @@ void launch_sweep16(const SweepArgs& a_, int nreads, int C, hipStream_t s) {
     a.table_members = a.rev ? a.rmembers : a.fmembers;
     // a sweep that writes records and is not asked for column maxima skips their tracking
     // (until round 5 the forward sweep of the record pipeline was a third form, kColmax = 2: packed maxima without their cells)
-    if (a.frec && !a.colmax_out) launch_sweep16_c<0, true>(a, nreads, C, s);
-    else if (a.frec) launch_sweep16_c<1, true>(a, nreads, C, s);
+    // (records WITH column maxima, <.., 1, true, ..>, were 16 more instantiations until the launch log showed that no pipeline asks
+    // for them: the maxima of a record sweep come out of its records, k_colmax_rec.  Not compiled; null = nothing was launched)
+    if (a.frec && a.colmax_out) return nullptr;
+    if (a.frec) return launch_sweep16_c<0, true>(a, nreads, C, s);
     // -m 4 / -m 5: no best-member tracking at all (the variant below carries the column-maxima / threshold registers it
     // would never use and spilled 57 of them)
-    else if (!a.track_best && !a.colmax_out && !a.cand) launch_sweep16_c<0, false>(a, nreads, C, s);
-    else launch_sweep16_c<1, false>(a, nreads, C, s);
+    if (!a.track_best && !a.colmax_out && !a.cand) return launch_sweep16_c<0, false>(a, nreads, C, s);
+    return launch_sweep16_c<1, false>(a, nreads, C, s);
 }
 
 }  // namespace rg

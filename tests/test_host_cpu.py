@@ -124,7 +124,7 @@ def test_option_switches(rg):
     option table round-trips, a switch normalises to 0 / 1, an integer is clamped at both ends of its range."""
     from recgraph_amd import _lib, api
     lib = _lib.load()
-    for name in ("sweep_i32", "three_sweeps", "no_frec", "debug"):
+    for name in ("sweep_i32", "three_sweeps", "no_frec", "debug", "launch_log"):
         assert lib.rg_get_option(name.encode()) == 0
         api.set_option(name, 1)
         assert lib.rg_get_option(name.encode()) == 1
@@ -133,7 +133,7 @@ def test_option_switches(rg):
     assert lib.rg_get_option(b"chunk_reads") == 2048
     api.set_option("chunk_reads", 0)
     table = _option_table()
-    assert len(table) == 20 and {"spec4_margin_x10", "retire_shift", "dsel_edge", "no_dsel"} <= {r[0] for r in table}
+    assert len(table) == 21 and {"spec4_margin_x10", "retire_shift", "dsel_edge", "no_dsel", "launch_log"} <= {r[0] for r in table}
     get = lambda n: lib.rg_get_option(n.encode())                      # noqa: E731
     for name, env, kind, lo, hi, default in table:
         assert env == "RG_" + name.upper() and lo <= default <= hi
@@ -162,12 +162,13 @@ def test_option_defaults_from_the_environment(rg):
     import subprocess
     import sys
     code = ("import json; from recgraph_amd import _lib; lib = _lib.load();"
-            "print(json.dumps({n: lib.rg_get_option(n.encode()) for n in ('no_spec', 'debug', 'no_frec', 'spec_margin', 'retire_shift', 'spec4_margin_x10', 'chunk_reads')}))")
+            "print(json.dumps({n: lib.rg_get_option(n.encode()) for n in ('no_spec', 'debug', 'no_frec', 'spec_margin', 'retire_shift', 'spec4_margin_x10', 'chunk_reads', 'launch_log')}))")
     env = dict(os.environ, RG_NO_SPEC="1", RG_DEBUG="0", RG_NO_FREC="", RG_SPEC_MARGIN="77", RG_RETIRE_SHIFT="99", RG_SPEC4_MARGIN_X10="30",
-               PYTHONPATH=ROOT)
+               RG_LAUNCH_LOG="1", PYTHONPATH=ROOT)
     env.pop("RG_CHUNK_READS", None)
     out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, check=True, cwd=ROOT).stdout
-    assert json.loads(out) == {"no_spec": 1, "debug": 0, "no_frec": 0, "spec_margin": 77, "retire_shift": 12, "spec4_margin_x10": 30, "chunk_reads": 0}
+    assert json.loads(out) == {"no_spec": 1, "debug": 0, "no_frec": 0, "spec_margin": 77, "retire_shift": 12, "spec4_margin_x10": 30, "chunk_reads": 0,
+                               "launch_log": 1}
 
 
 def test_graphs_that_are_not_topological_are_rejected(rg):

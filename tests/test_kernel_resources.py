@@ -9,33 +9,34 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_headline_sweep_variants_use_no_scratch():
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import kernel_resources
+    import kernel_matrix as KM          # the instantiation names: one statement of them for this test and the kernel matrix
     ks = {k["name"]: k for k in kernel_resources.report("rg_sweep16.hip")}
     # (template arguments: C, kColmax, kRec, kWide, kSemi)
-    headline = ["rg::k_sweep16<16, 0, true, false, false>",     # -m 8, both sweeps since round 5: records, no column maxima in the sweep
-                "rg::k_sweep16<16, 0, false, false, false>"]    # -m 4: no tracking at all
+    headline = [KM.SWEEP16_M8,     # -m 8, both sweeps since round 5: records, no column maxima in the sweep
+                KM.SWEEP16_M4]     # -m 4: no tracking at all
     for name in headline:
         k = ks[name]
         assert k["ScratchSize [bytes/lane]"] == 0 and k["VGPRs Spill"] == 0, (name, k)
         assert k["VGPRs"] <= 256 and k["Occupancy [waves/SIMD]"] >= 2, (name, k)
     # the -m 4 sweep: two waves per SIMD since the path retirement of round 6 went in (196 registers; compiled for three it spills
     # 25 and the stream loses: 279-319 k against 324-370 k reads/s at config 4) — and it must leave the small kernels their room
-    assert ks["rg::k_sweep16<16, 0, false, false, false>"]["VGPRs"] <= 200
+    assert ks[KM.SWEEP16_M4]["VGPRs"] <= 200
     # reads of 1024-2047 bases (32 columns per lane): a row is 16 registers and the record variant is at the 256-register limit —
     # a few spilled registers are tolerated, a relapse (one uniform branch in the alpha took it from 13 to 67) is not
     # (round 6: gather runs are compiled into this variant — 32 spilled registers, 132 bytes of scratch per lane — because they
     # pay all the same: 21.4 k -> 24.9 k reads/s at 1.5 kbp, profiles/r06_notes.md)
-    k32 = ks["rg::k_sweep16<32, 0, true, false, false>"]
+    k32 = ks[KM.SWEEP16_M8_C32]
     assert k32["VGPRs Spill"] <= 40 and k32["ScratchSize [bytes/lane]"] <= 160, k32
     # the record variant leaves 64 of a SIMD's 512 registers to the other handles' small kernels (two waves of <= 224), and
     # k_layer16 at <= 16 columns per lane fits into them: one more allocation granule on either side costs 2-3 % in the stream
-    assert ks["rg::k_sweep16<16, 0, true, false, false>"]["VGPRs"] <= 224, ks["rg::k_sweep16<16, 0, true, false, false>"]
-    kl = next(k for n, k in ks.items() if n.startswith("rg::k_layer16<16>"))
+    assert ks[KM.SWEEP16_M8]["VGPRs"] <= 224, ks[KM.SWEEP16_M8]
+    kl = ks[KM.LAYER16_C16]
     assert kl["VGPRs"] <= 64 and kl["VGPRs Spill"] <= 2, kl
     # the narrower instantiations of the same variants (shorter reads) and their semiglobal forms do not spill either
-    for c in (4, 8):
-        for v in ("0, true, false, false", "0, false, false, false", "0, true, false, true", "0, false, false, true"):
-            k = ks["rg::k_sweep16<%d, %s>" % (c, v)]
-            assert k["ScratchSize [bytes/lane]"] == 0, (c, v, k)
+    assert len(KM.SWEEP16_NO_SCRATCH) == 8
+    for name in KM.SWEEP16_NO_SCRATCH:
+        k = ks[name]
+        assert k["ScratchSize [bytes/lane]"] == 0, (name, k)
 
 
 def test_no_valu_write_into_a_wide_buffer_store_in_flight():
@@ -84,9 +85,11 @@ def test_poa_kernels_use_no_scratch():
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import kernel_resources
     seen = 0
-    for src, prefix in (("rg_poa.hip", "rg::k_m0_simd<"), ("rg_poa_banded.hip", "rg::k_poa_banded<")):
+    import kernel_matrix as KM
+    for src, kernel in (("rg_poa.hip", "k_m0_simd"), ("rg_poa_banded.hip", "k_poa_banded")):
+        variants = {KM.templ(kernel, a, b) for a in (True, False) for b in (True, False)}
         for k in kernel_resources.report(src):
-            if k["name"].startswith(prefix):
+            if k["name"] in variants:
                 seen += 1
                 assert k["ScratchSize [bytes/lane]"] == 0 and k["VGPRs Spill"] == 0, k
     assert seen == 8

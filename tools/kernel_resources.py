@@ -60,8 +60,21 @@ def report(src, defines=()):
                 cur[k.strip()] = v.strip()
     names = demangle([k["mangled"] for k in kernels])
     for k in kernels:
-        k["name"] = names.get(k["mangled"], k["mangled"]).replace("(rg::SweepArgs)", "").replace("void ", "")
+        k["name"] = kernel_name(names.get(k["mangled"], k["mangled"]))
     return kernels
+
+
+def kernel_name(demangled):
+    """The demangled symbol of a kernel without its return type and parameter list: "void rg::k_layer<16, true>(rg::LayerArgs)"
+    -> "rg::k_layer<16, true>" — the name the launch log records (csrc/rg_launch_log.hpp) and tests/kernel_matrix.py is keyed by."""
+    s = demangled[5:] if demangled.startswith("void ") else demangled
+    if s.endswith(")"):
+        depth = 0
+        for i in range(len(s) - 1, -1, -1):
+            depth += (s[i] == ")") - (s[i] == "(")
+            if depth == 0:
+                return s[:i]
+    return s
 
 
 # ---- --isa: static issue-class histogram of a kernel's loops (VERDICT r4 item 1a) -------------------------------------------
@@ -114,7 +127,7 @@ def isa_report(src, defines, want):
     names = demangle([n for _, n in starts])
     res = {}
     for (i, mangled) in starts:
-        name = names.get(mangled, mangled).replace("(rg::SweepArgs)", "").replace("void ", "")
+        name = kernel_name(names.get(mangled, mangled))
         if not any(w in name for w in want):
             continue
         end = next(j for j in range(i, len(text)) if text[j].startswith(".Lfunc_end"))
