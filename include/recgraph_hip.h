@@ -406,7 +406,7 @@ int32_t rg_stream_handles(rg_stream* s);      /* batch handles that aligned at l
  *   sweeps stores its direction word, not only those with a picked path), "no_pick2" (RG_NO_PICK2: the speculative bound from
  *   one-path picks only), "layer_i32" (RG_LAYER_I32: the layer rebuild in its i32 form), "lds_pad" (RG_LDS_PAD, 0..40960 bytes,
  *   experiments only: extra dynamic LDS per k_sweep16 workgroup, which lowers the waves per CU), "chunk_reads" (RG_CHUNK_READS,
- *   0..2^20: most reads one pathwise kernel launch takes; 0 = what the memory budget allows), "launch_log" (RG_LAUNCH_LOG: every
+ *   0..2^20: most reads one launch of a DP kernel takes, in the pathwise and in the POA modes; 0 = what the memory budget allows), "launch_log" (RG_LAUNCH_LOG: every
  *   kernel launch of a batch leaves a pseudo-entry "inst:<instantiation>" in rg_batch_kernel_* / rg_stream_kernel_* — the
  *   demangled kernel name with its template arguments, e.g. "inst:rg::k_sweep16<16, 0, true, false, false>", ms 0, launches
  *   counted; off: no such entry).

@@ -1,6 +1,6 @@
-// extern "C" surface of librecgraph_hip (see include/recgraph_hip.h) and the batch driver:
-// uploads graph + reads, sizes the HBM work buffers, launches the DP / search / traceback kernels
-// on one HIP stream with HIP-event timing per kernel, copies the packed records back.
+// extern "C" surface of librecgraph_hip (see include/recgraph_hip.h): handle creation and validation, the read loader (uploads
+// the reads, sizes the per-read buffers), the result accessors and the GAF text assembly.  The kernels are launched by the batch
+// drivers: rg_poa_driver.hip (POA modes), rg_strand_driver.hip over rg_path_driver.hip (pathwise modes).
 //
 // There is deliberately NO CPU fallback: without a usable HIP device every batch call returns
 // RG_ERR_NO_DEVICE.
@@ -41,182 +41,6 @@ int wait_stream_sleeping(void* stream, void* ev, bool spin) {
 }
 }  // namespace rg
 
-namespace {
-
-struct Timed {
-    rg_batch* b;
-    std::vector<std::pair<int, int>> pending;  // (stat index, event index)
-    size_t used = 0;
-    const bool log;                            // the launch log is on: "inst:" pseudo-entries, counted in collect()
-    std::vector<const char*> insts;
-    explicit Timed(rg_batch* b_) : b(b_), log(options().launch_log != 0) {}
-    int stat(const char* name) {
-        for (size_t i = 0; i < b->stats.size(); ++i) if (b->stats[i].name == name) return (int)i;
-        b->stats.push_back(KernelStat{name, 0, 0});
-        return (int)b->stats.size() - 1;
-    }
-    template <typename F>
-    int run(const char* name, F&& launch) {
-        if (used == b->ev_pool.size()) {
-            hipEvent_t a, c;
-            HIPCHK(hipEventCreate(&a));
-            HIPCHK(hipEventCreate(&c));
-            b->ev_pool.emplace_back(a, c);
-        }
-        auto& ev = b->ev_pool[used];
-        HIPCHK(hipEventRecord(ev.first, b->stream));
-        const char* label = launch();      // what the launcher dispatched (rg_launch_log.hpp)
-        if (log && label) insts.push_back(label);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(ev.second, b->stream));
-        pending.emplace_back(stat(name), (int)used);
-        ++used;
-        return RG_OK;
-    }
-    int collect() {
-        if (!b->done_ev) HIPCHK(hipEventCreateWithFlags(&b->done_ev, hipEventDisableTiming));
-        HIPCHK((hipError_t)wait_stream_sleeping(b->stream, b->done_ev, b->spin_wait));
-        for (auto& pe : pending) {
-            float ms = 0;
-            HIPCHK(hipEventElapsedTime(&ms, b->ev_pool[pe.second].first, b->ev_pool[pe.second].second));
-            b->stats[pe.first].ms += ms;
-            b->stats[pe.first].launches += 1;
-        }
-        pending.clear();
-        used = 0;
-        for (const char* l : insts) add_stat(b->stats, std::string("inst:") + l, 0, 1);
-        insts.clear();
-        return RG_OK;
-    }
-};
-
-// a new run of a handle: the kernels keep their slots, the launch log's entries go (a run with the log off shows none)
-void reset_stats(KernelStats& stats) {
-    stats.erase(std::remove_if(stats.begin(), stats.end(), [](const KernelStat& s) { return s.name.compare(0, 5, "inst:") == 0; }), stats.end());
-    for (auto& s : stats) { s.ms = 0; s.launches = 0; }
-}
-
-bool is_local(int mode) { return mode == RG_MODE_LOCAL_POA || mode == RG_MODE_LOCAL_POA_SCALAR || mode == RG_MODE_GAP_LOCAL_POA; }
-bool is_poa(int mode) {
-    return mode == RG_MODE_GLOBAL_POA || mode == RG_MODE_GLOBAL_POA_SCALAR || mode == RG_MODE_GAP_POA || is_local(mode);
-}
-
-// Local modes fill full (L-1) x W matrices: reads are processed in launches of as many reads as fit the free HBM.
-int run_local(rg_batch* b) {
-    const GraphTables* g = b->gt;
-    const HostGraph& h = b->g->h;
-    const int mode = b->p.mode;
-    const int planes = mode == RG_MODE_GAP_LOCAL_POA ? 2 : 1;
-    const int variant = mode == RG_MODE_LOCAL_POA ? 0 : mode == RG_MODE_LOCAL_POA_SCALAR ? 1 : 2;
-    const char* kname = variant == 0 ? "k_m1_local_simd" : variant == 1 ? "k_m1_local_scalar" : "k_m3_gap_local";
-    Timed T(b);
-    reset_stats(b->stats);
-    b->cap_cells = (long long)(h.L - 1) * (b->max_n + 1);
-    const size_t per_read = (size_t)b->cap_cells * planes * (sizeof(int) + sizeof(uint32_t));
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(hipMemGetInfo(&free_b, &total_b));
-    free_b += b->d_arena_m.bytes() + b->d_arena_pw.bytes();   // arenas of a previous run are reused
-    const size_t budget = b->mem_budget ? std::min(b->mem_budget, free_b / 10 * 9) : free_b / 4 * 3;
-    if (per_read > budget) return fail(RG_ERR_CAPACITY, "local POA: one read's L x W matrices exceed the free HBM");
-    const long long chunk = (long long)std::min<size_t>((size_t)b->nreads, budget / per_read);
-    int rc;
-    if ((rc = b->d_arena_m.alloc((size_t)chunk * b->cap_cells * planes)) ||
-        (rc = b->d_arena_pw.alloc((size_t)chunk * b->cap_cells * planes)))
-        return rc;
-    HIPCHK(hipMemsetAsync(b->d_cells.p, 0, sizeof(unsigned long long), b->stream));
-    PoaArgs a;
-    a.g = DevLnz{h.L, g->d_lnz.p, g->d_pred_off.p, g->d_pred_rows.p, g->d_r_values.p, g->d_min_pred.p};
-    for (int i = 0; i < 36; ++i) a.sc.t[i] = b->p.scores[i];
-    a.reads = b->in.reads; a.read_off = b->in.off; a.bad = b->in.bad; a.bta = b->in.bta; a.col0 = b->d_col0.p; a.rowmeta = b->d_rowmeta.p; a.rowmeta_b = b->d_rowmeta_b.p;
-    a.gap_open = b->p.gap_open; a.gap_ext = b->p.gap_ext; a.max_n = b->max_n; a.lds_read = b->max_n <= 16000 ? 1 : 0;
-    a.cap_cells = b->cap_cells; a.arena_m = b->d_arena_m.p; a.arena_pw = b->d_arena_pw.p; a.rinfo = b->d_rinfo.p;
-    a.rec = b->d_rec.p; a.ops = b->d_ops.p; a.oprows = b->d_oprows.p; a.ops_stride = b->ops_stride;
-    a.cells = b->d_cells.p;
-    for (long long base = 0; base < b->nreads; base += chunk) {
-        a.read_base = (int)base;
-        a.nreads = (int)std::min<long long>(chunk, b->nreads - base);
-        if ((rc = T.run(kname, [&] { return launch_local(a, variant, b->stream); }))) return rc;
-    }
-    if ((rc = T.collect())) return rc;
-    unsigned long long c = 0;
-    HIPCHK(hipMemcpy(&c, b->d_cells.p, sizeof c, hipMemcpyDeviceToHost));
-    b->cells = c;
-    b->cells_performed = c;
-    return RG_OK;
-}
-
-int run_poa(rg_batch* b) {
-    const GraphTables* g = b->gt;
-    const HostGraph& h = b->g->h;
-    if (!h.has_lnz) return fail(RG_ERR_ARG, "graph has no LnzGraph view");
-    const int mode = b->p.mode;
-    if (is_local(mode)) return run_local(b);
-    const int planes = mode == RG_MODE_GAP_POA ? 2 : 1;   // m2: m | y score planes, w0 | w1 path planes
-    Timed T(b);
-    reset_stats(b->stats);
-    int oom_shift = 0;      // the budget is halved every time an arena allocation fails (other handles / threads took the memory)
-    for (int attempt = 0; attempt < 24; ++attempt) {
-        int rc;
-        // Reads per launch: the band arenas of one launch take at most 45 % of the HBM that is free (plus what this
-        // handle already holds), so that a second handle of a streaming caller fits beside this one; a handle of the
-        // streaming engine has its own share of the device instead (mem_budget).
-        const size_t per_read = (size_t)b->cap_cells * planes * (sizeof(int) + sizeof(uint32_t)) + (size_t)h.L * sizeof(int4);
-        size_t free_b = 0, total_b = 0;
-        HIPCHK(hipMemGetInfo(&free_b, &total_b));
-        free_b += b->d_arena_m.bytes() + b->d_arena_pw.bytes() + b->d_rinfo.bytes();
-        const size_t budget = (b->mem_budget ? std::min(b->mem_budget, free_b / 10 * 9) : free_b / 100 * 45) >> oom_shift;
-        if (per_read > budget) return fail(RG_ERR_CAPACITY, "band arena of one read exceeds the free HBM");
-        const long long maxchunk = (long long)std::min<size_t>((size_t)b->nreads, budget / per_read);
-        const long long nchunks = (b->nreads + maxchunk - 1) / maxchunk;
-        const long long chunk = (b->nreads + nchunks - 1) / nchunks;      // even launches
-        if (options().debug) fprintf(stderr, "[rg] run_poa attempt %d: cap_cells %lld, budget %.1f GB, per read %.2f MB, chunk %lld of %lld reads\n", attempt,
-                                     b->cap_cells, budget / 1e9, per_read / 1e6, chunk, (long long)b->nreads);
-        if ((rc = b->d_arena_m.alloc((size_t)chunk * b->cap_cells * planes)) ||
-            (rc = b->d_arena_pw.alloc((size_t)chunk * b->cap_cells * planes)) || (rc = b->d_rinfo.alloc((size_t)chunk * h.L))) {
-            if (rc == RG_ERR_HIP && chunk > 1 && oom_shift < 8) { ++oom_shift; continue; }   // out of memory: smaller launches
-            return rc;
-        }
-        HIPCHK(hipMemsetAsync(b->d_cells.p, 0, sizeof(unsigned long long), b->stream));
-        PoaArgs a;
-        a.g = DevLnz{h.L, g->d_lnz.p, g->d_pred_off.p, g->d_pred_rows.p, g->d_r_values.p, g->d_min_pred.p};
-        for (int i = 0; i < 36; ++i) a.sc.t[i] = b->p.scores[i];
-        a.reads = b->in.reads; a.read_off = b->in.off; a.bad = b->in.bad; a.bta = b->in.bta; a.col0 = b->d_col0.p; a.rowmeta = b->d_rowmeta.p; a.rowmeta_b = b->d_rowmeta_b.p;
-        a.max_n = b->max_n; a.lds_read = b->max_n <= 16000 ? 1 : 0; a.gap_open = b->p.gap_open; a.gap_ext = b->p.gap_ext;
-        a.cap_cells = b->cap_cells; a.arena_m = b->d_arena_m.p; a.arena_pw = b->d_arena_pw.p; a.rinfo = b->d_rinfo.p;
-        a.rec = b->d_rec.p; a.ops = b->d_ops.p; a.oprows = b->d_oprows.p; a.ops_stride = b->ops_stride;
-        a.cells = b->d_cells.p;
-        for (long long base = 0; base < b->nreads; base += chunk) {
-            a.read_base = (int)base;
-            a.nreads = (int)std::min<long long>(chunk, b->nreads - base);
-            if (mode == RG_MODE_GLOBAL_POA) { if ((rc = T.run("k_m0_simd", [&] { return launch_m0_simd(a, b->stream); }))) return rc; }
-            else if (mode == RG_MODE_GAP_POA) { if ((rc = T.run("k_m2_gap", [&] { return launch_m2(a, b->stream); }))) return rc; }
-            else { if ((rc = T.run("k_m0_scalar", [&] { return launch_m0_scalar(a, b->stream); }))) return rc; }
-        }
-        if ((rc = T.collect())) return rc;
-        // overflow check: a read whose band cells did not fit asks for a bigger arena
-        b->rec.resize(b->nreads);
-        HIPCHK(hipMemcpy(b->rec.data(), b->d_rec.p, sizeof(DevRecord) * b->nreads, hipMemcpyDeviceToHost));
-        bool ovf = false;
-        for (auto& r : b->rec) if (r.status & ST_OVERFLOW) { ovf = true; break; }
-        if (!ovf) {
-            unsigned long long c = 0;
-            HIPCHK(hipMemcpy(&c, b->d_cells.p, sizeof c, hipMemcpyDeviceToHost));
-            b->cells = c;
-            b->cells_performed = c;      // (the POA kernels evaluate exactly the band cells they count)
-            return RG_OK;
-        }
-        const long long full = (long long)h.L * (b->max_n + 1);
-        if (b->cap_cells >= full) return fail(RG_ERR_CAPACITY, "band arena overflow at full size");
-        b->cap_cells = std::min(full, b->cap_cells * 2);
-        reset_stats(b->stats);
-    }
-    return fail(RG_ERR_CAPACITY, "band arena overflow");
-}
-
-}  // namespace
-
-// pathwise driver lives in rg_path_driver.hip
-int rg_run_pathwise(rg_batch* b);
 // Text of read i exactly as the reference prints it (warning lines + GAFStruct::to_string), appended to `out`.
 extern "C" {
 static bool build_fields(const rg_batch* b, int64_t i, const char* name, GafFields& out);
@@ -509,15 +333,7 @@ static int load_reads(rg_batch* b, const char* reads, const int64_t* read_off, i
     const bool both = !is_poa(mode) && (p->amb_mode & RG_AMB_BOTH_STRANDS);
     if (both) b->ops_stride = (b->ops_stride + 15) & ~15ll;      // k_strand_merge moves op bytes in 16-byte pieces
     if ((rc = b->d_ops.alloc((size_t)nreads * b->ops_stride))) return rc;
-    if (both) {
-        // the second pass's inputs and its record / op area: 64 B + ops_stride per read, worst case every read
-        if ((rc = b->d_sidx.alloc((size_t)nreads)) || (rc = b->d_ssum.alloc(2)) || (rc = b->d_rcoff.alloc((size_t)nreads + 1)) ||
-            (rc = b->d_rc.alloc(total + 64)) || (rc = b->d_rcbad.alloc((size_t)nreads)) || (rc = b->d_rec2.alloc((size_t)nreads)) ||
-            (rc = b->d_ops2.alloc((size_t)nreads * b->ops_stride)) || (rc = b->h_ssum.alloc(2)))
-            return rc;
-        if ((p->amb_mode & RG_AMB_STRAND_VOTE) && ((rc = b->d_first_rev.alloc((size_t)nreads)) || (rc = b->d_pa.alloc(total + 64))))
-            return rc;
-    }
+    if (both && (rc = size_strand_buffers(b, total))) return rc;
     if (is_poa(mode)) {
         if ((rc = b->d_oprows.alloc((size_t)nreads * b->ops_stride))) return rc;
         long long maxbta = 0;
@@ -582,37 +398,8 @@ int32_t rg_batch_create(const rg_graph* gc, const rg_params* p, const char* read
         if (hipStreamCreateWithPriority(&b->stream, hipStreamNonBlocking, greatest) != hipSuccess)
             HIPCHK(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
     }
-    if (is_poa(mode)) {
-        // column-0 chain of m0 (global_abpoa.rs:36-46): depends on graph + scores only
-        const HostGraph& h = g->h;
-        std::vector<int> col0(h.L, 0);
-        for (int i = 1; i + 1 < h.L; ++i) {
-            int c = base_code(h.lnz[i]);
-            col0[i] = col0[h.min_pred[i]] + p->scores[c * 6 + 5];
-        }
-        if ((rc = b->d_col0.upload(col0))) return rc;
-        if (mode == RG_MODE_GLOBAL_POA) {
-            // (k_m0_simd only) the per-row record of PoaArgs::rowmeta
-            std::vector<int4> rm(h.L, make_int4(0, 0, 0, 0));
-            for (int i = 0; i < h.L; ++i) {
-                const int pbeg = (int)h.pred_off[i], pend = (int)h.pred_off[i + 1];
-                const int p0 = pend > pbeg ? (int)h.pred_rows[pbeg] : -1;
-                const int c = (i >= 1 && i + 1 < h.L) ? base_code(h.lnz[i]) : 4;
-                rm[i] = make_int4(pend, (int)h.r_values[i], col0[i], (p0 + 1) | ((c < 0 ? 4 : c) << 24));
-            }
-            if ((rc = b->d_rowmeta.upload(rm))) return rc;
-        }
-        if (mode == RG_MODE_GLOBAL_POA_SCALAR || mode == RG_MODE_GAP_POA) {
-            std::vector<int4> rm(h.L, make_int4(0, 0, 0, 0));
-            for (int i = 0; i < h.L; ++i) {
-                const int pbeg = (int)h.pred_off[i], pend = (int)h.pred_off[i + 1];
-                const int p0 = pend > pbeg ? (int)h.pred_rows[pbeg] : -1;
-                const int c = (i >= 1 && i + 1 < h.L) ? base_code(h.lnz[i]) : 4;
-                rm[i] = make_int4(pend, (int)h.r_values[i], i > 0 ? (int)h.min_pred[i] : 0, (p0 + 1) | ((c < 0 ? 4 : c) << 24));
-            }
-            if ((rc = b->d_rowmeta_b.upload(rm))) return rc;
-        }
-    }
+    b->timer.stream = b->stream;
+    if (is_poa(mode) && (rc = poa_upload_tables(b.get()))) return rc;
     if ((rc = load_reads(b.get(), reads, read_off, nreads))) return rc;
     *out = b.release();
     return RG_OK;
@@ -636,8 +423,11 @@ int32_t rg_batch_run(rg_batch* b) {
     b->fetched = false;
     DevGuard dg(b->dev);
     HIPCHK(dg.err);
-    if (is_poa(b->p.mode)) return run_poa(b);
-    return rg_run_pathwise(b);
+    // one rule for the statistics: reset here, once; every pass of either driver adds (rg_path_args.hpp)
+    reset_stats(b->stats);
+    b->timer.reset();
+    b->timer.spin = b->spin_wait;
+    return is_poa(b->p.mode) ? run_poa(b) : rg_run_pathwise(b);
 }
 
 int32_t rg_batch_fetch(rg_batch* b) {
@@ -750,70 +540,3 @@ int32_t rg_align_batch(const rg_graph* g, const rg_params* p, const char* reads,
 }
 
 }  // extern "C"
-
-// ---- pathwise modes: buffers are owned by PathWork, kernels by rg_path_driver.hip ----
-int rg_run_pathwise(rg_batch* b) {
-    const GraphTables* g = b->gt;
-    const HostGraph& h = b->g->h;
-    PathGraphDev gd;
-    gd.L = h.L; gd.P = h.P; gd.lnz = g->d_lnz.p; gd.row_mask = g->d_row_mask.p; gd.knm = g->d_knm.p;
-    gd.dfs = g->d_dfs.p; gd.dfe = g->d_dfe.p; gd.fgoff = g->d_fgoff.p; gd.rgoff = g->d_rgoff.p;
-    gd.fgroups = g->d_fgroups.p; gd.rgroups = g->d_rgroups.p; gd.fslots = h.fslots; gd.rslots = h.rslots;
-    gd.node_id = g->d_node_id.p; gd.segfirst = g->d_segfirst.p; gd.seglast = g->d_seglast.p;
-    gd.eoff = g->d_eoff.p; gd.epred = g->d_epred.p; gd.emask = g->d_emask.p; gd.roff = g->d_roff.p; gd.rsucc = g->d_rsucc.p;
-    gd.rmask = g->d_rmask.p; gd.pnwp = g->d_pnwp.p; gd.rnwp = g->d_rnwp.p;
-    // what this handle already holds counts towards its share of the device
-    unsigned long long c[2] = {0, 0};
-    b->pw.spin_wait = b->spin_wait;
-    const int n = (int)b->nreads;
-    const bool vote = (b->p.amb_mode & RG_AMB_STRAND_VOTE) != 0;
-    Timed T(b);
-    int rc;
-    // the reads of the first pass: as given, or (RG_AMB_STRAND_VOTE, rg_strand_vote.hip) each on the strand its 12-mers vote
-    // for, at the same offsets; no host synchronisation in front of the pass
-    const uint8_t* reads_a = b->in.reads;
-    if (vote) {
-        const uint32_t* keys = nullptr;
-        unsigned table_mask = 0;
-        if ((rc = path_driver_vote_table(h, b->pw, &keys, &table_mask))) return rc;
-        b->stats.clear();
-        StrandVoteArgs va{b->in.reads, b->in.off, b->in.bad, keys, table_mask, b->d_first_rev.p};
-        if ((rc = T.run("k_strand_vote", [&] { return launch_strand_vote(va, n, b->stream); }))) return rc;
-        StrandOrientArgs oa{b->in.reads, b->in.off, b->d_first_rev.p, b->d_pa.p};
-        if ((rc = T.run("k_strand_orient", [&] { return launch_strand_orient(oa, n, b->stream); }))) return rc;
-        reads_a = b->d_pa.p;
-        KernelStats st1;
-        if ((rc = path_driver_run(h, gd, b->p, b->pw, reads_a, b->in.off, b->in.bad, n, b->max_n, b->d_rec.p, b->d_ops.p, b->ops_stride,
-                                  b->d_cells.p, b->stream, b->mem_budget, c, st1, 0)))
-            return rc;
-        for (auto& e : st1) add_stat(b->stats, e.name, e.ms, e.launches);
-    } else if ((rc = path_driver_run(h, gd, b->p, b->pw, b->in.reads, b->in.off, b->in.bad, n, b->max_n, b->d_rec.p, b->d_ops.p,
-                                     b->ops_stride, b->d_cells.p, b->stream, b->mem_budget, c, b->stats, 0)))
-        return rc;
-    b->cells = c[0];
-    b->cells_performed = c[1];
-    if (!(b->p.amb_mode & RG_AMB_BOTH_STRANDS)) return RG_OK;
-    // ---- RG_AMB_BOTH_STRANDS (rg_strand.hip): the qualifying reads once more, on the other strand, in the same work buffers ----
-    const int recomb = b->p.mode == RG_MODE_RECOMBINATION || b->p.mode == RG_MODE_RECOMBINATION_SEMI ? 1 : 0;
-    StrandGateArgs ga{b->d_rec.p, b->in.off, n, recomb, b->d_sidx.p, b->d_rcoff.p, b->d_ssum.p, vote ? b->d_first_rev.p : nullptr};
-    if ((rc = T.run("k_strand_gate", [&] { return launch_strand_gate(ga, b->stream); }))) return rc;
-    RevcompArgs ra{reads_a, b->in.off, b->d_sidx.p, b->d_rcoff.p, b->d_ssum.p, b->d_rc.p};
-    if ((rc = T.run("k_revcomp", [&] { return launch_revcomp(ra, n, b->stream); }))) return rc;
-    HIPCHK(hipMemcpyAsync(b->h_ssum.p, b->d_ssum.p, 2 * sizeof(int), hipMemcpyDeviceToHost, b->stream));
-    if ((rc = T.collect())) return rc;
-    const int count = b->h_ssum.p[0], max_len = b->h_ssum.p[1];
-    if (count <= 0) return RG_OK;
-    if (count > n || max_len < 1 || max_len > b->max_n) return fail(RG_ERR_HIP, "k_strand_gate returned an impossible read count / length");
-    HIPCHK(hipMemsetAsync(b->d_rcbad.p, 0, (size_t)count, b->stream));
-    KernelStats st2;
-    unsigned long long c2[2] = {0, 0};
-    if ((rc = path_driver_run(h, gd, b->p, b->pw, b->d_rc.p, b->d_rcoff.p, b->d_rcbad.p, count, max_len, b->d_rec2.p, b->d_ops2.p,
-                              b->ops_stride, b->d_cells.p, b->stream, b->mem_budget, c2, st2, 0)))
-        return rc;
-    for (auto& e : st2) add_stat(b->stats, e.name, e.ms, e.launches);
-    b->cells += c2[0];                  // (the workload grew: both counters include the second pass)
-    b->cells_performed += c2[1];
-    StrandMergeArgs ma{b->d_rec.p, b->d_ops.p, b->d_rec2.p, b->d_ops2.p, b->ops_stride, b->d_sidx.p, count, recomb};
-    if ((rc = T.run("k_strand_merge", [&] { return launch_strand_merge(ma, b->stream); }))) return rc;
-    return T.collect();
-}

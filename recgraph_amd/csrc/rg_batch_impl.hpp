@@ -1,5 +1,6 @@
-// Private definitions shared by rg_abi.hip (the extern "C" surface + batch driver) and rg_stream.hip (the streaming
-// engine): pinned buffers (device buffers: DevBuf in rg_path_args.hpp), the per-device graph tables and the batch handle.  Not part of the C ABI.
+// Private definitions shared by rg_abi.hip (the extern "C" surface, read loading, result accessors), the batch drivers
+// (rg_poa_driver.hip, rg_strand_driver.hip) and rg_stream.hip (the streaming engine): pinned buffers (device buffers and HIPCHK:
+// rg_path_args.hpp), the per-device graph tables and the batch handle.  Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -11,21 +12,12 @@
 #include <vector>
 
 #include "rg_host.hpp"
+#include "rg_kernel_timer.hpp"
 #include "rg_path_args.hpp"
 #include "rg_poa_args.hpp"
 #include "rg_strand.hpp"
 
 using namespace rg;
-
-#define HIPCHK(x)                                                                                       \
-    do {                                                                                                \
-        hipError_t e_ = (x);                                                                            \
-        if (e_ != hipSuccess) {                                                                         \
-            (void)hipGetLastError(); /* clears the sticky error: the handle stays usable after a failed call */ \
-            return fail(e_ == hipErrorNoDevice || e_ == hipErrorInvalidDevice ? RG_ERR_NO_DEVICE : RG_ERR_HIP, \
-                        std::string(#x) + ": " + hipGetErrorString(e_));                                \
-        }                                                                                               \
-    } while (0)
 
 // Device copy of the flattened graph: one per HIP device that has a batch on this graph (built on first use, under the
 // graph's mutex; the host arrays are immutable after creation, so a graph handle is shareable across threads and devices).
@@ -42,6 +34,7 @@ struct GraphTables {
     DevBuf<int> d_eoff, d_epred, d_roff, d_rsucc;
     DevBuf<uint64_t> d_emask, d_rmask;
     DevBuf<uint8_t> d_pnwp, d_rnwp;
+    PathGraphDev pgd{};                // the PathGraph view as the pathwise kernels take it (graph + device only: filled once, here)
 };
 
 struct rg_graph {
@@ -111,6 +104,9 @@ static int upload_graph(rg_graph* gr, GraphTables** out) {
             (rc = g->d_emask.upload(flat(h.emask))) || (rc = g->d_roff.upload(h.roff)) || (rc = g->d_rsucc.upload(h.rsucc)) ||
             (rc = g->d_rmask.upload(flat(h.rmask))) || (rc = g->d_pnwp.upload(h.pnwp)) || (rc = g->d_rnwp.upload(h.rnwp)))
             return rc;
+        g->pgd = PathGraphDev{h.L, h.P, g->d_lnz.p, g->d_row_mask.p, g->d_knm.p, g->d_dfs.p, g->d_dfe.p, g->d_fgoff.p, g->d_rgoff.p,
+                              g->d_fgroups.p, g->d_rgroups.p, h.fslots, h.rslots, g->d_node_id.p, g->d_segfirst.p, g->d_seglast.p,
+                              g->d_eoff.p, g->d_epred.p, g->d_emask.p, g->d_roff.p, g->d_rsucc.p, g->d_rmask.p, g->d_pnwp.p, g->d_rnwp.p};
     }
     *out = g.get();
     gr->tables[dev] = std::move(g);
@@ -199,16 +195,20 @@ struct rg_batch {
     std::vector<int32_t> oprows;
     bool fetched = false;
     uint64_t cells = 0, cells_performed = 0;
-    KernelStats stats;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
-    hipEvent_t done_ev = nullptr;      // end-of-run marker polled by wait_stream_sleeping
+    KernelStats stats;                 // reset once per rg_batch_run, added to by every pass (rg_path_args.hpp)
+    KernelTimer timer;                 // ... through this, the handle's one event pool
     ~rg_batch() {
-        for (auto& e : ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-        if (done_ev) (void)hipEventDestroy(done_ev);
         if (stream) (void)hipStreamDestroy(stream);
     }
 };
 
+// ---- the batch drivers behind rg_batch_create / rg_batch_run ----
+bool is_poa(int mode);                 // one of the six POA modes (rg_poa_driver.hip: its mode table)
+int poa_upload_tables(rg_batch* b);    // column 0 and the per-row records of the handle's POA kernel (graph + scores only)
+int run_poa(rg_batch* b);
+int rg_run_pathwise(rg_batch* b);      // rg_strand_driver.hip: the pathwise modes, one strand or both
+// the buffers RG_AMB_BOTH_STRANDS / RG_AMB_STRAND_VOTE add to a pathwise handle, for `total` bases in b->nreads reads
+int size_strand_buffers(rg_batch* b, size_t total);
 
 // ---- internals shared with the streaming engine (rg_stream.hip) ----
 void rg_batch_destroy_impl(rg_batch* b);

@@ -43,7 +43,7 @@ extern thread_local std::string g_last_error;
     X(no_pick2, "RG_NO_PICK2", B, 0, 1, 0)            /* the speculative bound from one-path picks only (no two-path picks) */ \
     X(layer_i32, "RG_LAYER_I32", B, 0, 1, 0)          /* k_layer in its i32 form even when the sweep ran packed (test hook) */ \
     X(lds_pad, "RG_LDS_PAD", I, 0, 40 << 10, 0)       /* (experiments only) extra dynamic LDS bytes per k_sweep16 workgroup: lowers the waves per CU */ \
-    X(chunk_reads, "RG_CHUNK_READS", I, 0, 1 << 20, 0)   /* most reads one pathwise kernel launch takes (0: what the HBM budget allows, <= 8192) */ \
+    X(chunk_reads, "RG_CHUNK_READS", I, 0, 1 << 20, 0)   /* most reads one launch of a DP kernel takes, pathwise and POA (0: what the HBM budget allows; pathwise: <= 8192) */ \
     X(launch_log, "RG_LAUNCH_LOG", B, 0, 1, 0)        /* every kernel launch leaves an "inst:<instantiation>" pseudo-entry in the batch's kernel statistics (rg_launch_log.hpp: ms 0, launches counted) */
 struct Options {
 #define RG_OPTION_FIELD(name, env, kind, lo, hi, def) std::atomic<int> name{def};
@@ -70,6 +70,13 @@ Options& options();
 int wait_stream_sleeping(void* stream, void* ev, bool spin = false);   // spin: this handle asked for hipStreamSynchronize (rg_stream_opts.spin_wait)
 
 int fail(int code, const std::string& msg);
+
+// Reads per launch when `n` reads go through launches of at most `maxchunk` (both >= 1): as few launches as that allows, and
+// those even, so no short tail launch.  Every launch but the last takes the result, the last what is left (at least one read).
+inline long long even_chunks(long long n, long long maxchunk) {
+    const long long nchunks = (n + maxchunk - 1) / maxchunk;
+    return (n + nchunks - 1) / nchunks;
+}
 
 // Path sets: the reference uses BitVec(paths_number) (pathwise_graph.rs:10-18); here a fixed 256-bit mask (4 words),
 // of which the kernels see one 64-path PAGE at a time.

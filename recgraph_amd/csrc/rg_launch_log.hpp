@@ -4,8 +4,9 @@
 // symbol of the code object without its parameter list (what tools/kernel_resources.py report() prints:
 // "rg::k_sweep16<16, 0, true, false, false>", "rg::k_pick").  The macro takes the template arguments ONCE and uses that one
 // token list for the launch and for the name, inside the `case` / `if` that dispatches: the log cannot state another rule
-// than the dispatch.  The drivers hand the name to their timers (Timer::inst, Timed::run), which turn it into an "inst:<name>"
-// pseudo-entry of the batch's KernelStats (ms 0, launches counted) when the option is on and drop it otherwise.  Host code only.
+// than the dispatch.  The drivers hand the name to the handle's timer (KernelTimer::run, KernelTimer::inst: rg_kernel_timer.hpp), which
+// turns it into an "inst:<name>" pseudo-entry of the batch's KernelStats (ms 0, launches counted) when the option is on and drops it
+// otherwise; a launcher that returns null launched nothing, and the timer reports RG_ERR_ARG.  Host code only.
 #pragma once
 #include <hip/hip_runtime.h>
 

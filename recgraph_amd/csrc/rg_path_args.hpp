@@ -1,5 +1,5 @@
-// Argument blocks and work buffers of the pathwise (-m 4 / -m 8) kernels; device buffers, kernel statistics and the entry of
-// their driver (rg_path_driver.hip) as the batch code (rg_abi.hip) sees them.
+// Argument blocks and work buffers of the pathwise (-m 4 / -m 8) kernels; device buffers, the HIP error check, kernel statistics
+// and the entry of their driver (rg_path_driver.hip) as its callers (rg_strand_driver.hip, and the driver itself) see it.
 #pragma once
 #include <string>
 #include <utility>
@@ -36,6 +36,24 @@ struct PathGraphDev {
     const uint8_t* rnwp;
 };
 
+// A failed HIP call as a status code (the sticky error is cleared: the handle stays usable after a failed call); a lost or
+// absent device is RG_ERR_NO_DEVICE in every driver.
+inline int hip_fail(hipError_t e, const std::string& what) {
+    (void)hipGetLastError();
+    return fail(e == hipErrorNoDevice || e == hipErrorInvalidDevice ? RG_ERR_NO_DEVICE : RG_ERR_HIP, what + ": " + hipGetErrorString(e));
+}
+#define HIPCHK(x)                                             \
+    do {                                                      \
+        hipError_t e_ = (x);                                  \
+        if (e_ != hipSuccess) return ::rg::hip_fail(e_, #x);  \
+    } while (0)
+// a status code other than RG_OK ends the calling function
+#define RG_TRY(x)                 \
+    do {                          \
+        const int rc_ = (x);      \
+        if (rc_) return rc_;      \
+    } while (0)
+
 // device buffer that only grows
 template <typename T>
 struct DevBuf {
@@ -51,11 +69,9 @@ struct DevBuf {
         if (count == 0) count = 1;
         const hipError_t e = hipMalloc((void**)&p, count * sizeof(T));
         if (e != hipSuccess) {
-            (void)hipGetLastError();      // clears the sticky error: the handle stays usable after a failed call
             p = nullptr;
             if (oom && e == hipErrorOutOfMemory) *oom = true;
-            return fail(e == hipErrorNoDevice || e == hipErrorInvalidDevice ? RG_ERR_NO_DEVICE : RG_ERR_HIP,
-                        std::string("hipMalloc of ") + std::to_string(count * sizeof(T)) + " bytes: " + hipGetErrorString(e));
+            return hip_fail(e, "hipMalloc of " + std::to_string(count * sizeof(T)) + " bytes");
         }
         n = count;
         return RG_OK;
@@ -67,41 +83,66 @@ struct DevBuf {
         if (rc) return rc;
         if (v.empty()) return RG_OK;
         const hipError_t e = hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-        if (e == hipSuccess) return RG_OK;
-        (void)hipGetLastError();
-        return fail(e == hipErrorNoDevice || e == hipErrorInvalidDevice ? RG_ERR_NO_DEVICE : RG_ERR_HIP,
-                    std::string("hipMemcpy of ") + std::to_string(v.size() * sizeof(T)) + " bytes to the device: " + hipGetErrorString(e));
+        return e == hipSuccess ? RG_OK : hip_fail(e, "hipMemcpy of " + std::to_string(v.size() * sizeof(T)) + " bytes to the device");
     }
 };
 
-// per-kernel device time of a batch; "mem:work_bytes_per_read" is a pseudo-entry of the pathwise driver (`ms` holds bytes)
+// Per-kernel device time of a batch.  rg_batch_run resets the handle's statistics once (reset_stats); every pass of every driver
+// then ADDS into them (add_stat), so a name has one entry however many passes and chunks launched it.  Pseudo-entries:
+// "mem:work_bytes_per_read" of the pathwise driver (`ms` holds bytes summed over the chunks, `launches` the chunks) and the
+// launch log's "inst:<instantiation>" (rg_launch_log.hpp).
 struct KernelStat {
     std::string name;
     double ms = 0;
     long long launches = 0;
 };
 using KernelStats = std::vector<KernelStat>;
-// adds (ms, count) to the entries called `name`, or appends one
 inline void add_stat(KernelStats& stats, const std::string& name, double ms, long long count) {
-    bool found = false;
     for (auto& st : stats)
-        if (st.name == name) { st.ms += ms; st.launches += count; found = true; }
-    if (!found) stats.push_back(KernelStat{name, ms, count});
+        if (st.name == name) { st.ms += ms; st.launches += count; return; }
+    stats.push_back(KernelStat{name, ms, count});
+}
+// a new run (or a new attempt of a regrown one): the kernels keep their slots, the launch log's entries go (a run with the log off shows none)
+inline void reset_stats(KernelStats& stats) {
+    size_t n = 0;
+    for (auto& s : stats)
+        if (s.name.compare(0, 5, "inst:") != 0) stats[n++] = KernelStat{s.name, 0, 0};
+    stats.resize(n);
 }
 
 struct PathWorkImpl;
 struct PathWork {
     PathWorkImpl* impl = nullptr;
-    bool spin_wait = false;     // the owning handle waits for the device with hipStreamSynchronize (rg_stream_opts.spin_wait)
     ~PathWork();
 };
 
-// One pathwise batch on `stream` (rg_path_driver.hip).  cells_out [2]: cell updates counted | performed; stats: cleared, then one
-// entry per kernel name; spec_level: 0 from outside (the driver calls itself with 1 and 2 for reads whose speculative bound failed).
-int path_driver_run(const HostGraph& h, const PathGraphDev& gd, const rg_params& p, PathWork& w, const uint8_t* d_reads,
-                    const long long* d_off, const uint8_t* d_bad, int nreads, int max_n, DevRecord* d_rec, uint8_t* d_ops,
-                    long long ops_stride, unsigned long long* d_cells, hipStream_t stream, size_t mem_budget,
-                    unsigned long long* cells_out, KernelStats& stats, int spec_level);
+// One pathwise batch (rg_path_driver.hip) is a CONTEXT, what every pass of a run shares, and a JOB, the reads of one pass and where
+// their records go.  spec_level: 0 from outside (the driver calls itself with 1 and 2 for reads whose speculative bound failed,
+// on work buffers and a cell counter of that pass's own).
+struct KernelTimer;
+struct PathCtx {
+    const HostGraph& h;
+    const PathGraphDev& gd;
+    const rg_params& p;
+    PathWork& w;
+    hipStream_t stream;
+    unsigned long long* d_cells;    // [2] device counters: cell updates counted | performed
+    size_t mem_budget;              // bytes the work buffers of one chunk may take (0: three quarters of the free HBM)
+    KernelTimer& T;
+    KernelStats& stats;             // added to
+    int spec_level;
+};
+struct PathJob {
+    const uint8_t* reads;           // base codes at `off`
+    const long long* off;           // [nreads + 1]
+    const uint8_t* bad;             // [nreads]
+    int nreads, max_n;
+    DevRecord* rec;                 // out [nreads]
+    uint8_t* ops;                   // out [nreads][ops_stride]
+    long long ops_stride;
+};
+// cells [2]: the job's cell updates, counted | performed, are ADDED
+int path_driver_run(const PathCtx& c, const PathJob& j, unsigned long long* cells);
 
 // The 12-mer table of the paths that `w` holds for k_pick (built with the handle's other per-graph tables on first use):
 // its keys and slot mask, for a vote that runs before the first path_driver_run (RG_AMB_STRAND_VOTE, rg_strand_vote.hip).

@@ -1,5 +1,6 @@
-// Batch driver of the pathwise modes (-m 4, -m 8): sizes the HBM work buffers, runs the kernel
-// pipeline on one stream with HIP-event timing per kernel, regrows the candidate lists on overflow.
+// Pipeline driver of the pathwise modes (-m 4, -m 8): one pass (path_driver_run: a context and a job, rg_path_args.hpp) sizes
+// the HBM work buffers, runs the kernel pipeline on the handle's stream in even chunks, timed by the handle's KernelTimer, and
+// regrows the candidate lists on overflow.  The passes of a batch are put together by rg_strand_driver.hip.
 //
 //   -m 4:  sweep(F, dirs) -> seed -> layer(F) -> trace
 //   -m 8:  sweep(F1: column maxima) -> seed -> thr -> sweep(R: dirs, candidates, column maxima)
@@ -10,16 +11,11 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "rg_kernel_timer.hpp"
 #include "rg_path_kernels.hpp"
 #include "rg_path_plan.hpp"
 
 namespace rg {
-
-#define HIPCHK(x)                                                                            \
-    do {                                                                                     \
-        hipError_t e_ = (x);                                                                 \
-        if (e_ != hipSuccess) { (void)hipGetLastError(); /* clears the sticky error */ return fail(RG_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); } \
-    } while (0)
 
 struct PathWorkImpl {
     bool tables = false;
@@ -39,8 +35,6 @@ struct PathWorkImpl {
     int retire_shift = RG_SWEEP16_RETIRE_SHIFT;              // the evaluation period the lead tables were built for
     unsigned long long fmembers = 0, rmembers = 0;           // member rows of the forward / reverse table (sum of the group sizes)
     unsigned fcap = 0, rcap = 0;
-    std::vector<hipEvent_t> ev;
-    hipEvent_t done_ev = nullptr;       // end-of-chunk marker polled by wait_stream_sleeping (no spinning host thread per handle)
     DevBuf<unsigned> need;                 // [8] per chunk: largest nf, nr, forward / reverse record count of a read (k_need); [4] reads whose
                                         // speculative bound failed (k_verify)
     // speculative bound (PickArgs): 12-mer table of the paths, per-read pick, and what aligning the failed reads again needs
@@ -54,76 +48,11 @@ struct PathWorkImpl {
     DevBuf<unsigned long long> rt_cells;
     PathWork retry;                     // work buffers of that second pass (a handful of reads)
     unsigned long long* h_sum = nullptr;  // pinned: {cell updates of the chunk, need[0..3]} read back once per chunk
-    ~PathWorkImpl() {
-        for (auto e : ev) (void)hipEventDestroy(e);
-        if (done_ev) (void)hipEventDestroy(done_ev);
-        if (h_sum) (void)hipHostFree(h_sum);
-    }
+    ~PathWorkImpl() { if (h_sum) (void)hipHostFree(h_sum); }
 };
 PathWork::~PathWork() { delete impl; }
 
 namespace {
-
-struct Timer {
-    PathWorkImpl* w;
-    hipStream_t s;
-    bool spin = false;
-    bool log = false;                  // the launch log (rg_launch_log.hpp) is on
-    size_t used = 0;
-    struct Pend { std::string name; size_t e0, e1; };
-    std::vector<Pend> pend;
-    std::vector<const char*> insts;    // what the launchers of this chunk said they launched
-    // takes a launcher's result: the instantiation it dispatched (null: it launched nothing — an argument block no kernel is compiled for)
-    void inst(const char* label) {
-        if (!label) bad_launch = true;
-        else if (log) insts.push_back(label);
-    }
-    bool bad_launch = false;
-    int begin(const char* name) {
-        while (w->ev.size() < used + 2) {
-            hipEvent_t e;
-            HIPCHK(hipEventCreate(&e));
-            w->ev.push_back(e);
-        }
-        HIPCHK(hipEventRecord(w->ev[used], s));
-        pend.push_back(Pend{name, used, used + 1});
-        return RG_OK;
-    }
-    int end() {
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(w->ev[used + 1], s));
-        used += 2;
-        if (bad_launch) return fail(RG_ERR_ARG, "no kernel is compiled for this launch: " + pend.back().name);
-        return RG_OK;
-    }
-    int collect(KernelStats& stats) {
-        if (!w->done_ev) HIPCHK(hipEventCreateWithFlags(&w->done_ev, hipEventDisableTiming));
-        HIPCHK((hipError_t)wait_stream_sleeping(s, w->done_ev, spin));
-        for (auto& p : pend) {
-            float ms = 0;
-            HIPCHK(hipEventElapsedTime(&ms, w->ev[p.e0], w->ev[p.e1]));
-            add_stat(stats, p.name, ms, 1);
-        }
-        pend.clear();
-        used = 0;
-        flush(stats);
-        return RG_OK;
-    }
-    void flush(KernelStats& stats) {
-        for (const char* l : insts) add_stat(stats, std::string("inst:") + l, 0, 1);
-        insts.clear();
-    }
-};
-
-#define TIMED(T, name, call)                    \
-    do {                                        \
-        int rc_ = (T).begin(name);              \
-        if (rc_) return rc_;                    \
-        (T).inst(call);                         \
-        rc_ = (T).end();                        \
-        if (rc_) return rc_;                    \
-    } while (0)
-
 
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
@@ -145,10 +74,10 @@ struct Run {
     hipStream_t stream;
     KernelStats& stats;
     int spec_level;
-    Timer T;
+    KernelTimer& T;
     bool debug;
     int done = 0, chunk = 0;
-    hipError_t async_err = hipSuccess;       // of calls inside TIMED(..) launches: reported once the chunk is through
+    hipError_t async_err = hipSuccess;       // of calls inside timed launches: reported once the chunk is through
     DevScores sc{};
 
     const long long* off() const { return d_off + done; }
@@ -275,18 +204,18 @@ int Run::enqueue_pathwise(const SweepArgs& sa, const SeedArgs& se) {
     f.retire = 0;
     if (plan.spec4) {
         PickArgs pa{d_reads, off(), bad(), w.kmer_keys.p, w.kmer_masks.p, w.kmer_mask, h.P, w.pick.p, w.fpoff.p, w.fprow.p, nullptr};
-        TIMED(T, "k_pick", launch_pick(pa, chunk, stream));
+        RG_TRY(T.run("k_pick", [&] { return launch_pick(pa, chunk, stream); }));
         Opt0Args oa{gd, sc, d_reads, off(), bad(), w.fpoff.p, w.fprow.p, w.lb.p, 0, w.pick.p, plan.spec4_margin, plan.nwv, nullptr, 0};
-        TIMED(T, "k_opt0", launch_opt0_16(oa, chunk, plan.C, stream));
+        RG_TRY(T.run("k_opt0", [&] { return launch_opt0_16(oa, chunk, plan.C, stream); }));
         if (plan.retire4) {
             f.retire = 1; f.lb = w.lb.p; f.maxmatch = plan.maxmatch;
-            if (plan.order) { T.inst(launch_order(w.pick.p, nullptr, w.order.p, chunk, stream)); f.order = w.order.p; }
+            if (plan.order) { RG_TRY(T.inst(launch_order(w.pick.p, nullptr, w.order.p, chunk, stream))); f.order = w.order.p; }
         }
         if (plan.dsel4) { f.dsel_pick = w.pick.p; f.dsel_pick2 = nullptr; f.dsel_lo = 0; f.dsel_hi = h.L; }     // (no recombination: no edge rows)
     }
-    TIMED(T, plan.use16 ? "k_sweep16_fwd" : "k_sweep_fwd", sweep(f));
-    TIMED(T, "k_seed", launch_seed(se, stream));
-    if (plan.spec4) T.inst(launch_verify4(w.state.p, w.lb.p, w.need.p + 4, w.rt_flags.p, chunk, f.dsel_pick, stream));
+    RG_TRY(T.run(plan.use16 ? "k_sweep16_fwd" : "k_sweep_fwd", [&] { return sweep(f); }));
+    RG_TRY(T.run("k_seed", [&] { return launch_seed(se, stream); }));
+    if (plan.spec4) RG_TRY(T.inst(launch_verify4(w.state.p, w.lb.p, w.need.p + 4, w.rt_flags.p, chunk, f.dsel_pick, stream)));
     return RG_OK;
 }
 
@@ -296,7 +225,7 @@ int Run::check_opt0_16(const Opt0Args& oa) {
     std::vector<int> h16(chunk), h32(chunk);
     HIPCHK(hipMemcpyAsync(h16.data(), w.lb.p, sizeof(int) * chunk, hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
-    T.inst(launch_opt0(oa, chunk, plan.C, stream));
+    RG_TRY(T.inst(launch_opt0(oa, chunk, plan.C, stream)));
     HIPCHK(hipMemcpyAsync(h32.data(), w.lb.p, sizeof(int) * chunk, hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
     for (int k = 0; k < chunk; ++k)
@@ -313,15 +242,15 @@ int Run::enqueue_forward_bounded(SweepArgs& sa, const SeedArgs& se) {
                     plan.pick_two ? w.pick2.p : nullptr};
         oa.pick2 = pa.pick2;
         oa.rec_pen = plan.rec_pen;
-        TIMED(T, "k_pick", launch_pick(pa, chunk, stream));
+        RG_TRY(T.run("k_pick", [&] { return launch_pick(pa, chunk, stream); }));
         if (plan.retire && plan.order) {
-            T.inst(launch_order(w.pick.p, pa.pick2, w.order.p, chunk, stream));
+            RG_TRY(T.inst(launch_order(w.pick.p, pa.pick2, w.order.p, chunk, stream)));
             sa.order = w.order.p;
         }
         oa.pick = w.pick.p;
         oa.margin = plan.spec_margin;
     }
-    TIMED(T, "k_opt0", plan.opt16 ? launch_opt0_16(oa, chunk, plan.C, stream) : launch_opt0(oa, chunk, plan.C, stream));
+    RG_TRY(T.run("k_opt0", [&] { return plan.opt16 ? launch_opt0_16(oa, chunk, plan.C, stream) : launch_opt0(oa, chunk, plan.C, stream); }));
     if (plan.opt16 && debug) {
         const int rc = check_opt0_16(oa);
         if (rc) return rc;
@@ -342,13 +271,13 @@ int Run::enqueue_forward_bounded(SweepArgs& sa, const SeedArgs& se) {
     }
     f.dirs = w.fdirs.p; f.dirs_stride = plan.fdirs_stride; f.count_cells = 1;
     f.retire = plan.retire_fwd ? 1 : 0;
-    TIMED(T, plan.use16 ? "k_sweep16_fwd" : "k_sweep_fwd", sweep(f));
+    RG_TRY(T.run(plan.use16 ? "k_sweep16_fwd" : "k_sweep_fwd", [&] { return sweep(f); }));
     if (plan.use_rec) {
         ExpandArgs fc{w.state.p, w.frec.p, w.frec_cap, w.nrec.p, nullptr, 0, nullptr, nullptr, plan.wpad, p.base_rec_cost, gd.knm, 0, off(),
                       p.rec_band_width, p.scores[5]};
-        TIMED(T, "k_colmax_rec_fwd", launch_colmax_rec(fc, w.mf.p, w.mfarg.p, chunk, plan.C, stream));
+        RG_TRY(T.run("k_colmax_rec_fwd", [&] { return launch_colmax_rec(fc, w.mf.p, w.mfarg.p, chunk, plan.C, stream); }));
     }
-    TIMED(T, "k_seed", launch_seed(se, stream));
+    RG_TRY(T.run("k_seed", [&] { return launch_seed(se, stream); }));
     return RG_OK;
 }
 
@@ -362,11 +291,11 @@ int Run::enqueue_recombination(SweepArgs& sa, const SeedArgs& se) {
     } else {
         SweepArgs f1 = sa;
         f1.rev = 0; f1.track_best = 1; f1.colmax_out = w.mf.p; f1.colarg_out = w.mfarg.p; f1.count_cells = 0;
-        TIMED(T, plan.use16 ? "k_sweep16_fwd_colmax" : "k_sweep_fwd_colmax", sweep(f1));
-        TIMED(T, "k_seed", launch_seed(se, stream));
+        RG_TRY(T.run(plan.use16 ? "k_sweep16_fwd_colmax" : "k_sweep_fwd_colmax", [&] { return sweep(f1); }));
+        RG_TRY(T.run("k_seed", [&] { return launch_seed(se, stream); }));
     }
     ThrArgs t1{w.state.p, w.mf.p, w.thr.p, wpad, p.base_rec_cost, 0, plan.two_sweep ? w.lb.p : nullptr};
-    TIMED(T, "k_threshold", launch_threshold(t1, chunk, stream));
+    RG_TRY(T.run("k_threshold", [&] { return launch_threshold(t1, chunk, stream); }));
     SweepArgs r = sa;
     r.rev = 1; r.track_best = 1; r.thr = w.thr.p; r.colmax_out = w.wr.p; r.colarg_out = w.wrarg.p; r.cand = w.rcand.p; r.cand_cap = w.rcap; r.ncand_out = w.nr.p;
     if (plan.use_rec) {
@@ -376,35 +305,35 @@ int Run::enqueue_recombination(SweepArgs& sa, const SeedArgs& se) {
     }
     r.dirs = w.rdirs.p; r.dirs_stride = plan.rdirs_stride; r.count_cells = 1;
     r.retire = plan.retire_rev ? 1 : 0;
-    TIMED(T, plan.use16 ? "k_sweep16_rev" : "k_sweep_rev", sweep(r));
+    RG_TRY(T.run(plan.use16 ? "k_sweep16_rev" : "k_sweep_rev", [&] { return sweep(r); }));
     if (plan.use_rec) {
         ExpandArgs ec{w.state.p, w.rrec.p, w.rrec_cap, w.nrrec.p, nullptr, 0, nullptr, nullptr, wpad, p.base_rec_cost, gd.knm, 1, off(),
                       p.rec_band_width, p.scores[5]};
-        TIMED(T, "k_colmax_rec", launch_colmax_rec(ec, w.wr.p, w.wrarg.p, chunk, plan.C, stream));
+        RG_TRY(T.run("k_colmax_rec", [&] { return launch_colmax_rec(ec, w.wr.p, w.wrarg.p, chunk, plan.C, stream); }));
     }
     BoundArgs ba{gd, w.state.p, off(), w.mf.p, w.mfarg.p, w.wr.p, w.wrarg.p, wpad, p.base_rec_cost, p.multi_rec_cost, p.rec_band_width};
-    TIMED(T, "k_bound", launch_bound(ba, chunk, stream));
+    RG_TRY(T.run("k_bound", [&] { return launch_bound(ba, chunk, stream); }));
     if (!plan.two_sweep) {
         ThrArgs t2{w.state.p, w.wr.p, w.thr.p, wpad, p.base_rec_cost, 1, nullptr};
-        TIMED(T, "k_threshold", launch_threshold(t2, chunk, stream));
+        RG_TRY(T.run("k_threshold", [&] { return launch_threshold(t2, chunk, stream); }));
         SweepArgs f2 = sa;
         f2.rev = 0; f2.track_best = 1; f2.thr = w.thr.p; f2.cand = w.fcand.p; f2.cand_cap = w.fcap; f2.ncand_out = w.nf.p;
         f2.dirs = w.fdirs.p; f2.dirs_stride = plan.fdirs_stride; f2.count_cells = 1;
-        TIMED(T, plan.use16 ? "k_sweep16_fwd" : "k_sweep_fwd", sweep(f2));
+        RG_TRY(T.run(plan.use16 ? "k_sweep16_fwd" : "k_sweep_fwd", [&] { return sweep(f2); }));
     }
     if (plan.use_rec) {
         HIPCHK(hipMemsetAsync(w.nf.p, 0, sizeof(unsigned) * chunk, stream));
         HIPCHK(hipMemsetAsync(w.nr.p, 0, sizeof(unsigned) * chunk, stream));
         ExpandArgs ea{w.state.p, w.frec.p, w.frec_cap, w.nrec.p, w.fcand.p, w.fcap, w.nf.p, w.wr.p, wpad, p.base_rec_cost, gd.knm, 0, off(), p.rec_band_width, p.scores[5]};
-        TIMED(T, "k_expand", launch_expand(ea, chunk, plan.C, stream));
+        RG_TRY(T.run("k_expand", [&] { return launch_expand(ea, chunk, plan.C, stream); }));
         ExpandArgs er{w.state.p, w.rrec.p, w.rrec_cap, w.nrrec.p, w.rcand.p, w.rcap, w.nr.p, w.mf.p, wpad, p.base_rec_cost, gd.knm, 1, off(), p.rec_band_width, p.scores[5]};
-        TIMED(T, "k_expand", launch_expand(er, chunk, plan.C, stream));
+        RG_TRY(T.run("k_expand", [&] { return launch_expand(er, chunk, plan.C, stream); }));
     }
     SearchArgs sr{gd, w.state.p, w.fcand.p, w.rcand.p, w.nf.p, w.nr.p, w.ridx.p, w.fcap, w.rcap, w.wr.p, wpad, p.base_rec_cost, p.multi_rec_cost};
-    TIMED(T, "k_search", launch_search(sr, chunk, stream));
+    RG_TRY(T.run("k_search", [&] { return launch_search(sr, chunk, stream); }));
     // largest list / record counts of the chunk, read back once after the traceback (no host round trip here)
-    T.inst(launch_need(w.state.p, w.nf.p, w.nr.p, plan.use_rec ? w.nrec.p : nullptr, plan.use_rec ? w.nrrec.p : nullptr, w.need.p, chunk, stream));
-    if (plan.spec) T.inst(launch_verify(w.state.p, w.lb.p, w.need.p + 4, w.rt_flags.p, chunk, sa.dsel_pick, sa.dsel_pick2, sa.dsel_lo, sa.dsel_hi, stream));
+    RG_TRY(T.inst(launch_need(w.state.p, w.nf.p, w.nr.p, plan.use_rec ? w.nrec.p : nullptr, plan.use_rec ? w.nrrec.p : nullptr, w.need.p, chunk, stream)));
+    if (plan.spec) RG_TRY(T.inst(launch_verify(w.state.p, w.lb.p, w.need.p + 4, w.rt_flags.p, chunk, sa.dsel_pick, sa.dsel_pick2, sa.dsel_lo, sa.dsel_hi, stream)));
     return RG_OK;
 }
 
@@ -420,10 +349,10 @@ int Run::enqueue_tail() {
     la.rpoff = w.rpoff.p; la.rprow = w.rprow.p; la.rpslot = w.rpslot.p;
     la.rev = 0; la.dirs = w.fdirs.p; la.dirs_stride = plan.fdirs_stride; la.layer = w.flayer.p;
     auto layer = [&]() { return plan.layer16 ? launch_layer16(la, chunk, C, stream) : launch_layer(la, chunk, C, stream); };
-    TIMED(T, "k_layer_fwd", layer());
+    RG_TRY(T.run("k_layer_fwd", layer));
     if (plan.mode == RG_MODE_RECOMBINATION) {
         la.rev = 1; la.dirs = w.rdirs.p; la.dirs_stride = plan.rdirs_stride; la.layer = w.rlayer.p;
-        TIMED(T, "k_layer_rev", layer());
+        RG_TRY(T.run("k_layer_rev", layer));
     }
     TraceArgs ta;
     memset(&ta, 0, sizeof ta);
@@ -431,7 +360,7 @@ int Run::enqueue_tail() {
     ta.ops = d_ops + (long long)done * ops_stride; ta.ops_stride = ops_stride; ta.flayer = w.flayer.p;
     ta.rlayer = w.rlayer.p; ta.layer_stride = plan.layer_stride; ta.fpoff = w.fpoff.p; ta.fprow = w.fprow.p;
     ta.rpoff = w.rpoff.p; ta.rprow = w.rprow.p; ta.nreads = chunk; ta.mode = p.mode; ta.semi = plan.semi ? 1 : 0; ta.nwv = plan.nwv;
-    TIMED(T, "k_trace", launch_trace(ta, C, stream));
+    RG_TRY(T.run("k_trace", [&] { return launch_trace(ta, C, stream); }));
     // ONE read-back per chunk: cell updates + overflow summary, through pinned memory on the batch's stream
     HIPCHK(hipMemcpyAsync(w.h_sum, d_cells, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
     HIPCHK(hipMemcpyAsync(w.h_sum + 5, d_cells + 1, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
@@ -558,18 +487,16 @@ int Run::second_pass(unsigned long long& cells_perf) {
         (rc = w.rt_cells.alloc(2)))
         return rc;
     HIPCHK(hipMemsetAsync(w.rt_bad.p, 0, (size_t)nr, stream));
-    T.inst(launch_gather_reads(d_reads, off(), w.rt_idx.p, w.rt_off.p, w.rt_reads.p, nr, stream));
-    KernelStats st2;
+    RG_TRY(T.inst(launch_gather_reads(d_reads, off(), w.rt_idx.p, w.rt_off.p, w.rt_reads.p, nr, stream)));
+    // the same timer and statistics; work buffers and a cell counter of its own, three quarters of what is free now, one level up
+    const PathCtx again{h, gd, p, w.retry, stream, w.rt_cells.p, 0, T, stats, spec_level + 1};
+    const PathJob failed{w.rt_reads.p, w.rt_off.p, w.rt_bad.p, nr, max_n, w.rt_rec.p, w.rt_ops.p, ops_stride};
     unsigned long long c2[2] = {0, 0};
-    if ((rc = path_driver_run(h, gd, p, w.retry, w.rt_reads.p, w.rt_off.p, w.rt_bad.p, nr, max_n, w.rt_rec.p, w.rt_ops.p, ops_stride,
-                              w.rt_cells.p, stream, 0, c2, st2, spec_level + 1)))
-        return rc;
-    T.inst(launch_scatter_results(w.rt_idx.p, w.rt_rec.p, w.rt_ops.p, d_rec + done, d_ops + (long long)done * ops_stride, ops_stride, nr, stream));
+    RG_TRY(path_driver_run(again, failed, c2));
+    RG_TRY(T.inst(launch_scatter_results(w.rt_idx.p, w.rt_rec.p, w.rt_ops.p, d_rec + done, d_ops + (long long)done * ops_stride, ops_stride, nr, stream)));
     HIPCHK(hipStreamSynchronize(stream));
     cells_perf += c2[1];             // the second pass is work the sweeps performed too (the counted figure stays the workload's)
-    for (auto& e : st2) add_stat(stats, e.name, e.ms, e.launches);
-    T.flush(stats);                  // (the gather / scatter pair was launched behind the chunk's collect)
-    return RG_OK;
+    return T.collect(stats);         // (the labels of the scatter, launched behind the nested pass's last collect: nothing to wait for)
 }
 
 }  // namespace
@@ -583,19 +510,20 @@ int path_driver_vote_table(const HostGraph& h, PathWork& pw, const uint32_t** ke
     return RG_OK;
 }
 
-int path_driver_run(const HostGraph& h, const PathGraphDev& gd, const rg_params& p, PathWork& pw, const uint8_t* d_reads,
-                    const long long* d_off, const uint8_t* d_bad, int nreads, int max_n, DevRecord* d_rec, uint8_t* d_ops,
-                    long long ops_stride, unsigned long long* d_cells, hipStream_t stream, size_t mem_budget,
-                    unsigned long long* cells_out /* [2]: counted | performed */, KernelStats& stats, int spec_level) {
-    stats.clear();
-    if (!pw.impl) pw.impl = new PathWorkImpl();
-    PathWorkImpl& w = *pw.impl;
+int path_driver_run(const PathCtx& c, const PathJob& j, unsigned long long* cells /* [2]: counted | performed, added to */) {
+    const HostGraph& h = c.h;
+    const rg_params& p = c.p;
+    hipStream_t stream = c.stream;
+    unsigned long long* d_cells = c.d_cells;
+    KernelStats& stats = c.stats;
+    const int nreads = j.nreads;
+    if (!c.w.impl) c.w.impl = new PathWorkImpl();
+    PathWorkImpl& w = *c.w.impl;
     const Options& opt = options();
     PathPlan plan;
-    int rc = plan_pathwise(p, PathPlanInput{h.P, h.L, h.fslots, h.rslots, h.max_path_rows, max_n}, opt, spec_level, plan);
+    int rc = plan_pathwise(p, PathPlanInput{h.P, h.L, h.fslots, h.rslots, h.max_path_rows, j.max_n}, opt, c.spec_level, plan);
     if (rc) return rc;
-    Run r{h, gd, p, w, plan, d_reads, d_off, d_bad, max_n, d_rec, d_ops, ops_stride, d_cells, stream, stats, spec_level,
-          Timer{&w, stream, pw.spin_wait, opt.launch_log != 0}, opt.debug != 0};
+    Run r{h, c.gd, p, w, plan, j.reads, j.off, j.bad, j.max_n, j.rec, j.ops, j.ops_stride, d_cells, stream, stats, c.spec_level, c.T, opt.debug != 0};
     for (int i = 0; i < 36; ++i) r.sc.t[i] = p.scores[i];
     if (!w.h_sum) HIPCHK(hipHostMalloc((void**)&w.h_sum, 8 * sizeof(unsigned long long), hipHostMallocDefault));
     if ((rc = w.need.alloc(8)) || (rc = ensure_tables(h, w))) return rc;
@@ -606,7 +534,7 @@ int path_driver_run(const HostGraph& h, const PathGraphDev& gd, const rg_params&
         size_t fr = 0, tot = 0;
         if (hipMemGetInfo(&fr, &tot) == hipSuccess) budget = fr / 4 * 3;
         // a handle of the streaming engine has its own share of the device (what it already holds counts towards it)
-        if (mem_budget) budget = mem_budget;
+        if (c.mem_budget) budget = c.mem_budget;
     }
     unsigned long long cells_done = 0, cells_perf = 0;
     int oom_shift = 0;      // the budget is halved every time a work-buffer allocation fails (other handles / the retry pass took the memory)
@@ -617,9 +545,7 @@ int path_driver_run(const HostGraph& h, const PathGraphDev& gd, const rg_params&
         int maxchunk = (int)std::min<size_t>(8192, std::max<size_t>(1, (budget >> oom_shift) / per_read_all));
         if (opt.chunk_reads > 0) maxchunk = std::min<int>(maxchunk, opt.chunk_reads);
         const double dbg_t0 = r.debug ? now_s() : 0;
-        const int left = nreads - r.done;
-        const int nchunks = (left + maxchunk - 1) / maxchunk;
-        const int chunk = r.chunk = (left + nchunks - 1) / nchunks;   // even chunks: no short tail launch
+        const int chunk = r.chunk = (int)even_chunks(nreads - r.done, maxchunk);
         bool oom = false;
         if ((rc = r.alloc_chunk(&oom))) {
             // out of memory (the share was measured before other buffers of the device existed): smaller launches, like run_poa.
@@ -644,10 +570,11 @@ int path_driver_run(const HostGraph& h, const PathGraphDev& gd, const rg_params&
         cells_done += chunk_cells;
         r.done += chunk;
         // HBM work buffers of one read of this chunk (rolling rows, direction words, layers, candidate and record lists): reported
-        // as a pseudo-kernel so that callers see the footprint without another ABI entry ("ms" holds bytes, summed per chunk)
-        stats.push_back(KernelStat{"mem:work_bytes_per_read", (double)per_read_all, 1});
+        // as a pseudo-kernel so that callers see the footprint without another ABI entry ("ms" holds bytes, summed over the chunks)
+        add_stat(stats, "mem:work_bytes_per_read", (double)per_read_all, 1);
     }
-    if (cells_out) { cells_out[0] = cells_done; cells_out[1] = cells_perf; }
+    cells[0] += cells_done;
+    cells[1] += cells_perf;
     return RG_OK;
 }
 

@@ -12,6 +12,7 @@
 // the strand its 12-mers vote for: the gate presets the strand flag from `first_rev`, and the merge keeps the reverse record
 // only when it is strictly greater, whichever pass produced it.
 //
+// This file holds the kernels and their launchers; rg_strand_driver.hip launches them between the passes.
 // The kernels are memory-shaped and small on purpose: they run beside the sweeps of other handles, which leave 64 VGPRs
 // per SIMD (tests/test_both_strands_cpu.py holds them to that, without scratch).  Plain vector stores only.
 #include "rg_strand.hpp"

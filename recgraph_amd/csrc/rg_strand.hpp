@@ -1,5 +1,6 @@
 // Both strands inside a pathwise batch (RG_AMB_BOTH_STRANDS, include/recgraph_hip.h): the three small kernels between the
-// forward pass and the pass over the reverse complements (rg_strand.hip), launched by rg_run_pathwise (rg_abi.hip).
+// forward pass and the pass over the reverse complements (rg_strand.hip), and the two of the strand vote in front of the first
+// pass (rg_strand_vote.hip).  Their host half — buffer sizing and the order of the passes — is rg_strand_driver.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 

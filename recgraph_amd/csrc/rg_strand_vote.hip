@@ -3,6 +3,7 @@
 //
 //   k_strand_vote  ->  k_strand_orient  ->  pass A (path_driver_run over the oriented reads)  ->  k_strand_gate  ->  ...
 //
+// (launched by rg_run_pathwise, rg_strand_driver.hip: no host synchronisation between the vote and pass A).
 // The vote is a pure function of (graph, read): V_f / V_r = how many sampled 12-mers of the read / of its reverse
 // complement occur in some path (k_pick's sampling, k_pick's table, membership only).  The first pass aligns the reverse
 // complement iff V_r > V_f.

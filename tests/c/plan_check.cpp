@@ -251,7 +251,24 @@ static void second_pass_levels() {
     CHECK(plan(hoxd_like(RG_MODE_RECOMBINATION), shape(6, 150), z, 1).spec_margin == 320);
 }
 
+// even_chunks (rg_host.hpp): the reads per launch of both batch drivers — as few launches as `maxchunk` allows, no short tail
+static void even_launches() {
+    for (long long n = 1; n <= 300; ++n)
+        for (long long maxchunk = 1; maxchunk <= 300; ++maxchunk) {
+            const long long chunk = even_chunks(n, maxchunk);
+            const long long launches = (n + chunk - 1) / chunk, last = n - (launches - 1) * chunk;
+            if (!(1 <= chunk && chunk <= maxchunk) || launches != (n + maxchunk - 1) / maxchunk || !(1 <= last && last <= chunk)) {
+                ++failures;
+                fprintf(stderr, "even_chunks(%lld, %lld) = %lld: %lld launches, the last of %lld\n", n, maxchunk, chunk, launches, last);
+            }
+        }
+    CHECK(even_chunks(5, 2) == 2);
+    CHECK(even_chunks(10000, 8192) == 5000);
+    CHECK(even_chunks(7, 100) == 7);
+}
+
 int main() {
+    even_launches();
     headline_route();
     single_options();
     modes();

@@ -16,7 +16,7 @@ How the cases are shaped:
     sets) on the wide side;
   * k_sweep16: every C x {records (-m 8 / 9), no tracking (-m 4 / 5), column maxima (three_sweeps / no_frec)} x {<= 64, > 64
     paths} x {global, semiglobal}; the i32 kernels through sweep_i32 (uniform gaps) and a matrix with per-base gap costs;
-  * the POA kernels on both sides of `lds_read = max_n <= 16000` (rg_abi.hip): a longest read of 16000 and of 16001 bases;
+  * the POA kernels on both sides of `lds_read = max_n <= 16000` (rg_poa_driver.hip): a longest read of 16000 and of 16001 bases;
   * graphs alternate between synth.random_dag_graph and synth.haplotype_graph; graphs for C <= 8 run at retire_shift 4 so that
     path retirement is live on them.
 

@@ -81,3 +81,31 @@ def test_handle_reuse_with_new_reads(oracle):
             b.fetch()
             fresh, _ = api.align_batch(g, rs, None, mode=mode)
             assert [b.gaf_text(i, "read%d" % i, i + 1) for i in range(len(rs))] == fresh, (mode, k)
+
+
+def test_one_handle_run_twice():
+    """rg_batch_run resets the handle's statistics and its event cursor: a second run() of the same reads reports the same
+    kernel names and launch counts as the first (nothing accumulates, no name twice) and the same records as a fresh handle.
+    The pathwise case takes both strands with the vote: its vote kernels are recorded in front of pass A and collected with it."""
+    from recgraph_amd import api, synth
+    from strand_vote_rule import rc
+    sg = synth.haplotype_graph(600, 6, path_len=200, seed=31)
+    g = api.Graph.from_gfa_text(sg.gfa())
+    good = synth.haplotype_reads(sg, 12, 200, seed=5, mosaic_frac=0.5)
+    reads = [rc(r) if i % 3 == 0 else r for i, r in enumerate(good)] + ["ACGT" * 30]       # (the palindrome reaches pass B)
+    lib = api._lib.load()
+    for mode, amb in ((api.MODE_GAP_POA, None), (api.MODE_RECOMBINATION, api.AMB_BOTH_STRANDS | api.AMB_STRAND_VOTE)):
+        seen = []
+        for handle in range(2):
+            b = api.Batch(g, reads, api.make_params(mode, amb=amb))
+            for run in range(2 if handle == 0 else 1):
+                b.run()
+                b.fetch()
+                names = [lib.rg_batch_kernel_name(b._h, k).decode() for k in range(lib.rg_batch_kernel_count(b._h))]
+                assert len(names) == len(set(names)), names
+                seen.append(({k: v[1] for k, v in b.kernel_stats().items()}, [b.gaf_text(i, "q%d" % i, i + 1) for i in range(len(reads))]))
+        assert seen[0] == seen[1] == seen[2], (mode, [s[0] for s in seen])
+        assert all(n >= 1 for n in seen[0][0].values())
+        if amb:
+            assert {"k_strand_vote", "k_strand_orient", "k_strand_gate", "k_strand_merge", "mem:work_bytes_per_read"} <= set(seen[0][0])
+            assert any("\t-\t" in t for t in seen[0][1]) and any("\t+\t" in t for t in seen[0][1])

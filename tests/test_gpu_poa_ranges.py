@@ -10,14 +10,17 @@ pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
-def _compare(oracle, gfa, reads, mode, omode, scores=None, **kw):
-    """Byte-identical text and the same Batch.score(i) as the oracle for every read; returns the scores."""
+def _compare(oracle, gfa, reads, mode, omode, scores=None, stats=None, **kw):
+    """Byte-identical text and the same Batch.score(i) as the oracle for every read; returns the scores (stats: a dict that
+    receives the batch's kernel_stats())."""
     from recgraph_amd import api
     og = oracle.Graph.from_gfa_text(gfa, want_path=False)
     g = api.Graph.from_gfa_text(gfa)
     b = api.Batch(g, reads, api.make_params(mode, score_matrix=scores, **kw))
     b.run()
     b.fetch()
+    if stats is not None:
+        stats.update(b.kernel_stats())
     bad, out = [], []
     for i, rd in enumerate(reads):
         name = "r%d" % i
@@ -98,7 +101,7 @@ def test_realistic_inputs_are_admitted():
 
 
 # ---- reads past the LDS cut ------------------------------------------------------------------------------------------------
-# lds_read = max_n <= 16000 (rg_abi.hip): a batch whose longest read has 16 000 bases runs the LDS variants of all three POA
+# lds_read = max_n <= 16000 (rg_poa_driver.hip): a batch whose longest read has 16 000 bases runs the LDS variants of all three POA
 # kernels, one with a longer read the variants that read the bases from global memory.
 def _long_reads(walk, n, rng):
     tail = "".join("ACGT"[int(x)] for x in rng.integers(0, 4, size=n - len(walk)))
@@ -141,6 +144,9 @@ def test_band_widths_at_chunk_edges_and_register_limit(oracle):
                 _compare(oracle, sg.gfa(), reads, mode, omode, bta=bta)
 
 
+KERNEL = {0: "k_m0_simd", 10: "k_m0_scalar", 2: "k_m2_gap", 1: "k_m1_local_simd", 11: "k_m1_local_scalar", 3: "k_m3_gap_local"}   # by api.MODE_*
+
+
 def test_band_arena_regrowth(oracle, capfd):
     """Reads 200 bases longer than a linear graph with a small bta: their bands are ~200 columns wider than the first arena
     (L * (2 bta + 40) cells per read), the first attempt overflows and run_poa runs again with a doubled arena."""
@@ -153,8 +159,57 @@ def test_band_arena_regrowth(oracle, capfd):
     try:
         for mode, omode in ((api.MODE_GLOBAL_POA, oracle.M0_SIMD), (api.MODE_GLOBAL_POA_SCALAR, oracle.M0_SCALAR), (api.MODE_GAP_POA, oracle.M2)):
             capfd.readouterr()
-            _compare(oracle, sg.gfa(), reads, mode, omode, bta=4)
+            stats = {}
+            _compare(oracle, sg.gfa(), reads, mode, omode, stats=stats, bta=4)
             err = capfd.readouterr().err
             assert "run_poa attempt 0" in err and "run_poa attempt 1" in err, (mode, err[-600:])
+            # the statistics are those of the last attempt alone (one launch of the four reads), and the launch log is off
+            assert stats[KERNEL[mode]][1] == 1 and not [k for k in stats if k.startswith("inst:")], (mode, stats)
     finally:
         api.set_option("debug", 0)
+
+
+# ---- launches behind the first: read_base > 0 ----------------------------------------------------------------------------------
+# A POA batch goes through as many launches as the free HBM asks for, which is one below full-size batches; "chunk_reads" caps
+# the reads of a launch, so 5 reads at chunk_reads = 2 are 3 launches (2, 2, 1) with read_base 0, 2, 4 and launch-relative arena
+# slots.  Rows with several predecessors (a 4-path haplotype graph), reads of different lengths, one with a bad base.
+def test_poa_launches_with_a_read_base(oracle):
+    from recgraph_amd import api, synth
+    assert {getattr(api, n) for n in ("MODE_GLOBAL_POA", "MODE_GLOBAL_POA_SCALAR", "MODE_GAP_POA", "MODE_LOCAL_POA", "MODE_LOCAL_POA_SCALAR",
+                                      "MODE_GAP_LOCAL_POA")} == set(KERNEL)
+    sg = synth.haplotype_graph(300, 4, path_len=250, seed=23)
+    gfa = sg.gfa()
+    w = [sg.path_sequence(k) for k in range(4)]
+    assert min(len(x) for x in w) >= 200
+    reads = [w[0][:250], w[1][20:80], w[2][:90] + "X" + w[2][91:180], w[3][40:160], w[1][:97]]
+    assert sorted(len(r) for r in reads) == [60, 97, 120, 180, min(250, len(w[0]))]
+    og = oracle.Graph.from_gfa_text(gfa, want_path=False)
+    g = api.Graph.from_gfa_text(gfa)
+    modes = ((api.MODE_GLOBAL_POA, oracle.M0_SIMD, {"bta": 30}), (api.MODE_GLOBAL_POA_SCALAR, oracle.M0_SCALAR, {"bta": 30}),
+             (api.MODE_GAP_POA, oracle.M2, {"bta": 30, "o": -4, "e": -2}), (api.MODE_LOCAL_POA, oracle.M1_SIMD, {}),
+             (api.MODE_LOCAL_POA_SCALAR, oracle.M1_SCALAR, {}), (api.MODE_GAP_LOCAL_POA, oracle.M3, {"o": -6, "e": -1}))
+    try:
+        api.set_option("launch_log", 1)
+        for mode, omode, kw in modes:
+            exp = [og.align(omode, rd, name="r%d" % i, idx=i + 1, **kw) for i, rd in enumerate(reads)]
+            assert [bool(e[2]) for e in exp] == [False, False, True, False, False]        # the oracle refuses the bad base alone
+            runs = []
+            for cap, launches in ((2, 3), (0, 1)):
+                api.set_option("chunk_reads", cap)
+                b = api.Batch(g, reads, api.make_params(mode, **kw))
+                b.run()
+                b.fetch()
+                texts = [b.gaf_text(i, "r%d" % i, i + 1) for i in range(len(reads))]
+                for i, (text, score, panic, _) in enumerate(exp):
+                    if panic:
+                        assert b.status(i) & api.READ_BAD_BASE and texts[i] == "", (mode, cap, i)
+                    else:
+                        assert texts[i] == text and b.score(i) == score, (mode, cap, i, texts[i][-300:], text[-300:])
+                st = b.kernel_stats()
+                inst = {k: v[1] for k, v in st.items() if k.startswith("inst:")}
+                assert st[KERNEL[mode]][1] == launches and list(inst.values()) == [launches], (mode, cap, st)
+                runs.append((texts, b.cell_updates))
+            assert runs[0] == runs[1], mode
+    finally:
+        api.set_option("chunk_reads", 0)
+        api.set_option("launch_log", 0)
