@@ -48,6 +48,41 @@ typedef enum rg_status {
 #define RG_MODE_LOCAL_POA 1         /* local_poa::exec_simd             src/local_poa.rs:9          */
 #define RG_MODE_LOCAL_POA_SCALAR 11 /* local_poa::exec (no-AVX2 path)   src/local_poa.rs:176        */
 #define RG_MODE_GAP_LOCAL_POA 3     /* gap_local_poa::exec              src/gap_local_poa.rs:6      */
+/*
+ * RG_MODE_PATHWISE_GAP (6, global) and RG_MODE_PATHWISE_GAP_SEMI (7, semiglobal): pathwise alignment with affine gaps.
+ * The reference lists both as EXPERIMENTAL (README.md:62), prints only "Best path sequence i: k" for them (main.rs:271-288)
+ * and its pathwise_alignment_gap.rs disagrees with itself (:338), so there is nothing to be byte-identical to.  The two
+ * modes therefore have A DEFINITION OF THEIR OWN, and they return a GAF record in the -m 4 format:
+ *   INPUTS.  For path k, b_1..b_m are the bases of its rows in path order (without row 0 and without 'F'); s_1..s_n is the
+ *     read after the usual canonicalisation; o = gap_open <= 0, e = gap_ext <= 0, a gap of length g costs o + g * e
+ *     (pathwise_alignment_gap.rs:28,45); sc(a, b) = scores[a * 6 + b] (the '-' entries are not read, as in -m 2).  i32
+ *     arithmetic; NEG is a sentinel that can never win.
+ *   RECURRENCE, independently for every path (exact Gotoh per path, not the alpha-follows-member coding of -m 4):
+ *     H[0][0] = 0
+ *     X[0][j] = o + e * j,  H[0][j] = X[0][j],  Y[0][j] = NEG                        (j >= 1)
+ *     -m 6:  Y[i][0] = o + e * i,  H[i][0] = Y[i][0],  X[i][0] = NEG                 (i >= 1)
+ *     -m 7:  H[i][0] = 0,  Y[i][0] = X[i][0] = NEG                                   (i >= 1: the path may start anywhere)
+ *     Y[i][j] = max(H[i-1][j] + o + e, Y[i-1][j] + e)                                (consumes a path base: op U)
+ *     X[i][j] = max(H[i][j-1] + o + e, X[i][j-1] + e)                                (consumes a read base: op L)
+ *     H[i][j] = max(H[i-1][j-1] + sc(b_i, s_j), Y[i][j], X[i][j])
+ *   CHOICE.  -m 6: the score of path k is H_k[m_k][n]; the highest score wins, ties go to the lowest path index; end_row is
+ *     the path's last row.  -m 7: maximise H_k[i][n] over paths k and i >= 1; ties go to the smallest graph row, then to
+ *     the lowest path index (the iteration order of best_ending_node, pathwise_alignment_semiglobal.rs:244-276); end_row
+ *     is that row.
+ *   TRACEBACK from state H at the chosen cell.  In H: D if H == H[i-1][j-1] + sc, else U (to state Y) if H == Y, else L (to
+ *     state X): the project's D > U > L order.  In Y at (i, j): emit U; the run was opened at (i-1, j) (back to H) iff
+ *     H[i-1][j] + o + e >= Y[i-1][j] + e, otherwise stay in Y (the reference's `u_dpm >= u_y` prefers opening likewise).  X
+ *     is symmetric.  On the borders the walk follows the only finite state.  -m 6 ends at (0, 0); -m 7 ends when j == 0.
+ *   RECORD.  Ops, best path, end row and score fill the record of -m 4, and the line is that mode's:
+ *     "<cigar>, best path: k, score: S\t<path bases>".
+ *   REFUSALS.  A read with a character outside ACGTN: RG_READ_BAD_BASE.  gap_open > 0 or gap_ext > 0, any amb_mode bit, a
+ *     read longer than 2047 bases: RG_ERR_ARG.  (rows of the longest path + longest read) * max(|sc|, |o + e|) >= 2^28:
+ *     RG_ERR_CAPACITY.  All of them are answered by rg_batch_create before a device is needed.
+ * rg_batch_cell_updates counts rows_k * n per path and read; rg_batch_cell_updates_performed adds the direction pass of the
+ * chosen path.
+ */
+#define RG_MODE_PATHWISE_GAP 6
+#define RG_MODE_PATHWISE_GAP_SEMI 7
 
 /*
  * Scoring and banding parameters.  Replaces the HashMap<(char,char),i32|f32> score matrix arguments

@@ -43,6 +43,10 @@ MODE_RECOMBINATION_SEMI = 9
 MODE_LOCAL_POA = 1
 MODE_LOCAL_POA_SCALAR = 11
 MODE_GAP_LOCAL_POA = 3
+# pathwise alignment with affine gaps, global / semiglobal: a definition of this project's own (RG_MODE_PATHWISE_GAP in
+# include/recgraph_hip.h), GAF in the -m 4 format
+MODE_PATHWISE_GAP = 6
+MODE_PATHWISE_GAP_SEMI = 7
 
 READ_BAND_WARNING, READ_BAND_NOT_ENOUGH, READ_WOULD_PANIC, READ_BAD_BASE = 1, 2, 4, 8
 
@@ -52,6 +56,7 @@ AMB_BOTH_STRANDS = _lib.AMB_BOTH_STRANDS
 # bit 3 (RG_AMB_STRAND_VOTE), only together with bit 2: the strand that is aligned first is picked per read by a 12-mer vote
 AMB_STRAND_VOTE = _lib.AMB_STRAND_VOTE
 PATHWISE_MODES = (MODE_PATHWISE, MODE_PATHWISE_SEMI, MODE_RECOMBINATION, MODE_RECOMBINATION_SEMI)
+PATHWISE_GAP_MODES = (MODE_PATHWISE_GAP, MODE_PATHWISE_GAP_SEMI)      # (they align the reads as given: no both_strands)
 
 
 def _both_strands_kw(mode, both_strands, kw, strand_vote=False):
@@ -59,6 +64,8 @@ def _both_strands_kw(mode, both_strands, kw, strand_vote=False):
     outside the pathwise modes, where ``amb_strand`` (``-s true``) is the way."""
     if not both_strands and not strand_vote:
         return kw
+    if mode in PATHWISE_GAP_MODES:
+        raise _lib.RecGraphError(-1, "%s is not available in the affine-gap pathwise modes (6, 7)" % ("strand_vote" if strand_vote else "both_strands"))
     if mode not in PATHWISE_MODES:
         raise _lib.RecGraphError(-1, "%s applies to the pathwise modes (4, 5, 8, 9) only: the POA modes align both "
                                      "strands with amb_strand (`-s true`)" % ("strand_vote" if strand_vote else "both_strands"))
@@ -835,6 +842,20 @@ def pathwise_alignment_exec(sequence, graph, score_matrix=None):
 def pathwise_alignment_semiglobal_exec(sequence, graph, score_matrix=None):
     """pathwise_alignment_semiglobal::exec (pathwise_alignment_semiglobal.rs:6)."""
     _, text = _single(graph, "".join(sequence[1:]), "Temp", MODE_PATHWISE_SEMI, 1, score_matrix=score_matrix)
+    return GAFStruct.from_line(text.rstrip("\n"))
+
+
+def pathwise_alignment_gap_exec(sequence, graph, score_matrix=None, o=-4, e=-2):
+    """-m 6: global pathwise alignment with affine gaps (a gap of length g costs o + g * e; the rule: RG_MODE_PATHWISE_GAP in
+    include/recgraph_hip.h).  The reference's pathwise_alignment_gap::exec returns the index of the best path only; here that
+    index is the "best path" of the GAFStruct's comments.  ``sequence`` carries the leading '$' like the reference's read arrays."""
+    _, text = _single(graph, "".join(sequence[1:]), "Temp", MODE_PATHWISE_GAP, 1, score_matrix=score_matrix, o=o, e=e)
+    return GAFStruct.from_line(text.rstrip("\n"))
+
+
+def pathwise_alignment_gap_semi_exec(sequence, graph, score_matrix=None, o=-4, e=-2):
+    """-m 7: the semiglobal twin of ``pathwise_alignment_gap_exec`` (the alignment may start and end inside a path)."""
+    _, text = _single(graph, "".join(sequence[1:]), "Temp", MODE_PATHWISE_GAP_SEMI, 1, score_matrix=score_matrix, o=o, e=e)
     return GAFStruct.from_line(text.rstrip("\n"))
 
 

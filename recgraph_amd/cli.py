@@ -1,6 +1,7 @@
 """Command line front-end mirroring the mode dispatch of the reference's ``src/main.rs`` for the modes on
 the accelerated path (``-m 0, 1, 2, 3, 4, 5, 8, 9``): same positional arguments, flag names and defaults
 (``src/args_parser.rs:3-147``), GAF on stdout (or written to ``-o`` with the reference's create/append rule, ``utils.rs:200-219``), ``Done in N.`` on stderr.
+``-m 6`` and ``-m 7`` (affine-gap pathwise alignment) follow this project's own rule and write GAF in the ``-m 4`` format.
 
     python -m recgraph_amd.cli reads.fa graph.gfa -m 8 -R 4 -r 0.1 -B 1
 """
@@ -57,7 +58,7 @@ def build_parser():
     p.add_argument("-b", "--extra-b", type=int, default=1)
     p.add_argument("-f", "--extra-f", type=float, default=0.01)
     p.add_argument("--both-strands", action="store_true", dest="both_strands",
-                   help="modes 4, 5, 8, 9 (not a flag of the reference): reads that score below 0 are aligned again as their reverse "
+                   help="modes 4, 5, 8, 9 (not a flag of the reference; refused in 6 and 7): reads that score below 0 are aligned again as their reverse "
                         "complement; a strictly better reverse record is written with strand '-'")
     p.add_argument("--strand-vote", action="store_true", dest="strand_vote",
                    help="modes 4, 5, 8, 9 (not a flag of the reference; implies --both-strands): the strand that is aligned first is "
@@ -82,8 +83,10 @@ def main(argv=None):
         return time.time()
     from . import api
     tp = mark("import", t0)
-    if a.alignment_mode not in (0, 1, 2, 3, 4, 5, 8, 9):
-        raise SystemExit("Alignment mode must be in [0..5] or [8, 9]")   # main.rs:315-317
+    if a.alignment_mode not in (0, 1, 2, 3, 4, 5, 6, 7, 8, 9):
+        raise SystemExit("Alignment mode must be in [0..9]")   # main.rs:315-317
+    if a.alignment_mode in (6, 7) and (a.both_strands or a.strand_vote):
+        raise SystemExit("--both-strands / --strand-vote are not available in modes 6 and 7: they align the reads as given")
     amb = a.amb_strand == "true" and a.alignment_mode in (0, 1, 2, 3)     # modes 4+ ignore -s (main.rs:254-313)
     if a.strand_vote and a.alignment_mode in (0, 1, 2, 3):
         raise SystemExit("--strand-vote applies to modes 4, 5, 8 and 9: for modes 0-3 use `-s true`")
@@ -98,7 +101,7 @@ def main(argv=None):
     tp = mark("graph", tp)
     mode = {0: api.MODE_GLOBAL_POA_SCALAR if a.scalar else api.MODE_GLOBAL_POA, 2: api.MODE_GAP_POA,
             1: api.MODE_LOCAL_POA_SCALAR if a.scalar else api.MODE_LOCAL_POA, 3: api.MODE_GAP_LOCAL_POA,
-            4: api.MODE_PATHWISE, 5: api.MODE_PATHWISE_SEMI, 8: api.MODE_RECOMBINATION,
+            4: api.MODE_PATHWISE, 5: api.MODE_PATHWISE_SEMI, 6: api.MODE_PATHWISE_GAP, 7: api.MODE_PATHWISE_GAP_SEMI, 8: api.MODE_RECOMBINATION,
             9: api.MODE_RECOMBINATION_SEMI}[a.alignment_mode]
     kw = dict(score_matrix=scores, o=-a.gap_open, e=-a.gap_extension, b=float(a.extra_b), f=a.extra_f,
               R=a.base_rec_cost, r=a.multi_rec_cost, B=a.rec_band_width)

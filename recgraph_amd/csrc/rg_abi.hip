@@ -18,6 +18,7 @@
 #include <cstdlib>
 
 #include "rg_batch_impl.hpp"
+#include "rg_path_plan.hpp"
 
 void rg_batch_destroy_impl(rg_batch* b) {
     if (!b) return;
@@ -358,10 +359,11 @@ int32_t rg_batch_create(const rg_graph* gc, const rg_params* p, const char* read
     if (!gc || !p || !reads || !read_off || !out || nreads < 1) return fail(RG_ERR_ARG, "null/empty argument");
     const rg_graph* g = gc;
     const int mode = p->mode;
+    const bool path_gap = mode == RG_MODE_PATHWISE_GAP || mode == RG_MODE_PATHWISE_GAP_SEMI;
     if (!(is_poa(mode) || mode == RG_MODE_PATHWISE || mode == RG_MODE_RECOMBINATION || mode == RG_MODE_PATHWISE_SEMI ||
-          mode == RG_MODE_RECOMBINATION_SEMI))
+          mode == RG_MODE_RECOMBINATION_SEMI || path_gap))
         return fail(RG_ERR_ARG, "unsupported mode");
-    if ((mode == RG_MODE_GAP_POA || mode == RG_MODE_GAP_LOCAL_POA) && (p->gap_open > 0 || p->gap_ext > 0))
+    if ((mode == RG_MODE_GAP_POA || mode == RG_MODE_GAP_LOCAL_POA || path_gap) && (p->gap_open > 0 || p->gap_ext > 0))
         return fail(RG_ERR_ARG, "gap penalties must be <= 0");
     if (is_poa(mode) && !g->h.has_lnz) return fail(RG_ERR_ARG, "graph has no LnzGraph view");
     if (!is_poa(mode) && !g->h.has_path)
@@ -382,6 +384,17 @@ int32_t rg_batch_create(const rg_graph* gc, const rg_params* p, const char* read
         return fail(RG_ERR_ARG, "RG_AMB_BOTH_STRANDS applies to the pathwise modes only: the POA modes align both strands through "
                                 "rg_stream_opts.amb_strand (`-s true`, main.rs:82,132,188,229)");
     if ((p->amb_mode & 3) && !is_poa(mode)) return fail(RG_ERR_ARG, "amb_mode bits 0 and 1 apply to the POA modes only (main.rs:82,132,188,229)");
+    if (path_gap) {
+        // what the plan of -m 6 / -m 7 refuses (amb_mode bits, reads over 2047 bases, scores outside the i32 budget) is host
+        // arithmetic on the longest read: answered here, before a device is needed
+        int64_t longest = 0;
+        for (int64_t r = 0; r < nreads; ++r) longest = std::max<int64_t>(longest, read_off[r + 1] - read_off[r]);
+        PathPlan plan;
+        const HostGraph& h = g->h;
+        const int prc = plan_pathwise(*p, PathPlanInput{h.P, h.L, h.fslots, h.rslots, h.max_path_rows, (int)std::min<int64_t>(longest, INT32_MAX)},
+                                      options(), 0, plan);
+        if (prc) return prc;
+    }
     GraphTables* gt = nullptr;
     int rc = upload_graph(const_cast<rg_graph*>(g), &gt);   // per-device tables, under the graph's mutex
     if (rc) return rc;

@@ -3,6 +3,7 @@
 // regrows the candidate lists on overflow.  The passes of a batch are put together by rg_strand_driver.hip.
 //
 //   -m 4:  sweep(F, dirs) -> seed -> layer(F) -> trace
+//   -m 6:  gap_score(every path) -> gap_pick -> gap_dirs(picked path) -> gap_trace          (gap/rg_path_gap.hip; -m 7 likewise)
 //   -m 8:  sweep(F1: column maxima) -> seed -> thr -> sweep(R: dirs, candidates, column maxima)
 //          -> thr -> sweep(F2: dirs, candidates) -> search -> layer(F) -> layer(R) -> trace
 #include <algorithm>
@@ -11,6 +12,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "gap/rg_path_gap.hpp"
 #include "rg_kernel_timer.hpp"
 #include "rg_path_kernels.hpp"
 #include "rg_path_plan.hpp"
@@ -22,7 +24,7 @@ struct PathWorkImpl {
     DevBuf<int> fpoff, fprow, fpslot, rpoff, rprow, rpslot;
     DevBuf<ReadState> state;
     DevBuf<int> roll, mf, wr, mfarg, wrarg, thr, flayer, rlayer;
-    DevBuf<uint32_t> fdirs, rdirs;
+    DevBuf<uint32_t> fdirs, rdirs, gdirs;
     DevBuf<Cand> fcand, rcand;
     DevBuf<unsigned> nf, nr, ridx, nrec, nrrec;
     DevBuf<int> frec, rrec;
@@ -90,6 +92,8 @@ struct Run {
     SweepArgs sweep_args() const;
     const char* sweep(const SweepArgs& sa);     // (what it launched, like the launchers: rg_launch_log.hpp)
     int enqueue_pathwise(const SweepArgs& sa, const SeedArgs& se);
+    int enqueue_pathwise_gap();
+    int read_back();
     int enqueue_recombination(SweepArgs& sa, const SeedArgs& se);
     int enqueue_forward_bounded(SweepArgs& sa, const SeedArgs& se);
     int check_opt0_16(const Opt0Args& oa);
@@ -143,6 +147,10 @@ int ensure_tables(const HostGraph& h, PathWorkImpl& w) {
 int Run::alloc_chunk(bool* oom) {
     const size_t n = (size_t)chunk, wpad = (size_t)plan.wpad;
     int rc;
+    if (plan.gap) {
+        if ((rc = w.state.alloc(n, oom)) || (rc = w.gdirs.alloc(n * (size_t)plan.gdirs_stride, oom))) return rc;
+        return RG_OK;
+    }
     if ((rc = w.state.alloc(n, oom)) || (rc = w.fdirs.alloc(n * plan.fdirs_stride, oom)) || (rc = w.flayer.alloc(n * plan.layer_stride, oom)) ||
         (rc = w.roll.alloc(n * (h.P + 2) * wpad, oom)))
         return rc;
@@ -217,6 +225,22 @@ int Run::enqueue_pathwise(const SweepArgs& sa, const SeedArgs& se) {
     RG_TRY(T.run("k_seed", [&] { return launch_seed(se, stream); }));
     if (plan.spec4) RG_TRY(T.inst(launch_verify4(w.state.p, w.lb.p, w.need.p + 4, w.rt_flags.p, chunk, f.dsel_pick, stream)));
     return RG_OK;
+}
+
+// -m 6 / -m 7:  gap_score(every path) -> gap_pick -> gap_dirs(picked path) -> gap_trace -> the chunk's one read-back
+int Run::enqueue_pathwise_gap() {
+    GapArgs ga;
+    memset(&ga, 0, sizeof ga);
+    ga.sc = sc; ga.lnz = gd.lnz; ga.reads = d_reads; ga.read_off = off(); ga.bad = bad(); ga.poff = w.fpoff.p; ga.prow = w.fprow.p;
+    ga.P = h.P; ga.o = p.gap_open; ga.e = p.gap_ext; ga.state = w.state.p; ga.dirs = w.gdirs.p; ga.dirs_stride = plan.gdirs_stride;
+    ga.cells = d_cells; ga.rec = d_rec + done; ga.ops = d_ops + (long long)done * ops_stride; ga.ops_stride = ops_stride;
+    const int C = plan.C;
+    const bool semi = plan.semi;
+    RG_TRY(T.run("k_gap_score", [&] { return launch_gap_score(ga, chunk, C, semi, stream); }));
+    RG_TRY(T.run("k_gap_pick", [&] { return launch_gap_pick(ga, chunk, C, semi, stream); }));
+    RG_TRY(T.run("k_gap_dirs", [&] { return launch_gap_dirs(ga, chunk, C, semi, stream); }));
+    RG_TRY(T.run("k_gap_trace", [&] { return launch_gap_trace(ga, chunk, C, semi, stream); }));
+    return read_back();
 }
 
 // RG_DEBUG: the i32 form of k_opt0 beside the packed one — the two must agree on every read (the bound only steers the pruning,
@@ -361,7 +385,11 @@ int Run::enqueue_tail() {
     ta.rlayer = w.rlayer.p; ta.layer_stride = plan.layer_stride; ta.fpoff = w.fpoff.p; ta.fprow = w.fprow.p;
     ta.rpoff = w.rpoff.p; ta.rprow = w.rprow.p; ta.nreads = chunk; ta.mode = p.mode; ta.semi = plan.semi ? 1 : 0; ta.nwv = plan.nwv;
     RG_TRY(T.run("k_trace", [&] { return launch_trace(ta, C, stream); }));
-    // ONE read-back per chunk: cell updates + overflow summary, through pinned memory on the batch's stream
+    return read_back();
+}
+
+// ONE read-back per chunk: cell updates + overflow summary, through pinned memory on the batch's stream
+int Run::read_back() {
     HIPCHK(hipMemcpyAsync(w.h_sum, d_cells, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
     HIPCHK(hipMemcpyAsync(w.h_sum + 5, d_cells + 1, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
     HIPCHK(hipMemcpyAsync(w.h_sum + 1, w.need.p, 8 * sizeof(unsigned), hipMemcpyDeviceToHost, stream));
@@ -371,6 +399,7 @@ int Run::enqueue_tail() {
 // the whole pipeline of the chunk, enqueued on the stream and waited for
 int Run::enqueue_chunk() {
     HIPCHK(hipMemsetAsync(w.state.p, 0, sizeof(ReadState) * chunk, stream));
+    if (plan.gap) return enqueue_pathwise_gap();
     SweepArgs sa = sweep_args();
     SeedArgs se;
     se.g = gd; se.state = w.state.p; se.nreads = chunk; se.mode = p.mode; se.sc = sc; se.reads = d_reads; se.read_off = off();

@@ -76,8 +76,40 @@ bool sweep16_admissible(const DevScores& sc, int max_path_rows, int max_n, int C
     return true;
 }
 
+// -m 6 / -m 7: one wave per (read, path) keeps H and Y of the current row in registers, C columns per lane (n + 1 <= 64 C), so a
+// read must fit one wave; the only HBM work buffer beside ReadState holds the 4-bit directions of the picked path.
+static int plan_pathwise_gap(const rg_params& p, const PathPlanInput& in, PathPlan& o) {
+    if (p.gap_open > 0 || p.gap_ext > 0) return fail(RG_ERR_ARG, "gap penalties must be <= 0");
+    if (p.amb_mode) return fail(RG_ERR_ARG, "amb_mode must be 0 in the affine-gap pathwise modes (-m 6 / -m 7): they align the reads as given");
+    if (in.max_n > 32 * WAVE - 1)
+        return fail(RG_ERR_ARG, "reads longer than 2047 bases are not supported by the affine-gap pathwise modes (-m 6 / -m 7)");
+    // every value of H, X, Y is a sum of at most (rows + n) steps of at most max(|sc|, |o + e|) each: kept inside +-2^28, so that
+    // the NEG sentinel (-2^29) plus any such sum can neither win nor wrap
+    long long maxabs = std::llabs((long long)p.gap_open + (long long)p.gap_ext);
+    for (int x = 0; x < 5; ++x)
+        for (int y = 0; y < 5; ++y)
+            if (p.scores[x * 6 + y] != RG_SCORE_MISSING) maxabs = std::max<long long>(maxabs, std::llabs((long long)p.scores[x * 6 + y]));
+    if ((long long)(in.max_path_rows + in.max_n) * maxabs >= (1ll << 28))
+        return fail(RG_ERR_CAPACITY, "scores of this batch can reach 2^28 in magnitude: outside the i32 range of the affine-gap pathwise kernels");
+    o.gap = true;
+    o.mode = RG_MODE_PATHWISE_GAP;
+    o.semi = p.mode == RG_MODE_PATHWISE_GAP_SEMI;
+    int C = 4;
+    while (C * WAVE < in.max_n + 1) C *= 2;
+    o.C = C;
+    o.nwv = 1;
+    o.wpad = C * WAVE;
+    o.gap_words = std::max(1, C / 8);
+    o.gdirs_stride = (long long)(in.max_path_rows + 1) * o.gap_words * WAVE;
+    o.per_read = (size_t)o.gdirs_stride * 4 + sizeof(ReadState);
+    for (int x = 0; x < 5; ++x)
+        for (int y = 0; y < 5; ++y) o.maxmatch = std::max(o.maxmatch, p.scores[x * 6 + y]);
+    return RG_OK;
+}
+
 int plan_pathwise(const rg_params& p, const PathPlanInput& in, const Options& opt, int spec_level, PathPlan& o) {
     o = PathPlan{};
+    if (p.mode == RG_MODE_PATHWISE_GAP || p.mode == RG_MODE_PATHWISE_GAP_SEMI) return plan_pathwise_gap(p, in, o);
     const int P = in.P, L = in.L, max_n = in.max_n;
     o.semi = p.mode == RG_MODE_PATHWISE_SEMI || p.mode == RG_MODE_RECOMBINATION_SEMI;
     o.mode = p.mode == RG_MODE_PATHWISE_SEMI ? RG_MODE_PATHWISE : p.mode == RG_MODE_RECOMBINATION_SEMI ? RG_MODE_RECOMBINATION : p.mode;

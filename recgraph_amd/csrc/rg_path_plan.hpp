@@ -54,6 +54,11 @@ struct PathPlan {
     bool order;                   // longest-first launch order of the sweeps' waves wherever paths retire
     int spec_margin, spec4_margin, dsel_lo, dsel_hi, rec_pen;
     unsigned fcap, rcap, frec_cap, rrec_cap;    // what the lists of a handle start with (regrown on overflow)
+    // -m 6 / -m 7 (affine gaps, gap/rg_path_gap.hip): `mode` is RG_MODE_PATHWISE_GAP, `semi` says -m 7; one wave per (read, path),
+    // C columns per lane; the direction pass stores gap_words dwords per lane and row (4 bits per cell) for the picked path
+    bool gap;
+    int gap_words;
+    long long gdirs_stride;       // words per read: (rows of the longest path + 1) * gap_words * 64
 
     // ... with candidate lists of fcap / rcap entries and record lists of frec_cap / rrec_cap records
     size_t per_read_all(unsigned fcap_, unsigned rcap_, unsigned frec_cap_, unsigned rrec_cap_) const {

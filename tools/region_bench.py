@@ -3,7 +3,7 @@
 engine on other read lengths, score parameters and path counts, with the sweep kernel that ran and a parity check of a
 few reads against the oracle.  One JSON line per case.
 
-    python tools/region_bench.py [case ...]        cases: c5 x6 m3x5 hoxd70 len1500 p128 len600 (default: all but the strand cases)
+    python tools/region_bench.py [case ...]        cases: c5 x6 m3x5 hoxd70 len1500 p128 len600 gap (default: all but the strand cases and `gap`)
 
 The strand cases (RG_AMB_BOTH_STRANDS, config-5 shape; `reads_per_s` counts SOURCE reads): `both_strands_fwd` — option on, every
 read forward (what the option costs when nothing qualifies: compare with `c5`); `both_strands` — option on, half of the reads
@@ -11,6 +11,10 @@ reverse-complemented; `two_n` — option off, every read AND its reverse complem
 the option has to submit (half of a tile's reads are source reads).  `strand_vote_fwd` / `strand_vote` — the same two read sets
 (the same seeds) with RG_AMB_STRAND_VOTE on top: the first strand by a 12-mer vote; their parity check builds the expected
 text by that option's rule (include/recgraph_hip.h) from the oracle and the vote stated below.
+
+`gap` (only when named): -m 6 beside -m 4 on the same inputs — the C4 / C5 graph shapes (16 paths on 5 000 rows, 32 on 10 000) with
+reads of 150 and 1000 bases; one batch handle, timed over whole rg_batch_run calls after a warm-up run; a few reads of every
+-m 6 batch are checked against the rule (tests/pathwise_gap_rule.py).  One JSON line per (shape, length, mode).
 
 Every case: TILES tiles of TILE reads through one rg_stream (3 handles), timed after one warm-up tile per handle."""
 import json
@@ -51,9 +55,49 @@ def vote_first_reverse(kmers, read):
     return count("".join(comp[c] for c in reversed(read))) > count(read)
 
 
+def gap_case():
+    from recgraph_amd import api, synth
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import pathwise_gap_rule as R
+    runs = 3
+    for shape, rows, paths in (("C4", 5000, 16), ("C5", 10000, 32)):
+        for rlen, nreads in ((150, 4096), (1000, 2048)):
+            g = synth.haplotype_graph(rows, paths, path_len=rlen, seed=1234)
+            gg = api.Graph.from_gfa_text(g.gfa())
+            reads = synth.haplotype_reads(g, nreads, length=rlen, seed=900, mosaic_frac=0.0)
+            for mode in (api.MODE_PATHWISE_GAP, api.MODE_PATHWISE):
+                b = api.Batch(gg, reads, api.make_params(mode))
+                b.run()
+                ks0 = b.kernel_stats()
+                t0 = time.perf_counter()
+                ks = {}
+                for _ in range(runs):
+                    b.run()
+                    for k, v in b.kernel_stats().items():
+                        if not k.startswith(("host:", "mem:", "inst:")):
+                            ks[k] = ks.get(k, 0.0) + v[0] / runs
+                dt = (time.perf_counter() - t0) / runs
+                b.fetch()
+                ok = True
+                if mode == api.MODE_PATHWISE_GAP:
+                    lnz, prow = R.graph_paths(gg)
+                    for i in sorted({0, nreads - 1, nreads // 2, nreads // 3, 777 % nreads}):
+                        ok = ok and "\t".join(b.gaf_text(i, "r", 1)[:-1].split("\t")[12:]) == R.comments(lnz, prow, reads[i])
+                print(json.dumps({"case": "gap", "shape": shape, "mode": mode, "rows": gg.rows, "paths": paths, "read_len": rlen, "reads": nreads,
+                                  "reads_per_s": round(nreads / dt, 1), "ms_per_batch": round(dt * 1e3, 2), "cell_updates_per_s": round(b.cell_updates / dt),
+                                  "cell_updates_performed_per_s": round(b.cell_updates_performed / dt),
+                                  "kernel_ms_per_batch": {k: round(v, 2) for k, v in ks.items()}, "first_run_kernels": sorted(k for k in ks0 if not k.startswith(("mem:", "inst:"))),
+                                  "rule_checked": 5 if ok else "FAILED"}), flush=True)
+
+
 def main():
     from recgraph_amd import api, synth
     from oracle import oracle as O
+    if "gap" in sys.argv[1:]:
+        gap_case()
+        sys.argv = [a for a in sys.argv if a != "gap"]
+        if len(sys.argv) == 1:
+            return
     names = [a for a in sys.argv[1:] if not a.startswith("-")] or [c for c in CASES if "strands" not in CASES[c][4]]
     check = 12
     handles = int(os.environ.get("RG_REGION_HANDLES", "3"))      # (1: the kernels' lone durations)
