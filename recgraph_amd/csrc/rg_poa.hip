@@ -12,13 +12,10 @@
 // arena (only band cells [start,right) are stored); rinfo[row] = {arena offset, start, right,
 // best_scoring_pos}.  A cell that the reference never writes reads as min_score / "-1" exactly as
 // in its full-width matrices (global_abpoa.rs:20-22).
-#include "rg_device.hpp"
 #include "rg_band.hpp"
-#include "rg_poa_args.hpp"
+#include "rg_poa_common.hpp"
 
 namespace rg {
-
-__device__ __forceinline__ int sc_at(const DevScores& sc, int a, int b) { return sc.t[a * 6 + b]; }
 
 // band_simd (utils.rs:17-98, simd_version = true): rg_band.hpp
 
@@ -45,38 +42,20 @@ template <bool kLdsRead, bool kUniGap>
 // instead of 77 — were tried in round 4: the same 1.40 M reads/s with 16 % MORE instructions (rematerialisation): 12 %
 // VALU-active per wave at 6-8 waves is a SIMD that issues most of the time; the kernel is bound by its instruction count.)
 __global__ __launch_bounds__(64) void k_m0_simd(PoaArgs a) {
-    const int slot = blockIdx.x;              // arena slot of this launch
-    const int rd = a.read_base + slot;        // read of the batch
-    const int lane = threadIdx.x;
+    extern __shared__ int m0_lds[];
+    PoaRead<kLdsRead> P;
+    if (!P.init(a, m0_lds, 1)) return;
+    const int rd = P.rd, lane = P.lane, W = P.W;
+    const int* sct = P.sct;
+    DevRecord* rec = P.rec;
+    int* am = P.am;
+    uint32_t* apw = P.pw0;
     const DevLnz& g = a.g;
     const int L = g.L;
-    const long long ro = a.read_off[rd];
-    const int n = (int)(a.read_off[rd + 1] - ro);
-    const uint8_t* gread = a.reads + ro - 1;  // read_at(j), j = 1..n
-    // Score table and (when it fits) the read's base codes live in LDS: both are indexed per lane every row, and as
-    // kernel-argument / global loads each lookup was a dependent memory round trip (78 % of the wave cycles waiting).
-    extern __shared__ int m0_lds[];
-    int* sct = m0_lds;                                       // [36]
-    uint8_t* lread = reinterpret_cast<uint8_t*>(m0_lds + 36);   // [n + 1] when a.lds_read
-    if (lane < 36) sct[lane] = a.sc.t[lane];
-    if (kLdsRead)
-        for (int j = 1 + lane; j <= n; j += WAVE) lread[j] = gread[j];
-    __syncthreads();
-    // (a run-time choice between the two pointers would turn every access into a FLAT load)
-    auto read_at = [&](int j) -> int { return kLdsRead ? (int)lread[j] : (int)gread[j]; };
-    DevRecord* rec = a.rec + rd;
-    const int W = n + 1;
-    if (a.bad[rd]) {
-        if (lane == 0) { rec->status = ST_BAD_BASE; rec->n_ops = 0; rec->score = 0; }
-        return;
-    }
-    int* am = a.arena_m + (long long)slot * a.cap_cells;
-    uint32_t* apw = a.arena_pw + (long long)slot * a.cap_cells;
-    int4* rinfo = a.rinfo + (long long)slot * L;
+    int4* rinfo = a.rinfo + (long long)P.slot * L;
     const unsigned bta = (unsigned)a.bta[rd];
-    const int GAP = 5;
     const int ugap = sct[GAP];            // (kUniGap: the cost of every read base)
-    M0Ctx cx{am, rinfo, a.col0, 2 * W * sct[read_at(1) * 6 + GAP]};  // global_abpoa.rs:20
+    M0Ctx cx{am, rinfo, a.col0, 2 * W * sct[P.at(1) * 6 + GAP]};  // global_abpoa.rs:20
     long long off = 0;
     unsigned long long ncells = 0;
     bool overflow = false;
@@ -95,7 +74,7 @@ __global__ __launch_bounds__(64) void k_m0_simd(PoaArgs a) {
             int carry = 0;
             for (int cb = 0; cb < (int)right; cb += WAVE) {
                 int c = cb + lane;
-                int gc = (c >= 1 && c < (int)right) ? sct[read_at(c) * 6 + GAP] : 0;
+                int gc = (c >= 1 && c < (int)right) ? sct[P.at(c) * 6 + GAP] : 0;
                 int s = wave_incl_sum(gc, lane) + carry;
                 if (c < (int)right) { am[c] = s; apw[c] = (c == 0) ? 0u : 3u; }  // path 0.3 -> (pred 0, L)
                 row0_v0 = cb == 0 ? s : row0_v0;
@@ -240,7 +219,7 @@ __global__ __launch_bounds__(64) void k_m0_simd(PoaArgs a) {
                 // per SIMD issue SALU 96 % of the time) and every divergent `if` costs it three instructions (save exec,
                 // branch, restore): the nest this replaces — active / SIMD part or tail / strict or weak compare — was a
                 // third of the row's scalar instructions.
-                const int rc = read_at(min(c, W - 1));
+                const int rc = P.at(min(c, W - 1));
                 const int us = bu + g_row;
                 // SIMD part (:144): key (row base, read base), ties -> up; tail (:175-181, :206): D > U > L and, behind a row
                 // with listed predecessors, the swapped key
@@ -250,18 +229,15 @@ __global__ __launch_bounds__(64) void k_m0_simd(PoaArgs a) {
                 pw = isd ? ((uint32_t)pd << 2 | 1u) : ((uint32_t)pu << 2 | 2u);
                 if (!kUniGap) {
                     const int head = start + ((c - start) / 8) * 8;
-                    const int gk = simd ? read_at(min(head, W - 1)) : rc;  // gap key: the chunk head's base (:157) / the cell's own
+                    const int gk = simd ? P.at(min(head, W - 1)) : rc;  // gap key: the chunk head's base (:157) / the cell's own
                     gc = act ? sct[gk * 6 + GAP] : 0;
                 }
             }
             // active lanes are a prefix of the wave: with one gap cost for every base the inclusive sum is (lane + 1) * g
             const int G = kUniGap ? carry_G + (lane + 1) * ugap : dpp_incl_sum(gc) + carry_G;
-            const int y = act ? b - G : INT32_MIN / 2;
-            const int zi = dpp_incl_max(y, INT32_MIN / 2);
-            int zprev = dpp_shr1(zi, INT32_MIN / 2);
-            zprev = lane == 0 ? carry_z : max(zprev, carry_z);
-            const bool tl = act && zprev > y;                                 // strict '>' (:158)
-            const int v = tl ? zprev + G : b;
+            const LinScan z = lin_scan(b, G, act, INT32_MIN / 2, lane, carry_z);
+            const bool tl = act && z.zprev > z.y;                                // strict '>' (:158)
+            const int v = tl ? z.zprev + G : b;
             pw = tl ? (((uint32_t)i << 2) | 3u) : pw;
             if (act) {
                 am[off + (c - start)] = v;
@@ -282,8 +258,8 @@ __global__ __launch_bounds__(64) void k_m0_simd(PoaArgs a) {
                 const unsigned long long at = __ballot(act && v == cmx);
                 best_v = cmx; best_c = cb + 63 - __clzll((long long)at);
             }
-            carry_z = max(carry_z, __builtin_amdgcn_readlane(zi, WAVE - 1));
-            carry_G = kUniGap ? carry_G + min(WAVE, right - cb) * ugap : __builtin_amdgcn_readlane(G, WAVE - 1);
+            const int last_G = lin_carry(z, G, carry_z);
+            carry_G = kUniGap ? carry_G + min(WAVE, right - cb) * ugap : last_G;
         }
         if (lane == 0) rinfo[i] = make_int4((int)off, start, right, best_c);
         off += width;
@@ -312,9 +288,8 @@ __global__ __launch_bounds__(64) void k_m0_simd(PoaArgs a) {
     }
     // ---- traceback over the stored path words (gaf_output.rs:777-817), one lane ----
     if (lane == 0) {
-        uint8_t* ops = a.ops + (long long)rd * a.ops_stride;
-        int32_t* orow = a.oprows + (long long)rd * a.ops_stride;
-        int row = last_row, col = W - 1, nops = 0;
+        OpsOut out(a, rd);
+        int row = last_row, col = W - 1;
         uint32_t status = 0;
         while (true) {
             uint32_t pw;
@@ -329,40 +304,20 @@ __global__ __launch_bounds__(64) void k_m0_simd(PoaArgs a) {
                 pw = (col >= ri.y && col < ri.z) ? apw[ri.x + (col - ri.y)] : 0xffffffffu;
             }
             if (pw == 0xffffffffu) { status |= ST_BAND_NOT_ENOUGH; break; }
-            const int dir = (int)(pw & 3u), pred = (int)(pw >> 2);
-            if (nops >= a.ops_stride) { status |= ST_WOULD_PANIC; break; }
-            if (dir == 1) {
-                if (col == 0) { status |= ST_WOULD_PANIC; break; }
-                ops[nops] = OP_D; orow[nops] = pred; row = pred; col -= 1;
-            } else if (dir == 2) {
-                ops[nops] = OP_U; orow[nops] = pred; row = pred;
-            } else {
-                if (col == 0) { status |= ST_WOULD_PANIC; break; }
-                ops[nops] = OP_L; orow[nops] = -1; col -= 1;
-            }
-            ++nops;
+            const uint32_t dir = pw & 3u;             // the f32 path's .1 / .2 / .3
+            if (out.n >= a.ops_stride) { status |= ST_WOULD_PANIC; break; }
+            if (!walk_step(SameColumn{}, dir == 1 ? PD_D : dir == 2 ? PD_U : PD_L, (int)(pw >> 2), row, col, out)) { status |= ST_WOULD_PANIC; break; }
         }
-        rec->status = status;
-        rec->score = best;
-        rec->fscore = (float)best;
-        rec->end_row = last_row;
-        rec->end_col = W - 1;
-        rec->stop_row = row;
-        rec->stop_col = col;
-        rec->n_ops = nops;
-        rec->n_fwd_ops = 0;
+        write_record(rec, status, best, last_row, W - 1, row, col, out.n);
         atomicAdd(a.cells, ncells);
     }
 }
 
 const char* launch_m0_simd(const PoaArgs& a, hipStream_t s) {
-    const size_t bytes = 36 * sizeof(int) + (a.lds_read ? (((size_t)a.max_n + 2 + 3) & ~(size_t)3) : 0);
     bool uni = true;                     // one gap cost for every read base (ACGTN)
     for (int b = 1; b < 5; ++b) uni = uni && a.sc.t[b * 6 + 5] == a.sc.t[5];
-    if (a.lds_read && uni) RG_LAUNCH(k_m0_simd, (true, true), dim3(a.nreads), dim3(64), bytes, s, a);
-    else if (a.lds_read) RG_LAUNCH(k_m0_simd, (true, false), dim3(a.nreads), dim3(64), bytes, s, a);
-    else if (uni) RG_LAUNCH(k_m0_simd, (false, true), dim3(a.nreads), dim3(64), bytes, s, a);
-    else RG_LAUNCH(k_m0_simd, (false, false), dim3(a.nreads), dim3(64), bytes, s, a);
+    if (uni) RG_POA_LAUNCH(k_m0_simd, (true, true), (false, true), a, s);
+    else RG_POA_LAUNCH(k_m0_simd, (true, false), (false, false), a, s);
 }
 
 }  // namespace rg

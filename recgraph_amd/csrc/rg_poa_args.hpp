@@ -22,12 +22,12 @@ struct PoaArgs {
     const int4* rowmeta_b;
     int nreads;
     int max_n;                 // longest read of the batch
-    int lds_read;              // m0: the read's base codes are staged in LDS (max_n + 2 bytes per wave)
-    int read_base;             // local modes: first read of this launch (arena slots are launch-relative)
+    int lds_read;              // every POA kernel: the read's base codes are staged in LDS (max_n + 2 bytes per wave)
+    int read_base;             // every mode: first read of this launch (arena slots are launch-relative)
     int gap_open, gap_ext;     // m2
     long long cap_cells;       // arena capacity per read (cells)
-    int* arena_m;              // [nreads][cap_cells] (m2: 3 planes)
-    uint32_t* arena_pw;        // [nreads][cap_cells] (m2: 3 planes)
+    int* arena_m;              // [nreads][planes][cap_cells]: 2 planes (m | y) in the affine modes (-m 2, -m 3), else 1
+    uint32_t* arena_pw;        // path words, the same layout (w0 | w1)
     int4* rinfo;               // [nreads][L]  {arena offset, first stored column, right, best_scoring_pos}
     DevRecord* rec;            // [nreads]
     uint8_t* ops;              // [nreads][ops_stride]

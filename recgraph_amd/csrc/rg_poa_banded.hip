@@ -11,24 +11,12 @@
 //   m0 scalar:  m[j] = max(du[j], m[j-1] + g(read[c]))            (du = max(d, u), L on strict '>')
 //   m2:         x[j] = e + max(x[j-1], m[j-1] + o),  m[j] = max(t[j], x[j]),  t = max(d, y)
 //               => x[j] - e*j = max(boundary, max_{k<j}(t[k] + o - e*k))      (needs o <= 0)
-#include "rg_device.hpp"
 #include "rg_band.hpp"
-#include "rg_poa_args.hpp"
+#include "rg_poa_common.hpp"
 
 namespace rg {
 
-namespace {
-
-constexpr int NEGB = INT32_MIN / 4;
-
-__device__ __forceinline__ int scb(const DevScores& sc, int a, int b) { return sc.t[a * 6 + b]; }
-
 // band_plain (utils.rs:17-72, simd_version = false): rg_band.hpp
-
-// direction codes of bitfield_path.rs:3-15 that these modes use
-enum : uint32_t { PD_O = 0, PD_D = 1, PD_d = 2, PD_L = 3, PD_U = 4 };
-
-}  // namespace
 
 // kGap = false: scalar -m 0;  kGap = true: -m 2.
 // Arena planes per read (cap_cells each): m | y (m2) ; path words: w0 = pred<<3 | dir | X<<31, w1 = predY<<1 | Y.
@@ -36,38 +24,18 @@ template <bool kGap, bool kLdsRead>
 // (8 waves per SIMD — 64 VGPRs — were tried like in rg_poa.hip: 6 registers spill and config 3 loses 2-8 %: not bound by
 // occupancy either.  profiles/r04_notes.md)
 __global__ __launch_bounds__(64) void k_poa_banded(PoaArgs a) {
-    const int slot = blockIdx.x;              // arena slot of this launch
-    const int rd = a.read_base + slot;        // read of the batch
-    const int lane = threadIdx.x;
+    extern __shared__ int pb_lds[];
+    PoaRead<kLdsRead> P;
+    if (!P.init(a, pb_lds, kGap ? 2 : 1)) return;
+    const int rd = P.rd, lane = P.lane, W = P.W;
+    const int* sct = P.sct;
+    DevRecord* rec = P.rec;
+    int *am = P.am, *ay = P.ay;
+    uint32_t *pw0 = P.pw0, *pw1 = P.pw1;
     const DevLnz& g = a.g;
     const int L = g.L;
-    const long long ro = a.read_off[rd];
-    const int n = (int)(a.read_off[rd + 1] - ro);
-    const uint8_t* gread = a.reads + ro - 1;
-    DevRecord* rec = a.rec + rd;
-    const int W = n + 1;
-    // score table and read codes in LDS (per-lane lookups every row; as kernel-argument / global loads each one is a
-    // dependent memory round trip), wave-uniform graph tables through the scalar cache (uload)
-    extern __shared__ int pb_lds[];
-    int* sct = pb_lds;
-    uint8_t* lread = reinterpret_cast<uint8_t*>(pb_lds + 36);
-    if (lane < 36) sct[lane] = a.sc.t[lane];
-    if (kLdsRead)
-        for (int jj = 1 + lane; jj <= n; jj += WAVE) lread[jj] = gread[jj];
-    __syncthreads();
-    auto read_at = [&](int jj) -> int { return kLdsRead ? (int)lread[jj] : (int)gread[jj]; };
-    if (a.bad[rd]) {
-        if (lane == 0) { rec->status = ST_BAD_BASE; rec->n_ops = 0; rec->score = 0; }
-        return;
-    }
-    constexpr int planes = kGap ? 2 : 1;
-    int* am = a.arena_m + (long long)slot * a.cap_cells * planes;
-    int* ay = am + a.cap_cells;
-    uint32_t* pw0 = a.arena_pw + (long long)slot * a.cap_cells * planes;
-    uint32_t* pw1 = pw0 + a.cap_cells;
-    int4* rinfo = a.rinfo + (long long)slot * L;
+    int4* rinfo = a.rinfo + (long long)P.slot * L;
     const unsigned long long bta = (unsigned long long)a.bta[rd];
-    const int GAP = 5;
     const int o = a.gap_open, e = a.gap_ext;
     long long off = 0;
     unsigned long long ncells = 0;
@@ -79,7 +47,7 @@ __global__ __launch_bounds__(64) void k_poa_banded(PoaArgs a) {
     // fire and forget.  Rows with other predecessors take the memory path; a barrier orders the earlier stores first.
     constexpr int KC = 8;
     int pvm[KC] = {}, pvy[kGap ? KC : 1] = {};
-    int p_left = 0, p_right = 0, p_best = 0, p_off = 0;
+    int p_left = 0, p_right = 0, p_best = 0;
     bool p_valid = false, dirty = false;
     // (the empty asm statements keep the selects apart: left alone the compiler fuses a chain of them into a dynamically
     // indexed vector which it keeps in SCRATCH — 48 bytes per lane, stores every row and dependent loads every chunk of the
@@ -128,16 +96,15 @@ __global__ __launch_bounds__(64) void k_poa_banded(PoaArgs a) {
         int keep_m[KC] = {}, keep_y[kGap ? KC : 1] = {};
         int ci = 0;
         // carries of the scans across 64-column chunks
-        int carry_z = NEGB;       // running prefix max (exclusive) of the scan variable
+        int carry_z = NEG;        // m0 scalar: running prefix max (exclusive) of the scan variable
         int carry_G = 0;          // m0 scalar: prefix sum of gap costs
-        int carry_t = NEGB;       // m2: t of the last column of the previous chunk (for the X flag)
-        int carry_zprev = NEGB;   // m2: exclusive prefix max at the previous chunk's last column
+        AffCarry ac{NEG, NEG, NEG};   // m2
         long long best_key = ((long long)INT32_MIN) * 4294967296ll;
         for (int cb = 0; cb < width; cb += WAVE, ++ci) {
             const int j = cb + lane;
             const bool act = j < width;
             const int c = left + j;
-            const int rc = (act && c >= 1) ? read_at(c) : 4;
+            const int rc = (act && c >= 1) ? P.at(c) : 4;
             // fast path: m[i-1] at columns c-1 and c (and y[i-1] at c) from the registers of the row above
             int f_md = 0, f_mu = 0, f_yu = 0;
             if (fast) {
@@ -185,7 +152,7 @@ __global__ __launch_bounds__(64) void k_poa_banded(PoaArgs a) {
             bool fixed = false;          // cell fully determined without the left chain
             int mval = 0;
             uint32_t w0 = 0, w1 = 0;
-            int tval = NEGB;             // non-left candidate of the cell (max(d,u) / max(d,y))
+            int tval = NEG;             // non-left candidate of the cell (max(d,u) / max(d,y))
             uint32_t tw0 = 0;            // its path word
             int yval = 0;
             if (act) {
@@ -238,9 +205,9 @@ __global__ __launch_bounds__(64) void k_poa_banded(PoaArgs a) {
                 // ---------------- scalar m0 (global_abpoa.rs:318-390) ----------------
                 int gc = 0;
                 bool chain = false;           // cell takes part in the left chain
-                int lfb = NEGB;               // left fallback of a band-left cell (:337-339)
+                int lfb = NEG;               // left fallback of a band-left cell (:337-339)
                 if (act && !fixed) {
-                    if (i == 0) { chain = true; gc = sct[(GAP) * 6 + (rc)]; tval = NEGB; }   // key ('-', base) (:307)
+                    if (i == 0) { chain = true; gc = sct[(GAP) * 6 + (rc)]; tval = NEG; }   // key ('-', base) (:307)
                     else {
                         const int dv = have_d ? d + sct[(li) * 6 + (rc)] : sct[(li) * 6 + (GAP)] * (i + left);
                         const int uv = have_u ? u + sct[(li) * 6 + (GAP)] : sct[(li) * 6 + (GAP)] * (i + left + j);
@@ -260,29 +227,26 @@ __global__ __launch_bounds__(64) void k_poa_banded(PoaArgs a) {
                 if (act && !fixed && !chain && i > 0) {   // band-left cell with left > 0: l is a constant
                     if (lfb > tval) { v0 = lfb; v0w = ((uint32_t)(minp & 0xffff) << 3) | PD_L; }
                 }
-                const int y = act ? v0 - G : NEGB;
-                const int zi = dpp_incl_max(y, NEGB);
-                int zprev = dpp_shr1(zi, NEGB);
-                zprev = lane == 0 ? carry_z : max(zprev, carry_z);
+                const LinScan z = lin_scan(v0, G, act, NEG, lane, carry_z);
                 if (act) {
                     int v = v0;
                     uint32_t w = v0w;
-                    if (chain && zprev > y) { v = zprev + G; w = ((uint32_t)(i & 0xffff) << 3) | PD_L; }
-                    if (chain && i == 0) { v = zprev + G; w = (0u << 3) | PD_L; }
+                    if (chain && z.zprev > z.y) { v = z.zprev + G; w = ((uint32_t)(i & 0xffff) << 3) | PD_L; }
+                    if (chain && i == 0) { v = z.zprev + G; w = (0u << 3) | PD_L; }
                     am[off + j] = v;
                     pw0[off + j] = w;
                     mval = v;
-                    if (!fixed && i > 0) ncells += 0;  // counted below per wave
+                    // (no effect, and not dead weight: without this statement k_poa_banded<false, false> allocates 58 VGPRs instead of 57)
+                    if (!fixed && i > 0) ncells += 0;
                 }
-                carry_z = max(carry_z, __builtin_amdgcn_readlane(zi, WAVE - 1));
-                carry_G = __builtin_amdgcn_readlane(G, WAVE - 1);
+                carry_G = lin_carry(z, G, carry_z);
 #pragma unroll
                 for (int k = 0; k < KC; ++k) { keep_m[k] = ci == k ? mval : keep_m[k]; asm volatile("" : "+v"(keep_m[k])); }
             } else {
                 // ---------------- m2 (gap_global_abpoa.rs:67-196) ----------------
                 const bool fixed0 = act && i > 0 && j == 0 && left == 0;   // first column (:78-92)
                 const bool general = act && i > 0 && !fixed0;
-                int dv = NEGB, up_pred = minp, tcur = NEGB, xb = NEGB;
+                int dv = NEG, up_pred = minp, tcur = NEG, xb = NEG;
                 bool fromy = false;
                 if (act && i == 0) { mval = j == 0 ? 0 : o + e * c; yval = mval; w0 = j == 0 ? (uint32_t)PD_O : ((0u << 3) | PD_L); }
                 if (fixed0) { mval = o + e * (minp + 1); xb = mval; w0 = ((uint32_t)(minp & 0xffff) << 3) | PD_U; yval = 0; }
@@ -296,19 +260,20 @@ __global__ __launch_bounds__(64) void k_poa_banded(PoaArgs a) {
                     if (j == 0) xb = 2 * o + e * (minp + 1) + e * c;                    // (:117)
                 }
                 // x[j] - e*j = max over k < j of max(t[k] + o, xb[k]) - e*k   (x[j] = e + max(x[j-1], m[j-1] + o), o <= 0)
-                int zsrc = NEGB;
-                if (fixed0 || general) zsrc = max(tcur > NEGB ? tcur + o : NEGB, xb) - e * j;
-                const int zi = dpp_incl_max(zsrc, NEGB);
-                int ze = dpp_shr1(zi, NEGB);
-                ze = lane == 0 ? carry_z : max(ze, carry_z);
-                int xval = NEGB;
-                if (fixed0 || general) xval = j == 0 ? xb : ze + e * j;
+                int zsrc = NEG;
+                if (fixed0 || general) zsrc = max(tcur > NEG ? tcur + o : NEG, xb) - e * j;
+                AffScan x;
+                x.zi = dpp_incl_max(zsrc, NEG);
+                int ze = dpp_shr1(x.zi, NEG);
+                ze = lane == 0 ? ac.z : max(ze, ac.z);
+                x.xval = NEG;
+                if (fixed0 || general) x.xval = j == 0 ? xb : ze + e * j;
+                x.xprev = dpp_shr1(x.xval, NEG); x.tprev = dpp_shr1(tcur, NEG);
+                if (lane == 0) { x.xprev = ac.x; x.tprev = ac.t; }
                 // path_x = 'X' iff x[j-1] > m[j-1] + o, i.e. (o < 0) x[j-1] > t[j-1] + o   (:350-368)
-                int xprev = dpp_shr1(xval, NEGB), tprev = dpp_shr1(tcur, NEGB);
-                if (lane == 0) { xprev = carry_zprev; tprev = carry_t; }
-                const bool xflag = general && j > 0 && o != 0 && xprev > (tprev > NEGB ? tprev + o : NEGB);
+                const bool xflag = general && j > 0 && o != 0 && x.xprev > (x.tprev > NEG ? x.tprev + o : NEG);
                 if (general) {
-                    const int l = xval, uu = yval;
+                    const int l = x.xval, uu = yval;
                     const uint32_t lpred = (uint32_t)((j > 0 ? i : minp) & 0xffff);
                     int mv; uint32_t w;
                     if (have_d) {                                    // (:145-180)
@@ -326,7 +291,7 @@ __global__ __launch_bounds__(64) void k_poa_banded(PoaArgs a) {
                         else { mv = l; w = (lpred << 3) | PD_L; }
                     }
                     mval = mv;
-                    w0 = w | (xflag ? 0x80000000u : 0u);
+                    w0 = w | (xflag ? X_BIT : 0u);
                     w1 = fromy ? (((uint32_t)(up_pred & 0xffff) << 1) | 1u) : 0u;
                 }
                 if (act) {
@@ -335,9 +300,7 @@ __global__ __launch_bounds__(64) void k_poa_banded(PoaArgs a) {
                     pw0[off + j] = w0;
                     pw1[off + j] = w1;
                 }
-                carry_zprev = __builtin_amdgcn_readlane(xval, WAVE - 1);     // x of the chunk's last column
-                carry_t = __builtin_amdgcn_readlane(tcur, WAVE - 1);
-                carry_z = max(carry_z, __builtin_amdgcn_readlane(zi, WAVE - 1));
+                aff_carry(x, tcur, ac);
 #pragma unroll
                 for (int k = 0; k < KC; ++k) {
                     keep_m[k] = ci == k ? mval : keep_m[k];
@@ -359,7 +322,7 @@ __global__ __launch_bounds__(64) void k_poa_banded(PoaArgs a) {
             ncells += (unsigned long long)general;
         }
         if (lane == 0) rinfo[i] = make_int4((int)off, left, right, (int)(best_key & 0xffffffffll) + left);
-        p_best = (int)(best_key & 0xffffffffll) + left; p_left = left; p_right = right; p_off = (int)off;
+        p_best = (int)(best_key & 0xffffffffll) + left; p_left = left; p_right = right;
         p_valid = width <= KC * WAVE;
 #pragma unroll
         for (int k = 0; k < KC; ++k) { pvm[k] = keep_m[k]; if (kGap) pvy[kGap ? k : 0] = keep_y[kGap ? k : 0]; }
@@ -391,17 +354,8 @@ __global__ __launch_bounds__(64) void k_poa_banded(PoaArgs a) {
         const int v = am[rp.x + tl];
         if (v > bestv) { bestv = v; last_row = p; last_col = tl; }
     }
-    auto word0 = [&](int r, int cidx) -> uint32_t { return pw0[rinfo[r].x + cidx]; };
-    auto word1 = [&](int r, int cidx) -> uint32_t { return pw1[rinfo[r].x + cidx]; };
-    auto widthof = [&](int r) { const int4 q = rinfo[r]; return q.z - q.y; };
-    // j_pos of the reference: column of (row, col) translated into pred's band; false = usize wrap
-    auto jpos = [&](int row, int col, int pred, int& out) -> bool {
-        const int lr = rinfo[row].y, lp = rinfo[pred].y;
-        if (lp < lr) { out = col + (lr - lp); return true; }
-        if (col < lp - lr) return false;
-        out = col - (lp - lr);
-        return true;
-    };
+    const BandRel cells{pw0, pw1, rinfo};
+    OpsOut out(a, rd);
     // ---- band_ampl_enough (global_abpoa.rs:428-476, gap_global_abpoa.rs:371-455) ----
     {
         int i = last_row, j = last_col;
@@ -409,8 +363,8 @@ __global__ __launch_bounds__(64) void k_poa_banded(PoaArgs a) {
         int guard = 0;
         while (true) {
             if (++guard > 4 * (L + W)) { status |= ST_WOULD_PANIC; break; }
-            if (i < 0 || i >= L - 1 || j < 0 || j >= widthof(i)) { status |= ST_WOULD_PANIC; break; }
-            const uint32_t w = word0(i, j);
+            if (i < 0 || i >= L - 1 || j < 0 || j >= cells.width(i)) { status |= ST_WOULD_PANIC; break; }
+            const uint32_t w = cells.w0(i, j);
             const uint32_t dir = w & 7u;
             if (dir == PD_O) break;
             const int4 ri = rinfo[i];
@@ -419,27 +373,17 @@ __global__ __launch_bounds__(64) void k_poa_banded(PoaArgs a) {
             const int pred = (int)((w >> 3) & 0xffffu);
             if (dir == PD_D || dir == PD_d) {
                 int jp;
-                if (!jpos(i, j, pred, jp) || jp == 0) { status |= ST_WOULD_PANIC; break; }
+                if (!cells.pred_col(i, j, pred, jp) || jp == 0) { status |= ST_WOULD_PANIC; break; }
                 j = jp - 1; i = pred;
             } else if (dir == PD_L) {
-                if (kGap && (w >> 31)) { while (j > 0 && j < widthof(i) && (word0(i, j) >> 31)) j -= 1; }
+                if (kGap && (w >> 31)) { while (j > 0 && j < cells.width(i) && (cells.w0(i, j) >> 31)) j -= 1; }
                 else j -= 1;
             } else if (dir == PD_U) {
-                if (kGap && (word1(i, j) & 1u)) {
-                    bool bad = false;
-                    while (true) {
-                        if (j < 0 || j >= widthof(i)) { bad = true; break; }
-                        const uint32_t y1 = word1(i, j);
-                        if (!(y1 & 1u)) break;
-                        const int p = (int)(y1 >> 1);
-                        int jp;
-                        if (!jpos(i, j, p, jp)) { bad = true; break; }
-                        j = jp; i = p;
-                    }
-                    if (bad) { status |= ST_WOULD_PANIC; break; }
+                if (kGap && (cells.w1(i, j) & 1u)) {
+                    if (!walk_u_run<false>(cells, i, j, out)) { status |= ST_WOULD_PANIC; break; }
                 } else {
                     int jp;
-                    if (!jpos(i, j, pred, jp)) { status |= ST_WOULD_PANIC; break; }
+                    if (!cells.pred_col(i, j, pred, jp)) { status |= ST_WOULD_PANIC; break; }
                     j = jp; i = pred;
                 }
             } else { if (kGap) { ok = false; } else { status |= ST_WOULD_PANIC; } break; }
@@ -447,79 +391,16 @@ __global__ __launch_bounds__(64) void k_poa_banded(PoaArgs a) {
         if (!ok) status |= ST_BAND_WARNING;
     }
     // ---- traceback (gaf_output.rs:124-213 / 280-344) ----
-    uint8_t* ops = a.ops + (long long)rd * a.ops_stride;
-    int32_t* orow = a.oprows + (long long)rd * a.ops_stride;
-    int nops = 0;
     int row = last_row, col = last_col;
-    if (!(status & ST_WOULD_PANIC)) {
-        int guard = 0;
-        while (true) {
-            if (++guard > 4 * (L + W) || nops + 2 >= a.ops_stride) { status |= ST_WOULD_PANIC; break; }
-            if (row < 0 || row >= L - 1 || col < 0 || col >= widthof(row)) { status |= ST_WOULD_PANIC; break; }
-            const uint32_t w = word0(row, col);
-            const uint32_t dir = w & 7u;
-            if (dir == PD_O) break;
-            const int pred = (int)((w >> 3) & 0xffffu);
-            int jp = 0;
-            const bool jp_ok = jpos(row, col, pred, jp);
-            if (dir == PD_D || dir == PD_d) {
-                if (!jp_ok || jp == 0) { status |= ST_WOULD_PANIC; break; }
-                ops[nops] = OP_D | (dir == PD_d ? 0x40 : 0); orow[nops] = pred; ++nops;
-                row = pred; col = jp - 1;
-            } else if (dir == PD_L) {
-                if (kGap && (w >> 31)) {
-                    bool first = true, bad = false;
-                    while (true) {
-                        if (col < 0 || col >= widthof(row)) { bad = true; break; }
-                        if (!(word0(row, col) >> 31)) break;
-                        if (col == 0 || nops + 2 >= a.ops_stride) { bad = true; break; }
-                        ops[nops] = OP_L | (first ? 0 : OP_CONT); orow[nops] = -1; ++nops; first = false;
-                        col -= 1;
-                    }
-                    if (bad) { status |= ST_WOULD_PANIC; break; }
-                } else {
-                    if (col == 0) { status |= ST_WOULD_PANIC; break; }
-                    ops[nops] = OP_L; orow[nops] = -1; ++nops; col -= 1;
-                }
-            } else if (dir == PD_U) {
-                if (kGap && (word1(row, col) & 1u)) {
-                    bool first = true, bad = false;
-                    while (true) {
-                        if (col < 0 || col >= widthof(row)) { bad = true; break; }
-                        const uint32_t y1 = word1(row, col);
-                        if (!(y1 & 1u)) break;
-                        const int p = (int)(y1 >> 1);
-                        int jq;
-                        if (!jpos(row, col, p, jq) || nops + 2 >= a.ops_stride) { bad = true; break; }
-                        ops[nops] = OP_U | (first ? 0 : OP_CONT); orow[nops] = p; ++nops; first = false;
-                        col = jq; row = p;
-                    }
-                    if (bad) { status |= ST_WOULD_PANIC; break; }
-                } else {
-                    if (!jp_ok) { status |= ST_WOULD_PANIC; break; }
-                    ops[nops] = OP_U; orow[nops] = pred; ++nops;
-                    row = pred; col = jp;
-                }
-            } else { status |= ST_WOULD_PANIC; break; }
-        }
-    }
-    rec->status = status;
-    rec->score = bestv;
-    rec->fscore = (float)bestv;
-    rec->end_row = last_row;
-    rec->end_col = last_col + rinfo[last_row].y;   // query_end = last_col + left(last_row)
-    rec->stop_row = row;
-    rec->stop_col = col;                           // query_start = band-relative col where the walk stopped
-    rec->n_ops = (status & ST_WOULD_PANIC) ? 0 : nops;
-    rec->n_fwd_ops = 0;
+    if (!(status & ST_WOULD_PANIC)) status |= walk_trace<kGap>(cells, L, W, row, col, out);
+    // query_end = last_col + left(last_row); query_start = the band-relative column where the walk stopped
+    write_record(rec, status, bestv, last_row, last_col + rinfo[last_row].y, row, col, (status & ST_WOULD_PANIC) ? 0 : out.n);
     atomicAdd(a.cells, ncells);
 }
 
 template <bool kGap>
 static const char* launch_banded(const PoaArgs& a, hipStream_t s) {
-    const size_t bytes = 36 * sizeof(int) + (a.lds_read ? (((size_t)a.max_n + 2 + 3) & ~(size_t)3) : 0);
-    if (a.lds_read) RG_LAUNCH(k_poa_banded, (kGap, true), dim3(a.nreads), dim3(64), bytes, s, a);
-    else RG_LAUNCH(k_poa_banded, (kGap, false), dim3(a.nreads), dim3(64), bytes, s, a);
+    RG_POA_LAUNCH(k_poa_banded, (kGap, true), (kGap, false), a, s);
 }
 const char* launch_m2(const PoaArgs& a, hipStream_t s) { return launch_banded<true>(a, s); }
 const char* launch_m0_scalar(const PoaArgs& a, hipStream_t s) { return launch_banded<false>(a, s); }
