@@ -36,6 +36,7 @@ typedef enum rg_status {
 #define RG_READ_BAND_NOT_ENOUGH 2u  /* reference prints "band not enough for correct output" and an empty GAF (gaf_output.rs:861-864) */
 #define RG_READ_WOULD_PANIC 4u      /* reference would panic on this read (index out of range, set_path_cell('u') ...) */
 #define RG_READ_BAD_BASE 8u         /* read contains a character outside ACGTN (reference: HashMap unwrap panic) */
+#define RG_READ_UNALIGNED 16u       /* RG_MODE_PATHWISE_GAP_LOCAL only: the read has no local alignment (best score 0); no record, no text */
 
 /* Alignment modes: the `-m` values of the reference CLI (args_parser.rs:31-38) on the hot path. */
 #define RG_MODE_GLOBAL_POA 0        /* global_abpoa::exec_simd          src/global_abpoa.rs:10      */
@@ -83,6 +84,33 @@ typedef enum rg_status {
  */
 #define RG_MODE_PATHWISE_GAP 6
 #define RG_MODE_PATHWISE_GAP_SEMI 7
+/*
+ * RG_MODE_PATHWISE_GAP_LOCAL (12): LOCAL pathwise alignment with affine gaps (Smith-Waterman-Gotoh against every path): the
+ * third member of the family above, for reads that are only partly on the graph (overhangs, adapters, chimeras).  Like modes 6
+ * and 7 it is A DEFINITION OF THIS PROJECT'S OWN.  Inputs and score lookups are those of mode 6.
+ *   RECURRENCE, independently for every path:
+ *     H[0][j] = 0,  H[i][0] = 0;  X and Y are NEG on both borders
+ *     Y[i][j] = max(H[i-1][j] + o + e, Y[i-1][j] + e)
+ *     X[i][j] = max(H[i][j-1] + o + e, X[i][j-1] + e)
+ *     H[i][j] = max(0, H[i-1][j-1] + sc(b_i, s_j), Y[i][j], X[i][j])
+ *   CHOICE.  Maximise H_k[i][j] over paths k, i >= 1, 1 <= j <= n; ties go to the smallest graph row, then to the lowest path
+ *     index (the order of mode 7), then to the smallest column.  end_row is that row, end_col = j.
+ *   UNALIGNED.  If the maximum is 0 the read has no local alignment: status RG_READ_UNALIGNED, score 0, a record without ops.
+ *     rg_result_gaf, rg_result_fields, rg_batch_format_all and the stream's text treat such a read as they treat a
+ *     RG_READ_BAD_BASE read of a pathwise mode: it has no line.
+ *   TRACEBACK from state H at (end_row, end_col).  In H: stop if H[i][j] == 0 (checked first); otherwise D if
+ *     H == H[i-1][j-1] + sc, else U (to state Y) if H == Y, else L (to state X).  The Y and X states and their "prefer to have
+ *     been opened" rule are those of mode 6.  The walk always ends on a cell with H == 0 (every border cell is one); stop_col
+ *     is the column where it ends.
+ *   RECORD and LINE.  The record and the comments of -m 4, "<cigar>, best path: k, score: S\t<path bases>", except that query
+ *     start is stop_col, query end is end_col - 1 (inclusive, as modes 4-7 print 0 and n - 1), and CIGAR and path bases cover
+ *     the aligned part only: clipped read bases appear nowhere else.  Path string, length, start and end are derived from (best
+ *     path, end row, ops) as for mode 7.
+ *   REFUSALS.  Those of modes 6 and 7, answered by rg_batch_create before a device is needed.
+ * rg_batch_cell_updates counts rows_k * n per path and read; rg_batch_cell_updates_performed adds the direction pass, which
+ * covers the rows of the chosen path up to the end row.
+ */
+#define RG_MODE_PATHWISE_GAP_LOCAL 12
 
 /*
  * Scoring and banding parameters.  Replaces the HashMap<(char,char),i32|f32> score matrix arguments

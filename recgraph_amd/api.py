@@ -47,8 +47,11 @@ MODE_GAP_LOCAL_POA = 3
 # include/recgraph_hip.h), GAF in the -m 4 format
 MODE_PATHWISE_GAP = 6
 MODE_PATHWISE_GAP_SEMI = 7
+# ... and local (RG_MODE_PATHWISE_GAP_LOCAL): soft-clipped reads; a read without a local alignment has READ_UNALIGNED and no line
+MODE_PATHWISE_GAP_LOCAL = _lib.MODE_PATHWISE_GAP_LOCAL
 
 READ_BAND_WARNING, READ_BAND_NOT_ENOUGH, READ_WOULD_PANIC, READ_BAD_BASE = 1, 2, 4, 8
+READ_UNALIGNED = _lib.READ_UNALIGNED
 
 # rg_params.amb_mode bit 2 (RG_AMB_BOTH_STRANDS, include/recgraph_hip.h): both strands inside a pathwise batch — an extension
 # the reference does not have (its `-s true` covers modes 0-3 only)
@@ -56,7 +59,7 @@ AMB_BOTH_STRANDS = _lib.AMB_BOTH_STRANDS
 # bit 3 (RG_AMB_STRAND_VOTE), only together with bit 2: the strand that is aligned first is picked per read by a 12-mer vote
 AMB_STRAND_VOTE = _lib.AMB_STRAND_VOTE
 PATHWISE_MODES = (MODE_PATHWISE, MODE_PATHWISE_SEMI, MODE_RECOMBINATION, MODE_RECOMBINATION_SEMI)
-PATHWISE_GAP_MODES = (MODE_PATHWISE_GAP, MODE_PATHWISE_GAP_SEMI)      # (they align the reads as given: no both_strands)
+PATHWISE_GAP_MODES = (MODE_PATHWISE_GAP, MODE_PATHWISE_GAP_SEMI, MODE_PATHWISE_GAP_LOCAL)      # (they align the reads as given: no both_strands)
 
 
 def _both_strands_kw(mode, both_strands, kw, strand_vote=False):
@@ -65,7 +68,7 @@ def _both_strands_kw(mode, both_strands, kw, strand_vote=False):
     if not both_strands and not strand_vote:
         return kw
     if mode in PATHWISE_GAP_MODES:
-        raise _lib.RecGraphError(-1, "%s is not available in the affine-gap pathwise modes (6, 7)" % ("strand_vote" if strand_vote else "both_strands"))
+        raise _lib.RecGraphError(-1, "%s is not available in the affine-gap pathwise modes (6, 7, 12)" % ("strand_vote" if strand_vote else "both_strands"))
     if mode not in PATHWISE_MODES:
         raise _lib.RecGraphError(-1, "%s applies to the pathwise modes (4, 5, 8, 9) only: the POA modes align both "
                                      "strands with amb_strand (`-s true`)" % ("strand_vote" if strand_vote else "both_strands"))
@@ -747,6 +750,8 @@ def _single(graph, read, name, mode, seq_index=1, **kw):
     st = b.status(0)
     if st & (READ_WOULD_PANIC | READ_BAD_BASE):
         raise _lib.RecGraphError(-1, "the reference panics on this input (status %d)" % st)
+    if st & READ_UNALIGNED:
+        raise _lib.RecGraphError(-1, "the read has no local alignment (status %d)" % st)
     return b, b.gaf_text(0, name, seq_index)
 
 
@@ -856,6 +861,14 @@ def pathwise_alignment_gap_exec(sequence, graph, score_matrix=None, o=-4, e=-2):
 def pathwise_alignment_gap_semi_exec(sequence, graph, score_matrix=None, o=-4, e=-2):
     """-m 7: the semiglobal twin of ``pathwise_alignment_gap_exec`` (the alignment may start and end inside a path)."""
     _, text = _single(graph, "".join(sequence[1:]), "Temp", MODE_PATHWISE_GAP_SEMI, 1, score_matrix=score_matrix, o=o, e=e)
+    return GAFStruct.from_line(text.rstrip("\n"))
+
+
+def pathwise_alignment_gap_local_exec(sequence, graph, score_matrix=None, o=-4, e=-2):
+    """-m 12: the local member of the family (RG_MODE_PATHWISE_GAP_LOCAL in include/recgraph_hip.h): the best-scoring piece of the
+    read against a piece of one path; query_start / query_end of the GAFStruct say which piece of the read.  A read without a
+    local alignment (READ_UNALIGNED) raises, like a read with a bad base."""
+    _, text = _single(graph, "".join(sequence[1:]), "Temp", MODE_PATHWISE_GAP_LOCAL, 1, score_matrix=score_matrix, o=o, e=e)
     return GAFStruct.from_line(text.rstrip("\n"))
 
 

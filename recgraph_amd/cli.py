@@ -83,10 +83,12 @@ def main(argv=None):
         return time.time()
     from . import api
     tp = mark("import", t0)
-    if a.alignment_mode not in (0, 1, 2, 3, 4, 5, 6, 7, 8, 9):
-        raise SystemExit("Alignment mode must be in [0..9]")   # main.rs:315-317
+    if a.alignment_mode not in (0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 12):
+        raise SystemExit("Alignment mode must be in [0..9], or 12")   # main.rs:315-317; 12: local affine-gap pathwise, this project's own
     if a.alignment_mode in (6, 7) and (a.both_strands or a.strand_vote):
         raise SystemExit("--both-strands / --strand-vote are not available in modes 6 and 7: they align the reads as given")
+    if a.alignment_mode == 12 and (a.both_strands or a.strand_vote):
+        raise SystemExit("--both-strands / --strand-vote are not available in mode 12: it aligns the reads as given")
     amb = a.amb_strand == "true" and a.alignment_mode in (0, 1, 2, 3)     # modes 4+ ignore -s (main.rs:254-313)
     if a.strand_vote and a.alignment_mode in (0, 1, 2, 3):
         raise SystemExit("--strand-vote applies to modes 4, 5, 8 and 9: for modes 0-3 use `-s true`")
@@ -102,7 +104,7 @@ def main(argv=None):
     mode = {0: api.MODE_GLOBAL_POA_SCALAR if a.scalar else api.MODE_GLOBAL_POA, 2: api.MODE_GAP_POA,
             1: api.MODE_LOCAL_POA_SCALAR if a.scalar else api.MODE_LOCAL_POA, 3: api.MODE_GAP_LOCAL_POA,
             4: api.MODE_PATHWISE, 5: api.MODE_PATHWISE_SEMI, 6: api.MODE_PATHWISE_GAP, 7: api.MODE_PATHWISE_GAP_SEMI, 8: api.MODE_RECOMBINATION,
-            9: api.MODE_RECOMBINATION_SEMI}[a.alignment_mode]
+            9: api.MODE_RECOMBINATION_SEMI, 12: api.MODE_PATHWISE_GAP_LOCAL}[a.alignment_mode]
     kw = dict(score_matrix=scores, o=-a.gap_open, e=-a.gap_extension, b=float(a.extra_b), f=a.extra_f,
               R=a.base_rec_cost, r=a.multi_rec_cost, B=a.rec_band_width)
     to_file = a.out_file != "standard output"
@@ -117,6 +119,8 @@ def main(argv=None):
         records, numbers = [], []
         # warning lines are println!'d by the exec functions whatever -o says; only the record goes through write_gaf
         for k, t in enumerate(texts):
+            if not t and a.alignment_mode == 12:       # a read without a local alignment (RG_READ_UNALIGNED) has no record
+                continue
             lines = t.split("\n")[:-1]
             sys.stdout.write("".join(ln + "\n" for ln in lines[:-1]))
             records.append(lines[-1])

@@ -30,27 +30,7 @@ namespace rg {
 
 namespace {
 
-constexpr int GNEG = -(1 << 29);
-constexpr int gap_words(int C) { return C >= 8 ? C / 8 : 1; }
-
-// The base codes of the lane's columns (4 = N for the columns past the read).  kPack: four codes per dword — the direction pass,
-// whose masks and packed words compete with the three C-wide arrays for registers, pays one v_bfe per cell for 3 C / 4 registers
-template <int C, bool kPack>
-struct ReadCols {
-    int v[kPack ? C / 4 : C];
-    __device__ __forceinline__ void load(const uint8_t* read /* read[1..n] */, int n, int lane) {
-#pragma unroll
-        for (int i = 0; i < (kPack ? C / 4 : C); ++i) v[i] = 0;
-#pragma unroll
-        for (int q = 0; q < C; ++q) {
-            const int j = lane * C + q;
-            const int code = (j >= 1 && j <= n) ? (int)read[j] : 4;
-            if (kPack) v[q / 4] |= code << (8 * (q % 4));
-            else v[q] = code;
-        }
-    }
-    __device__ __forceinline__ int get(int q) const { return kPack ? (v[kPack ? q / 4 : 0] >> (8 * (q % 4))) & 0xff : v[kPack ? 0 : q]; }
-};
+#include "rg_path_gap_common.hpp"      // GNEG, gap_words, ReadCols, DirWords, NoDirs, row_index
 
 // what a wave needs besides: the score table in LDS as [path base][8], and row 0
 template <int C>
@@ -64,11 +44,6 @@ __device__ __forceinline__ void gap_setup(const GapArgs& a, int lane, int* sct, 
         Y[q] = GNEG;
     }
 }
-
-// the direction words of one row (k_gap_dirs) / nothing (k_gap_score: the row step then has no direction code at all)
-template <int C>
-struct DirWords { uint32_t w[gap_words(C)]; };
-struct NoDirs {};
 
 // One path row with base b.  Dirs = DirWords<C>: 4 bits per cell: bits 0-1 the source of H (1 D, 2 U, 3 L), bit 2 "Y[i][j] was
 // opened from H[i-1][j]", bit 3 "an X run that goes on to column j + 1 opens here" (H[i][j] + o >= X[i][j]).
@@ -130,17 +105,6 @@ __device__ __forceinline__ int pick_col(const int (&H)[C], int qn) {
 #pragma unroll
     for (int q = 0; q < C; ++q) v = max(v, q == qn ? H[q] : INT32_MIN);
     return v;
-}
-
-// index of `row` among the ascending rows of a path (-1: not there)
-__device__ __forceinline__ int row_index(const int* rows, int m, int row) {
-    int lo = 0, hi = m - 1;
-    while (lo <= hi) {
-        const int mid = (lo + hi) >> 1, r = rows[mid];
-        if (r == row) return mid;
-        if (r < row) lo = mid + 1; else hi = mid - 1;
-    }
-    return -1;
 }
 
 }  // namespace

@@ -80,7 +80,7 @@ static void append_gaf(const rg_batch* b, int64_t i, const char* name, int64_t s
     // write_gaf only, and read 0 gets its record like every other read.
     const bool score_only = seq_index == 0 && is_poa(b->p.mode);
     const int64_t k = amb && amb->rb && amb->rev_index ? amb->rev_index[i] : -1;
-    if (k >= 0 && !score_only && !(amb->rb->rec[(size_t)k].status & (ST_BAD_BASE | ST_WOULD_PANIC))) {
+    if (k >= 0 && !score_only && !(amb->rb->rec[(size_t)k].status & ST_NO_RECORD)) {
         // both exec calls print their warning lines while they run; write_gaf then prints the record the comparison picks
         GafFields r;
         if (build_fields(b, i, name, f) && build_fields(amb->rb, k, name, r)) {
@@ -91,7 +91,7 @@ static void append_gaf(const rg_batch* b, int64_t i, const char* name, int64_t s
             return;
         }
     }
-    if (!score_only && !is_poa(b->p.mode) && !(d.status & (ST_BAD_BASE | ST_WOULD_PANIC))) {
+    if (!score_only && !is_poa(b->p.mode) && !(d.status & ST_NO_RECORD)) {
         // the pathwise modes: straight into the buffer (the same bytes as build_fields(..).text(): tests/test_gpu_stream.py
         // holds the stream's text, written here, equal to rg_result_gaf's, written there)
         ReadRecord r;
@@ -103,7 +103,7 @@ static void append_gaf(const rg_batch* b, int64_t i, const char* name, int64_t s
         return;
     }
     if (!score_only && build_fields(b, i, name, f)) out += f.text();
-    else if ((d.status & (ST_BAD_BASE | ST_WOULD_PANIC)) == 0 && (d.status & ST_BAND_WARNING))
+    else if ((d.status & ST_NO_RECORD) == 0 && (d.status & ST_BAND_WARNING))
         out += "Band length probably too short, maybe try with larger b and f\n";
 }
 
@@ -359,7 +359,7 @@ int32_t rg_batch_create(const rg_graph* gc, const rg_params* p, const char* read
     if (!gc || !p || !reads || !read_off || !out || nreads < 1) return fail(RG_ERR_ARG, "null/empty argument");
     const rg_graph* g = gc;
     const int mode = p->mode;
-    const bool path_gap = mode == RG_MODE_PATHWISE_GAP || mode == RG_MODE_PATHWISE_GAP_SEMI;
+    const bool path_gap = mode == RG_MODE_PATHWISE_GAP || mode == RG_MODE_PATHWISE_GAP_SEMI || mode == RG_MODE_PATHWISE_GAP_LOCAL;
     if (!(is_poa(mode) || mode == RG_MODE_PATHWISE || mode == RG_MODE_RECOMBINATION || mode == RG_MODE_PATHWISE_SEMI ||
           mode == RG_MODE_RECOMBINATION_SEMI || path_gap))
         return fail(RG_ERR_ARG, "unsupported mode");
@@ -385,7 +385,7 @@ int32_t rg_batch_create(const rg_graph* gc, const rg_params* p, const char* read
                                 "rg_stream_opts.amb_strand (`-s true`, main.rs:82,132,188,229)");
     if ((p->amb_mode & 3) && !is_poa(mode)) return fail(RG_ERR_ARG, "amb_mode bits 0 and 1 apply to the POA modes only (main.rs:82,132,188,229)");
     if (path_gap) {
-        // what the plan of -m 6 / -m 7 refuses (amb_mode bits, reads over 2047 bases, scores outside the i32 budget) is host
+        // what the plan of -m 6 / -m 7 / -m 12 refuses (amb_mode bits, reads over 2047 bases, scores outside the i32 budget) is host
         // arithmetic on the longest read: answered here, before a device is needed
         int64_t longest = 0;
         for (int64_t r = 0; r < nreads; ++r) longest = std::max<int64_t>(longest, read_off[r + 1] - read_off[r]);
@@ -476,7 +476,7 @@ int32_t rg_result_score(const rg_batch* b, int64_t i) {
 // GAFStruct of read i (false: the reference produces none — score-only call, or it panics on this read)
 static bool build_fields(const rg_batch* b, int64_t i, const char* name, GafFields& out) {
     const DevRecord& d = b->rec[i];
-    if (d.status & (ST_BAD_BASE | ST_WOULD_PANIC)) return false;
+    if (d.status & ST_NO_RECORD) return false;
     ReadRecord r;
     fill_record(b, i, r);
     std::string read((size_t)(b->off[i + 1] - b->off[i]), 'N');

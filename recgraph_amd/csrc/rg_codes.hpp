@@ -8,7 +8,9 @@ namespace rg {
 enum : uint8_t { OP_D = 1, OP_U = 2, OP_L = 3, OP_CONT = 0x80 };
 
 // status bits mirror include/recgraph_hip.h
-enum : uint32_t { ST_BAND_WARNING = 1u, ST_BAND_NOT_ENOUGH = 2u, ST_WOULD_PANIC = 4u, ST_BAD_BASE = 8u, ST_OVERFLOW = 0x100u };
+enum : uint32_t { ST_BAND_WARNING = 1u, ST_BAND_NOT_ENOUGH = 2u, ST_WOULD_PANIC = 4u, ST_BAD_BASE = 8u, ST_UNALIGNED = 16u, ST_OVERFLOW = 0x100u };
+// a read with one of these has no record: no ops, no text, score 0 (ST_UNALIGNED: -m 12 only, where it is no error)
+constexpr uint32_t ST_NO_RECORD = ST_BAD_BASE | ST_WOULD_PANIC | ST_UNALIGNED;
 
 constexpr int WAVE = 64;
 

@@ -344,7 +344,7 @@ void walk_pathwise(const HostGraph& g, const uint8_t* codes, int n, const ReadRe
     // helpers receive `start = i + 1` for the row i the walk stopped on (recombination_output.rs:186,331)
     if (!w.rec) {
         PathCursor pc(g, r.best_path, r.end_row);
-        int j = n;
+        int j = mode == RG_MODE_PATHWISE_GAP_LOCAL ? r.end_col : n;       // (-m 12: the alignment ends inside the read)
         const size_t N = (size_t)r.n_ops;
         size_t plen = 0;
         // the walk runs from the end of the alignment to its start: ops, bases and ids are written back to front
@@ -476,6 +476,7 @@ GafFields fields_pathwise(const HostGraph& g, const std::string& read, const std
     walk_pathwise(g, codes.data(), n, r, mode, sc, w);
     GafFields f;
     f.name = name; f.qlen = (size_t)n; f.qstart = 0; f.qend = (size_t)(n - 1);
+    if (mode == RG_MODE_PATHWISE_GAP_LOCAL) { f.qstart = (size_t)r.stop_col; f.qend = (size_t)(r.end_col - 1); }
     f.strand = strand;
     f.path.assign(w.ids, w.ids + w.nids);
     f.pstart = w.pstart; f.pend = w.pend; f.plen = w.plen;
@@ -508,7 +509,12 @@ void append_pathwise_text(const HostGraph& g, const uint8_t* codes, int n, const
     Cursor c{&out[before]};
     c.mem(name, nlen);
     c.ch('\t'); c.num((unsigned long long)n);
-    c.str("\t0\t"); c.num((unsigned long long)(n - 1));
+    if (mode == RG_MODE_PATHWISE_GAP_LOCAL) {
+        c.ch('\t'); c.num((unsigned long long)r.stop_col);
+        c.ch('\t'); c.num((unsigned long long)(r.end_col - 1));
+    } else {
+        c.str("\t0\t"); c.num((unsigned long long)(n - 1));
+    }
     c.ch('\t'); c.ch(strand); c.str("\t>");
     for (size_t i = 0; i < w.nids; ++i) { if (i) c.ch('>'); c.num(w.ids[i]); }
     c.ch('\t'); c.num(w.plen);

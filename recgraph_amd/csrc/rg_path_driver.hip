@@ -4,6 +4,7 @@
 //
 //   -m 4:  sweep(F, dirs) -> seed -> layer(F) -> trace
 //   -m 6:  gap_score(every path) -> gap_pick -> gap_dirs(picked path) -> gap_trace          (gap/rg_path_gap.hip; -m 7 likewise)
+//   -m 12: the same four steps with the local kernels                                       (gap_local/rg_path_gap_local.hip)
 //   -m 8:  sweep(F1: column maxima) -> seed -> thr -> sweep(R: dirs, candidates, column maxima)
 //          -> thr -> sweep(F2: dirs, candidates) -> search -> layer(F) -> layer(R) -> trace
 #include <algorithm>
@@ -13,6 +14,7 @@
 #include <cstring>
 
 #include "gap/rg_path_gap.hpp"
+#include "gap_local/rg_path_gap_local.hpp"
 #include "rg_kernel_timer.hpp"
 #include "rg_path_kernels.hpp"
 #include "rg_path_plan.hpp"
@@ -227,7 +229,7 @@ int Run::enqueue_pathwise(const SweepArgs& sa, const SeedArgs& se) {
     return RG_OK;
 }
 
-// -m 6 / -m 7:  gap_score(every path) -> gap_pick -> gap_dirs(picked path) -> gap_trace -> the chunk's one read-back
+// -m 6 / -m 7 / -m 12:  gap_score(every path) -> gap_pick -> gap_dirs(picked path) -> gap_trace -> the chunk's one read-back
 int Run::enqueue_pathwise_gap() {
     GapArgs ga;
     memset(&ga, 0, sizeof ga);
@@ -236,6 +238,13 @@ int Run::enqueue_pathwise_gap() {
     ga.cells = d_cells; ga.rec = d_rec + done; ga.ops = d_ops + (long long)done * ops_stride; ga.ops_stride = ops_stride;
     const int C = plan.C;
     const bool semi = plan.semi;
+    if (plan.local) {
+        RG_TRY(T.run("k_gap_score_local", [&] { return launch_gap_score_local(ga, chunk, C, stream); }));
+        RG_TRY(T.run("k_gap_pick_local", [&] { return launch_gap_pick_local(ga, chunk, C, stream); }));
+        RG_TRY(T.run("k_gap_dirs_local", [&] { return launch_gap_dirs_local(ga, chunk, C, stream); }));
+        RG_TRY(T.run("k_gap_trace_local", [&] { return launch_gap_trace_local(ga, chunk, C, stream); }));
+        return read_back();
+    }
     RG_TRY(T.run("k_gap_score", [&] { return launch_gap_score(ga, chunk, C, semi, stream); }));
     RG_TRY(T.run("k_gap_pick", [&] { return launch_gap_pick(ga, chunk, C, semi, stream); }));
     RG_TRY(T.run("k_gap_dirs", [&] { return launch_gap_dirs(ga, chunk, C, semi, stream); }));

@@ -76,13 +76,17 @@ bool sweep16_admissible(const DevScores& sc, int max_path_rows, int max_n, int C
     return true;
 }
 
-// -m 6 / -m 7: one wave per (read, path) keeps H and Y of the current row in registers, C columns per lane (n + 1 <= 64 C), so a
+// -m 6 / -m 7 / -m 12: one wave per (read, path) keeps H and Y of the current row in registers, C columns per lane (n + 1 <= 64 C), so a
 // read must fit one wave; the only HBM work buffer beside ReadState holds the 4-bit directions of the picked path.
 static int plan_pathwise_gap(const rg_params& p, const PathPlanInput& in, PathPlan& o) {
     if (p.gap_open > 0 || p.gap_ext > 0) return fail(RG_ERR_ARG, "gap penalties must be <= 0");
-    if (p.amb_mode) return fail(RG_ERR_ARG, "amb_mode must be 0 in the affine-gap pathwise modes (-m 6 / -m 7): they align the reads as given");
+    const bool local = p.mode == RG_MODE_PATHWISE_GAP_LOCAL;
+    if (p.amb_mode)
+        return fail(RG_ERR_ARG, local ? "amb_mode must be 0 in the local affine-gap pathwise mode (-m 12): it aligns the reads as given"
+                                      : "amb_mode must be 0 in the affine-gap pathwise modes (-m 6 / -m 7): they align the reads as given");
     if (in.max_n > 32 * WAVE - 1)
-        return fail(RG_ERR_ARG, "reads longer than 2047 bases are not supported by the affine-gap pathwise modes (-m 6 / -m 7)");
+        return fail(RG_ERR_ARG, local ? "reads longer than 2047 bases are not supported by the local affine-gap pathwise mode (-m 12)"
+                                      : "reads longer than 2047 bases are not supported by the affine-gap pathwise modes (-m 6 / -m 7)");
     // every value of H, X, Y is a sum of at most (rows + n) steps of at most max(|sc|, |o + e|) each: kept inside +-2^28, so that
     // the NEG sentinel (-2^29) plus any such sum can neither win nor wrap
     long long maxabs = std::llabs((long long)p.gap_open + (long long)p.gap_ext);
@@ -94,6 +98,7 @@ static int plan_pathwise_gap(const rg_params& p, const PathPlanInput& in, PathPl
     o.gap = true;
     o.mode = RG_MODE_PATHWISE_GAP;
     o.semi = p.mode == RG_MODE_PATHWISE_GAP_SEMI;
+    o.local = local;          // (-m 12: neither end is pinned; `semi` stays false)
     int C = 4;
     while (C * WAVE < in.max_n + 1) C *= 2;
     o.C = C;
@@ -109,7 +114,7 @@ static int plan_pathwise_gap(const rg_params& p, const PathPlanInput& in, PathPl
 
 int plan_pathwise(const rg_params& p, const PathPlanInput& in, const Options& opt, int spec_level, PathPlan& o) {
     o = PathPlan{};
-    if (p.mode == RG_MODE_PATHWISE_GAP || p.mode == RG_MODE_PATHWISE_GAP_SEMI) return plan_pathwise_gap(p, in, o);
+    if (p.mode == RG_MODE_PATHWISE_GAP || p.mode == RG_MODE_PATHWISE_GAP_SEMI || p.mode == RG_MODE_PATHWISE_GAP_LOCAL) return plan_pathwise_gap(p, in, o);
     const int P = in.P, L = in.L, max_n = in.max_n;
     o.semi = p.mode == RG_MODE_PATHWISE_SEMI || p.mode == RG_MODE_RECOMBINATION_SEMI;
     o.mode = p.mode == RG_MODE_PATHWISE_SEMI ? RG_MODE_PATHWISE : p.mode == RG_MODE_RECOMBINATION_SEMI ? RG_MODE_RECOMBINATION : p.mode;

@@ -57,6 +57,7 @@ struct PathPlan {
     // -m 6 / -m 7 (affine gaps, gap/rg_path_gap.hip): `mode` is RG_MODE_PATHWISE_GAP, `semi` says -m 7; one wave per (read, path),
     // C columns per lane; the direction pass stores gap_words dwords per lane and row (4 bits per cell) for the picked path
     bool gap;
+    bool local;                   // -m 12 (gap_local/rg_path_gap_local.hip): the same geometry and buffers, the local kernels
     int gap_words;
     long long gdirs_stride;       // words per read: (rows of the longest path + 1) * gap_words * 64
 

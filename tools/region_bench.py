@@ -3,7 +3,7 @@
 engine on other read lengths, score parameters and path counts, with the sweep kernel that ran and a parity check of a
 few reads against the oracle.  One JSON line per case.
 
-    python tools/region_bench.py [case ...]        cases: c5 x6 m3x5 hoxd70 len1500 p128 len600 gap (default: all but the strand cases and `gap`)
+    python tools/region_bench.py [case ...]        cases: c5 x6 m3x5 hoxd70 len1500 p128 len600 gap gap_local (default: all but the strand cases, `gap` and `gap_local`)
 
 The strand cases (RG_AMB_BOTH_STRANDS, config-5 shape; `reads_per_s` counts SOURCE reads): `both_strands_fwd` — option on, every
 read forward (what the option costs when nothing qualifies: compare with `c5`); `both_strands` — option on, half of the reads
@@ -15,6 +15,11 @@ text by that option's rule (include/recgraph_hip.h) from the oracle and the vote
 `gap` (only when named): -m 6 beside -m 4 on the same inputs — the C4 / C5 graph shapes (16 paths on 5 000 rows, 32 on 10 000) with
 reads of 150 and 1000 bases; one batch handle, timed over whole rg_batch_run calls after a warm-up run; a few reads of every
 -m 6 batch are checked against the rule (tests/pathwise_gap_rule.py).  One JSON line per (shape, length, mode).
+
+`gap_local` (only when named): -m 12 beside -m 7 on the same inputs in the same process — the shapes of `gap`, reads whose ends
+are random overhangs (an eighth of the read on either side); both handles are warmed up, then timed over whole rg_batch_run calls in
+alternating rounds (median and minimum per mode, and -m 12 as a ratio to -m 7); five reads of every -m 12 batch are checked against
+the rule (tests/pathwise_gap_local_rule.py).  One JSON line per (shape, length).
 
 Every case: TILES tiles of TILE reads through one rg_stream (3 handles), timed after one warm-up tile per handle."""
 import json
@@ -90,9 +95,67 @@ def gap_case():
                                   "rule_checked": 5 if ok else "FAILED"}), flush=True)
 
 
+def gap_local_case():
+    import numpy as np
+    from recgraph_amd import api, synth
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import pathwise_gap_local_rule as L
+    rounds = 5
+    for shape, rows, paths in (("C4", 5000, 16), ("C5", 10000, 32)):
+        for rlen, nreads in ((150, 4096), (1000, 2048)):
+            g = synth.haplotype_graph(rows, paths, path_len=rlen, seed=1234)
+            gg = api.Graph.from_gfa_text(g.gfa())
+            rng = np.random.default_rng(901)
+            hang = rlen // 8
+
+            def flank():
+                return "".join("ACGT"[int(x)] for x in rng.integers(0, 4, size=hang))
+            reads = [flank() + r[hang:len(r) - hang] + flank() for r in synth.haplotype_reads(g, nreads, length=rlen, seed=900, mosaic_frac=0.0)]
+            modes = (api.MODE_PATHWISE_GAP_LOCAL, api.MODE_PATHWISE_GAP_SEMI)
+            batch = {m: api.Batch(gg, reads, api.make_params(m)) for m in modes}
+            times = {m: [] for m in modes}
+            ks = {m: {} for m in modes}
+            for m in modes:
+                batch[m].run()                       # warm-up: code objects, work buffers
+            for _ in range(rounds):
+                for m in modes:                      # alternating: both modes see the same machine
+                    t0 = time.perf_counter()
+                    batch[m].run()                   # (returns after the chunk's read-back: the device is idle again)
+                    times[m].append(time.perf_counter() - t0)
+                    for k, v in batch[m].kernel_stats().items():
+                        if not k.startswith(("host:", "mem:", "inst:")):
+                            ks[m][k] = ks[m].get(k, 0.0) + v[0] / rounds
+            for m in modes:
+                batch[m].fetch()
+            b = batch[api.MODE_PATHWISE_GAP_LOCAL]
+            lnz, prow = L.graph_paths(gg)
+            ids = L.graph_node_ids(gg)
+            ok = all(b.gaf_text(i, "r", 1) == L.line_local(lnz, prow, ids, "r", reads[i])
+                     for i in sorted({0, nreads - 1, nreads // 2, nreads // 3, 777 % nreads}))
+            clipped = sum(1 for i in range(nreads) if b.gaf_text(i, "r", 1).split("\t")[2:4] != ["0", str(rlen - 1)])
+            med = {m: sorted(times[m])[rounds // 2] for m in modes}
+            out = {"case": "gap_local", "shape": shape, "rows": gg.rows, "paths": paths, "read_len": rlen, "overhang": hang, "reads": nreads,
+                   "rounds": rounds, "reads_clipped_by_m12": clipped, "unaligned": sum(1 for i in range(nreads) if b.status(i) & api.READ_UNALIGNED)}
+            for m in modes:
+                bm = batch[m]
+                out["m%d" % m] = {"ms_per_batch_median": round(med[m] * 1e3, 2), "ms_per_batch_min": round(min(times[m]) * 1e3, 2),
+                                  "reads_per_s": round(nreads / med[m], 1), "cell_updates_per_s": round(bm.cell_updates / med[m]),
+                                  "performed_over_counted": round(bm.cell_updates_performed / bm.cell_updates, 3),
+                                  "kernel_ms_per_batch": {k: round(v, 2) for k, v in ks[m].items()}}
+            out["m12_over_m7_time_median"] = round(med[modes[0]] / med[modes[1]], 3)
+            out["m12_over_m7_time_min"] = round(min(times[modes[0]]) / min(times[modes[1]]), 3)
+            out["rule_checked"] = 5 if ok else "FAILED"
+            print(json.dumps(out), flush=True)
+
+
 def main():
     from recgraph_amd import api, synth
     from oracle import oracle as O
+    if "gap_local" in sys.argv[1:]:
+        gap_local_case()
+        sys.argv = [a for a in sys.argv if a != "gap_local"]
+        if len(sys.argv) == 1:
+            return
     if "gap" in sys.argv[1:]:
         gap_case()
         sys.argv = [a for a in sys.argv if a != "gap"]
