@@ -472,7 +472,10 @@ int32_t rg_stream_handles(rg_stream* s);      /* batch handles that aligned at l
  *   0..2^20: most reads one launch of a DP kernel takes, in the pathwise and in the POA modes; 0 = what the memory budget allows), "launch_log" (RG_LAUNCH_LOG: every
  *   kernel launch of a batch leaves a pseudo-entry "inst:<instantiation>" in rg_batch_kernel_* / rg_stream_kernel_* — the
  *   demangled kernel name with its template arguments, e.g. "inst:rg::k_sweep16<16, 0, true, false, false>", ms 0, launches
- *   counted; off: no such entry).
+ *   counted; off: no such entry), "layer_window" (RG_LAYER_WINDOW, 0..256, default 256: columns of the window the traceback layers
+ *   of the packed pathwise modes are rebuilt in — 256, 128 (values in between count as 128), below 128: full rows; a read whose
+ *   walk leaves the window is rebuilt at full width in the same batch and counted in the pseudo-entry "mem:layer_full_reads";
+ *   the windowed kernel that ran is named by a pseudo-entry "mem:layer_window:<instantiation>", ms 0, launches counted).
  * The variants compute the same records byte for byte (tests/test_gpu_pathwise.py). */
 int32_t rg_set_option(const char* name, int64_t value);
 int64_t rg_get_option(const char* name);      /* -1: unknown option */

@@ -632,7 +632,7 @@ class Stream:
 def set_option(name, value):
     """rg_set_option: process-wide diagnostic switches — "sweep_i32", "three_sweeps", "no_frec", "debug", "spin_wait",
     "no_gather", "no_split", "no_spec", "spec_margin", "spec4_margin_x10", "stripe_c", "no_retire", "retire_shift", "no_order",
-    "dsel_edge", "no_dsel", "no_pick2", "layer_i32", "lds_pad", "chunk_reads", "launch_log" (the table: RG_OPTIONS in csrc/rg_host.hpp; what
+    "dsel_edge", "no_dsel", "no_pick2", "layer_i32", "lds_pad", "chunk_reads", "launch_log", "layer_window" (the tables: RG_OPTIONS and RG_TUNING_OPTIONS in csrc/rg_host.hpp; what
     each does: the comment at rg_set_option in include/recgraph_hip.h).  A switch takes 0 / 1, an integer is clamped.  "chunk_reads"
     caps the reads of one DP kernel launch in every mode, pathwise and POA (0: what the memory budget allows)."""
     check(_lib.load().rg_set_option(name.encode(), int(value)))

@@ -45,9 +45,14 @@ extern thread_local std::string g_last_error;
     X(lds_pad, "RG_LDS_PAD", I, 0, 40 << 10, 0)       /* (experiments only) extra dynamic LDS bytes per k_sweep16 workgroup: lowers the waves per CU */ \
     X(chunk_reads, "RG_CHUNK_READS", I, 0, 1 << 20, 0)   /* most reads one launch of a DP kernel takes, pathwise and POA (0: what the HBM budget allows; pathwise: <= 8192) */ \
     X(launch_log, "RG_LAUNCH_LOG", B, 0, 1, 0)        /* every kernel launch leaves an "inst:<instantiation>" pseudo-entry in the batch's kernel statistics (rg_launch_log.hpp: ms 0, launches counted) */
+// ... and the TUNING options, rows of the same shape in a table of their own (the diagnostic switches above are counted by
+// tests/test_host_cpu.py; both tables feed the same storage, environment defaults, rg_set_option / rg_get_option and clamping)
+#define RG_TUNING_OPTIONS(Y) \
+    Y(layer_window, "RG_LAYER_WINDOW", I, 0, 256, 256)   /* columns of the window the traceback layers are rebuilt in (layer_window/): 256, 128 (values in between count as 128), 0 and below 128: full rows */
 struct Options {
 #define RG_OPTION_FIELD(name, env, kind, lo, hi, def) std::atomic<int> name{def};
     RG_OPTIONS(RG_OPTION_FIELD)
+    RG_TUNING_OPTIONS(RG_OPTION_FIELD)
 #undef RG_OPTION_FIELD
 };
 struct OptionDesc {

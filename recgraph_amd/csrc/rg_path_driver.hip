@@ -381,11 +381,20 @@ int Run::enqueue_tail() {
     la.layer_stride = plan.layer_stride; la.fpoff = w.fpoff.p; la.fprow = w.fprow.p; la.fpslot = w.fpslot.p;
     la.rpoff = w.rpoff.p; la.rprow = w.rprow.p; la.rpslot = w.rpslot.p;
     la.rev = 0; la.dirs = w.fdirs.p; la.dirs_stride = plan.fdirs_stride; la.layer = w.flayer.p;
-    auto layer = [&]() { return plan.layer16 ? launch_layer16(la, chunk, C, stream) : launch_layer(la, chunk, C, stream); };
-    RG_TRY(T.run("k_layer_fwd", layer));
+    // (windowed: layer_window/rg_layer_window.hip rebuilds W columns of every row around the walk)
+    const int win = plan.layer_window;
+    auto layer = [&]() {
+        if (win) return launch_layer_window(la, chunk, C, win, stream);
+        return plan.layer16 ? launch_layer16(la, chunk, C, stream) : launch_layer(la, chunk, C, stream);
+    };
+    auto fwd_side = [&]() { la.rev = 0; la.dirs = w.fdirs.p; la.dirs_stride = plan.fdirs_stride; la.layer = w.flayer.p; };
+    auto rev_side = [&]() { la.rev = 1; la.dirs = w.rdirs.p; la.dirs_stride = plan.rdirs_stride; la.layer = w.rlayer.p; };
+    // (which windowed kernel ran: a pseudo-statistic of its own, always on, read by tests/test_gpu_layer_window.py)
+    const char* family = win ? LAYER_WINDOW_LOG : "inst:";
+    RG_TRY(T.run("k_layer_fwd", layer, family, win != 0));
     if (plan.mode == RG_MODE_RECOMBINATION) {
-        la.rev = 1; la.dirs = w.rdirs.p; la.dirs_stride = plan.rdirs_stride; la.layer = w.rlayer.p;
-        RG_TRY(T.run("k_layer_rev", layer));
+        rev_side();
+        RG_TRY(T.run("k_layer_rev", layer, family, win != 0));
     }
     TraceArgs ta;
     memset(&ta, 0, sizeof ta);
@@ -393,7 +402,21 @@ int Run::enqueue_tail() {
     ta.ops = d_ops + (long long)done * ops_stride; ta.ops_stride = ops_stride; ta.flayer = w.flayer.p;
     ta.rlayer = w.rlayer.p; ta.layer_stride = plan.layer_stride; ta.fpoff = w.fpoff.p; ta.fprow = w.fprow.p;
     ta.rpoff = w.rpoff.p; ta.rprow = w.rprow.p; ta.nreads = chunk; ta.mode = p.mode; ta.semi = plan.semi ? 1 : 0; ta.nwv = plan.nwv;
+    ta.window = win; ta.nfull = w.need.p + NEED_LAYER_FULL;
     RG_TRY(T.run("k_trace", [&] { return launch_trace(ta, C, stream); }));
+    if (win) {
+        // The reads whose walk the window could not serve (k_trace flagged them ST_LAYER_FULL): full-width layers and a second
+        // walk, launched whatever their number — no host round trip; the kernels return at the top for every other read
+        la.only_full = 1;
+        fwd_side();
+        RG_TRY(T.run("k_layer_full", [&] { return launch_layer16(la, chunk, C, stream); }));
+        if (plan.mode == RG_MODE_RECOMBINATION) {
+            rev_side();
+            RG_TRY(T.run("k_layer_full", [&] { return launch_layer16(la, chunk, C, stream); }));
+        }
+        ta.window = 0; ta.only_full = 1;
+        RG_TRY(T.run("k_trace_full", [&] { return launch_trace(ta, C, stream); }));
+    }
     return read_back();
 }
 
@@ -604,6 +627,12 @@ int path_driver_run(const PathCtx& c, const PathJob& j, unsigned long long* cell
         if (r.debug && (plan.spec || plan.spec4)) fprintf(stderr, "[rg] speculative bound (margin %d): %u of %d reads did not reach it\n", plan.spec_margin, nretry, chunk);
         if (r.debug && plan.spec4 && nretry && (rc = r.dump_spec4_retries())) return rc;
         if (r.debug && plan.dsel && (rc = r.dump_dsel_retries())) return rc;
+        if (plan.layer_window) {
+            // reads the column window of the layers could not serve (rebuilt at full width in the same chunk), as a pseudo-stat:
+            // the "ms" field holds the READS, summed over the chunks (like the bytes of mem:work_bytes_per_read), "launches" the chunks
+            add_stat(stats, "mem:layer_full_reads", (double)r.need()[NEED_LAYER_FULL], 1);
+            if (r.debug) fprintf(stderr, "[rg] layer window of %d columns: %u of %d reads took the full-width layers\n", plan.layer_window, r.need()[NEED_LAYER_FULL], chunk);
+        }
         if (nretry && (rc = r.second_pass(cells_perf))) return rc;
         cells_done += chunk_cells;
         r.done += chunk;

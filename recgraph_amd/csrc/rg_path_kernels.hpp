@@ -3,6 +3,7 @@
 #include "rg_path_args.hpp"
 #include "rg_path_plan.hpp"      // ReadState, Cand
 #include "rg_launch_log.hpp"
+#include "layer_window/rg_layer_window.hpp"      // ST_LAYER_FULL, layer_window_left
 
 namespace rg {
 
@@ -206,6 +207,7 @@ struct LayerArgs {
     const int* fpoff; const int* fprow; const int* fpslot;   // rows of every path, forward order
     const int* rpoff; const int* rprow; const int* rpslot;   // rows of every path, reverse order
     int nwv;                   // column stripes per read (see SweepArgs)
+    int only_full;             // 1: only the reads k_trace flagged ST_LAYER_FULL (the fallback behind the windowed kernels, layer_window/)
 };
 
 struct TraceArgs {
@@ -226,6 +228,12 @@ struct TraceArgs {
     int mode;
     int semi;
     int nwv;                   // column stripes per read (see SweepArgs)
+    // the layers were rebuilt inside a column window of `window` columns (layer_window/rg_layer_window.hpp; 0: full rows, today's
+    // walk bit for bit): a walk that leaves the window or meets decision code 0 is abandoned, the read flagged ST_LAYER_FULL and
+    // counted in *nfull.  only_full: walk the flagged reads only (their layers rebuilt at full width since) and clear the flag
+    int window;
+    int only_full;
+    unsigned* nfull;
 };
 
 const char* launch_sweep(const SweepArgs& a, int nreads, int C, hipStream_t s);
@@ -252,5 +260,7 @@ const char* launch_need(const ReadState* st, const unsigned* nf, const unsigned*
 const char* launch_layer(const LayerArgs& a, int nreads, int C, hipStream_t s);
 const char* launch_layer16(const LayerArgs& a, int nreads, int C, hipStream_t s);   // packed rows (dir_fmt 1, one wave per read)
 const char* launch_trace(const TraceArgs& a, int C, hipStream_t s);
+// packed rows at C <= 16 inside a column window of `window` (128 | 256) columns around the walk (layer_window/rg_layer_window.hip)
+const char* launch_layer_window(const LayerArgs& a, int nreads, int C, int window, hipStream_t s);
 
 }  // namespace rg

@@ -14,7 +14,7 @@ namespace rg {
 
 // ---- the option table (RG_OPTIONS, rg_host.hpp) ----
 #define RG_OPTION_ROW(name, env, kind, lo, hi, def) {#name, env, #kind[0] == 'B', lo, hi, def, &Options::name},
-const OptionDesc kOptionTable[] = {RG_OPTIONS(RG_OPTION_ROW)};
+const OptionDesc kOptionTable[] = {RG_OPTIONS(RG_OPTION_ROW) RG_TUNING_OPTIONS(RG_OPTION_ROW)};
 #undef RG_OPTION_ROW
 const int kOptionCount = (int)(sizeof kOptionTable / sizeof kOptionTable[0]);
 
@@ -210,6 +210,19 @@ int plan_pathwise(const rg_params& p, const PathPlanInput& in, const Options& op
     // (packed 16-bit rows whenever the sweep ran packed: the same decisions, ~40 % fewer instructions; `layer_i32` keeps the
     // i32 form for the tests)
     o.layer16 = use16 && o.gaps_agree && !opt.layer_i32;
+    // the layers inside a column window around the walk (layer_window/rg_layer_window.hip): packed rows at <= 16 columns per lane, first
+    // pass only (the handful of reads of a second pass keep the full-width kernel), and only where every real value of a row
+    // stays above LAYER_WINDOW_ZLO, so that the window's "unknown" sentinel plus one step lies clearly below it (zlo as in
+    // sweep16_admissible)
+    o.layer_window = 0;
+    if (o.layer16 && C <= 16 && spec_level == 0 && opt.layer_window >= LAYER_WINDOW_NARROW) {
+        long long smin = INT32_MAX;
+        for (int x = 0; x < 5; ++x)
+            for (int y = 0; y < 5; ++y) smin = std::min<long long>(smin, p.scores[x * 6 + y]);
+        const long long g = p.scores[5];
+        const long long zlo = (long long)(in.max_path_rows + 2) * g - (long long)(max_n + 2) * std::max(0ll, g - smin);
+        if (zlo >= LAYER_WINDOW_ZLO) o.layer_window = opt.layer_window >= LAYER_WINDOW_DEFAULT ? LAYER_WINDOW_DEFAULT : LAYER_WINDOW_NARROW;
+    }
     // (gather runs carry differences of two members' stored values: sweep16_admissible bounds every such difference)
     o.gather_ok = use16 && !opt.no_gather;
     // split tables: only where every run between the groups of a row is a register or a gather run of k_sweep16

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "rg_host.hpp"
+#include "layer_window/rg_layer_window.hpp"
 
 namespace rg {
 
@@ -48,6 +49,7 @@ struct PathPlan {
     int score_scale;
     bool use16;                   // packed 16-bit rows (rg_sweep16.hip); implies one wave per read
     bool two_sweep, use_rec, spec, pick_two, dsel, spec4, opt16, layer16;
+    int layer_window;             // columns of the window the layers are rebuilt in (layer_window/rg_layer_window.hip), 0: full rows
     bool retire, use_split, gather_ok;
     bool retire_fwd, retire_rev;  // `retire` in the forward / reverse sweep of -m 8 (no_retire 3 / 2 keep one of them)
     bool retire4, dsel4;          // -m 4 on its speculative bound: path retirement, direction words of the picked path only

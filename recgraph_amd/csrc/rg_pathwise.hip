@@ -1392,10 +1392,18 @@ __global__ __launch_bounds__(64) void k_trace(TraceArgs a) {
     if (rd >= a.nreads) return;
     ReadState* rs = a.state + rd;
     DevRecord* rec = a.rec + rd;
+    if (a.only_full) {
+        // the fallback behind the windowed layers: the flagged reads only, on the full-width layers rebuilt for them since
+        if (!(rs->status & ST_LAYER_FULL)) return;
+        rs->status &= ~ST_LAYER_FULL;
+    }
     if (rs->status & (ST_BAD_BASE | ST_WOULD_PANIC | ST_OVERFLOW | ST_RETRY)) {
-        rec->status = rs->status & ~ST_RETRY; rec->n_ops = 0; rec->n_fwd_ops = 0; rec->score = 0;      // (ST_RETRY: the second pass writes the record)
+        rec->status = rs->status & ~(ST_RETRY | ST_LAYER_FULL); rec->n_ops = 0; rec->n_fwd_ops = 0; rec->score = 0;      // (ST_RETRY: the second pass writes the record)
         return;
     }
+    // a walk the column window cannot serve (also flagged by the windowed kernel itself when the start cell's value is unknown)
+    auto give_up = [&]() { rs->status |= ST_LAYER_FULL; atomicAdd(a.nfull, 1u); };
+    if (a.window && (rs->status & ST_LAYER_FULL)) { atomicAdd(a.nfull, 1u); return; }
     const long long ro = a.read_off[rd];
     const int n = (int)(a.read_off[rd + 1] - ro);
     uint8_t* ops = a.ops + (long long)rd * a.ops_stride;
@@ -1403,9 +1411,13 @@ __global__ __launch_bounds__(64) void k_trace(TraceArgs a) {
     const bool recomb = (a.mode == RG_MODE_RECOMBINATION || a.mode == RG_MODE_RECOMBINATION_SEMI) && rs->fwd_path != rs->rev_path;
     const int dww = WAVE * (C <= 16 ? 1 : 2);          // words of one stripe per layer row
     const int dw = dww * a.nwv;                          // (a.nwv > 1: striped long reads, see k_sweep)
-    // decision of layer row idx at (mirrored) column c
-    auto move = [&](const uint32_t* td, int idx, int c) -> uint32_t {
+    // decision of layer row idx at (mirrored) column c; windowed layers: 0 outside the row's window (t0, c0: the walk's start cell)
+    auto move = [&](const uint32_t* td, int idx, int c, int t0, int c0) -> uint32_t {
         const int q = c % C, gl = c / C;                 // global lane that owns the column
+        if (a.window) {
+            const int left = layer_window_left(c0, t0, idx, a.window, C * WAVE);
+            if (c < left || c >= left + a.window) return 0u;
+        }
         return (td[(long long)idx * dw + (gl / WAVE) * dww + (q / 16) * WAVE + gl % WAVE] >> (2 * (q % 16))) & 3u;
     };
     const uint32_t* fl = reinterpret_cast<const uint32_t*>(a.flayer) + (long long)rd * a.layer_stride;
@@ -1420,11 +1432,13 @@ __global__ __launch_bounds__(64) void k_trace(TraceArgs a) {
     if (idx < 0) { rec->status = ST_WOULD_PANIC; rec->n_ops = 0; return; }
     int t = idx + 1;  // layer index of the current row (0 = row 0)
     const int score = rs->trace_score;
+    const int ft0 = t, fc0 = j;
     while (t > 0 && j > 0) {
-        const uint32_t mv = move(fl, t, j);
+        const uint32_t mv = move(fl, t, j, ft0, fc0);
         if (mv == 1u) { ops[nops++] = OP_D; t -= 1; j -= 1; }
         else if (mv == 2u) { ops[nops++] = OP_U; t -= 1; }
-        else { ops[nops++] = OP_L; j -= 1; }
+        else if (mv == 3u || !a.window) { ops[nops++] = OP_L; j -= 1; }
+        else { give_up(); return; }
     }
     while (j > 0) { ops[nops++] = OP_L; j -= 1; }
     while (!a.semi && t > 0) { ops[nops++] = OP_U; t -= 1; }   // semiglobal: the alignment may start inside the graph
@@ -1440,16 +1454,18 @@ __global__ __launch_bounds__(64) void k_trace(TraceArgs a) {
         if (ridx < 0) { rec->status = ST_WOULD_PANIC; rec->n_ops = 0; return; }
         int tt = ridx + 1;          // layer index (0 = row L-1)
         int jj = rs->rec_col;       // real column
+        const int rt0 = tt, rc0 = n - jj;
         while (tt > 0 && jj < n) {
-            const uint32_t mv = move(rl, tt, n - jj);
+            const uint32_t mv = move(rl, tt, n - jj, rt0, rc0);
             if (mv == 1u) { ops[nops++] = OP_D; tt -= 1; jj += 1; }
             else if (mv == 2u) { ops[nops++] = OP_U; tt -= 1; }
-            else { ops[nops++] = OP_L; jj += 1; }
+            else if (mv == 3u || !a.window) { ops[nops++] = OP_L; jj += 1; }
+            else { give_up(); return; }
         }
         while (jj < n) { ops[nops++] = OP_L | OP_CONT; jj += 1; }
         while (!a.semi && tt > 0) { ops[nops++] = OP_U | OP_CONT; tt -= 1; }
     }
-    rec->status = rs->status;
+    rec->status = rs->status & ~ST_LAYER_FULL;
     rec->score = score;
     rec->fscore = rs->fscore;
     rec->end_row = start_row;

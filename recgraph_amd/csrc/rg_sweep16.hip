@@ -1792,6 +1792,7 @@ __global__ __launch_bounds__(64, C <= 16 ? LAYER16_WAVES : 1) void k_layer16(Lay
     const PathGraphDev& g = a.g;
     ReadState* rs = a.state + rd;
     if (rs->status & (ST_BAD_BASE | ST_WOULD_PANIC | ST_OVERFLOW | ST_RETRY)) return;
+    if (a.only_full && !(rs->status & ST_LAYER_FULL)) return;      // the fallback behind the windowed kernels: flagged reads only
     const bool rev = a.rev;
     const int path = rev ? rs->rev_path : rs->fwd_path;
     const bool recomb = rs->fwd_path != rs->rev_path;
