@@ -89,10 +89,13 @@ struct DevBuf {
 
 // Per-kernel device time of a batch.  rg_batch_run resets the handle's statistics once (reset_stats); every pass of every driver
 // then ADDS into them (add_stat), so a name has one entry however many passes and chunks launched it.  Pseudo-entries:
-// "mem:work_bytes_per_read" of the pathwise driver (`ms` holds bytes summed over the chunks, `launches` the chunks),
-// "mem:layer_full_reads" (`ms` holds the READS the column window of the layers could not serve, summed over the chunks — a count,
-// not a time; `launches` the chunks), "mem:layer_window:<instantiation>" (the windowed layer kernel that ran: ms 0, launches
-// counted, always on) and the launch log's "inst:<instantiation>" (rg_launch_log.hpp).
+//   "mem:work_bytes_per_read"            of the pathwise driver: `ms` holds bytes summed over the chunks, `launches` the chunks
+//   "mem:layer_full_reads"               `ms` holds the READS the column window of the layers could not serve, summed over the chunks
+//                                        (a count, not a time); `launches` the chunks
+//   "mem:silent_rows" / "mem:run_rows"   of the record pipelines: `ms` holds the ROWS of the silent register runs / of all register
+//                                        runs of both sweeps, summed over the chunks and passes
+//   "mem:layer_window:<instantiation>"   the windowed layer kernel that ran: ms 0, launches counted, always on
+//   "inst:<instantiation>"               the launch log (rg_launch_log.hpp)
 struct KernelStat {
     std::string name;
     double ms = 0;

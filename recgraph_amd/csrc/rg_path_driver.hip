@@ -40,7 +40,7 @@ struct PathWorkImpl {
     unsigned long long fmembers = 0, rmembers = 0;           // member rows of the forward / reverse table (sum of the group sizes)
     unsigned fcap = 0, rcap = 0;
     DevBuf<unsigned> need;                 // [8] per chunk: largest nf, nr, forward / reverse record count of a read (k_need); [4] reads whose
-                                        // speculative bound failed (k_verify)
+                                        // speculative bound failed (k_verify); [5] NEED_LAYER_FULL; [6], [7] NEED_SILENT_ROWS, NEED_RUN_ROWS
     // speculative bound (PickArgs): 12-mer table of the paths, per-read pick, and what aligning the failed reads again needs
     DevBuf<uint32_t> kmer_keys;
     DevBuf<unsigned long long> kmer_masks;
@@ -195,6 +195,7 @@ SweepArgs Run::sweep_args() const {
     sa.dsel_pick = plan.dsel ? w.pick.p : nullptr; sa.dsel_pick2 = plan.dsel && plan.pick_two ? w.pick2.p : nullptr;
     sa.dsel_lo = plan.dsel_lo; sa.dsel_hi = plan.dsel_hi;
     sa.rbw = p.rec_band_width; sa.cand_cap = 0; sa.dir_words = plan.dir_words; sa.cells = d_cells;
+    sa.runstat = w.need.p + NEED_SILENT_ROWS;
     return sa;
 }
 
@@ -632,6 +633,12 @@ int path_driver_run(const PathCtx& c, const PathJob& j, unsigned long long* cell
             // the "ms" field holds the READS, summed over the chunks (like the bytes of mem:work_bytes_per_read), "launches" the chunks
             add_stat(stats, "mem:layer_full_reads", (double)r.need()[NEED_LAYER_FULL], 1);
             if (r.debug) fprintf(stderr, "[rg] layer window of %d columns: %u of %d reads took the full-width layers\n", plan.layer_window, r.need()[NEED_LAYER_FULL], chunk);
+        }
+        if (plan.use_rec) {
+            // rows of the silent register runs of both record sweeps and of all their register runs (k_sweep16, SILENT RUNS), as
+            // pseudo-stats: "ms" holds the ROWS, summed over the chunks and the passes
+            add_stat(stats, "mem:silent_rows", (double)r.need()[NEED_SILENT_ROWS], 1);
+            add_stat(stats, "mem:run_rows", (double)r.need()[NEED_RUN_ROWS], 1);
         }
         if (nretry && (rc = r.second_pass(cells_perf))) return rc;
         cells_done += chunk_cells;

@@ -77,7 +77,14 @@ struct SweepArgs {
     // whatever its members: the reference's search likes to switch to another path for the last few columns of a read (ties
     // among the paths of a shared end segment go to the highest path id), and such a path's layer is only rebuilt over those rows
     int dsel_lo, dsel_hi;
+    // k_sweep16, SILENT RUNS (narrow record variants): [2] rows of the silent register runs | rows of all register runs of the
+    // launch — words NEED_SILENT_ROWS / NEED_RUN_ROWS of the chunk's need[] read-back — or null
+    unsigned* runstat;
 };
+// words of the chunk's need[] read-back that count the rows of the silent runs and of all register runs of the record sweeps
+// (0 .. 3: k_need, 4: k_verify, 5: NEED_LAYER_FULL); reported as "mem:silent_rows" / "mem:run_rows"
+constexpr int NEED_SILENT_ROWS = 6;
+constexpr int NEED_RUN_ROWS = 7;
 
 // expands the (row, lane) records of the forward sweep into Cand entries, keeping only cells that can still reach
 // the final bound with the best reverse partner of their column

@@ -393,6 +393,7 @@ __global__ __launch_bounds__(64, SWEEP16_WAVES) void k_sweep16(SweepArgs a) {
     int* sprof = gT + GTW;               // [4][64][H]
     const int PR_RVL = P, PR_NPROF = P + 1;     // pseudo-rows behind the P rolling rows (same [lane][r] layout)
     if (lane < 36) sct[lane] = a.sc.t[lane];
+    else if (lane < 44) sct[lane] = 0;      // (40 .. 43: the silent set and its counters, see SILENT RUNS)
     __syncthreads();
     // uniform gap cost (checked by the driver's plan, sweep16_admissible in rg_path_plan.cpp: score(b, '-') is the same for b = A, C, G, T, N): the
     // z-space slope — and, being the same table column, what a U move adds in EVERY row (g_i below): no per-row lookup
@@ -905,6 +906,29 @@ __global__ __launch_bounds__(64, SWEEP16_WAVES) void k_sweep16(SweepArgs a) {
     // the bound k_verify checks; the needed paths see exactly the decisions they would see in the full sweep.
     // tests/c/band_experiment.cpp measures why this — not a column band — is the exact way to skip hopeless work here.
     bool row_open = false;               // some group of the current several-group row has put its keys into LDS (keys_st)
+    // SILENT RUNS (the narrow record variants of -m 8, both sweeps).  `silent` = every path retire_eval has proven hopeless so
+    // far, retired or not: the bound covers every FUTURE cell of the path, so a path once in the set stays in it.  A hopeless path goes
+    // on being computed while it leads a group with a needed member further down the table, and a register run all of whose computed
+    // members are such paths owes the sweep its new row values and nothing else: no cell of it reaches an emission threshold (that IS
+    // the hopeless test — in the forward sweep only while brc >= 0: the test compares against lb, the threshold is lb + brc - ...; a
+    // launch with a negative brc keeps the set empty), so with the direction word not asked for (no picked path among the members,
+    // no edge row: the sweep visits its edge rows first and rows only move away from them, so the run's first row decides) and the
+    // row not one that every path visits (its pretest takes the lane's LOWEST threshold: a superset that may write a record
+    // k_expand then drops) today's body stores nothing for such a row.  run_rows has a lean form for these runs.
+    // Why the run's FIRST row decides for all of its rows, whichever way the run goes on (run_rows: a counted stretch of up to 63
+    // rows, another stretch of the same segment behind it, or — split tables — the inner rows of ANOTHER segment with the same
+    // members): the records of register runs stay in sweep order in every table (split_tails only moves TAIL groups forward, runs
+    // move whole), so row numbers only rise in the forward sweep and only fall in the reverse one, and the edge rows are the
+    // interval a sweep STARTS with (forward: rows < dsel_lo, reverse: rows > dsel_hi) — a run that starts outside it never comes
+    // back.  knm is a function of the set of paths through the row, and every row of a run has one group, the run's members (rgm).
+    // Not at 32 columns per lane: that variant is at the 256-register limit and spills 32 VGPRs already (tests/test_kernel_resources.py
+    // holds it to 40); four more loop bodies and the set would be paid for in scratch traffic in every row, silent or not.
+    constexpr bool kSilent = kRec && kColmax == 0 && !kWide && !kSemi && C <= 16;
+    const bool silent_ok = kSilent && (rev || (a.thr == nullptr && a.brc >= 0));
+    // (the set and the two row counters — rows of the silent runs | of all register runs of this read, SweepArgs::runstat — live in
+    // four free words behind the score table: read once per run, written once per evaluation / run.  As registers across the run
+    // loops they cost the 4-member loop the two VGPRs that take the variant past 224)
+    int* sil = sct + 40;                 // [0], [1]: the set; [2]: silent rows; [3]: run rows
 #ifdef RG_SWEEP16_RETSTAT
     // (statistics build, tools/sweep_variants.sh RETSTAT: the counters carry evaluations | needed paths << 32 and not-hopeless paths)
     unsigned long long stat_e = 0, stat_n = 0, stat_h = 0;
@@ -943,6 +967,9 @@ __global__ __launch_bounds__(64, SWEEP16_WAVES) void k_sweep16(SweepArgs a) {
                 }
             }
             hop.set(pg, hp);
+        }
+        if constexpr (kSilent) {
+            if (silent_ok) { sil[0] |= (int)(unsigned)hop.w0; sil[1] |= (int)(unsigned)(hop.w0 >> 32); }
         }
         // lead table (rg_steps.cpp): [evaluation point][path, padded to whole pages][word]: lane l of page pg asks for path 64 pg + l
         const int nw = kWide ? (P + 63) >> 6 : 1;
@@ -1327,8 +1354,12 @@ __global__ __launch_bounds__(64, SWEEP16_WAVES) void k_sweep16(SweepArgs a) {
             // member count a run-time value the `kk < rnm` tests compiled to ~13 branches per row, the conditions re-materialised as
             // v_cndmask / v_cmp pairs, and the members' rows were shuffled through v_mov pairs where the paths of different counts
             // meet (profiles/r05_isa_sweep16.txt: 25 % of the hot loop's issue slots were SALU / branch / wait)
-            auto run_rows = [&](auto rn_tag) __attribute__((always_inline)) {
+            // kLean (SILENT RUNS): the rows of a silent run — the row's base code, its profile, the alpha and the members' steps; no slot
+            // / knm fetch, no direction word, no key pretest.  Its tail takes the tail code below like any other (it folds into a row that
+            // other, needed paths may share); the tail's direction word is not asked for either: the run's members, a later row.
+            auto run_rows = [&](auto rn_tag, auto lean_tag) __attribute__((always_inline)) {
             constexpr int RN = decltype(rn_tag)::value;
+            constexpr bool kLean = decltype(lean_tag)::value;
             // (every row of the run — and its tail — has the run's members; wide runs: a member of any page may be a picked path)
             const unsigned long long run_sel = kWide ? (wide_sel ? ~0ull : 0ull) : rgm;
             const int run_page = 0;
@@ -1343,7 +1374,9 @@ __global__ __launch_bounds__(64, SWEEP16_WAVES) void k_sweep16(SweepArgs a) {
                 if (!kAhead) load_steps(rli, s);
                 int lmax;
                 RowOps16<C>::alpha(rr[0], s, g_i, g0, lane, XU, XL, lmax);
-                if (kWide ? ((kColmax == 0 || dirs != nullptr) && (wide_sel || edge_row(ri))) : want_dirs(run_sel, run_page, ri)) store_dirs(rslot, XU, XL);
+                if constexpr (!kLean) {
+                    if (kWide ? ((kColmax == 0 || dirs != nullptr) && (wide_sel || edge_row(ri))) : want_dirs(run_sel, run_page, ri)) store_dirs(rslot, XU, XL);
+                }
                 if constexpr (RN > 1) {
                     int MU[H], ML[H];
                     const unsigned lmask = RowOps16<C>::masks(XU, XL, MU, ML);
@@ -1379,6 +1412,8 @@ __global__ __launch_bounds__(64, SWEEP16_WAVES) void k_sweep16(SweepArgs a) {
                         if (rfl & F_LAST) { row_end(ri, ((rw1 >> 20) & 511) - 1, key); row_open = false; }
                         else keys_st(key);
                     }
+                } else if constexpr (kLean) {
+                    // (a silent row: no column of it reaches a threshold)
                 } else if (track && kRec && kColmax == 0) {
                     // LAZY KEYS (rows in registers): the best VALUE per column is a packed maximum over the members (8
                     // v_pk_max per member instead of 32 key instructions), and
@@ -1459,6 +1494,13 @@ __global__ __launch_bounds__(64, SWEEP16_WAVES) void k_sweep16(SweepArgs a) {
                     // of the same segment — same group, flags 7 (rg_steps.cpp builds the field that way and moves runs whole) —
                     // so neither its flags nor its members are looked at, and only two of its four words are fetched
                     if ((t >> 6) != blk) to_block(t >> 6);
+                    if constexpr (kLean) {
+                        // (a tail behind the run fetches its own row, slot and knm below)
+                        const int nw0 = __builtin_amdgcn_readlane(recs.x, t & (WAVE - 1));
+                        rli = (nw0 >> 20) & 7;
+                        rleft = (nw0 >> 26) & 63;
+                        continue;
+                    }
                     const int nw0 = __builtin_amdgcn_readlane(recs.x, t & (WAVE - 1)), nw1 = __builtin_amdgcn_readlane(recs.y, t & (WAVE - 1));
                     ri = nw0 & 0xfffff; rli = (nw0 >> 20) & 7; rslot = nw1 & 0xfffff; rw1 = nw1;
                     rleft = (nw0 >> 26) & 63;
@@ -1481,8 +1523,24 @@ __global__ __launch_bounds__(64, SWEEP16_WAVES) void k_sweep16(SweepArgs a) {
             }
             cells += (unsigned long long)nrows * (unsigned long long)(kWide ? wide_total : __popcll(rgm));
             done += (unsigned long long)nrows * (unsigned long long)RN;
+            if constexpr (kSilent) {
+                sil[3] += (int)nrows;          // (every lane the same word, the same value)
+                if constexpr (kLean) sil[2] += (int)(nrows - (tail ? 1u : 0u));
+            }
             };
-            run_dispatch_from<1, (KRUN > 0 ? KRUN : 1)>(run_rows, rnm);
+            auto run_rows_full = [&](auto rn_tag) __attribute__((always_inline)) { run_rows(rn_tag, std::false_type{}); };
+            if constexpr (kSilent) {
+                // (gm is not empty here; retirement off: `silent` is empty.  knm + 1 of the first row: the rows of a run are rows of one
+                // path set.  gm, i and w1 are the FIRST record's although this sits inside the loop of the chained runs: kSilent implies
+                // kRec, kChain is !kTrack — no silent variant chains, the loop body runs once per record)
+                static_assert(!kChain, "a chained run would need the members, row and knm of ITS first record");
+                const unsigned long long silent = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane(sil[1]) << 32) | (unsigned)__builtin_amdgcn_readfirstlane(sil[0]);
+                const bool lean = (gm & ~silent) == 0ull && (rgm & dsel_w.w0) == 0ull && !edge_row(i) && ((w1 >> 20) & 511) != 0;
+                auto run_rows_lean = [&](auto rn_tag) __attribute__((always_inline)) { run_rows(rn_tag, std::true_type{}); };
+                if (lean) run_dispatch_from<1, (KRUN > 0 ? KRUN : 1)>(run_rows_lean, rnm);
+                else run_dispatch_from<1, (KRUN > 0 ? KRUN : 1)>(run_rows_full, rnm);
+            } else
+            run_dispatch_from<1, (KRUN > 0 ? KRUN : 1)>(run_rows_full, rnm);
             // ---- the run (and its tail) is over: rows in rr, t = the next record
             if (tail) {
                 if (semi_end && (rfl & F_LAST)) end_row_done(ri);
@@ -1648,6 +1706,9 @@ __global__ __launch_bounds__(64, SWEEP16_WAVES) void k_sweep16(SweepArgs a) {
     if (semi_end) {
         for (int k = lane; k < P; k += WAVE) { rs->sink_val[k] = endv[k]; rs->path_end_row[k] = endr[k]; }
         if (lane == ln_end) { rs->s0 = gbest_val; rs->end_row_best = gbest_row; rs->seed_path = gbest_path; }
+    }
+    if constexpr (kSilent) {
+        if (lane == 0 && a.runstat) { atomicAdd(a.runstat, (unsigned)sil[2]); atomicAdd(a.runstat + 1, (unsigned)sil[3]); }
     }
     if (lane == 0 && a.count_cells) {
         // counted: every member row of the table (what the reference updates) — from the table builder when records may have
