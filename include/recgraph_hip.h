@@ -111,6 +111,23 @@ typedef enum rg_status {
  * covers the rows of the chosen path up to the end row.
  */
 #define RG_MODE_PATHWISE_GAP_LOCAL 12
+/*
+ * RG_MODE_PATHWISE_GAP_LONG (16), RG_MODE_PATHWISE_GAP_SEMI_LONG (17), RG_MODE_PATHWISE_GAP_LOCAL_LONG (22): the long-read
+ * flavours of modes 6, 7 and 12, numbered `mode + 10` as the scalar flavours of modes 0 and 1 are.  THERE IS NO NEW RULE: mode
+ * m + 10 is the definition of mode m above with one word changed — reads of 1 to 16383 bases.  Recurrence, choice, tie order,
+ * traceback, record, line, RG_READ_UNALIGNED (mode 22) and both cell counters are those of mode m, and for every read of at
+ * most 2047 bases mode m + 10 returns the bytes, the status and the score of mode m.
+ *   REFUSALS.  gap_open > 0 or gap_ext > 0, any amb_mode bit, a read longer than 16383 bases: RG_ERR_ARG.  (rows of the longest
+ *     path + longest read) * max(|sc|, |o + e|) >= 2^28: RG_ERR_CAPACITY.  All answered by rg_batch_create before a device is
+ *     needed.
+ *   COST.  A batch whose longest read has at most 2047 bases runs exactly as in mode m.  Otherwise every read of the batch is
+ *     aligned in column stripes of 2048 (a read of n bases runs ceil((n + 1) / 2048) of them), and the direction words of the
+ *     chosen path take stripes * (rows of the longest path + 1) * 1 KiB per read of the batch: about 140 MB for one 16383-base
+ *     read on 17000 rows.  Modes 6, 7 and 12 themselves keep their limit of 2047 bases.
+ */
+#define RG_MODE_PATHWISE_GAP_LONG 16
+#define RG_MODE_PATHWISE_GAP_SEMI_LONG 17
+#define RG_MODE_PATHWISE_GAP_LOCAL_LONG 22
 
 /*
  * Scoring and banding parameters.  Replaces the HashMap<(char,char),i32|f32> score matrix arguments

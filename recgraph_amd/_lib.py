@@ -44,6 +44,10 @@ class Params(C.Structure):
 AMB_BOTH_STRANDS = 4     # RG_AMB_BOTH_STRANDS (include/recgraph_hip.h): bit 2 of Params.amb_mode, pathwise modes
 AMB_STRAND_VOTE = 8      # RG_AMB_STRAND_VOTE: bit 3, only together with bit 2 — the first strand by a 12-mer vote
 MODE_PATHWISE_GAP_LOCAL = 12    # RG_MODE_PATHWISE_GAP_LOCAL: a value of Params.mode, no entry point of its own
+# RG_MODE_PATHWISE_GAP_LONG / _SEMI_LONG / _LOCAL_LONG: modes 6, 7, 12 for reads of up to 16383 bases (`mode + 10`)
+MODE_PATHWISE_GAP_LONG = 16
+MODE_PATHWISE_GAP_SEMI_LONG = 17
+MODE_PATHWISE_GAP_LOCAL_LONG = 22
 READ_UNALIGNED = 16     # RG_READ_UNALIGNED: status bit of that mode — the read has no local alignment, and no record
 
 

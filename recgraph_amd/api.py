@@ -49,6 +49,10 @@ MODE_PATHWISE_GAP = 6
 MODE_PATHWISE_GAP_SEMI = 7
 # ... and local (RG_MODE_PATHWISE_GAP_LOCAL): soft-clipped reads; a read without a local alignment has READ_UNALIGNED and no line
 MODE_PATHWISE_GAP_LOCAL = _lib.MODE_PATHWISE_GAP_LOCAL
+# ... and the three again for reads of up to 16383 bases (RG_MODE_PATHWISE_GAP_LONG ...: `mode + 10`, the same rule and the same bytes)
+MODE_PATHWISE_GAP_LONG = _lib.MODE_PATHWISE_GAP_LONG
+MODE_PATHWISE_GAP_SEMI_LONG = _lib.MODE_PATHWISE_GAP_SEMI_LONG
+MODE_PATHWISE_GAP_LOCAL_LONG = _lib.MODE_PATHWISE_GAP_LOCAL_LONG
 
 READ_BAND_WARNING, READ_BAND_NOT_ENOUGH, READ_WOULD_PANIC, READ_BAD_BASE = 1, 2, 4, 8
 READ_UNALIGNED = _lib.READ_UNALIGNED
@@ -59,7 +63,8 @@ AMB_BOTH_STRANDS = _lib.AMB_BOTH_STRANDS
 # bit 3 (RG_AMB_STRAND_VOTE), only together with bit 2: the strand that is aligned first is picked per read by a 12-mer vote
 AMB_STRAND_VOTE = _lib.AMB_STRAND_VOTE
 PATHWISE_MODES = (MODE_PATHWISE, MODE_PATHWISE_SEMI, MODE_RECOMBINATION, MODE_RECOMBINATION_SEMI)
-PATHWISE_GAP_MODES = (MODE_PATHWISE_GAP, MODE_PATHWISE_GAP_SEMI, MODE_PATHWISE_GAP_LOCAL)      # (they align the reads as given: no both_strands)
+PATHWISE_GAP_MODES = (MODE_PATHWISE_GAP, MODE_PATHWISE_GAP_SEMI, MODE_PATHWISE_GAP_LOCAL,
+                      MODE_PATHWISE_GAP_LONG, MODE_PATHWISE_GAP_SEMI_LONG, MODE_PATHWISE_GAP_LOCAL_LONG)      # (they align the reads as given: no both_strands)
 
 
 def _both_strands_kw(mode, both_strands, kw, strand_vote=False):
@@ -68,7 +73,7 @@ def _both_strands_kw(mode, both_strands, kw, strand_vote=False):
     if not both_strands and not strand_vote:
         return kw
     if mode in PATHWISE_GAP_MODES:
-        raise _lib.RecGraphError(-1, "%s is not available in the affine-gap pathwise modes (6, 7, 12)" % ("strand_vote" if strand_vote else "both_strands"))
+        raise _lib.RecGraphError(-1, "%s is not available in the affine-gap pathwise modes (6, 7, 12 and their long-read flavours 16, 17, 22)" % ("strand_vote" if strand_vote else "both_strands"))
     if mode not in PATHWISE_MODES:
         raise _lib.RecGraphError(-1, "%s applies to the pathwise modes (4, 5, 8, 9) only: the POA modes align both "
                                      "strands with amb_strand (`-s true`)" % ("strand_vote" if strand_vote else "both_strands"))
@@ -850,25 +855,26 @@ def pathwise_alignment_semiglobal_exec(sequence, graph, score_matrix=None):
     return GAFStruct.from_line(text.rstrip("\n"))
 
 
-def pathwise_alignment_gap_exec(sequence, graph, score_matrix=None, o=-4, e=-2):
+def pathwise_alignment_gap_exec(sequence, graph, score_matrix=None, o=-4, e=-2, long_reads=False):
     """-m 6: global pathwise alignment with affine gaps (a gap of length g costs o + g * e; the rule: RG_MODE_PATHWISE_GAP in
     include/recgraph_hip.h).  The reference's pathwise_alignment_gap::exec returns the index of the best path only; here that
-    index is the "best path" of the GAFStruct's comments.  ``sequence`` carries the leading '$' like the reference's read arrays."""
-    _, text = _single(graph, "".join(sequence[1:]), "Temp", MODE_PATHWISE_GAP, 1, score_matrix=score_matrix, o=o, e=e)
+    index is the "best path" of the GAFStruct's comments.  ``sequence`` carries the leading '$' like the reference's read arrays.
+    ``long_reads=True`` (here and in the two wrappers below): the long-read flavour of the mode, reads of up to 16383 bases."""
+    _, text = _single(graph, "".join(sequence[1:]), "Temp", MODE_PATHWISE_GAP_LONG if long_reads else MODE_PATHWISE_GAP, 1, score_matrix=score_matrix, o=o, e=e)
     return GAFStruct.from_line(text.rstrip("\n"))
 
 
-def pathwise_alignment_gap_semi_exec(sequence, graph, score_matrix=None, o=-4, e=-2):
+def pathwise_alignment_gap_semi_exec(sequence, graph, score_matrix=None, o=-4, e=-2, long_reads=False):
     """-m 7: the semiglobal twin of ``pathwise_alignment_gap_exec`` (the alignment may start and end inside a path)."""
-    _, text = _single(graph, "".join(sequence[1:]), "Temp", MODE_PATHWISE_GAP_SEMI, 1, score_matrix=score_matrix, o=o, e=e)
+    _, text = _single(graph, "".join(sequence[1:]), "Temp", MODE_PATHWISE_GAP_SEMI_LONG if long_reads else MODE_PATHWISE_GAP_SEMI, 1, score_matrix=score_matrix, o=o, e=e)
     return GAFStruct.from_line(text.rstrip("\n"))
 
 
-def pathwise_alignment_gap_local_exec(sequence, graph, score_matrix=None, o=-4, e=-2):
+def pathwise_alignment_gap_local_exec(sequence, graph, score_matrix=None, o=-4, e=-2, long_reads=False):
     """-m 12: the local member of the family (RG_MODE_PATHWISE_GAP_LOCAL in include/recgraph_hip.h): the best-scoring piece of the
     read against a piece of one path; query_start / query_end of the GAFStruct say which piece of the read.  A read without a
     local alignment (READ_UNALIGNED) raises, like a read with a bad base."""
-    _, text = _single(graph, "".join(sequence[1:]), "Temp", MODE_PATHWISE_GAP_LOCAL, 1, score_matrix=score_matrix, o=o, e=e)
+    _, text = _single(graph, "".join(sequence[1:]), "Temp", MODE_PATHWISE_GAP_LOCAL_LONG if long_reads else MODE_PATHWISE_GAP_LOCAL, 1, score_matrix=score_matrix, o=o, e=e)
     return GAFStruct.from_line(text.rstrip("\n"))
 
 

@@ -5,6 +5,7 @@
 //   -m 4:  sweep(F, dirs) -> seed -> layer(F) -> trace
 //   -m 6:  gap_score(every path) -> gap_pick -> gap_dirs(picked path) -> gap_trace          (gap/rg_path_gap.hip; -m 7 likewise)
 //   -m 12: the same four steps with the local kernels                                       (gap_local/rg_path_gap_local.hip)
+//   -m 16, 17, 22: the rules of -m 6, 7, 12; a batch with a read over 2047 bases runs the striped kernels    (gap_long/rg_path_gap_long.hip)
 //   -m 8:  sweep(F1: column maxima) -> seed -> thr -> sweep(R: dirs, candidates, column maxima)
 //          -> thr -> sweep(F2: dirs, candidates) -> search -> layer(F) -> layer(R) -> trace
 #include <algorithm>
@@ -15,6 +16,7 @@
 
 #include "gap/rg_path_gap.hpp"
 #include "gap_local/rg_path_gap_local.hpp"
+#include "gap_long/rg_path_gap_long.hpp"
 #include "rg_kernel_timer.hpp"
 #include "rg_path_kernels.hpp"
 #include "rg_path_plan.hpp"
@@ -27,6 +29,7 @@ struct PathWorkImpl {
     DevBuf<ReadState> state;
     DevBuf<int> roll, mf, wr, mfarg, wrarg, thr, flayer, rlayer;
     DevBuf<uint32_t> fdirs, rdirs, gdirs;
+    DevBuf<int> gbnd, gdbnd;            // -m 16 / 17 / 22: the stripe boundaries of the score pass and of the direction pass
     DevBuf<Cand> fcand, rcand;
     DevBuf<unsigned> nf, nr, ridx, nrec, nrrec;
     DevBuf<int> frec, rrec;
@@ -151,6 +154,7 @@ int Run::alloc_chunk(bool* oom) {
     int rc;
     if (plan.gap) {
         if ((rc = w.state.alloc(n, oom)) || (rc = w.gdirs.alloc(n * (size_t)plan.gdirs_stride, oom))) return rc;
+        if (plan.nwv > 1 && ((rc = w.gbnd.alloc(n * (size_t)plan.gbnd_stride, oom)) || (rc = w.gdbnd.alloc(n * (size_t)plan.gdbnd_stride, oom)))) return rc;
         return RG_OK;
     }
     if ((rc = w.state.alloc(n, oom)) || (rc = w.fdirs.alloc(n * plan.fdirs_stride, oom)) || (rc = w.flayer.alloc(n * plan.layer_stride, oom)) ||
@@ -239,6 +243,20 @@ int Run::enqueue_pathwise_gap() {
     ga.cells = d_cells; ga.rec = d_rec + done; ga.ops = d_ops + (long long)done * ops_stride; ga.ops_stride = ops_stride;
     const int C = plan.C;
     const bool semi = plan.semi;
+    if (plan.nwv > 1) {
+        // column stripes (a long mode with a read over 2047 bases): the pick kernels are the base modes', told the striped width
+        GapLongArgs la;
+        memset(&la, 0, sizeof la);
+        la.g = ga; la.S = plan.nwv; la.rows1 = h.max_path_rows + 1;
+        la.bnd = w.gbnd.p; la.bnd_stride = plan.gbnd_stride; la.dbnd = w.gdbnd.p;
+        const int kind = plan.local ? GAP_LONG_LOCAL : semi ? GAP_LONG_SEMI : GAP_LONG_GLOBAL;
+        RG_TRY(T.run("k_gap_score_long", [&] { return launch_gap_score_long(la, chunk, kind, stream); }));
+        if (plan.local) RG_TRY(T.run("k_gap_pick_local", [&] { return launch_gap_pick_local(ga, chunk, plan.nwv * C, stream); }));
+        else RG_TRY(T.run("k_gap_pick", [&] { return launch_gap_pick(ga, chunk, plan.nwv * C, semi, stream); }));
+        RG_TRY(T.run("k_gap_dirs_long", [&] { return launch_gap_dirs_long(la, chunk, kind, stream); }));
+        RG_TRY(T.run(plan.local ? "k_gap_trace_local_long" : "k_gap_trace_long", [&] { return launch_gap_trace_long(la, chunk, kind, stream); }));
+        return read_back();
+    }
     if (plan.local) {
         RG_TRY(T.run("k_gap_score_local", [&] { return launch_gap_score_local(ga, chunk, C, stream); }));
         RG_TRY(T.run("k_gap_pick_local", [&] { return launch_gap_pick_local(ga, chunk, C, stream); }));

@@ -77,18 +77,23 @@ bool sweep16_admissible(const DevScores& sc, int max_path_rows, int max_n, int C
 }
 
 // -m 6 / -m 7 / -m 12: one wave per (read, path) keeps H and Y of the current row in registers, C columns per lane (n + 1 <= 64 C), so a
-// read must fit one wave; the only HBM work buffer beside ReadState holds the 4-bit directions of the picked path.
+// read must fit one wave (-m 16 / -m 17 / -m 22: up to 8 column stripes of 2048, walked by that one wave, gap_long/rg_path_gap_long.hip); the only HBM work buffer beside ReadState holds the 4-bit directions of the picked path.
 static int plan_pathwise_gap(const rg_params& p, const PathPlanInput& in, PathPlan& o) {
     if (p.gap_open > 0 || p.gap_ext > 0) return fail(RG_ERR_ARG, "gap penalties must be <= 0");
-    const bool local = p.mode == RG_MODE_PATHWISE_GAP_LOCAL;
+    const bool lng = path_gap_long_mode(p.mode);
+    const int base = path_gap_base_mode(p.mode);
+    const bool local = base == RG_MODE_PATHWISE_GAP_LOCAL;
     if (p.amb_mode)
-        return fail(RG_ERR_ARG, local ? "amb_mode must be 0 in the local affine-gap pathwise mode (-m 12): it aligns the reads as given"
-                                      : "amb_mode must be 0 in the affine-gap pathwise modes (-m 6 / -m 7): they align the reads as given");
-    if (in.max_n > 32 * WAVE - 1)
+        return fail(RG_ERR_ARG, lng     ? "amb_mode must be 0 in the long-read affine-gap pathwise modes (-m 16 / -m 17 / -m 22): they align the reads as given"
+                                : local ? "amb_mode must be 0 in the local affine-gap pathwise mode (-m 12): it aligns the reads as given"
+                                        : "amb_mode must be 0 in the affine-gap pathwise modes (-m 6 / -m 7): they align the reads as given");
+    if (lng && in.max_n > 8 * 32 * WAVE - 1)
+        return fail(RG_ERR_ARG, "reads longer than 16383 bases are not supported by the long-read affine-gap pathwise modes (-m 16 / -m 17 / -m 22)");
+    if (!lng && in.max_n > 32 * WAVE - 1)
         return fail(RG_ERR_ARG, local ? "reads longer than 2047 bases are not supported by the local affine-gap pathwise mode (-m 12)"
                                       : "reads longer than 2047 bases are not supported by the affine-gap pathwise modes (-m 6 / -m 7)");
     // every value of H, X, Y is a sum of at most (rows + n) steps of at most max(|sc|, |o + e|) each: kept inside +-2^28, so that
-    // the NEG sentinel (-2^29) plus any such sum can neither win nor wrap
+    // the NEG sentinel (-2^29) plus any such sum can neither win nor wrap (the striped kernels' z in global columns: their header)
     long long maxabs = std::llabs((long long)p.gap_open + (long long)p.gap_ext);
     for (int x = 0; x < 5; ++x)
         for (int y = 0; y < 5; ++y)
@@ -97,16 +102,22 @@ static int plan_pathwise_gap(const rg_params& p, const PathPlanInput& in, PathPl
         return fail(RG_ERR_CAPACITY, "scores of this batch can reach 2^28 in magnitude: outside the i32 range of the affine-gap pathwise kernels");
     o.gap = true;
     o.mode = RG_MODE_PATHWISE_GAP;
-    o.semi = p.mode == RG_MODE_PATHWISE_GAP_SEMI;
+    o.semi = base == RG_MODE_PATHWISE_GAP_SEMI;
     o.local = local;          // (-m 12: neither end is pinned; `semi` stays false)
     int C = 4;
-    while (C * WAVE < in.max_n + 1) C *= 2;
+    while (C * WAVE < in.max_n + 1 && C < 32) C *= 2;
     o.C = C;
-    o.nwv = 1;
-    o.wpad = C * WAVE;
+    // a long mode whose longest read fits one wave runs the base mode's kernels on the base mode's plan; beyond that, column stripes
+    o.nwv = (in.max_n + 1 + C * WAVE - 1) / (C * WAVE);
+    o.wpad = o.nwv * C * WAVE;
     o.gap_words = std::max(1, C / 8);
-    o.gdirs_stride = (long long)(in.max_path_rows + 1) * o.gap_words * WAVE;
+    o.gdirs_stride = (long long)o.nwv * (in.max_path_rows + 1) * o.gap_words * WAVE;
     o.per_read = (size_t)o.gdirs_stride * 4 + sizeof(ReadState);
+    if (o.nwv > 1) {
+        o.gbnd_stride = 2ll * (in.max_path_rows + 1) * in.P;
+        o.gdbnd_stride = 2ll * (in.max_path_rows + 1);
+        o.per_read += (size_t)(o.gbnd_stride + o.gdbnd_stride) * 4;
+    }
     for (int x = 0; x < 5; ++x)
         for (int y = 0; y < 5; ++y) o.maxmatch = std::max(o.maxmatch, p.scores[x * 6 + y]);
     return RG_OK;
@@ -114,7 +125,8 @@ static int plan_pathwise_gap(const rg_params& p, const PathPlanInput& in, PathPl
 
 int plan_pathwise(const rg_params& p, const PathPlanInput& in, const Options& opt, int spec_level, PathPlan& o) {
     o = PathPlan{};
-    if (p.mode == RG_MODE_PATHWISE_GAP || p.mode == RG_MODE_PATHWISE_GAP_SEMI || p.mode == RG_MODE_PATHWISE_GAP_LOCAL) return plan_pathwise_gap(p, in, o);
+    const int gbase = path_gap_base_mode(p.mode);
+    if (gbase == RG_MODE_PATHWISE_GAP || gbase == RG_MODE_PATHWISE_GAP_SEMI || gbase == RG_MODE_PATHWISE_GAP_LOCAL) return plan_pathwise_gap(p, in, o);
     const int P = in.P, L = in.L, max_n = in.max_n;
     o.semi = p.mode == RG_MODE_PATHWISE_SEMI || p.mode == RG_MODE_RECOMBINATION_SEMI;
     o.mode = p.mode == RG_MODE_PATHWISE_SEMI ? RG_MODE_PATHWISE : p.mode == RG_MODE_RECOMBINATION_SEMI ? RG_MODE_RECOMBINATION : p.mode;

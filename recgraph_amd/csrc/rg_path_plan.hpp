@@ -62,6 +62,10 @@ struct PathPlan {
     bool local;                   // -m 12 (gap_local/rg_path_gap_local.hip): the same geometry and buffers, the local kernels
     int gap_words;
     long long gdirs_stride;       // words per read: (rows of the longest path + 1) * gap_words * 64
+    // -m 16 / -m 17 / -m 22 (gap_long/rg_path_gap_long.hip) when the longest read has more than 2047 bases — otherwise the plan IS the
+    // base mode's: C = 32, nwv = S = ceil((max_n + 1) / 2048) column stripes walked by ONE wave, gdirs_stride = S * (rows + 1) * 4 * 64,
+    // and two boundary buffers (ints per read): 2 * (rows + 1) per path for the score pass, 2 * (rows + 1) for the direction pass
+    long long gbnd_stride, gdbnd_stride;
 
     // ... with candidate lists of fcap / rcap entries and record lists of frec_cap / rrec_cap records
     size_t per_read_all(unsigned fcap_, unsigned rcap_, unsigned frec_cap_, unsigned rrec_cap_) const {

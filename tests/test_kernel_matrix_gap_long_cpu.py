@@ -1,0 +1,63 @@
+"""CPU: tests/kernel_matrix_gap_long.py is complete and the rules answer every case of it.
+
+The key set of the matrix must equal the set of `__global__` instantiations hipcc compiles from
+recgraph_amd/csrc/gap_long/rg_path_gap_long.hip (tools/kernel_resources.py report(): cross-compiled for gfx950, no GPU), and no other
+file of that directory may hold a kernel without a matrix."""
+import os
+import sys
+import time
+
+import kernel_matrix_gap_long as KG
+import pathwise_gap_local_rule as L
+import pathwise_gap_rule as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GAP_LONG = os.path.join(ROOT, "recgraph_amd", "csrc", "gap_long")
+
+
+def test_the_matrix_has_exactly_the_compiled_instantiations():
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import kernel_resources
+    assert sorted(f for f in os.listdir(GAP_LONG) if f.endswith(".hip")) == ["rg_path_gap_long.hip"]
+    names = [k["name"] for k in kernel_resources.report("gap_long/rg_path_gap_long.hip")]
+    assert len(names) == len(set(names))
+    compiled, keys = set(names), set(KG.MATRIX)
+    assert compiled == keys, {"compiled without an entry": sorted(compiled - keys), "entries without a kernel": sorted(keys - compiled)}
+    assert len(compiled) == 8
+
+
+def test_every_entry_names_a_case():
+    assert set(KG.MATRIX.values()) == set(KG.CASES)
+    assert {n for c in KG.CASES.values() for n in c.batches} == {2048, 4096}
+    assert {c.mode for c in KG.CASES.values()} == {16, 17, 22}
+    for name, cid in KG.MATRIX.items():
+        mode = KG.CASES[cid].mode
+        assert "<%d>" % (0, 1, 2)[(16, 17, 22).index(mode)] in name or name == KG.TRACE[mode], (name, cid)
+
+
+def test_the_rule_answers_every_case():
+    from recgraph_amd import api
+    t0 = time.perf_counter()
+    worst = (0, None)
+    for cid, case in KG.CASES.items():
+        g, batches = KG.build(case)
+        assert [max(len(r) for r in b) for b in batches] == case.batches and all(len(b[-1]) == 1 for b in batches), cid
+        assert all(len(b[0]) == hi for b, hi in zip(batches, case.batches)), cid
+        lnz, rows = R.graph_paths(api.Graph.from_gfa_text(g.gfa()))
+        cells = KG.rule_cells(rows, batches)
+        worst = max(worst, (cells, cid))
+        assert cells <= KG.CELL_CAP, (cid, cells)
+        o, e = case.kw.get("o", -4), case.kw.get("e", -2)
+        for reads in batches:
+            for rd in reads:
+                if case.mode == 22:
+                    res = L.align_local(lnz, rows, rd, None, o, e)
+                    assert res is not None and res[0] > 0, cid
+                else:
+                    res = R.align(lnz, rows, rd, None, o, e, case.mode == 17)
+                    assert len(res[3]) >= len(rd), cid
+            if case.mode == 22:
+                # the flanked read is clipped on the left, and its alignment ends beyond the first stripe boundary
+                score, k, end_row, end_col, stop_col, ops, pseq = L.align_local(lnz, rows, reads[0], None, o, e)
+                assert stop_col > 0 and 2048 <= end_col <= len(reads[0]), (cid, stop_col, end_col)
+    print("long gap kernel matrix: %d cases, rule wall time %.1f s, largest case %s at %.2e cells" % (len(KG.CASES), time.perf_counter() - t0, worst[1], worst[0]))

@@ -1,0 +1,118 @@
+"""CPU: the long-read flavours of the affine-gap pathwise modes (-m 16 / -m 17 / -m 22 = modes 6 / 7 / 12 for reads of up to 16383
+bases): admission and refusals of rg_batch_create (answered before a device is needed), the plan's routes
+(tests/c/gap_long_plan_check.cpp), the API and CLI surface and the registers of the new kernels."""
+import os
+import subprocess
+import sys
+
+import pytest
+
+from test_pathwise_gap_cpu import TWO_BUBBLES, _create, _no_device
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LONG = {16: 6, 17: 7, 22: 12}
+
+
+def test_the_constants():
+    from recgraph_amd import api
+    assert (api.MODE_PATHWISE_GAP_LONG, api.MODE_PATHWISE_GAP_SEMI_LONG, api.MODE_PATHWISE_GAP_LOCAL_LONG) == (16, 17, 22)
+    assert (api._lib.MODE_PATHWISE_GAP_LONG, api._lib.MODE_PATHWISE_GAP_SEMI_LONG, api._lib.MODE_PATHWISE_GAP_LOCAL_LONG) == (16, 17, 22)
+    assert (api.MODE_PATHWISE_GAP + 10, api.MODE_PATHWISE_GAP_SEMI + 10, api.MODE_PATHWISE_GAP_LOCAL + 10) == (16, 17, 22)
+    header = open(os.path.join(ROOT, "include", "recgraph_hip.h")).read()
+    for name, v in (("RG_MODE_PATHWISE_GAP_LONG", 16), ("RG_MODE_PATHWISE_GAP_SEMI_LONG", 17), ("RG_MODE_PATHWISE_GAP_LOCAL_LONG", 22)):
+        assert "#define %s %d\n" % (name, v) in header
+
+
+@pytest.mark.parametrize("mode", sorted(LONG))
+def test_the_long_modes_are_admitted_and_refuse_before_a_device_is_needed(mode):
+    ok = -3 if _no_device() else 0
+    rc, msg = _create(TWO_BUBBLES, ["ATGCT"], mode)
+    # (on the parent commit: RG_ERR_ARG "unsupported mode")
+    assert rc == ok, (rc, msg)
+    # what the base modes refuse at 2048 bases is admitted up to 16383
+    for n in (2047, 2048, 16383):
+        rc, msg = _create(TWO_BUBBLES, ["A" * n], mode)
+        assert rc == ok, (n, rc, msg)
+    rc, msg = _create(TWO_BUBBLES, ["ATG", "A" * 16384], mode)
+    assert rc == -1 and "16383" in msg, (rc, msg)
+    assert _create(TWO_BUBBLES, ["ATGCT"], mode, o=1)[0] == -1
+    assert _create(TWO_BUBBLES, ["ATGCT"], mode, e=1)[0] == -1
+    assert _create(TWO_BUBBLES, ["A" * 5000], mode, o=1)[0] == -1
+    for amb in (1, 2, 4, 8, 12):
+        assert _create(TWO_BUBBLES, ["ATGCT"], mode, amb=amb)[0] == -1, amb
+        assert _create(TWO_BUBBLES, ["A" * 3000], mode, amb=amb)[0] == -1, amb
+    # (5 rows + 5 bases) * 2^25 >= 2^28, and (5 rows + 16379 bases) * 2^14 = 2^28
+    assert _create(TWO_BUBBLES, ["ATGCT"], mode, match=1 << 25)[0] == -5
+    assert _create(TWO_BUBBLES, ["ATGCT"], mode, o=-(1 << 25))[0] == -5
+    assert _create(TWO_BUBBLES, ["A" * 16379], mode, match=1 << 14)[0] == -5
+    assert _create(TWO_BUBBLES, ["A" * 16378], mode, match=1 << 14)[0] == ok
+
+
+def test_the_base_modes_keep_their_limit_and_the_gaps_between_the_modes_stay_closed():
+    for mode in (6, 7, 12):
+        rc, msg = _create(TWO_BUBBLES, ["A" * 2048], mode)
+        assert rc == -1 and "2047" in msg, (mode, rc, msg)
+    for other in (13, 14, 15, 18, 19, 20, 21, 23, -1):
+        rc, msg = _create(TWO_BUBBLES, ["ATGCT"], other)
+        assert rc == -1 and "unsupported mode" in msg, (other, rc, msg)
+
+
+def test_no_new_entry_point():
+    from recgraph_amd import _lib
+    assert len(_lib.SYMBOLS) == 63
+    exports = open(os.path.join(ROOT, "recgraph_amd", "csrc", "exports.map")).read()
+    assert "long" not in exports
+
+
+def test_the_api_refuses_both_strands_and_the_wrappers_take_the_long_modes():
+    import inspect
+    from recgraph_amd import api
+    g = api.Graph.from_gfa_text(TWO_BUBBLES)
+    for mode in sorted(LONG):
+        assert mode in api.PATHWISE_GAP_MODES
+        for fn in (api.align_batch, api.align_batch_multi, api.align_stream):
+            with pytest.raises(api._lib.RecGraphError):
+                fn(g, ["ATG"], mode=mode, both_strands=True)
+            with pytest.raises(api._lib.RecGraphError):
+                fn(g, ["ATG"], mode=mode, strand_vote=True)
+    for fn in (api.pathwise_alignment_gap_exec, api.pathwise_alignment_gap_semi_exec, api.pathwise_alignment_gap_local_exec):
+        assert inspect.signature(fn).parameters["long_reads"].default is False
+
+
+def test_the_cli_takes_the_modes():
+    from recgraph_amd import cli
+    for m in sorted(LONG):
+        a = cli.build_parser().parse_args(["reads.fa", "graph.gfa", "-m", str(m), "-O", "6", "-E", "1"])
+        assert a.alignment_mode == m and (a.gap_open, a.gap_extension) == (6, 1)
+        for flag in ("--both-strands", "--strand-vote"):
+            with pytest.raises(SystemExit) as ex:
+                cli.main(["reads.fa", "graph.gfa", "-m", str(m), flag])
+            assert "16, 17 and 22" in str(ex.value)
+    for m in ("13", "14", "15", "18", "19", "20", "21", "23"):
+        with pytest.raises(SystemExit) as ex:
+            cli.main(["reads.fa", "graph.gfa", "-m", m])
+        assert str(ex.value).startswith("Alignment mode must be in")
+
+
+def test_gap_long_plan_routes(tmp_path):
+    csrc = os.path.join(ROOT, "recgraph_amd", "csrc")
+    exe = tmp_path / "gap_long_plan_check"
+    srcs = [os.path.join(csrc, f) for f in ("rg_path_plan.cpp", "rg_steps.cpp", "rg_graph.cpp", "rg_gaf.cpp", "rg_reads.cpp")]
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-I", csrc, "-o", str(exe), os.path.join(ROOT, "tests", "c", "gap_long_plan_check.cpp")]
+                          + srcs + ["-lpthread"])
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.strip() == "gap long plan ok", (r.stdout, r.stderr[-4000:])
+
+
+def test_the_kernels_keep_their_rows_in_registers():
+    """The family's bar: no scratch, no spilled VGPR, no AGPR, at most 200 VGPRs and no LDS beyond the score table's 160 B in every
+    instantiation of gap_long/rg_path_gap_long.hip (DESIGN 4.10 lists the counts)."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import kernel_resources
+    ks = kernel_resources.report("gap_long/rg_path_gap_long.hip")
+    assert sorted(k["name"] for k in ks) == sorted(["rg::k_gap_score_long<%d>" % k for k in range(3)] + ["rg::k_gap_dirs_long<%d>" % k for k in range(3)] +
+                                                  ["rg::k_gap_trace_long", "rg::k_gap_trace_local_long"])
+    for k in ks:
+        assert k["ScratchSize [bytes/lane]"] == 0 and k["VGPRs Spill"] == 0 and k["AGPRs"] == 0, (k["name"], k)
+        assert k["VGPRs"] <= 200, (k["name"], k)
+        assert k["LDS Size [bytes/block]"] <= 160, (k["name"], k)

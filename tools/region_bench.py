@@ -3,7 +3,7 @@
 engine on other read lengths, score parameters and path counts, with the sweep kernel that ran and a parity check of a
 few reads against the oracle.  One JSON line per case.
 
-    python tools/region_bench.py [case ...]        cases: c5 x6 m3x5 hoxd70 len1500 p128 len600 gap gap_local (default: all but the strand cases, `gap` and `gap_local`)
+    python tools/region_bench.py [case ...]        cases: c5 x6 m3x5 hoxd70 len1500 p128 len600 gap gap_local gap_long (default: all but the strand cases and the three `gap` cases)
 
 The strand cases (RG_AMB_BOTH_STRANDS, config-5 shape; `reads_per_s` counts SOURCE reads): `both_strands_fwd` — option on, every
 read forward (what the option costs when nothing qualifies: compare with `c5`); `both_strands` — option on, half of the reads
@@ -20,6 +20,12 @@ reads of 150 and 1000 bases; one batch handle, timed over whole rg_batch_run cal
 are random overhangs (an eighth of the read on either side); both handles are warmed up, then timed over whole rg_batch_run calls in
 alternating rounds (median and minimum per mode, and -m 12 as a ratio to -m 7); five reads of every -m 12 batch are checked against
 the rule (tests/pathwise_gap_local_rule.py).  One JSON line per (shape, length).
+
+`gap_long` (only when named): -m 16 at 4000 bases beside -m 6 at 2047 bases (the same reads, cut) on the same graph — 16 paths of
+about 4000 rows — in the same process: both handles are warmed up, then timed over whole rg_batch_run calls in alternating rounds;
+median and minimum per mode, the time per COUNTED cell update (rows_k * n per path and read) of both and their ratio, and the time of
+every kernel.  Two reads of the -m 16 batch are checked against the rule (tests/pathwise_gap_rule.py): the printed score is the
+rule's, and the printed CIGAR re-scores to it.  One JSON line.
 
 Every case: TILES tiles of TILE reads through one rg_stream (3 handles), timed after one warm-up tile per handle."""
 import json
@@ -148,9 +154,62 @@ def gap_local_case():
             print(json.dumps(out), flush=True)
 
 
+def gap_long_case():
+    from recgraph_amd import api, synth
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import pathwise_gap_rule as R
+    rounds, paths, plen, nreads = 5, 16, 4000, 512
+    g = synth.haplotype_graph(3 * plen, paths, path_len=plen, seed=1234)
+    gg = api.Graph.from_gfa_text(g.gfa())
+    long_reads = synth.haplotype_reads(g, nreads, length=plen, seed=900, mosaic_frac=0.0)
+    reads = {api.MODE_PATHWISE_GAP_LONG: long_reads, api.MODE_PATHWISE_GAP: [r[:2047] for r in long_reads]}
+    modes = tuple(reads)
+    batch = {m: api.Batch(gg, reads[m], api.make_params(m)) for m in modes}
+    times = {m: [] for m in modes}
+    ks = {m: {} for m in modes}
+    for m in modes:
+        batch[m].run()                       # warm-up: code objects, work buffers
+    for _ in range(rounds):
+        for m in modes:                      # alternating: both modes see the same machine
+            t0 = time.perf_counter()
+            batch[m].run()                   # (returns after the chunk's read-back: the device is idle again)
+            times[m].append(time.perf_counter() - t0)
+            for k, v in batch[m].kernel_stats().items():
+                if not k.startswith(("host:", "mem:", "inst:")):
+                    ks[m][k] = ks[m].get(k, 0.0) + v[0] / rounds
+    for m in modes:
+        batch[m].fetch()
+    b = batch[api.MODE_PATHWISE_GAP_LONG]
+    lnz, prow = R.graph_paths(gg)
+    ok = True
+    for i in (0, nreads - 1):
+        f = b.gaf_text(i, "r", 1)[:-1].split("\t")
+        mm = re.fullmatch(r"([0-9MXID]+), best path: (\d+), score: (-?\d+)", f[12])
+        last, lens = R.all_paths_last(lnz, prow, long_reads[i], R.default_scores(), -4, -2, False)
+        best = max((int(last[k, lens[k]]), -k) for k in range(paths))
+        ok = ok and mm is not None and (int(mm.group(3)), -int(mm.group(2))) == best
+        ok = ok and R.rescore(mm.group(1), f[13], long_reads[i])[:2] == (best[0], len(long_reads[i]))
+    med = {m: sorted(times[m])[rounds // 2] for m in modes}
+    out = {"case": "gap_long", "rows": gg.rows, "paths": paths, "path_rows": max(len(r) for r in prow), "reads": nreads, "rounds": rounds}
+    for m in modes:
+        bm = batch[m]
+        out["m%d" % m] = {"read_len": len(reads[m][0]), "ms_per_batch_median": round(med[m] * 1e3, 2), "ms_per_batch_min": round(min(times[m]) * 1e3, 2),
+                          "counted_cell_updates": bm.cell_updates, "ps_per_counted_cell_update": round(med[m] / bm.cell_updates * 1e12, 3),
+                          "performed_over_counted": round(bm.cell_updates_performed / bm.cell_updates, 3),
+                          "kernel_ms_per_batch": {k: round(v, 2) for k, v in ks[m].items()}}
+    out["m16_over_m6_time_per_cell_median"] = round(out["m16"]["ps_per_counted_cell_update"] / out["m6"]["ps_per_counted_cell_update"], 3)
+    out["rule_checked"] = 2 if ok else "FAILED"
+    print(json.dumps(out), flush=True)
+
+
 def main():
     from recgraph_amd import api, synth
     from oracle import oracle as O
+    if "gap_long" in sys.argv[1:]:
+        gap_long_case()
+        sys.argv = [a for a in sys.argv if a != "gap_long"]
+        if len(sys.argv) == 1:
+            return
     if "gap_local" in sys.argv[1:]:
         gap_local_case()
         sys.argv = [a for a in sys.argv if a != "gap_local"]
