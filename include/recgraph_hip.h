@@ -128,6 +128,36 @@ typedef enum rg_status {
 #define RG_MODE_PATHWISE_GAP_LONG 16
 #define RG_MODE_PATHWISE_GAP_SEMI_LONG 17
 #define RG_MODE_PATHWISE_GAP_LOCAL_LONG 22
+/*
+ * RG_MODE_PATHWISE_GAP_STRANDS (26), RG_MODE_PATHWISE_GAP_SEMI_STRANDS (27), RG_MODE_PATHWISE_GAP_LOCAL_STRANDS (32): modes 6, 7
+ * and 12 on BOTH STRANDS, numbered `mode + 20`.  Write "pipeline m" for the long flavour 16, 17 or 22 of the base mode: the new
+ * modes take reads of 1 to 16383 bases, and every pass of theirs is one run of pipeline m (a pass without a read over 2047 bases
+ * runs the base mode's kernels).  THERE IS NO NEW RECURRENCE, CHOICE, TRACEBACK OR LINE; what is new is which strand is reported.
+ * RG_AMB_BOTH_STRANDS and RG_AMB_STRAND_VOTE are defined below.
+ *   MODES 26 AND 27, amb_mode 0 or 4 (bit 2 is implied and accepted as redundant): THE EXACT RULE.  Rules 1 to 5 of
+ *     RG_AMB_BOTH_STRANDS word for word, "the pipeline" being pipeline 16 or 17 and the score the integer the record prints: a
+ *     read qualifies for the reverse pass iff its status has neither RG_READ_BAD_BASE nor RG_READ_WOULD_PANIC and its forward
+ *     score is < 0; the reverse record wins only when its score is STRICTLY greater; a winning reverse read is reported exactly
+ *     as its reverse complement would be had it been submitted by itself in mode 16 or 17, except for strand column '-'.
+ *     CONSEQUENCE: a batch in which no forward score is negative returns the bytes, statuses and scores of mode 16 or 17.
+ *   MODES 26 AND 27, amb_mode 12: THE VOTE RULE.  Rules 1 to 7 of RG_AMB_STRAND_VOTE verbatim, pass A and pass B being pipeline
+ *     16 or 17.
+ *   MODE 32, amb_mode 0 or 4.  A local score is never negative, so a `< 0` gate could never fire.  Here EVERY read whose forward
+ *     status has neither RG_READ_BAD_BASE nor RG_READ_WOULD_PANIC is also aligned as its reverse complement, and the reverse
+ *     record wins only when its score is STRICTLY greater.  An RG_READ_UNALIGNED record has score 0: forward unaligned and
+ *     reverse aligned — the reverse record, status 0; both unaligned — RG_READ_UNALIGNED, strand '+', no line; ties (a
+ *     reverse-palindromic read included) — forward.  Query start and query end of a chosen reverse record are in the reverse
+ *     complement's coordinates (rule 5).  amb_mode 12 is RG_ERR_ARG in mode 32: no score of a local pass says "hopeless", so a
+ *     vote would have no pass-B rule.
+ *   REFUSALS.  amb_mode bits 0 and 1, bit 3 alone, any higher bit, and everything modes 16, 17 and 22 refuse (positive gap
+ *     costs, a read over 16383 bases: RG_ERR_ARG; the 2^28 budget: RG_ERR_CAPACITY).  All answered by rg_batch_create before a
+ *     device is needed.
+ * Both cell counters include pass B.  k_strand_gate (mode 32: k_gap_strands_gate), k_revcomp and k_strand_merge appear in the
+ * kernel statistics under their own names, with amb_mode 12 also k_strand_vote and k_strand_orient.
+ */
+#define RG_MODE_PATHWISE_GAP_STRANDS 26
+#define RG_MODE_PATHWISE_GAP_SEMI_STRANDS 27
+#define RG_MODE_PATHWISE_GAP_LOCAL_STRANDS 32
 
 /*
  * Scoring and banding parameters.  Replaces the HashMap<(char,char),i32|f32> score matrix arguments
@@ -407,7 +437,9 @@ typedef struct rg_stream_opts {
                                      2: the same for a POA stream; for a stream of a pathwise mode it sets
                                      RG_AMB_BOTH_STRANDS on the stream's handles (our extension, see there; the kept
                                      record is the chosen one, so keep_records is fine)
-                                     3: as 2, and on a pathwise stream RG_AMB_STRAND_VOTE as well                */
+                                     3: as 2, and on a pathwise stream RG_AMB_STRAND_VOTE as well
+                                     Modes 26, 27 and 32 align both strands whatever this field says: 0, 1 and 2 give
+                                     their exact rule, 3 the vote in modes 26 and 27 and RG_ERR_ARG in mode 32           */
     int64_t max_undelivered_bytes;/* > 0: see "Memory" above                                                     */
 } rg_stream_opts;
 typedef struct rg_stream_result {

@@ -48,6 +48,10 @@ MODE_PATHWISE_GAP_LOCAL = 12    # RG_MODE_PATHWISE_GAP_LOCAL: a value of Params.
 MODE_PATHWISE_GAP_LONG = 16
 MODE_PATHWISE_GAP_SEMI_LONG = 17
 MODE_PATHWISE_GAP_LOCAL_LONG = 22
+# RG_MODE_PATHWISE_GAP_STRANDS / _SEMI_STRANDS / _LOCAL_STRANDS: modes 6, 7, 12 on both strands (`mode + 20`), reads of up to 16383 bases
+MODE_PATHWISE_GAP_STRANDS = 26
+MODE_PATHWISE_GAP_SEMI_STRANDS = 27
+MODE_PATHWISE_GAP_LOCAL_STRANDS = 32
 READ_UNALIGNED = 16     # RG_READ_UNALIGNED: status bit of that mode — the read has no local alignment, and no record
 
 

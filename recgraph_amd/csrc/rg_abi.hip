@@ -56,8 +56,8 @@ static void fill_record(const rg_batch* b, int64_t i, ReadRecord& r) {
     r.ops = b->ops.data() + (size_t)i * b->ops_stride;
     r.rows = is_poa(b->p.mode) ? b->oprows.data() + (size_t)i * b->ops_stride : nullptr;
 }
-// RG_AMB_BOTH_STRANDS: the record of read i came from the reverse-complement pass (DevRecord.pad is written by that mode's
-// kernels only)
+// RG_AMB_BOTH_STRANDS (set by rg_batch_create on every handle of -m 26 / -m 27 / -m 32): the record of read i came from the
+// reverse-complement pass (DevRecord.pad is written by that mode's kernels only)
 static bool reverse_won(const rg_batch* b, int64_t i) {
     return (b->p.amb_mode & RG_AMB_BOTH_STRANDS) && !is_poa(b->p.mode) && (b->rec[i].pad & REC_REVERSE_STRAND);
 }
@@ -359,7 +359,7 @@ int32_t rg_batch_create(const rg_graph* gc, const rg_params* p, const char* read
     if (!gc || !p || !reads || !read_off || !out || nreads < 1) return fail(RG_ERR_ARG, "null/empty argument");
     const rg_graph* g = gc;
     const int mode = p->mode;
-    const int gbase = path_gap_base_mode(mode);       // (-m 16 / -m 17 / -m 22: the long-read flavours of 6, 7, 12)
+    const int gbase = path_gap_base_mode(mode);       // (-m 16 / -m 17 / -m 22: the long-read flavours of 6, 7, 12; -m 26 / -m 27 / -m 32: those on both strands)
     const bool path_gap = gbase == RG_MODE_PATHWISE_GAP || gbase == RG_MODE_PATHWISE_GAP_SEMI || gbase == RG_MODE_PATHWISE_GAP_LOCAL;
     if (!(is_poa(mode) || mode == RG_MODE_PATHWISE || mode == RG_MODE_RECOMBINATION || mode == RG_MODE_PATHWISE_SEMI ||
           mode == RG_MODE_RECOMBINATION_SEMI || path_gap))
@@ -403,6 +403,9 @@ int32_t rg_batch_create(const rg_graph* gc, const rg_params* p, const char* read
     b->g = g;
     b->gt = gt;
     b->p = *p;
+    // -m 26 / -m 27 / -m 32 align both strands whatever the bit says: from here on the handle IS a both-strands handle (the 16-byte
+    // ops_stride, the strand buffers, the strand of a record)
+    if (path_gap_strands_mode(mode)) b->p.amb_mode |= RG_AMB_BOTH_STRANDS;
     HIPCHK(hipGetDevice(&b->dev));
     {
         // the handle's stream at the highest priority: it carries the small kernels; the pathwise sweeps run on a low-priority

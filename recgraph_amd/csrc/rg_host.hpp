@@ -77,10 +77,15 @@ int wait_stream_sleeping(void* stream, void* ev, bool spin = false);   // spin: 
 int fail(int code, const std::string& msg);
 
 // the long-read flavours of the affine-gap pathwise modes are `mode + 10` (16, 17, 22): the rule, the record and the line of `mode`
-inline bool path_gap_long_mode(int mode) {
-    return mode == RG_MODE_PATHWISE_GAP_LONG || mode == RG_MODE_PATHWISE_GAP_SEMI_LONG || mode == RG_MODE_PATHWISE_GAP_LOCAL_LONG;
+// ... and their both-strands flavours `mode + 20` (26, 27, 32): every pass is one of the long flavour's, so they share its read limit
+inline bool path_gap_strands_mode(int mode) {
+    return mode == RG_MODE_PATHWISE_GAP_STRANDS || mode == RG_MODE_PATHWISE_GAP_SEMI_STRANDS || mode == RG_MODE_PATHWISE_GAP_LOCAL_STRANDS;
 }
-inline int path_gap_base_mode(int mode) { return path_gap_long_mode(mode) ? mode - 10 : mode; }
+inline bool path_gap_long_mode(int mode) {
+    return mode == RG_MODE_PATHWISE_GAP_LONG || mode == RG_MODE_PATHWISE_GAP_SEMI_LONG || mode == RG_MODE_PATHWISE_GAP_LOCAL_LONG ||
+           path_gap_strands_mode(mode);
+}
+inline int path_gap_base_mode(int mode) { return path_gap_strands_mode(mode) ? mode - 20 : path_gap_long_mode(mode) ? mode - 10 : mode; }
 
 // Reads per launch when `n` reads go through launches of at most `maxchunk` (both >= 1): as few launches as that allows, and
 // those even, so no short tail launch.  Every launch but the last takes the result, the last what is left (at least one read).

@@ -6,6 +6,7 @@
 //   -m 6:  gap_score(every path) -> gap_pick -> gap_dirs(picked path) -> gap_trace          (gap/rg_path_gap.hip; -m 7 likewise)
 //   -m 12: the same four steps with the local kernels                                       (gap_local/rg_path_gap_local.hip)
 //   -m 16, 17, 22: the rules of -m 6, 7, 12; a batch with a read over 2047 bases runs the striped kernels    (gap_long/rg_path_gap_long.hip)
+//   -m 26, 27, 32: two passes of -m 16, 17, 22, each planned here by its own longest read (the passes: rg_strand_driver.hip)
 //   -m 8:  sweep(F1: column maxima) -> seed -> thr -> sweep(R: dirs, candidates, column maxima)
 //          -> thr -> sweep(F2: dirs, candidates) -> search -> layer(F) -> layer(R) -> trace
 #include <algorithm>

@@ -83,12 +83,20 @@ static int plan_pathwise_gap(const rg_params& p, const PathPlanInput& in, PathPl
     const bool lng = path_gap_long_mode(p.mode);
     const int base = path_gap_base_mode(p.mode);
     const bool local = base == RG_MODE_PATHWISE_GAP_LOCAL;
-    if (p.amb_mode)
+    if (path_gap_strands_mode(p.mode)) {
+        // -m 26 / -m 27 / -m 32: both strands is what the mode does (bit 2 is redundant); the vote is a rule of the two modes whose
+        // scores can be negative.  Every pass of such a batch is planned here, with the pass's own longest read
+        if (local && p.amb_mode == (RG_AMB_BOTH_STRANDS | RG_AMB_STRAND_VOTE))
+            return fail(RG_ERR_ARG, "RG_AMB_STRAND_VOTE is not available in the local both-strands mode (-m 32): no score of a local pass says "
+                                    "\"hopeless\", so a vote would have no rule for a second pass");
+        if (p.amb_mode != 0 && p.amb_mode != RG_AMB_BOTH_STRANDS && p.amb_mode != (RG_AMB_BOTH_STRANDS | RG_AMB_STRAND_VOTE))
+            return fail(RG_ERR_ARG, "amb_mode must be 0, 4 or 12 in the both-strands affine-gap pathwise modes (-m 26 / -m 27), 0 or 4 in -m 32");
+    } else if (p.amb_mode)
         return fail(RG_ERR_ARG, lng     ? "amb_mode must be 0 in the long-read affine-gap pathwise modes (-m 16 / -m 17 / -m 22): they align the reads as given"
                                 : local ? "amb_mode must be 0 in the local affine-gap pathwise mode (-m 12): it aligns the reads as given"
                                         : "amb_mode must be 0 in the affine-gap pathwise modes (-m 6 / -m 7): they align the reads as given");
     if (lng && in.max_n > 8 * 32 * WAVE - 1)
-        return fail(RG_ERR_ARG, "reads longer than 16383 bases are not supported by the long-read affine-gap pathwise modes (-m 16 / -m 17 / -m 22)");
+        return fail(RG_ERR_ARG, "reads longer than 16383 bases are not supported by the long-read affine-gap pathwise modes (-m 16 / -m 17 / -m 22, and -m 26 / -m 27 / -m 32 on both strands)");
     if (!lng && in.max_n > 32 * WAVE - 1)
         return fail(RG_ERR_ARG, local ? "reads longer than 2047 bases are not supported by the local affine-gap pathwise mode (-m 12)"
                                       : "reads longer than 2047 bases are not supported by the affine-gap pathwise modes (-m 6 / -m 7)");

@@ -1,12 +1,16 @@
-// Batch driver of the pathwise modes (-m 4, 5, 8, 9) above the pipeline of rg_path_driver.hip: one pass over the reads, or, with
-// RG_AMB_BOTH_STRANDS, two passes joined by the small kernels of rg_strand.hip (and opened by those of rg_strand_vote.hip under
-// RG_AMB_STRAND_VOTE):
+// Batch driver of the pathwise modes (-m 4 to 9, 12, 16, 17, 22, and 26, 27, 32) above the pipeline of rg_path_driver.hip: one pass
+// over the reads, or, with RG_AMB_BOTH_STRANDS (-m 4, 5, 8, 9 by the bit; -m 26, 27, 32 always: rg_batch_create sets it on their
+// handles), two passes joined by the small kernels of rg_strand.hip (and opened by those of rg_strand_vote.hip under
+// RG_AMB_STRAND_VOTE, -m 4, 5, 8, 9, 26, 27):
 //
 //   [k_strand_vote -> k_strand_orient ->]  pass A  [-> k_strand_gate -> k_revcomp -> {count, max_len} to the host
 //   -> pass B over the reverse complements of the qualifying reads -> k_strand_merge]
 //
+// -m 32 gates with k_gap_strands_gate (gap_strands/rg_gap_strands.hip) instead: every read that has a record qualifies.  In the
+// affine-gap modes each pass is planned by its own longest read, so one may run the striped kernels and the other the base ones.
 // Every pass is path_driver_run on the same context; the passes differ in their PathJob alone.  The work buffers are owned by
 // PathWork, the strand buffers by the handle (size_strand_buffers).
+#include "gap_strands/rg_gap_strands.hpp"
 #include "rg_batch_impl.hpp"
 
 int size_strand_buffers(rg_batch* b, size_t total) {
@@ -54,7 +58,8 @@ int rg_run_pathwise(rg_batch* b) {
     // the qualifying reads once more, on the other strand, in the same work buffers
     const int recomb = b->p.mode == RG_MODE_RECOMBINATION || b->p.mode == RG_MODE_RECOMBINATION_SEMI ? 1 : 0;
     StrandGateArgs ga{b->d_rec.p, b->in.off, n, recomb, b->d_sidx.p, b->d_rcoff.p, b->d_ssum.p, vote ? b->d_first_rev.p : nullptr};
-    RG_TRY(T.run("k_strand_gate", [&] { return launch_strand_gate(ga, b->stream); }));
+    if (b->p.mode == RG_MODE_PATHWISE_GAP_LOCAL_STRANDS) RG_TRY(T.run("k_gap_strands_gate", [&] { return launch_gap_strands_gate(ga, b->stream); }));
+    else RG_TRY(T.run("k_strand_gate", [&] { return launch_strand_gate(ga, b->stream); }));
     RevcompArgs ra{a.reads, b->in.off, b->d_sidx.p, b->d_rcoff.p, b->d_ssum.p, b->d_rc.p};
     RG_TRY(T.run("k_revcomp", [&] { return launch_revcomp(ra, n, b->stream); }));
     HIPCHK(hipMemcpyAsync(b->h_ssum.p, b->d_ssum.p, 2 * sizeof(int), hipMemcpyDeviceToHost, b->stream));

@@ -3,7 +3,7 @@
 engine on other read lengths, score parameters and path counts, with the sweep kernel that ran and a parity check of a
 few reads against the oracle.  One JSON line per case.
 
-    python tools/region_bench.py [case ...]        cases: c5 x6 m3x5 hoxd70 len1500 p128 len600 gap gap_local gap_long (default: all but the strand cases and the three `gap` cases)
+    python tools/region_bench.py [case ...]        cases: c5 x6 m3x5 hoxd70 len1500 p128 len600 gap gap_local gap_long gap_strands (default: all but the strand cases and the four `gap` cases)
 
 The strand cases (RG_AMB_BOTH_STRANDS, config-5 shape; `reads_per_s` counts SOURCE reads): `both_strands_fwd` — option on, every
 read forward (what the option costs when nothing qualifies: compare with `c5`); `both_strands` — option on, half of the reads
@@ -26,6 +26,14 @@ about 4000 rows — in the same process: both handles are warmed up, then timed 
 median and minimum per mode, the time per COUNTED cell update (rows_k * n per path and read) of both and their ratio, and the time of
 every kernel.  Two reads of the -m 16 batch are checked against the rule (tests/pathwise_gap_rule.py): the printed score is the
 rule's, and the printed CIGAR re-scores to it.  One JSON line.
+
+`gap_strands` (only when named): -m 26 / 27 / 32 beside -m 16 / 17 / 22 OF THE SAME BUILD on the same reads, in one process, in
+alternating rounds — the C4 shape (16 paths on 5 000 rows) at 150 and 1000 bases and one set of 4000-base reads on 16 paths of about
+4000 rows.  Per set: (a) all-forward reads, -m 26 against -m 16 and -m 27 against -m 17 (the price of the gate, the reverse complement
+and the eight-byte read-back); (b) half of the reads reverse-complemented (synth.reverse_complement_share, seed 5678): -m 26 by the
+exact rule and by the vote rule, both relative to (a)'s -m 16; (c) -m 32 against -m 22 on the reads of (b).  Five reads of every
+both-strands batch are checked against the composed rule (tests/pathwise_gap_strands_rule.py; at 4000 bases: strand, score and the
+re-scored CIGAR of two reads).  One JSON line per set.
 
 Every case: TILES tiles of TILE reads through one rg_stream (3 handles), timed after one warm-up tile per handle."""
 import json
@@ -202,9 +210,80 @@ def gap_long_case():
     print(json.dumps(out), flush=True)
 
 
+def gap_strands_case():
+    from recgraph_amd import api, synth
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import pathwise_gap_rule as R
+    import pathwise_gap_strands_rule as S
+    import strand_vote_rule as V
+    rounds = 5
+    for shape, rows, paths, rlen, nreads in (("C4", 5000, 16, 150, 4096), ("C4", 5000, 16, 1000, 2048), ("long", 12000, 16, 4000, 256)):
+        g = synth.haplotype_graph(rows, paths, path_len=rlen, seed=1234)
+        gg = api.Graph.from_gfa_text(g.gfa())
+        fwd = synth.haplotype_reads(g, nreads, length=rlen, seed=900, mosaic_frac=0.0)
+        half, flipped = synth.reverse_complement_share(fwd, 0.5, seed=5678)
+        runs = {"m16_fwd": (16, 0, fwd), "m26_fwd": (26, 0, fwd), "m17_fwd": (17, 0, fwd), "m27_fwd": (27, 0, fwd),
+                "m26_half_exact": (26, 0, half), "m26_half_vote": (26, 12, half), "m22_half": (22, 0, half), "m32_half": (32, 0, half)}
+        batch = {k: api.Batch(gg, rd, api.make_params(m, amb=amb or None)) for k, (m, amb, rd) in runs.items()}
+        times = {k: [] for k in runs}
+        ks = {k: {} for k in runs}
+        for k in runs:
+            batch[k].run()                       # warm-up: code objects, work buffers of both passes
+        for _ in range(rounds):
+            for k in runs:                       # alternating: every run sees the same machine
+                t0 = time.perf_counter()
+                batch[k].run()
+                times[k].append(time.perf_counter() - t0)
+                for name, v in batch[k].kernel_stats().items():
+                    if not name.startswith(("host:", "mem:", "inst:")):
+                        ks[k][name] = ks[k].get(name, 0.0) + v[0] / rounds
+        for k in runs:
+            batch[k].fetch()
+        lnz, prow = R.graph_paths(gg)
+        ids = R.graph_node_ids(gg)
+        kmers = V.kmer_set([g.path_sequence(q) for q in range(paths)])
+        picks = sorted({0, nreads - 1, nreads // 2, nreads // 3, 777 % nreads})
+        ok = True
+        for k, (m, amb, rd) in runs.items():
+            if m not in (26, 27, 32):
+                continue
+            b = batch[k]
+            if rlen <= 1000:
+                for i in picks:
+                    text, status, strand, _ = S.expected(m, rd[i], S.line_fn(m, lnz, prow, ids, "r"), kmers if amb == 12 else None)
+                    ok = ok and b.gaf_text(i, "r", 1) == text and b.status(i) == status
+            elif m == 26:
+                for i in picks[:2]:
+                    f = b.gaf_text(i, "r", 1)[:-1].split("\t")
+                    mm = re.fullmatch(r"([0-9MXID]+), best path: (\d+), score: (-?\d+)", f[12])
+                    chosen = V.rc(rd[i]) if f[4] == "-" else rd[i]
+                    last, lens = R.all_paths_last(lnz, prow, chosen, R.default_scores(), -4, -2, False)
+                    best = max((int(last[q, lens[q]]), -q) for q in range(paths))
+                    ok = ok and mm is not None and (int(mm.group(3)), -int(mm.group(2))) == best and best[0] >= 0
+                    ok = ok and (f[4] == "-") == bool(rd is half and flipped[i])
+                    ok = ok and R.rescore(mm.group(1), f[13], chosen)[:2] == (best[0], len(chosen))
+        med = {k: sorted(times[k])[rounds // 2] for k in runs}
+        out = {"case": "gap_strands", "shape": shape, "rows": gg.rows, "paths": paths, "read_len": rlen, "reads": nreads, "rounds": rounds,
+               "reads_reverse_complemented": int(flipped.sum()), "seed": 5678}
+        for k in runs:
+            b = batch[k]
+            out[k] = {"ms_per_batch_median": round(med[k] * 1e3, 2), "ms_per_batch_min": round(min(times[k]) * 1e3, 2),
+                      "counted_cell_updates": b.cell_updates, "minus_records": sum(1 for i in range(nreads) if b.gaf_text(i, "r", 1).split("\t")[4:5] == ["-"]),
+                      "kernel_ms_per_batch": {name: round(v, 3) for name, v in ks[k].items()}}
+        for num, den in (("m26_fwd", "m16_fwd"), ("m27_fwd", "m17_fwd"), ("m26_half_exact", "m16_fwd"), ("m26_half_vote", "m16_fwd"), ("m32_half", "m22_half")):
+            out["%s_over_%s" % (num, den)] = {"median": round(med[num] / med[den], 3), "min": round(min(times[num]) / min(times[den]), 3)}
+        out["rule_checked"] = "FAILED" if not ok else 5 if rlen <= 1000 else 2
+        print(json.dumps(out), flush=True)
+
+
 def main():
     from recgraph_amd import api, synth
     from oracle import oracle as O
+    if "gap_strands" in sys.argv[1:]:
+        gap_strands_case()
+        sys.argv = [a for a in sys.argv if a != "gap_strands"]
+        if len(sys.argv) == 1:
+            return
     if "gap_long" in sys.argv[1:]:
         gap_long_case()
         sys.argv = [a for a in sys.argv if a != "gap_long"]
