@@ -158,6 +158,25 @@ typedef enum rg_status {
 #define RG_MODE_PATHWISE_GAP_STRANDS 26
 #define RG_MODE_PATHWISE_GAP_SEMI_STRANDS 27
 #define RG_MODE_PATHWISE_GAP_LOCAL_STRANDS 32
+/*
+ * RG_MODE_PATHWISE_GAP_XLONG (56), RG_MODE_PATHWISE_GAP_SEMI_XLONG (57), RG_MODE_PATHWISE_GAP_LOCAL_XLONG (62): modes 6, 7 and 12 for
+ * reads of 1 to 131071 bases (64 column stripes of 2048), numbered `mode + 50`.  THERE IS NO NEW RULE: mode m + 50 is the definition
+ * of mode m with the read length changed.  Recurrence, choice, tie order, traceback, record, line, RG_READ_UNALIGNED (mode 62) and
+ * rg_batch_cell_updates are those of mode m; for every read of at most 16383 bases mode m + 50 returns the bytes, the status and the
+ * score of mode m + 10, hence those of mode m for reads of at most 2047 bases.
+ *   REFUSALS.  gap_open > 0 or gap_ext > 0, any amb_mode bit (both strands at this length is not offered), a read longer than
+ *     131071 bases: RG_ERR_ARG.  (rows of the longest path + longest read) * max(|sc|, |o + e|) >= 2^28: RG_ERR_CAPACITY.  All
+ *     answered by rg_batch_create before a device is needed.
+ *   COST.  A batch whose longest read has at most 2047 bases runs exactly as in mode m.  Otherwise the traceback keeps the direction
+ *     words of ONE stripe per read, (rows of the longest path + 1) * 1 KiB, and per row of the chosen path two integers for each
+ *     stripe but the last: the walk only ever moves left, so each stripe's words are rebuilt from its checkpoint when the walk
+ *     enters it, once.  rg_batch_cell_updates_performed counts the score pass, the checkpoint pass (rows * n per read) and the
+ *     rebuilt cells (rows rebuilt * the stripe's columns that belong to the read).  Modes 16, 17, 22, 26, 27 and 32 keep their
+ *     limit of 16383 bases and their kernels.
+ */
+#define RG_MODE_PATHWISE_GAP_XLONG 56
+#define RG_MODE_PATHWISE_GAP_SEMI_XLONG 57
+#define RG_MODE_PATHWISE_GAP_LOCAL_XLONG 62
 
 /*
  * Scoring and banding parameters.  Replaces the HashMap<(char,char),i32|f32> score matrix arguments

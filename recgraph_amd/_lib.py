@@ -52,6 +52,10 @@ MODE_PATHWISE_GAP_LOCAL_LONG = 22
 MODE_PATHWISE_GAP_STRANDS = 26
 MODE_PATHWISE_GAP_SEMI_STRANDS = 27
 MODE_PATHWISE_GAP_LOCAL_STRANDS = 32
+# RG_MODE_PATHWISE_GAP_XLONG / _SEMI_XLONG / _LOCAL_XLONG: modes 6, 7, 12 for reads of up to 131071 bases (`mode + 50`)
+MODE_PATHWISE_GAP_XLONG = 56
+MODE_PATHWISE_GAP_SEMI_XLONG = 57
+MODE_PATHWISE_GAP_LOCAL_XLONG = 62
 READ_UNALIGNED = 16     # RG_READ_UNALIGNED: status bit of that mode — the read has no local alignment, and no record
 
 

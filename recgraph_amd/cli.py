@@ -47,7 +47,7 @@ def build_parser():
     p.add_argument("-o", "--out_file", default="standard output")
     p.add_argument("-m", "--aln-mode", type=int, default=0, dest="alignment_mode",
                    help="0 to 9 as in the reference; 12: local affine-gap pathwise; 16, 17, 22: modes 6, 7, 12 for reads of up to 16383 bases; "
-                        "26, 27, 32: those on both strands (--strand-vote: 26 and 27 only)")
+                        "26, 27, 32: those on both strands (--strand-vote: 26 and 27 only); 56, 57, 62: modes 6, 7, 12 for reads of up to 131071 bases")
     p.add_argument("-M", "--match", type=int, default=2, dest="match_score")
     p.add_argument("-X", "--mismatch", type=int, default=4, dest="mismatch_score")
     p.add_argument("-t", "--matrix", default="none")
@@ -87,7 +87,8 @@ def main(argv=None):
     tp = mark("import", t0)
     # 16, 17, 22: the long-read flavours of 6, 7, 12 (reads of up to 16383 bases), admitted beside the modes the message names
     # 26, 27, 32: the same three on both strands; --both-strands is redundant there, --strand-vote the vote rule of 26 and 27
-    if a.alignment_mode not in (0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 12, 16, 17, 22, 26, 27, 32):
+    # 56, 57, 62: 6, 7, 12 for reads of up to 131071 bases, as given
+    if a.alignment_mode not in (0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 12, 16, 17, 22, 26, 27, 32, 56, 57, 62):
         raise SystemExit("Alignment mode must be in [0..9], or 12")   # main.rs:315-317; 12: local affine-gap pathwise, this project's own
     if a.alignment_mode in (6, 7) and (a.both_strands or a.strand_vote):
         raise SystemExit("--both-strands / --strand-vote are not available in modes 6 and 7: they align the reads as given")
@@ -95,6 +96,8 @@ def main(argv=None):
         raise SystemExit("--both-strands / --strand-vote are not available in mode 12: it aligns the reads as given")
     if a.alignment_mode in (16, 17, 22) and (a.both_strands or a.strand_vote):
         raise SystemExit("--both-strands / --strand-vote are not available in modes 16, 17 and 22: they align the reads as given")
+    if a.alignment_mode in (56, 57, 62) and (a.both_strands or a.strand_vote):
+        raise SystemExit("--both-strands / --strand-vote are not available in modes 56, 57 and 62: they align the reads as given")
     if a.alignment_mode == 32 and a.strand_vote:
         raise SystemExit("--strand-vote is not available in mode 32: no score of a local pass says \"hopeless\", so a vote would have no rule for a second pass")
     amb = a.amb_strand == "true" and a.alignment_mode in (0, 1, 2, 3)     # modes 4+ ignore -s (main.rs:254-313)
@@ -114,7 +117,8 @@ def main(argv=None):
             4: api.MODE_PATHWISE, 5: api.MODE_PATHWISE_SEMI, 6: api.MODE_PATHWISE_GAP, 7: api.MODE_PATHWISE_GAP_SEMI, 8: api.MODE_RECOMBINATION,
             9: api.MODE_RECOMBINATION_SEMI, 12: api.MODE_PATHWISE_GAP_LOCAL, 16: api.MODE_PATHWISE_GAP_LONG,
             17: api.MODE_PATHWISE_GAP_SEMI_LONG, 22: api.MODE_PATHWISE_GAP_LOCAL_LONG, 26: api.MODE_PATHWISE_GAP_STRANDS,
-            27: api.MODE_PATHWISE_GAP_SEMI_STRANDS, 32: api.MODE_PATHWISE_GAP_LOCAL_STRANDS}[a.alignment_mode]
+            27: api.MODE_PATHWISE_GAP_SEMI_STRANDS, 32: api.MODE_PATHWISE_GAP_LOCAL_STRANDS, 56: api.MODE_PATHWISE_GAP_XLONG,
+            57: api.MODE_PATHWISE_GAP_SEMI_XLONG, 62: api.MODE_PATHWISE_GAP_LOCAL_XLONG}[a.alignment_mode]
     kw = dict(score_matrix=scores, o=-a.gap_open, e=-a.gap_extension, b=float(a.extra_b), f=a.extra_f,
               R=a.base_rec_cost, r=a.multi_rec_cost, B=a.rec_band_width)
     to_file = a.out_file != "standard output"
@@ -129,7 +133,7 @@ def main(argv=None):
         records, numbers = [], []
         # warning lines are println!'d by the exec functions whatever -o says; only the record goes through write_gaf
         for k, t in enumerate(texts):
-            if not t and a.alignment_mode in (12, 22, 32):       # a read without a local alignment (RG_READ_UNALIGNED) has no record
+            if not t and a.alignment_mode in (12, 22, 32, 62):       # a read without a local alignment (RG_READ_UNALIGNED) has no record
                 continue
             lines = t.split("\n")[:-1]
             sys.stdout.write("".join(ln + "\n" for ln in lines[:-1]))

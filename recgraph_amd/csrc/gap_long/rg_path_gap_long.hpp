@@ -21,8 +21,8 @@ struct GapLongArgs {
     int* dbnd;                    // direction pass, [reads][2][rows1]: the same two values for the picked path
 };
 
-// kind: GapLongKind (16: global, 17: semi, 22: local)
-const char* launch_gap_score_long(const GapLongArgs& a, int nreads, int kind, hipStream_t s);
+// kind: GapLongKind (16: global, 17: semi, 22: local); max_stripes: the host-side cap on a.S, lifted by the plan of gap_xlong/ alone
+const char* launch_gap_score_long(const GapLongArgs& a, int nreads, int kind, hipStream_t s, int max_stripes = GAP_LONG_MAX_STRIPES);
 const char* launch_gap_dirs_long(const GapLongArgs& a, int nreads, int kind, hipStream_t s);
 const char* launch_gap_trace_long(const GapLongArgs& a, int nreads, int kind, hipStream_t s);
 

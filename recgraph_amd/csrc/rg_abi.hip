@@ -359,7 +359,7 @@ int32_t rg_batch_create(const rg_graph* gc, const rg_params* p, const char* read
     if (!gc || !p || !reads || !read_off || !out || nreads < 1) return fail(RG_ERR_ARG, "null/empty argument");
     const rg_graph* g = gc;
     const int mode = p->mode;
-    const int gbase = path_gap_base_mode(mode);       // (-m 16 / -m 17 / -m 22: the long-read flavours of 6, 7, 12; -m 26 / -m 27 / -m 32: those on both strands)
+    const int gbase = path_gap_base_mode(mode);       // (-m 16 / -m 17 / -m 22: the long-read flavours of 6, 7, 12; -m 26 / -m 27 / -m 32: those on both strands; -m 56 / -m 57 / -m 62: reads of up to 131071 bases)
     const bool path_gap = gbase == RG_MODE_PATHWISE_GAP || gbase == RG_MODE_PATHWISE_GAP_SEMI || gbase == RG_MODE_PATHWISE_GAP_LOCAL;
     if (!(is_poa(mode) || mode == RG_MODE_PATHWISE || mode == RG_MODE_RECOMBINATION || mode == RG_MODE_PATHWISE_SEMI ||
           mode == RG_MODE_RECOMBINATION_SEMI || path_gap))
@@ -386,7 +386,7 @@ int32_t rg_batch_create(const rg_graph* gc, const rg_params* p, const char* read
                                 "rg_stream_opts.amb_strand (`-s true`, main.rs:82,132,188,229)");
     if ((p->amb_mode & 3) && !is_poa(mode)) return fail(RG_ERR_ARG, "amb_mode bits 0 and 1 apply to the POA modes only (main.rs:82,132,188,229)");
     if (path_gap) {
-        // what the plan of -m 6 / -m 7 / -m 12 refuses (amb_mode bits, reads over 2047 bases (16383 in the long modes), scores outside the i32 budget) is host
+        // what the plan of -m 6 / -m 7 / -m 12 refuses (amb_mode bits, reads over 2047 bases (16383 in the long modes, 131071 in -m 56 / -m 57 / -m 62), scores outside the i32 budget) is host
         // arithmetic on the longest read: answered here, before a device is needed
         int64_t longest = 0;
         for (int64_t r = 0; r < nreads; ++r) longest = std::max<int64_t>(longest, read_off[r + 1] - read_off[r]);

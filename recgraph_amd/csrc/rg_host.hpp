@@ -85,7 +85,14 @@ inline bool path_gap_long_mode(int mode) {
     return mode == RG_MODE_PATHWISE_GAP_LONG || mode == RG_MODE_PATHWISE_GAP_SEMI_LONG || mode == RG_MODE_PATHWISE_GAP_LOCAL_LONG ||
            path_gap_strands_mode(mode);
 }
-inline int path_gap_base_mode(int mode) { return path_gap_strands_mode(mode) ? mode - 20 : path_gap_long_mode(mode) ? mode - 10 : mode; }
+// ... and the flavours for reads of up to 131071 bases `mode + 50` (56, 57, 62): the long flavour's rule and bytes once more, with a
+// traceback that keeps one stripe of direction words (gap_xlong/); no amb_mode bit
+inline bool path_gap_xlong_mode(int mode) {
+    return mode == RG_MODE_PATHWISE_GAP_XLONG || mode == RG_MODE_PATHWISE_GAP_SEMI_XLONG || mode == RG_MODE_PATHWISE_GAP_LOCAL_XLONG;
+}
+inline int path_gap_base_mode(int mode) {
+    return path_gap_xlong_mode(mode) ? mode - 50 : path_gap_strands_mode(mode) ? mode - 20 : path_gap_long_mode(mode) ? mode - 10 : mode;
+}
 
 // Reads per launch when `n` reads go through launches of at most `maxchunk` (both >= 1): as few launches as that allows, and
 // those even, so no short tail launch.  Every launch but the last takes the result, the last what is left (at least one read).

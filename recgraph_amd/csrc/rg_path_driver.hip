@@ -6,6 +6,7 @@
 //   -m 6:  gap_score(every path) -> gap_pick -> gap_dirs(picked path) -> gap_trace          (gap/rg_path_gap.hip; -m 7 likewise)
 //   -m 12: the same four steps with the local kernels                                       (gap_local/rg_path_gap_local.hip)
 //   -m 16, 17, 22: the rules of -m 6, 7, 12; a batch with a read over 2047 bases runs the striped kernels    (gap_long/rg_path_gap_long.hip)
+//   -m 56, 57, 62: gap_score_long -> gap_pick -> gap_ckpt_long -> (gap_redo_long -> gap_walk_long) per stripe, last to first     (gap_xlong/rg_path_gap_xlong.hip)
 //   -m 26, 27, 32: two passes of -m 16, 17, 22, each planned here by its own longest read (the passes: rg_strand_driver.hip)
 //   -m 8:  sweep(F1: column maxima) -> seed -> thr -> sweep(R: dirs, candidates, column maxima)
 //          -> thr -> sweep(F2: dirs, candidates) -> search -> layer(F) -> layer(R) -> trace
@@ -18,6 +19,7 @@
 #include "gap/rg_path_gap.hpp"
 #include "gap_local/rg_path_gap_local.hpp"
 #include "gap_long/rg_path_gap_long.hpp"
+#include "gap_xlong/rg_path_gap_xlong.hpp"
 #include "rg_kernel_timer.hpp"
 #include "rg_path_kernels.hpp"
 #include "rg_path_plan.hpp"
@@ -31,6 +33,8 @@ struct PathWorkImpl {
     DevBuf<int> roll, mf, wr, mfarg, wrarg, thr, flayer, rlayer;
     DevBuf<uint32_t> fdirs, rdirs, gdirs;
     DevBuf<int> gbnd, gdbnd;            // -m 16 / 17 / 22: the stripe boundaries of the score pass and of the direction pass
+    DevBuf<int> gckpt;                  // -m 56 / 57 / 62: per stripe but the last, what it leaves to its right neighbour (picked path)
+    DevBuf<GapWalkState> gwalk;         // ... and where each read's walk stands between two rounds
     DevBuf<Cand> fcand, rcand;
     DevBuf<unsigned> nf, nr, ridx, nrec, nrrec;
     DevBuf<int> frec, rrec;
@@ -155,6 +159,10 @@ int Run::alloc_chunk(bool* oom) {
     int rc;
     if (plan.gap) {
         if ((rc = w.state.alloc(n, oom)) || (rc = w.gdirs.alloc(n * (size_t)plan.gdirs_stride, oom))) return rc;
+        if (plan.gap_xlong) {
+            if ((rc = w.gbnd.alloc(n * (size_t)plan.gbnd_stride, oom)) || (rc = w.gckpt.alloc(n * (size_t)plan.gckpt_stride, oom)) || (rc = w.gwalk.alloc(n, oom))) return rc;
+            return RG_OK;
+        }
         if (plan.nwv > 1 && ((rc = w.gbnd.alloc(n * (size_t)plan.gbnd_stride, oom)) || (rc = w.gdbnd.alloc(n * (size_t)plan.gdbnd_stride, oom)))) return rc;
         return RG_OK;
     }
@@ -251,6 +259,24 @@ int Run::enqueue_pathwise_gap() {
         la.g = ga; la.S = plan.nwv; la.rows1 = h.max_path_rows + 1;
         la.bnd = w.gbnd.p; la.bnd_stride = plan.gbnd_stride; la.dbnd = w.gdbnd.p;
         const int kind = plan.local ? GAP_LONG_LOCAL : semi ? GAP_LONG_SEMI : GAP_LONG_GLOBAL;
+        if (plan.gap_xlong) {
+            // one stripe of direction words: checkpoints first, then per stripe, last to first, the rebuild and the walk (no read-back
+            // in between: a read whose walk is elsewhere returns at once).  The score pass is the long modes', its stripe cap lifted
+            static_assert(sizeof(GapWalkState) == 32, "the plan counts 32 bytes of walk state per read");
+            GapXLongArgs xa;
+            memset(&xa, 0, sizeof xa);
+            la.dbnd = nullptr;
+            xa.l = la; xa.ckpt = w.gckpt.p; xa.ckpt_stride = plan.gckpt_stride; xa.walk = w.gwalk.p;
+            RG_TRY(T.run("k_gap_score_long", [&] { return launch_gap_score_long(la, chunk, kind, stream, GAP_XLONG_MAX_STRIPES); }));
+            if (plan.local) RG_TRY(T.run("k_gap_pick_local", [&] { return launch_gap_pick_local(ga, chunk, plan.nwv * C, stream); }));
+            else RG_TRY(T.run("k_gap_pick", [&] { return launch_gap_pick(ga, chunk, plan.nwv * C, semi, stream); }));
+            RG_TRY(T.run("k_gap_ckpt_long", [&] { return launch_gap_ckpt_long(xa, chunk, kind, stream); }));
+            for (int round = plan.nwv - 1; round >= 0; --round) {
+                RG_TRY(T.run("k_gap_redo_long", [&] { return launch_gap_redo_long(xa, chunk, kind, round, stream); }));
+                RG_TRY(T.run(plan.local ? "k_gap_walk_local_long" : "k_gap_walk_long", [&] { return launch_gap_walk_long(xa, chunk, kind, round, stream); }));
+            }
+            return read_back();
+        }
         RG_TRY(T.run("k_gap_score_long", [&] { return launch_gap_score_long(la, chunk, kind, stream); }));
         if (plan.local) RG_TRY(T.run("k_gap_pick_local", [&] { return launch_gap_pick_local(ga, chunk, plan.nwv * C, stream); }));
         else RG_TRY(T.run("k_gap_pick", [&] { return launch_gap_pick(ga, chunk, plan.nwv * C, semi, stream); }));

@@ -77,10 +77,11 @@ bool sweep16_admissible(const DevScores& sc, int max_path_rows, int max_n, int C
 }
 
 // -m 6 / -m 7 / -m 12: one wave per (read, path) keeps H and Y of the current row in registers, C columns per lane (n + 1 <= 64 C), so a
-// read must fit one wave (-m 16 / -m 17 / -m 22: up to 8 column stripes of 2048, walked by that one wave, gap_long/rg_path_gap_long.hip); the only HBM work buffer beside ReadState holds the 4-bit directions of the picked path.
+// read must fit one wave (-m 16 / -m 17 / -m 22: up to 8 column stripes of 2048, walked by that one wave, gap_long/rg_path_gap_long.hip; -m 56 / -m 57 / -m 62: up to 64, gap_xlong/); the only HBM work buffer beside ReadState holds the 4-bit directions of the picked path.
 static int plan_pathwise_gap(const rg_params& p, const PathPlanInput& in, PathPlan& o) {
     if (p.gap_open > 0 || p.gap_ext > 0) return fail(RG_ERR_ARG, "gap penalties must be <= 0");
     const bool lng = path_gap_long_mode(p.mode);
+    const bool xlng = path_gap_xlong_mode(p.mode);
     const int base = path_gap_base_mode(p.mode);
     const bool local = base == RG_MODE_PATHWISE_GAP_LOCAL;
     if (path_gap_strands_mode(p.mode)) {
@@ -92,12 +93,15 @@ static int plan_pathwise_gap(const rg_params& p, const PathPlanInput& in, PathPl
         if (p.amb_mode != 0 && p.amb_mode != RG_AMB_BOTH_STRANDS && p.amb_mode != (RG_AMB_BOTH_STRANDS | RG_AMB_STRAND_VOTE))
             return fail(RG_ERR_ARG, "amb_mode must be 0, 4 or 12 in the both-strands affine-gap pathwise modes (-m 26 / -m 27), 0 or 4 in -m 32");
     } else if (p.amb_mode)
-        return fail(RG_ERR_ARG, lng     ? "amb_mode must be 0 in the long-read affine-gap pathwise modes (-m 16 / -m 17 / -m 22): they align the reads as given"
+        return fail(RG_ERR_ARG, xlng    ? "amb_mode must be 0 in the affine-gap pathwise modes for reads of up to 131071 bases (-m 56 / -m 57 / -m 62): they align the reads as given"
+                                : lng   ? "amb_mode must be 0 in the long-read affine-gap pathwise modes (-m 16 / -m 17 / -m 22): they align the reads as given"
                                 : local ? "amb_mode must be 0 in the local affine-gap pathwise mode (-m 12): it aligns the reads as given"
                                         : "amb_mode must be 0 in the affine-gap pathwise modes (-m 6 / -m 7): they align the reads as given");
+    if (xlng && in.max_n > 64 * 32 * WAVE - 1)
+        return fail(RG_ERR_ARG, "reads longer than 131071 bases are not supported by the affine-gap pathwise modes -m 56 / -m 57 / -m 62");
     if (lng && in.max_n > 8 * 32 * WAVE - 1)
         return fail(RG_ERR_ARG, "reads longer than 16383 bases are not supported by the long-read affine-gap pathwise modes (-m 16 / -m 17 / -m 22, and -m 26 / -m 27 / -m 32 on both strands)");
-    if (!lng && in.max_n > 32 * WAVE - 1)
+    if (!lng && !xlng && in.max_n > 32 * WAVE - 1)
         return fail(RG_ERR_ARG, local ? "reads longer than 2047 bases are not supported by the local affine-gap pathwise mode (-m 12)"
                                       : "reads longer than 2047 bases are not supported by the affine-gap pathwise modes (-m 6 / -m 7)");
     // every value of H, X, Y is a sum of at most (rows + n) steps of at most max(|sc|, |o + e|) each: kept inside +-2^28, so that
@@ -121,7 +125,17 @@ static int plan_pathwise_gap(const rg_params& p, const PathPlanInput& in, PathPl
     o.gap_words = std::max(1, C / 8);
     o.gdirs_stride = (long long)o.nwv * (in.max_path_rows + 1) * o.gap_words * WAVE;
     o.per_read = (size_t)o.gdirs_stride * 4 + sizeof(ReadState);
-    if (o.nwv > 1) {
+    if (o.nwv > 1 && xlng) {
+        // -m 56 / -m 57 / -m 62 (gap_xlong/rg_path_gap_xlong.hip), whatever the stripe count: direction words of ONE stripe, a checkpoint
+        // slot of two ints per row for every stripe but the last, the score pass's boundary buffer and the walk state
+        const long long rows1 = in.max_path_rows + 1;
+        o.gap_xlong = true;
+        o.gdirs_stride = rows1 * o.gap_words * WAVE;
+        o.gbnd_stride = 2ll * rows1 * in.P;
+        o.gckpt_stride = (long long)(o.nwv - 1) * 2 * rows1;
+        o.gwalk_bytes = 32;
+        o.per_read = (size_t)o.gdirs_stride * 4 + (size_t)(o.gbnd_stride + o.gckpt_stride) * 4 + o.gwalk_bytes + sizeof(ReadState);
+    } else if (o.nwv > 1) {
         o.gbnd_stride = 2ll * (in.max_path_rows + 1) * in.P;
         o.gdbnd_stride = 2ll * (in.max_path_rows + 1);
         o.per_read += (size_t)(o.gbnd_stride + o.gdbnd_stride) * 4;

@@ -66,6 +66,12 @@ struct PathPlan {
     // base mode's: C = 32, nwv = S = ceil((max_n + 1) / 2048) column stripes walked by ONE wave, gdirs_stride = S * (rows + 1) * 4 * 64,
     // and two boundary buffers (ints per read): 2 * (rows + 1) per path for the score pass, 2 * (rows + 1) for the direction pass
     long long gbnd_stride, gdbnd_stride;
+    // -m 56 / -m 57 / -m 62 (gap_xlong/rg_path_gap_xlong.hip) when the longest read has more than 2047 bases — otherwise the plan IS the
+    // base mode's: C = 32, nwv = S = ceil((max_n + 1) / 2048) <= 64, gdirs_stride = (rows + 1) * 4 * 64 (ONE stripe), gbnd_stride as
+    // above, gdbnd_stride = 0, and (ints per read) (S - 1) * 2 * (rows + 1) of checkpoints; gwalk_bytes: the walk state of a read
+    bool gap_xlong;
+    long long gckpt_stride;
+    size_t gwalk_bytes;
 
     // ... with candidate lists of fcap / rcap entries and record lists of frec_cap / rrec_cap records
     size_t per_read_all(unsigned fcap_, unsigned rcap_, unsigned frec_cap_, unsigned rrec_cap_) const {

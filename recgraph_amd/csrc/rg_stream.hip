@@ -102,7 +102,8 @@ int usable_cpus() {
 
 bool mode_is_pathwise(int mode) {
     return mode == RG_MODE_PATHWISE || mode == RG_MODE_RECOMBINATION || mode == RG_MODE_PATHWISE_SEMI || mode == RG_MODE_RECOMBINATION_SEMI ||
-           mode == RG_MODE_PATHWISE_GAP || mode == RG_MODE_PATHWISE_GAP_SEMI || mode == RG_MODE_PATHWISE_GAP_LOCAL || path_gap_long_mode(mode);
+           mode == RG_MODE_PATHWISE_GAP || mode == RG_MODE_PATHWISE_GAP_SEMI || mode == RG_MODE_PATHWISE_GAP_LOCAL || path_gap_long_mode(mode) ||
+           path_gap_xlong_mode(mode);
 }
 bool mode_is_local(int mode) { return mode == RG_MODE_LOCAL_POA || mode == RG_MODE_LOCAL_POA_SCALAR || mode == RG_MODE_GAP_LOCAL_POA; }
 

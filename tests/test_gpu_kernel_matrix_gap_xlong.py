@@ -1,0 +1,61 @@
+"""GPU: every instantiation of the one-stripe traceback kernels (tests/kernel_matrix_gap_xlong.py) ran and was right.
+
+One test per entry: the entry's case is aligned with the launch log on, every read is checked against the rule (check_long of
+tests/test_gpu_pathwise_gap_long.py: whole line, re-scored CIGAR, status), and EVERY batch of the case — one per length — must have
+launched the entry's instantiation.  Cases that several entries share run once."""
+import pytest
+
+import kernel_matrix_gap_xlong as KX
+import pathwise_gap_rule as R
+from test_gpu_pathwise_gap_long import check_long
+
+pytestmark = pytest.mark.gpu
+_RESULTS = {}
+
+
+def _run_case(cid):
+    if cid in _RESULTS:
+        return _RESULTS[cid]
+    from recgraph_amd import api
+    case = KX.CASES[cid]
+    g, batches = KX.build(case)
+    gg = api.Graph.from_gfa_text(g.gfa())
+    lnz, rows = R.graph_paths(gg)
+    graph = (g, gg, lnz, rows, R.graph_node_ids(gg))
+    per_batch, coarse = [], set()
+    try:
+        api.set_option("launch_log", 1)
+        for reads in batches:
+            b = api.Batch(gg, reads, api.make_params(case.mode, **case.kw))
+            b.run()
+            b.fetch()
+            status = [b.status(i) for i in range(len(reads))]
+            assert status == [0] * len(reads), cid
+            texts = [b.gaf_text(i, "r%d" % i, i + 1) for i in range(len(reads))]
+            stats = b.kernel_stats()
+            per_batch.append({k[5:]: v[1] for k, v in stats.items() if k.startswith("inst:")})
+            coarse |= {k for k in stats if not k.startswith("inst:")}
+            api.set_option("launch_log", 0)
+            check_long(graph, reads, case.mode - 40, texts=texts, status=status, **case.kw)
+            api.set_option("launch_log", 1)
+    finally:
+        api.set_option("launch_log", 0)
+    _RESULTS[cid] = (per_batch, coarse)
+    return _RESULTS[cid]
+
+
+@pytest.mark.parametrize("name", sorted(KX.MATRIX))
+def test_instantiation_ran_and_matched_the_rule(name):
+    cid = KX.MATRIX[name]
+    mode = KX.CASES[cid].mode
+    kind = (56, 57, 62).index(mode)
+    per_batch, coarse = _run_case(cid)
+    assert len(per_batch) == len(KX.CASES[cid].batches)
+    for b, longest in zip(per_batch, KX.CASES[cid].batches):
+        assert b.get(name, 0) >= 1, (name, cid, sorted(b.items()))
+        # nothing but the score pass of this kind, the base mode's pick and the new kernels of this kind
+        assert set(b) == {KX.SCORE[mode], KX.PICK[mode], "rg::k_gap_ckpt_long<%d>" % kind, "rg::k_gap_redo_long<%d>" % kind, KX.WALK[mode]}, sorted(b)
+        # one rebuild and one walk launch per stripe of the batch's longest read, one checkpoint pass
+        stripes = (longest + 2048) // 2048
+        assert (b["rg::k_gap_ckpt_long<%d>" % kind], b["rg::k_gap_redo_long<%d>" % kind], b[KX.WALK[mode]]) == (1, stripes, stripes), sorted(b.items())
+    assert {"k_gap_score_long", "k_gap_ckpt_long", "k_gap_redo_long"} <= coarse and not {"k_gap_dirs_long", "k_gap_trace_long", "k_gap_trace_local_long"} & coarse

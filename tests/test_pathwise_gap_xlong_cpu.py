@@ -1,0 +1,157 @@
+"""CPU: the affine-gap pathwise modes for reads of up to 131071 bases (-m 56 / -m 57 / -m 62 = modes 6 / 7 / 12, `mode + 50`): admission
+and refusals of rg_batch_create (answered before a device is needed), the plan's routes (tests/c/gap_xlong_plan_check.cpp), the API
+and CLI surface and the registers of the new kernels."""
+import inspect
+import os
+import subprocess
+import sys
+
+import pytest
+
+from test_pathwise_gap_cpu import TWO_BUBBLES, _create, _no_device
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+XLONG = {56: 6, 57: 7, 62: 12}
+KERNELS = (["rg::k_gap_ckpt_long<%d>" % k for k in range(3)] + ["rg::k_gap_redo_long<%d>" % k for k in range(3)] +
+           ["rg::k_gap_walk_long", "rg::k_gap_walk_local_long"])
+
+
+def test_the_constants():
+    from recgraph_amd import api
+    assert (api.MODE_PATHWISE_GAP_XLONG, api.MODE_PATHWISE_GAP_SEMI_XLONG, api.MODE_PATHWISE_GAP_LOCAL_XLONG) == (56, 57, 62)
+    assert (api._lib.MODE_PATHWISE_GAP_XLONG, api._lib.MODE_PATHWISE_GAP_SEMI_XLONG, api._lib.MODE_PATHWISE_GAP_LOCAL_XLONG) == (56, 57, 62)
+    assert (api.MODE_PATHWISE_GAP + 50, api.MODE_PATHWISE_GAP_SEMI + 50, api.MODE_PATHWISE_GAP_LOCAL + 50) == (56, 57, 62)
+    assert api.PATHWISE_GAP_XLONG_MODES == (56, 57, 62)
+    assert not set(api.PATHWISE_GAP_XLONG_MODES) & (set(api.PATHWISE_GAP_MODES) | set(api.PATHWISE_GAP_STRANDS_MODES))
+    header = open(os.path.join(ROOT, "include", "recgraph_hip.h")).read()
+    for name, v in (("RG_MODE_PATHWISE_GAP_XLONG", 56), ("RG_MODE_PATHWISE_GAP_SEMI_XLONG", 57), ("RG_MODE_PATHWISE_GAP_LOCAL_XLONG", 62)):
+        assert "#define %s %d\n" % (name, v) in header
+    ffi = open(os.path.join(ROOT, "shim", "src", "hip_ffi.rs")).read()
+    assert "pub const RG_MODE_PATHWISE_GAP_LOCAL_XLONG: i32 = 62;" in ffi
+
+
+@pytest.mark.parametrize("mode", sorted(XLONG))
+def test_the_modes_are_admitted_and_refuse_before_a_device_is_needed(mode):
+    ok = -3 if _no_device() else 0
+    rc, msg = _create(TWO_BUBBLES, ["ATGCT"], mode)
+    # (on the parent commit: RG_ERR_ARG "unsupported mode")
+    assert rc == ok, (rc, msg)
+    # both sides of the limits of the base modes and of the long modes, and the new limit itself
+    for n in (2047, 2048, 16383, 16384, 131071):
+        rc, msg = _create(TWO_BUBBLES, ["A" * n], mode)
+        assert rc == ok, (n, rc, msg)
+    rc, msg = _create(TWO_BUBBLES, ["ATG", "A" * 131072], mode)
+    assert rc == -1 and "131071" in msg, (rc, msg)
+    assert _create(TWO_BUBBLES, ["ATGCT"], mode, o=1)[0] == -1
+    assert _create(TWO_BUBBLES, ["ATGCT"], mode, e=1)[0] == -1
+    assert _create(TWO_BUBBLES, ["A" * 50000], mode, o=1)[0] == -1
+    assert _create(TWO_BUBBLES, ["A" * 50000], mode, e=1)[0] == -1
+    for amb in (1, 2, 4, 8, 12):
+        assert _create(TWO_BUBBLES, ["ATGCT"], mode, amb=amb)[0] == -1, amb
+        assert _create(TWO_BUBBLES, ["A" * 30000], mode, amb=amb)[0] == -1, amb
+    # the two capacity edges: (5 rows + 5 bases) * 2^25 >= 2^28, and (5 rows + 131067 bases) * 2^11 = 2^28
+    assert _create(TWO_BUBBLES, ["ATGCT"], mode, match=1 << 25)[0] == -5
+    assert _create(TWO_BUBBLES, ["ATGCT"], mode, o=-(1 << 25))[0] == -5
+    assert _create(TWO_BUBBLES, ["A" * 131067], mode, match=1 << 11)[0] == -5
+    assert _create(TWO_BUBBLES, ["A" * 131066], mode, match=1 << 11)[0] == ok
+
+
+def test_the_earlier_modes_keep_their_limits_and_the_gaps_between_the_modes_stay_closed():
+    for mode in (6, 7, 12):
+        rc, msg = _create(TWO_BUBBLES, ["A" * 2048], mode)
+        assert rc == -1 and "2047" in msg, (mode, rc, msg)
+    for mode in (16, 17, 22, 26, 27, 32):
+        rc, msg = _create(TWO_BUBBLES, ["A" * 16384], mode)
+        assert rc == -1 and "16383" in msg, (mode, rc, msg)
+    for other in (36, 37, 42, 46, 47, 52, 50, 51, 53, 54, 55, 58, 59, 60, 61, 63, 66, 67, 72):
+        rc, msg = _create(TWO_BUBBLES, ["ATGCT"], other)
+        assert rc == -1 and "unsupported mode" in msg, (other, rc, msg)
+
+
+def test_no_new_entry_point():
+    from recgraph_amd import _lib
+    assert len(_lib.SYMBOLS) == 63
+    exports = open(os.path.join(ROOT, "recgraph_amd", "csrc", "exports.map")).read()
+    assert "xlong" not in exports and "walk" not in exports
+
+
+def test_the_api_refuses_both_strands_and_the_wrappers_take_the_modes():
+    from recgraph_amd import api
+    g = api.Graph.from_gfa_text(TWO_BUBBLES)
+    for mode in sorted(XLONG):
+        for fn in (api.align_batch, api.align_batch_multi, api.align_stream):
+            for kw in ({"both_strands": True}, {"strand_vote": True}):
+                with pytest.raises(api._lib.RecGraphError) as ex:
+                    fn(g, ["ATG"], mode=mode, **kw)
+                assert "56, 57, 62" in str(ex.value)
+    for fn in (api.pathwise_alignment_gap_exec, api.pathwise_alignment_gap_semi_exec, api.pathwise_alignment_gap_local_exec):
+        par = inspect.signature(fn).parameters
+        assert par["very_long_reads"].default is False and par["long_reads"].default is False and par["both_strands"].default is False
+        with pytest.raises(api._lib.RecGraphError) as ex:
+            fn(list("$ATG"), g, very_long_reads=True, both_strands=True)
+        assert "very_long_reads" in str(ex.value)
+    assert inspect.signature(api._gap_exec_mode).parameters["very_long_reads"].default is False
+    assert [api._gap_exec_mode(m, False, False, True) for m in (6, 7, 12)] == [56, 57, 62]
+    assert [api._gap_exec_mode(m, True, False, True) for m in (6, 7, 12)] == [56, 57, 62]
+    assert [api._gap_exec_mode(m, True, False) for m in (6, 7, 12)] == [16, 17, 22]
+    assert [api._gap_exec_mode(m, False, True) for m in (6, 7, 12)] == [26, 27, 32]
+    with pytest.raises(api._lib.RecGraphError):
+        api._gap_exec_mode(6, True, True, True)
+
+
+def test_the_cli_takes_the_modes():
+    from recgraph_amd import cli
+    for m in sorted(XLONG):
+        a = cli.build_parser().parse_args(["reads.fa", "graph.gfa", "-m", str(m), "-O", "6", "-E", "1"])
+        assert a.alignment_mode == m and (a.gap_open, a.gap_extension) == (6, 1)
+        for flag in ("--both-strands", "--strand-vote"):
+            with pytest.raises(SystemExit) as ex:
+                cli.main(["reads.fa", "graph.gfa", "-m", str(m), flag])
+            assert "56, 57 and 62" in str(ex.value)
+        # admitted: the run gets as far as the graph file
+        with pytest.raises((OSError, api_error())):
+            cli.main(["no_such_reads.fa", "no_such_graph.gfa", "-m", str(m)])
+    for m in ("36", "42", "46", "52", "55", "58", "61", "63", "66"):
+        with pytest.raises(SystemExit) as ex:
+            cli.main(["reads.fa", "graph.gfa", "-m", m])
+        assert str(ex.value) == "Alignment mode must be in [0..9], or 12"
+
+
+def api_error():
+    from recgraph_amd import api
+    return api._lib.RecGraphError
+
+
+def test_gap_xlong_plan_routes(tmp_path):
+    csrc = os.path.join(ROOT, "recgraph_amd", "csrc")
+    exe = tmp_path / "gap_xlong_plan_check"
+    srcs = [os.path.join(csrc, f) for f in ("rg_path_plan.cpp", "rg_steps.cpp", "rg_graph.cpp", "rg_gaf.cpp", "rg_reads.cpp")]
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-I", csrc, "-o", str(exe), os.path.join(ROOT, "tests", "c", "gap_xlong_plan_check.cpp")]
+                          + srcs + ["-lpthread"])
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.strip() == "gap xlong plan ok", (r.stdout, r.stderr[-4000:])
+
+
+def test_the_kernels_keep_their_rows_in_registers():
+    """The family's bar: no scratch, no spilled VGPR, no AGPR, at most 200 VGPRs and no LDS beyond the score table's 160 B in every
+    instantiation of gap_xlong/rg_path_gap_xlong.hip (DESIGN 4.12 lists the counts)."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import kernel_resources
+    ks = kernel_resources.report("gap_xlong/rg_path_gap_xlong.hip")
+    assert sorted(k["name"] for k in ks) == sorted(KERNELS)
+    for k in ks:
+        assert k["ScratchSize [bytes/lane]"] == 0 and k["VGPRs Spill"] == 0 and k["AGPRs"] == 0, (k["name"], k)
+        assert k["VGPRs"] <= 200, (k["name"], k)
+        assert k["LDS Size [bytes/block]"] <= 160, (k["name"], k)
+
+
+def test_the_shared_row_step_left_the_long_kernels_as_they_were():
+    """gap_long/ keeps its one kernel file and its eight instantiations; what it shares with gap_xlong/ is a header, and no
+    `__global__` lives there."""
+    gl = os.path.join(ROOT, "recgraph_amd", "csrc", "gap_long")
+    assert sorted(os.listdir(gl)) == ["rg_path_gap_long.hip", "rg_path_gap_long.hpp", "rg_path_gap_long_rows.hpp"]
+    assert "__global__" not in open(os.path.join(gl, "rg_path_gap_long_rows.hpp")).read()
+    gx = os.path.join(ROOT, "recgraph_amd", "csrc", "gap_xlong")
+    assert sorted(f for f in os.listdir(gx) if f.endswith(".hip")) == ["rg_path_gap_xlong.hip"]
+    src = open(os.path.join(gx, "rg_path_gap_xlong.hip")).read()
+    assert "../gap_long/rg_path_gap_long_rows.hpp" in src and "asm" not in src

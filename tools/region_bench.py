@@ -3,7 +3,7 @@
 engine on other read lengths, score parameters and path counts, with the sweep kernel that ran and a parity check of a
 few reads against the oracle.  One JSON line per case.
 
-    python tools/region_bench.py [case ...]        cases: c5 x6 m3x5 hoxd70 len1500 p128 len600 gap gap_local gap_long gap_strands (default: all but the strand cases and the four `gap` cases)
+    python tools/region_bench.py [case ...]        cases: c5 x6 m3x5 hoxd70 len1500 p128 len600 gap gap_local gap_long gap_strands gap_xlong (default: all but the strand cases and the five `gap` cases)
 
 The strand cases (RG_AMB_BOTH_STRANDS, config-5 shape; `reads_per_s` counts SOURCE reads): `both_strands_fwd` — option on, every
 read forward (what the option costs when nothing qualifies: compare with `c5`); `both_strands` — option on, half of the reads
@@ -34,6 +34,14 @@ and the eight-byte read-back); (b) half of the reads reverse-complemented (synth
 exact rule and by the vote rule, both relative to (a)'s -m 16; (c) -m 32 against -m 22 on the reads of (b).  Five reads of every
 both-strands batch are checked against the composed rule (tests/pathwise_gap_strands_rule.py; at 4000 bases: strand, score and the
 re-scored CIGAR of two reads).  One JSON line per set.
+
+`gap_xlong` (only when named): the protocol of `gap_long` — one process, warm-up, alternating rounds, whole rg_batch_run calls, the
+handle's kernel timer.  (a) -m 56 beside -m 16 OF THE SAME BUILD on the same 512 reads of 4000 bases and the 16-path graph of
+4000-row paths of `gap_long`: the same bytes (compared), the time per counted cell update of both and their ratio, the work bytes per
+read of both.  (b) one batch no earlier mode accepts: 32 reads of 50 000 bases on 16 paths of about 50 000 rows in -m 56 — time per
+counted cell update, the work bytes per read beside what the layout of -m 16 would have needed.  Two reads of each part are checked
+against the rule (tests/pathwise_gap_rule.py): the printed score is the rule's (part (b): the rule's score of the printed path), and
+the printed CIGAR re-scores to it and consumes the read.  One JSON line per part.
 
 Every case: TILES tiles of TILE reads through one rg_stream (3 handles), timed after one warm-up tile per handle."""
 import json
@@ -210,6 +218,91 @@ def gap_long_case():
     print(json.dumps(out), flush=True)
 
 
+def gap_xlong_case():
+    from recgraph_amd import api, synth
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import pathwise_gap_rule as R
+
+    def timed(batch, rounds):
+        times = {m: [] for m in batch}
+        ks = {m: {} for m in batch}
+        for m in batch:
+            batch[m].run()                       # warm-up: code objects, work buffers
+        for _ in range(rounds):
+            for m in batch:                      # alternating: both modes see the same machine
+                t0 = time.perf_counter()
+                batch[m].run()
+                times[m].append(time.perf_counter() - t0)
+                for k, v in batch[m].kernel_stats().items():
+                    if not k.startswith(("host:", "mem:", "inst:")):
+                        ks[m][k] = ks[m].get(k, 0.0) + v[0] / rounds
+        for m in batch:
+            batch[m].fetch()
+        return times, ks
+
+    def entry(bm, rd, times, ks, rounds):
+        med = sorted(times)[rounds // 2]
+        return {"read_len": len(rd[0]), "ms_per_batch_median": round(med * 1e3, 2), "ms_per_batch_min": round(min(times) * 1e3, 2),
+                "counted_cell_updates": bm.cell_updates, "ps_per_counted_cell_update": round(med / bm.cell_updates * 1e12, 3),
+                "performed_over_counted": round(bm.cell_updates_performed / bm.cell_updates, 3),
+                "work_bytes_per_read": int(bm.kernel_stats().get("mem:work_bytes_per_read", (0, 1))[0]),
+                "kernel_ms_per_batch": {k: round(v, 2) for k, v in ks.items()}}
+
+    def checked(b, reads, picks, lnz, prow, paths, all_paths):
+        ok = True
+        for i in picks:
+            f = b.gaf_text(i, "r", 1)[:-1].split("\t")
+            mm = re.fullmatch(r"([0-9MXID]+), best path: (\d+), score: (-?\d+)", f[12])
+            if mm is None:
+                return False
+            k = int(mm.group(2))
+            if all_paths:
+                last, lens = R.all_paths_last(lnz, prow, reads[i], R.default_scores(), -4, -2, False)
+                ok = ok and (int(mm.group(3)), -k) == max((int(last[q, lens[q]]), -q) for q in range(paths))
+            else:
+                last, lens = R.all_paths_last(lnz, [prow[k]], reads[i], R.default_scores(), -4, -2, False)
+                ok = ok and int(mm.group(3)) == int(last[0, lens[0]])
+            ok = ok and R.rescore(mm.group(1), f[13], reads[i])[:2] == (int(mm.group(3)), len(reads[i]))
+        return ok
+
+    # (a) -m 56 beside -m 16 on what both take
+    rounds, paths, plen, nreads = 5, 16, 4000, 512
+    g = synth.haplotype_graph(3 * plen, paths, path_len=plen, seed=1234)
+    gg = api.Graph.from_gfa_text(g.gfa())
+    reads = synth.haplotype_reads(g, nreads, length=plen, seed=900, mosaic_frac=0.0)
+    modes = (api.MODE_PATHWISE_GAP_XLONG, api.MODE_PATHWISE_GAP_LONG)
+    batch = {m: api.Batch(gg, reads, api.make_params(m)) for m in modes}
+    times, ks = timed(batch, rounds)
+    lnz, prow = R.graph_paths(gg)
+    same = all(batch[56].gaf_text(i, "r", 1) == batch[16].gaf_text(i, "r", 1) and batch[56].status(i) == batch[16].status(i) for i in range(nreads))
+    out = {"case": "gap_xlong", "part": "a", "rows": gg.rows, "paths": paths, "path_rows": max(len(r) for r in prow), "reads": nreads, "rounds": rounds}
+    for m in modes:
+        out["m%d" % m] = entry(batch[m], reads, times[m], ks[m], rounds)
+    out["m56_over_m16_time_median"] = round(out["m56"]["ms_per_batch_median"] / out["m16"]["ms_per_batch_median"], 3)
+    out["m56_over_m16_time_min"] = round(out["m56"]["ms_per_batch_min"] / out["m16"]["ms_per_batch_min"], 3)
+    out["same_bytes_as_m16"] = same
+    out["rule_checked"] = 2 if checked(batch[56], reads, (0, nreads - 1), lnz, prow, paths, True) else "FAILED"
+    print(json.dumps(out), flush=True)
+    del batch
+    # (b) what no earlier mode accepts
+    rounds, plen, nreads = 3, 50000, 32
+    g = synth.haplotype_graph(3 * plen, paths, path_len=plen, seed=1234)
+    gg = api.Graph.from_gfa_text(g.gfa())
+    reads = synth.haplotype_reads(g, nreads, length=plen, seed=901, mosaic_frac=0.0)
+    batch = {56: api.Batch(gg, reads, api.make_params(api.MODE_PATHWISE_GAP_XLONG))}
+    times, ks = timed(batch, rounds)
+    lnz, prow = R.graph_paths(gg)
+    rows1 = max(len(r) for r in prow) + 1
+    stripes = (max(len(r) for r in reads) + 2048) // 2048
+    out = {"case": "gap_xlong", "part": "b", "rows": gg.rows, "paths": paths, "path_rows": rows1 - 1, "reads": nreads, "rounds": rounds, "stripes": stripes}
+    out["m56"] = entry(batch[56], reads, times[56], ks[56], rounds)
+    # what the layout of -m 16 takes for this geometry: stripes x rows1 KiB of direction words and both boundary buffers
+    out["m16_layout_work_bytes_per_read"] = stripes * rows1 * 1024 + 8 * rows1 * (paths + 1)
+    print(json.dumps(dict(out, rule_checked="pending")), flush=True)
+    out["rule_checked"] = 2 if checked(batch[56], reads, (0, nreads - 1), lnz, prow, paths, False) else "FAILED"
+    print(json.dumps(out), flush=True)
+
+
 def gap_strands_case():
     from recgraph_amd import api, synth
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -279,6 +372,11 @@ def gap_strands_case():
 def main():
     from recgraph_amd import api, synth
     from oracle import oracle as O
+    if "gap_xlong" in sys.argv[1:]:
+        gap_xlong_case()
+        sys.argv = [a for a in sys.argv if a != "gap_xlong"]
+        if len(sys.argv) == 1:
+            return
     if "gap_strands" in sys.argv[1:]:
         gap_strands_case()
         sys.argv = [a for a in sys.argv if a != "gap_strands"]
