@@ -5,6 +5,9 @@
 
 namespace rg {
 
+// the three rules of the family (the values are the template arguments of the striped kernels: k_gap_score_long<0> is global)
+enum GapKind { GAP_GLOBAL = 0, GAP_SEMI = 1, GAP_LOCAL = 2 };
+
 struct GapArgs {
     DevScores sc;
     const uint8_t* lnz;           // base code per graph row

@@ -5,11 +5,12 @@
 //   k_gap_pick, k_gap_pick_local   the kernels of gap/ and gap_local/, launched with the striped width
 //   k_gap_dirs_long<kind>     one wave per read: the same row step for the picked path, 4 bits per cell to HBM
 //   k_gap_trace_long, k_gap_trace_local_long   one wave per read walks those bits
-// The row step, the boundary exchange and the nibble lookup live in rg_path_gap_long_rows.hpp, which gap_xlong/ (-m 56 / -m 57 / -m 62:
-// the same stripes with the direction words of one stripe at a time) includes as well.
+// The row step (gap_row, striped form), the nibble lookup, the walk and the record writer are the family's, in
+// gap/rg_path_gap_common.hpp; the stripe geometry and the boundary exchange live in rg_path_gap_long_rows.hpp, which gap_xlong/
+// (-m 56 / -m 57 / -m 62: the same stripes with the direction words of one stripe at a time) includes as well.
 //
 // COLUMN STRIPES, ONE WAVE.  A read of n bases has ceil((n + 1) / 2048) stripes of 2048 columns; inside a stripe lane t owns the 32
-// columns s * 2048 + t * 32 .. + 31, and the row step is the one of gap/rg_path_gap.hip (gap_local/ for the local kind): H and Y of
+// columns s * 2048 + t * 32 .. + 31, and the row step is the one of gap/rg_path_gap.hip with its stripe inputs: H and Y of
 // the current row in registers, X as one max-plus prefix scan over z_k = H'_k - e k with k the GLOBAL column.  The wave walks the
 // stripes of its (read, path) one after the other, all rows of a stripe before the next.  Per row, a stripe needs two integers from
 // everything to its left:
@@ -32,15 +33,14 @@ namespace rg {
 
 namespace {
 
-#include "../gap/rg_path_gap_common.hpp"      // GNEG, gap_words, ReadCols, DirWords, NoDirs, row_index
-
-#include "rg_path_gap_long_rows.hpp"                // CL, STRIPE, WL, load_cols, load_scores, row0, long_row, pick_col, Boundary, dir_cell
+#include "../gap/rg_path_gap_common.hpp"
+#include "rg_path_gap_long_rows.hpp"                // CL, STRIPE, WL, Boundary
 
 }  // namespace
 
 template <int kKind>
 __global__ __launch_bounds__(64) void k_gap_score_long(GapLongArgs la) {
-    constexpr bool kSemi = kKind == GAP_LONG_SEMI, kLocal = kKind == GAP_LONG_LOCAL;
+    constexpr bool kSemi = kKind == GAP_SEMI, kLocal = kKind == GAP_LOCAL;
     __shared__ int sct[40];
     const GapArgs& a = la.g;
     const int rd = blockIdx.y, k = blockIdx.x, lane = threadIdx.x;
@@ -60,8 +60,8 @@ __global__ __launch_bounds__(64) void k_gap_score_long(GapLongArgs la) {
         const bool first = s == 0, last = s == S - 1;
         int H[CL], Y[CL];
         ReadCols<CL, false> rc;
-        load_cols<false>(rc, a.reads + ro - 1, n, c0, lane);
-        row0<kKind>(H, Y, a.o, a.e, c0, lane);
+        rc.load(a.reads + ro - 1, n, lane, c0);
+        row0<CL, kKind>(H, Y, a.o, a.e, c0, lane);
         const int ej0 = a.e * (c0 + lane * CL);
         const int nl = n - c0;                           // the last stripe: 0 <= nl <= 2047, the read's last column is (ln, qn)
         const int ln = nl / CL, qn = nl % CL;
@@ -74,16 +74,14 @@ __global__ __launch_bounds__(64) void k_gap_score_long(GapLongArgs la) {
             const int cnt = min(WAVE, m - t0);
             for (int u = 0; u < cnt; ++u) {
                 const int b = __builtin_amdgcn_readlane(myb, u);
-                const int incl = long_row<kKind>(H, Y, rc, sct, b, a.o, a.e, ej0, lane == 0, first && lane == 0, bd.dnext, bd.zin(u), nd);
+                const int incl = gap_row<CL, kKind, true>(H, Y, rc, sct, b, a.o, a.e, ej0, lane == 0, first && lane == 0, bd.dnext, bd.zin(u), nd);
                 bd.after_row(u, lane, H[CL - 1], incl);
                 if (kSemi) {
                     const int v = pick_col(H, qn);
                     if (last && v > best) { best = v; bt = t0 + u; }      // strictly better: the first row that attains the maximum
                 }
                 if (kLocal) {
-                    int v = 0;
-#pragma unroll
-                    for (int q = 0; q < CL; ++q) v = max(v, q <= qlim ? H[q] : 0);
+                    const int v = best_own_col(H, qlim);
                     // rows repeat per stripe: highest value, then the smallest row (column 0 holds 0 and never beats the initial 0)
                     if (v > best || (v == best && t0 + u < bt)) { best = v; bt = t0 + u; }
                 }
@@ -121,19 +119,19 @@ __global__ __launch_bounds__(64) void k_gap_score_long(GapLongArgs la) {
 
 template <int kKind>
 __global__ __launch_bounds__(64) void k_gap_dirs_long(GapLongArgs la) {
-    constexpr bool kLocal = kKind == GAP_LONG_LOCAL;
+    constexpr bool kLocal = kKind == GAP_LOCAL;
     __shared__ int sct[40];
     const GapArgs& a = la.g;
     const int rd = blockIdx.x, lane = threadIdx.x;
     ReadState* rs = a.state + rd;
-    if (rs->status & (ST_BAD_BASE | ST_WOULD_PANIC | ST_UNALIGNED)) return;
+    if (rs->status & ST_NO_RECORD) return;
     const long long ro = a.read_off[rd];
     const int n = __builtin_amdgcn_readfirstlane((int)(a.read_off[rd + 1] - ro));
     const int k = __builtin_amdgcn_readfirstlane(rs->fwd_path);
     const int score = __builtin_amdgcn_readfirstlane(rs->trace_score);
     const int pbeg = a.poff[k];
     int m = a.poff[k + 1] - pbeg;
-    if (kKind != GAP_LONG_GLOBAL) m = row_index(a.prow + pbeg, m, rs->end_row) + 1;      // the rows up to the end row are all the walk can visit
+    if (kKind != GAP_GLOBAL) m = row_index(a.prow + pbeg, m, rs->end_row) + 1;      // the rows up to the end row are all the walk can visit
     m = __builtin_amdgcn_readfirstlane(min(m, la.rows1 - 1));
     if (n + 1 > la.S * STRIPE || (kLocal && m <= 0)) {
         if (lane == 0) rs->status = ST_WOULD_PANIC;
@@ -152,8 +150,8 @@ __global__ __launch_bounds__(64) void k_gap_dirs_long(GapLongArgs la) {
         const bool first = s == 0, last = s == S - 1;
         int H[CL], Y[CL];
         ReadCols<CL, true> rc;
-        load_cols<true>(rc, a.reads + ro - 1, n, c0, lane);
-        row0<kKind>(H, Y, a.o, a.e, c0, lane);
+        rc.load(a.reads + ro - 1, n, lane, c0);
+        row0<CL, kKind>(H, Y, a.o, a.e, c0, lane);
         const int ej0 = a.e * (c0 + lane * CL);
         bd.begin_stripe(first, kLocal ? 0 : a.o + a.e * (c0 - 1));      // H[0][c0 - 1]
         uint32_t* sout = out + (long long)s * la.rows1 * (WL * WAVE);
@@ -165,26 +163,16 @@ __global__ __launch_bounds__(64) void k_gap_dirs_long(GapLongArgs la) {
             const int cnt = min(WAVE, m - t0);
             for (int u = 0; u < cnt; ++u) {
                 const int b = __builtin_amdgcn_readlane(myb, u);
-                const int incl = long_row<kKind>(H, Y, rc, sct, b, a.o, a.e, ej0, lane == 0, first && lane == 0, bd.dnext, bd.zin(u), dw);
+                const int incl = gap_row<CL, kKind, true>(H, Y, rc, sct, b, a.o, a.e, ej0, lane == 0, first && lane == 0, bd.dnext, bd.zin(u), dw);
                 bd.after_row(u, lane, H[CL - 1], incl);
 #pragma unroll
                 for (int w = 0; w < WL; ++w) sout[((long long)(t0 + u + 1) * WL + w) * WAVE + lane] = dw.w[w];
-                if (kLocal && t0 + u == m - 1) {
-                    // H is the end row (inside the loop, as in k_gap_dirs_local: H live out of it costs registers)
-#pragma unroll
-                    for (int q = CL - 1; q >= 0; --q) c = H[q] == score ? q : c;
-                }
+                if (kLocal && t0 + u == m - 1) c = own_end_col(H, score, c);      // H is the end row
             }
             bd.end_block(last, t0, m, lane);
         }
-        if (kLocal && end_col == 0) {
-            // stripes in ascending order: the first one that holds the score decides (lowest lane, then lowest column of that lane)
-            const unsigned long long hit = __ballot(c < CL);
-            if (hit) {
-                const int l = __builtin_amdgcn_readfirstlane(__ffsll((long long)hit) - 1);
-                end_col = c0 + l * CL + __builtin_amdgcn_readlane(c, l);
-            }
-        }
+        // stripes in ascending order: the first one that holds the score decides
+        if (kLocal && end_col == 0) end_col = wave_end_col<CL>(c, c0);
     }
     if (lane == 0) {
         if (kLocal) {
@@ -195,160 +183,32 @@ __global__ __launch_bounds__(64) void k_gap_dirs_long(GapLongArgs la) {
     }
 }
 
-// The walk of -m 6 / -m 7 (k_gap_trace) over striped direction words.  Every value that steers it comes out of a readlane, so the
-// state is the same in all lanes; lane 0 writes.  The loop is bounded: a wrong direction word ends as ST_WOULD_PANIC, never as a hang.
-__global__ __launch_bounds__(64) void k_gap_trace_long(GapLongArgs la, int semi) {
-    const GapArgs& a = la.g;
-    const int rd = blockIdx.x, lane = threadIdx.x;
-    ReadState* rs = a.state + rd;
-    DevRecord* rec = a.rec + rd;
-    auto no_record = [&](uint32_t st) {
-        if (lane == 0) { rec->status = st; rec->n_ops = 0; rec->n_fwd_ops = 0; rec->score = 0; }
-    };
-    if (rs->status & (ST_BAD_BASE | ST_WOULD_PANIC)) { no_record(rs->status); return; }
-    const int n = (int)(a.read_off[rd + 1] - a.read_off[rd]);
-    const int k = rs->fwd_path;
-    const int pbeg = a.poff[k], m = a.poff[k + 1] - pbeg;
-    const int idx = row_index(a.prow + pbeg, m, rs->end_row);
-    if (idx < 0 || idx + 1 >= la.rows1 || n + 1 > la.S * STRIPE) { no_record(ST_WOULD_PANIC); return; }
-    const uint32_t* dirs = a.dirs + (long long)rd * a.dirs_stride;
-    uint32_t wd[WL] = {0, 0, 0, 0};
-    int have = -1;
-    uint8_t* ops = a.ops + (long long)rd * a.ops_stride;
-    enum { S_H, S_Y, S_X, S_XARRIVE };
-    int i = idx + 1, j = n, state = S_H, nops = 0, steps = 0;
-    const int cap = 3 * (m + n) + 3;                // (the count of k_gap_trace_local: at most 2 iterations per row, 3 per column)
-    auto emit = [&](uint8_t op) { if (lane == 0 && nops < a.ops_stride) ops[nops] = op; ++nops; };
-    while (i > 0 && j > 0 && steps < cap) {
-        ++steps;
-        const uint32_t cell = dir_cell(dirs, la.rows1, lane, i, j, have, wd);
-        if (state == S_XARRIVE) {                   // an L was walked into (i, j): does the run open here?
-            state = (cell & 8u) ? S_H : S_X;
-        } else if (state == S_H) {
-            const uint32_t src = cell & 3u;
-            if (src == 1u) { emit(OP_D); i -= 1; j -= 1; }
-            else state = src == 2u ? S_Y : S_X;
-        } else if (state == S_Y) {
-            emit(OP_U);
-            i -= 1;
-            state = (cell & 4u) ? S_H : S_Y;
-        } else {
-            emit(OP_L);
-            j -= 1;
-            state = S_XARRIVE;
-        }
-    }
-    if (i > 0 && j > 0) { no_record(ST_WOULD_PANIC); return; }
-    // the borders: only one state is finite there
-    while (j > 0) { emit(OP_L); j -= 1; }
-    while (!semi && i > 0) { emit(OP_U); i -= 1; }
-    if (nops > a.ops_stride) { no_record(ST_WOULD_PANIC); return; }
-    if (lane == 0) {
-        rec->status = rs->status;
-        rec->score = rs->trace_score;
-        rec->fscore = 0.f;
-        rec->end_row = rs->end_row;
-        rec->end_col = n;
-        rec->stop_row = 0; rec->stop_col = 0;
-        rec->best_path = k; rec->rev_path = k;
-        rec->fen = 0; rec->rsn = 0; rec->rec_col = 0; rec->displacement = 0;
-        rec->n_ops = nops; rec->n_fwd_ops = nops;
-        rec->pad = 0;
-    }
-}
+// The walks of k_gap_trace and k_gap_trace_local over striped direction words (gap_trace_wave with S stripes)
+__global__ __launch_bounds__(64) void k_gap_trace_long(GapLongArgs la, int semi) { gap_trace_wave<false>(la.g, semi, CL, la.S, la.rows1); }
 
-// The walk of -m 12 (k_gap_trace_local) over striped direction words: from (end row, end column) until a cell with H == 0.
-__global__ __launch_bounds__(64) void k_gap_trace_local_long(GapLongArgs la) {
-    const GapArgs& a = la.g;
-    const int rd = blockIdx.x, lane = threadIdx.x;
-    ReadState* rs = a.state + rd;
-    DevRecord* rec = a.rec + rd;
-    auto no_record = [&](uint32_t st) {
-        if (lane == 0) { rec->status = st; rec->n_ops = 0; rec->n_fwd_ops = 0; rec->score = 0; }
-    };
-    if (rs->status & (ST_BAD_BASE | ST_WOULD_PANIC | ST_UNALIGNED)) { no_record(rs->status); return; }
-    const int n = (int)(a.read_off[rd + 1] - a.read_off[rd]);
-    const int k = rs->fwd_path;
-    const int pbeg = a.poff[k], m = a.poff[k + 1] - pbeg;
-    const int idx = row_index(a.prow + pbeg, m, rs->end_row);
-    const int end_col = rs->rec_col;
-    if (idx < 0 || idx + 1 >= la.rows1 || n + 1 > la.S * STRIPE || end_col < 1 || end_col > n) { no_record(ST_WOULD_PANIC); return; }
-    const uint32_t* dirs = a.dirs + (long long)rd * a.dirs_stride;
-    uint32_t wd[WL] = {0, 0, 0, 0};
-    int have = -1;
-    uint8_t* ops = a.ops + (long long)rd * a.ops_stride;
-    enum { S_H, S_Y, S_X, S_XARRIVE };
-    int i = idx + 1, j = end_col, state = S_H, nops = 0, steps = 0;
-    const int cap = 3 * (m + n) + 3;                // (counted at k_gap_trace_local)
-    bool stopped = false;
-    auto emit = [&](uint8_t op) { if (lane == 0 && nops < a.ops_stride) ops[nops] = op; ++nops; };
-    while (i > 0 && j > 0 && steps < cap) {
-        ++steps;
-        const uint32_t cell = dir_cell(dirs, la.rows1, lane, i, j, have, wd);
-        if (state == S_XARRIVE) {
-            state = (cell & 8u) ? S_H : S_X;
-        } else if (state == S_H) {
-            const uint32_t src = cell & 3u;
-            if (src == 0u) { stopped = true; break; }          // H == 0: checked first
-            if (src == 1u) { emit(OP_D); i -= 1; j -= 1; }
-            else state = src == 2u ? S_Y : S_X;
-        } else if (state == S_Y) {
-            emit(OP_U);
-            i -= 1;
-            state = (cell & 4u) ? S_H : S_Y;
-        } else {
-            emit(OP_L);
-            j -= 1;
-            state = S_XARRIVE;
-        }
-    }
-    // a border cell is H = 0 (X and Y are NEG there): the walk may arrive in H, or by an L whose run opens on column 0
-    const bool border = (i == 0 || j == 0) && (state == S_H || (state == S_XARRIVE && j == 0));
-    if (!(stopped || border) || nops < 1 || nops > a.ops_stride) { no_record(ST_WOULD_PANIC); return; }
-    if (lane == 0) {
-        rec->status = rs->status;
-        rec->score = rs->trace_score;
-        rec->fscore = 0.f;
-        rec->end_row = rs->end_row;
-        rec->end_col = end_col;
-        rec->stop_row = i > 0 ? a.prow[pbeg + i - 1] : 0;
-        rec->stop_col = j;
-        rec->best_path = k; rec->rev_path = k;
-        rec->fen = 0; rec->rsn = 0; rec->rec_col = 0; rec->displacement = 0;
-        rec->n_ops = nops; rec->n_fwd_ops = nops;
-        rec->pad = 0;
-    }
-}
+__global__ __launch_bounds__(64) void k_gap_trace_local_long(GapLongArgs la) { gap_trace_wave<true>(la.g, 0, CL, la.S, la.rows1); }
 
 // ---- launchers ---------------------------------------------------------------------------------------------------------------
-#define RG_GAP_LONG_DISPATCH(K, grid)                                                       \
-    switch (kind) {                                                                         \
-        case GAP_LONG_GLOBAL: RG_LAUNCH(K, (0), grid, dim3(WAVE), 0, s, a);                 \
-        case GAP_LONG_SEMI: RG_LAUNCH(K, (1), grid, dim3(WAVE), 0, s, a);                   \
-        case GAP_LONG_LOCAL: RG_LAUNCH(K, (2), grid, dim3(WAVE), 0, s, a);                  \
-        default: return nullptr;                                                            \
-    }
-
 static bool geometry_ok(const GapLongArgs& a) { return a.S >= 1 && a.S <= GAP_LONG_MAX_STRIPES && a.rows1 >= 1 && a.bnd && a.dbnd && a.g.dirs; }
 
 const char* launch_gap_score_long(const GapLongArgs& a, int nreads, int kind, hipStream_t s, int max_stripes) {
     // (-m 56 / -m 57 / -m 62 run this pass on up to 64 stripes, without the buffers of the direction pass: the kernel itself has no cap)
     if (max_stripes == GAP_LONG_MAX_STRIPES ? !geometry_ok(a) : !(a.S >= 1 && a.S <= max_stripes && a.rows1 >= 1 && a.bnd)) return nullptr;
     const dim3 grid(a.g.P, nreads);
-    RG_GAP_LONG_DISPATCH(k_gap_score_long, grid)
+    RG_GAP_SWITCH_KIND(k_gap_score_long, grid, a);
     return nullptr;
 }
 const char* launch_gap_dirs_long(const GapLongArgs& a, int nreads, int kind, hipStream_t s) {
     if (!geometry_ok(a)) return nullptr;
     const dim3 grid(nreads);
-    RG_GAP_LONG_DISPATCH(k_gap_dirs_long, grid)
+    RG_GAP_SWITCH_KIND(k_gap_dirs_long, grid, a);
     return nullptr;
 }
 const char* launch_gap_trace_long(const GapLongArgs& a, int nreads, int kind, hipStream_t s) {
     if (!geometry_ok(a)) return nullptr;
-    if (kind == GAP_LONG_LOCAL) RG_LAUNCH0(k_gap_trace_local_long, dim3(nreads), dim3(WAVE), 0, s, a);
-    if (kind != GAP_LONG_GLOBAL && kind != GAP_LONG_SEMI) return nullptr;
-    RG_LAUNCH0(k_gap_trace_long, dim3(nreads), dim3(WAVE), 0, s, a, kind == GAP_LONG_SEMI ? 1 : 0);
+    if (kind == GAP_LOCAL) RG_LAUNCH0(k_gap_trace_local_long, dim3(nreads), dim3(WAVE), 0, s, a);
+    if (kind != GAP_GLOBAL && kind != GAP_SEMI) return nullptr;
+    RG_LAUNCH0(k_gap_trace_long, dim3(nreads), dim3(WAVE), 0, s, a, kind == GAP_SEMI ? 1 : 0);
 }
 
 }  // namespace rg

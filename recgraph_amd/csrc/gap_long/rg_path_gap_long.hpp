@@ -10,8 +10,6 @@ constexpr int GAP_LONG_C = 32;                        // columns per lane
 constexpr int GAP_LONG_STRIPE = GAP_LONG_C * WAVE;    // columns per stripe: 2048
 constexpr int GAP_LONG_MAX_STRIPES = 8;               // reads of up to 8 * 2048 - 1 = 16383 bases
 
-enum GapLongKind { GAP_LONG_GLOBAL = 0, GAP_LONG_SEMI = 1, GAP_LONG_LOCAL = 2 };
-
 struct GapLongArgs {
     GapArgs g;                    // g.dirs: [reads][dirs_stride], stripe s, row t of the picked path at ((s * rows1 + t + 1) * 4 + w) * 64 + lane
     int S;                        // stripes of the batch's longest read (a read runs ceil((n + 1) / 2048) of them)
@@ -21,7 +19,7 @@ struct GapLongArgs {
     int* dbnd;                    // direction pass, [reads][2][rows1]: the same two values for the picked path
 };
 
-// kind: GapLongKind (16: global, 17: semi, 22: local); max_stripes: the host-side cap on a.S, lifted by the plan of gap_xlong/ alone
+// kind: GapKind (16: global, 17: semi, 22: local); max_stripes: the host-side cap on a.S, lifted by the plan of gap_xlong/ alone
 const char* launch_gap_score_long(const GapLongArgs& a, int nreads, int kind, hipStream_t s, int max_stripes = GAP_LONG_MAX_STRIPES);
 const char* launch_gap_dirs_long(const GapLongArgs& a, int nreads, int kind, hipStream_t s);
 const char* launch_gap_trace_long(const GapLongArgs& a, int nreads, int kind, hipStream_t s);

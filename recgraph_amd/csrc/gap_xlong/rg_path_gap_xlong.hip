@@ -16,8 +16,9 @@
 // a stripe < r.  A stripe above the round is an inconsistent state and ends as ST_WOULD_PANIC; round 0 finishes every walk.  The
 // rebuild and the walk are separate launches: the walk reads what another kernel wrote.
 //
-// The row step, the stripe geometry, the boundary exchange and the nibble lookup are those of gap_long/ (rg_path_gap_long_rows.hpp):
-// the same registers hold the same values, so a rebuilt word equals the word k_gap_dirs_long stores for that (stripe, row, lane).
+// The row step, the nibble lookup, the walk and the record writer are the family's (gap/rg_path_gap_common.hpp: gap_row, dir_cell,
+// gap_walk), the stripe geometry and the boundary exchange those of gap_long/ (rg_path_gap_long_rows.hpp): the same registers hold
+// the same values, so a rebuilt word equals the word k_gap_dirs_long stores for that (stripe, row, lane).
 #include <type_traits>
 
 #include "rg_path_gap_xlong.hpp"
@@ -26,12 +27,8 @@ namespace rg {
 
 namespace {
 
-#include "../gap/rg_path_gap_common.hpp"            // GNEG, gap_words, ReadCols, DirWords, NoDirs, row_index
-#include "../gap_long/rg_path_gap_long_rows.hpp"    // CL, STRIPE, WL, load_cols, load_scores, row0, long_row, Boundary, dir_cell
-
-enum { S_H, S_Y, S_X, S_XARRIVE };
-
-constexpr uint32_t kNoWalk = ST_BAD_BASE | ST_WOULD_PANIC | ST_UNALIGNED;      // (ST_UNALIGNED is set in the local kind only)
+#include "../gap/rg_path_gap_common.hpp"
+#include "../gap_long/rg_path_gap_long_rows.hpp"    // CL, STRIPE, WL, Boundary
 
 // checkpoint slot s of a read: [2][rows1]
 __device__ __forceinline__ int* ckpt_slot(const GapXLongArgs& xa, int rd, int s) {
@@ -42,13 +39,13 @@ __device__ __forceinline__ int* ckpt_slot(const GapXLongArgs& xa, int rd, int s)
 
 template <int kKind>
 __global__ __launch_bounds__(64) void k_gap_ckpt_long(GapXLongArgs xa) {
-    constexpr bool kLocal = kKind == GAP_LONG_LOCAL;
+    constexpr bool kLocal = kKind == GAP_LOCAL;
     __shared__ int sct[40];
     const GapLongArgs& la = xa.l;
     const GapArgs& a = la.g;
     const int rd = blockIdx.x, lane = threadIdx.x;
     ReadState* rs = a.state + rd;
-    if (rs->status & kNoWalk) return;
+    if (rs->status & ST_NO_RECORD) return;
     const long long ro = a.read_off[rd];
     const int n = __builtin_amdgcn_readfirstlane((int)(a.read_off[rd + 1] - ro));
     const int k = __builtin_amdgcn_readfirstlane(rs->fwd_path);
@@ -56,7 +53,7 @@ __global__ __launch_bounds__(64) void k_gap_ckpt_long(GapXLongArgs xa) {
     const int pbeg = a.poff[k];
     int m = a.poff[k + 1] - pbeg;
     const int idx = __builtin_amdgcn_readfirstlane(row_index(a.prow + pbeg, m, rs->end_row));      // where the walk starts
-    if (kKind != GAP_LONG_GLOBAL) m = idx + 1;        // the rows up to the end row are all the walk can visit
+    if (kKind != GAP_GLOBAL) m = idx + 1;        // the rows up to the end row are all the walk can visit
     m = __builtin_amdgcn_readfirstlane(min(m, la.rows1 - 1));
     if (n + 1 > la.S * STRIPE || idx < 0 || idx + 1 >= la.rows1 || (kLocal && m <= 0)) {
         if (lane == 0) rs->status = ST_WOULD_PANIC;
@@ -74,8 +71,8 @@ __global__ __launch_bounds__(64) void k_gap_ckpt_long(GapXLongArgs xa) {
         int* const to = ckpt_slot(xa, rd, last ? 0 : s);
         int H[CL], Y[CL];
         ReadCols<CL, false> rc;
-        load_cols<false>(rc, a.reads + ro - 1, n, c0, lane);
-        row0<kKind>(H, Y, a.o, a.e, c0, lane);
+        rc.load(a.reads + ro - 1, n, lane, c0);
+        row0<CL, kKind>(H, Y, a.o, a.e, c0, lane);
         const int ej0 = a.e * (c0 + lane * CL);
         bd.begin_stripe(first, kLocal ? 0 : a.o + a.e * (c0 - 1));      // H[0][c0 - 1]
         int c = CL;
@@ -87,25 +84,15 @@ __global__ __launch_bounds__(64) void k_gap_ckpt_long(GapXLongArgs xa) {
             const int cnt = min(WAVE, m - t0);
             for (int u = 0; u < cnt; ++u) {
                 const int b = __builtin_amdgcn_readlane(myb, u);
-                const int incl = long_row<kKind>(H, Y, rc, sct, b, a.o, a.e, ej0, lane == 0, first && lane == 0, bd.dnext, bd.zin(u), nd);
+                const int incl = gap_row<CL, kKind, true>(H, Y, rc, sct, b, a.o, a.e, ej0, lane == 0, first && lane == 0, bd.dnext, bd.zin(u), nd);
                 bd.after_row(u, lane, H[CL - 1], incl);
-                if (kLocal && t0 + u == m - 1) {
-                    // H is the end row (as in k_gap_dirs_long<2>)
-#pragma unroll
-                    for (int q = CL - 1; q >= 0; --q) c = H[q] == score ? q : c;
-                }
+                if (kLocal && t0 + u == m - 1) c = own_end_col(H, score, c);      // H is the end row (as in k_gap_dirs_long<2>)
             }
             bd.h = to; bd.z = to + la.rows1;
             bd.end_block(last, t0, m, lane);
         }
-        if (kLocal && end_col == 0) {
-            // stripes in ascending order: the first one that holds the score decides (lowest lane, then lowest column of that lane)
-            const unsigned long long hit = __ballot(c < CL);
-            if (hit) {
-                const int l = __builtin_amdgcn_readfirstlane(__ffsll((long long)hit) - 1);
-                end_col = c0 + l * CL + __builtin_amdgcn_readlane(c, l);
-            }
-        }
+        // stripes in ascending order: the first one that holds the score decides
+        if (kLocal && end_col == 0) end_col = wave_end_col<CL>(c, c0);
     }
     if (lane == 0) {
         if (kLocal && (end_col < 1 || end_col > n)) {
@@ -122,13 +109,13 @@ __global__ __launch_bounds__(64) void k_gap_ckpt_long(GapXLongArgs xa) {
 
 template <int kKind>
 __global__ __launch_bounds__(64) void k_gap_redo_long(GapXLongArgs xa, int round) {
-    constexpr bool kLocal = kKind == GAP_LONG_LOCAL;
+    constexpr bool kLocal = kKind == GAP_LOCAL;
     __shared__ int sct[40];
     const GapLongArgs& la = xa.l;
     const GapArgs& a = la.g;
     const int rd = blockIdx.x, lane = threadIdx.x;
     const ReadState* rs = a.state + rd;
-    if (rs->status & kNoWalk) return;
+    if (rs->status & ST_NO_RECORD) return;
     const GapWalkState* ws = xa.walk + rd;
     if (ws->done) return;
     const int wi = __builtin_amdgcn_readfirstlane(ws->i), wj = __builtin_amdgcn_readfirstlane(ws->j);
@@ -149,8 +136,8 @@ __global__ __launch_bounds__(64) void k_gap_redo_long(GapXLongArgs xa, int round
     DirWords<CL> dw;
     int H[CL], Y[CL];
     ReadCols<CL, true> rc;
-    load_cols<true>(rc, a.reads + ro - 1, n, c0, lane);
-    row0<kKind>(H, Y, a.o, a.e, c0, lane);
+    rc.load(a.reads + ro - 1, n, lane, c0);
+    row0<CL, kKind>(H, Y, a.o, a.e, c0, lane);
     const int ej0 = a.e * (c0 + lane * CL);
     bd.begin_stripe(first, kLocal ? 0 : a.o + a.e * (c0 - 1));      // H[0][c0 - 1]
     for (int t0 = 0; t0 < m; t0 += WAVE) {
@@ -160,7 +147,7 @@ __global__ __launch_bounds__(64) void k_gap_redo_long(GapXLongArgs xa, int round
         const int cnt = min(WAVE, m - t0);
         for (int u = 0; u < cnt; ++u) {
             const int b = __builtin_amdgcn_readlane(myb, u);
-            const int incl = long_row<kKind>(H, Y, rc, sct, b, a.o, a.e, ej0, lane == 0, first && lane == 0, bd.dnext, bd.zin(u), dw);
+            const int incl = gap_row<CL, kKind, true>(H, Y, rc, sct, b, a.o, a.e, ej0, lane == 0, first && lane == 0, bd.dnext, bd.zin(u), dw);
             bd.after_row(u, lane, H[CL - 1], incl);
 #pragma unroll
             for (int w = 0; w < WL; ++w) sout[((long long)(t0 + u + 1) * WL + w) * WAVE + lane] = dw.w[w];
@@ -175,94 +162,36 @@ __global__ __launch_bounds__(64) void k_gap_redo_long(GapXLongArgs xa, int round
 
 namespace {
 
-// One round of a walk.  Every value that steers it comes out of a uniform load or a readlane, so the state is the same in all lanes;
-// lane 0 writes.  The iteration count runs over all rounds: a wrong direction word ends as ST_WOULD_PANIC, never as a hang.
+// One round of a walk: gap_walk resumed from the saved state, over the one-stripe buffer that holds stripe `round`.  The iteration
+// count runs over all rounds.
 template <bool kLocal>
 __device__ __forceinline__ void walk_round(const GapXLongArgs& xa, int semi, int round) {
     const GapLongArgs& la = xa.l;
     const GapArgs& a = la.g;
     const int rd = blockIdx.x, lane = threadIdx.x;
-    ReadState* rs = a.state + rd;
+    const ReadState* rs = a.state + rd;
     DevRecord* rec = a.rec + rd;
     GapWalkState* ws = xa.walk + rd;
-    auto no_record = [&](uint32_t st) {
-        if (lane == 0) { rec->status = st; rec->n_ops = 0; rec->n_fwd_ops = 0; rec->score = 0; ws->done = 1; }
-    };
-    if (rs->status & kNoWalk) {
-        if (round == la.S - 1) no_record(rs->status);      // (no walk state: reported in the first round)
+    auto over = [&] { if (lane == 0) ws->done = 1; };      // the record, or its absence, is written
+    if (rs->status & ST_NO_RECORD) {
+        if (round == la.S - 1) { no_record(rec, lane, rs->status); over(); }      // (no walk state: reported in the first round)
         return;
     }
     if (ws->done) return;
     const int n = (int)(a.read_off[rd + 1] - a.read_off[rd]);
     const int k = rs->fwd_path;
-    const int pbeg = a.poff[k], m = a.poff[k + 1] - pbeg;
-    int i = ws->i, j = ws->j, state = ws->state, nops = ws->nops, steps = ws->steps;
+    const int m = a.poff[k + 1] - a.poff[k];
+    WalkPos p{ws->i, ws->j, ws->state, ws->nops, ws->steps};
     // an unfinished walk stands on a cell inside the matrix, in a stripe at or below the round
-    if (i < 1 || i > m || i >= la.rows1 || j < 1 || j > n || n + 1 > la.S * STRIPE || (unsigned)state > (unsigned)S_XARRIVE || nops < 0 ||
-        steps < 0 || j / STRIPE > round) {
-        no_record(ST_WOULD_PANIC);
+    if (p.i < 1 || p.i > m || p.i >= la.rows1 || p.j < 1 || p.j > n || n + 1 > la.S * STRIPE || (unsigned)p.state > (unsigned)S_XARRIVE ||
+        p.nops < 0 || p.steps < 0 || p.j / STRIPE > round) {
+        no_record(rec, lane, ST_WOULD_PANIC);
+        over();
         return;
     }
-    if (j / STRIPE < round) return;                  // its stripe comes in a later round
-    const int c0 = round * STRIPE;
-    const int end_col = kLocal ? rs->rec_col : n;
-    const uint32_t* dirs = a.dirs + (long long)rd * a.dirs_stride;
-    uint32_t wd[WL] = {0, 0, 0, 0};
-    int have = -1;
-    uint8_t* ops = a.ops + (long long)rd * a.ops_stride;
-    const int cap = 3 * (m + n) + 3;                // (the count of k_gap_trace_local: at most 2 iterations per row, 3 per column)
-    bool stopped = false;
-    auto emit = [&](uint8_t op) { if (lane == 0 && nops < a.ops_stride) ops[nops] = op; ++nops; };
-    while (i > 0 && j > 0 && j >= c0 && steps < cap) {
-        ++steps;
-        const uint32_t cell = dir_cell(dirs, la.rows1, lane, i, j - c0, have, wd);      // (the buffer holds this stripe alone)
-        if (state == S_XARRIVE) {                   // an L was walked into (i, j): does the run open here?
-            state = (cell & 8u) ? S_H : S_X;
-        } else if (state == S_H) {
-            const uint32_t src = cell & 3u;
-            if (kLocal && src == 0u) { stopped = true; break; }          // H == 0: checked first
-            if (src == 1u) { emit(OP_D); i -= 1; j -= 1; }
-            else state = src == 2u ? S_Y : S_X;
-        } else if (state == S_Y) {
-            emit(OP_U);
-            i -= 1;
-            state = (cell & 4u) ? S_H : S_Y;
-        } else {
-            emit(OP_L);
-            j -= 1;
-            state = S_XARRIVE;
-        }
-    }
-    if (!stopped && i > 0 && j > 0) {
-        if (steps >= cap) { no_record(ST_WOULD_PANIC); return; }
-        // the column left the stripe: the next stripe's round goes on from here
-        if (lane == 0) { ws->i = i; ws->j = j; ws->state = state; ws->nops = nops; ws->steps = steps; }
-        return;
-    }
-    if (kLocal) {
-        // a border cell is H = 0 (X and Y are NEG there): the walk may arrive in H, or by an L whose run opens on column 0
-        const bool border = (i == 0 || j == 0) && (state == S_H || (state == S_XARRIVE && j == 0));
-        if (!(stopped || border) || nops < 1 || nops > a.ops_stride) { no_record(ST_WOULD_PANIC); return; }
-    } else {
-        // the borders: only one state is finite there, and no direction word is needed
-        while (j > 0) { emit(OP_L); j -= 1; }
-        while (!semi && i > 0) { emit(OP_U); i -= 1; }
-        if (nops > a.ops_stride) { no_record(ST_WOULD_PANIC); return; }
-    }
-    if (lane == 0) {
-        rec->status = rs->status;
-        rec->score = rs->trace_score;
-        rec->fscore = 0.f;
-        rec->end_row = rs->end_row;
-        rec->end_col = end_col;
-        rec->stop_row = kLocal && i > 0 ? a.prow[pbeg + i - 1] : 0;
-        rec->stop_col = kLocal ? j : 0;
-        rec->best_path = k; rec->rev_path = k;
-        rec->fen = 0; rec->rsn = 0; rec->rec_col = 0; rec->displacement = 0;
-        rec->n_ops = nops; rec->n_fwd_ops = nops;
-        rec->pad = 0;
-        ws->done = 1;
-    }
+    if (p.j / STRIPE < round) return;                // its stripe comes in a later round
+    if (gap_walk<kLocal>(a, rd, lane, semi, kLocal ? rs->rec_col : n, p, round * STRIPE, CL, la.rows1)) over();
+    else if (lane == 0) { ws->i = p.i; ws->j = p.j; ws->state = p.state; ws->nops = p.nops; ws->steps = p.steps; }      // the next stripe's round goes on from here
 }
 
 }  // namespace
@@ -274,14 +203,6 @@ __global__ __launch_bounds__(64) void k_gap_walk_long(GapXLongArgs xa, int semi,
 __global__ __launch_bounds__(64) void k_gap_walk_local_long(GapXLongArgs xa, int round) { walk_round<true>(xa, 0, round); }
 
 // ---- launchers ---------------------------------------------------------------------------------------------------------------
-#define RG_GAP_XLONG_DISPATCH(K, grid, ...)                                                 \
-    switch (kind) {                                                                         \
-        case GAP_LONG_GLOBAL: RG_LAUNCH(K, (0), grid, dim3(WAVE), 0, s, __VA_ARGS__);       \
-        case GAP_LONG_SEMI: RG_LAUNCH(K, (1), grid, dim3(WAVE), 0, s, __VA_ARGS__);         \
-        case GAP_LONG_LOCAL: RG_LAUNCH(K, (2), grid, dim3(WAVE), 0, s, __VA_ARGS__);        \
-        default: return nullptr;                                                            \
-    }
-
 static bool geometry_ok(const GapXLongArgs& a) {
     return a.l.S >= 2 && a.l.S <= GAP_XLONG_MAX_STRIPES && a.l.rows1 >= 1 && a.l.g.dirs && a.l.g.dirs_stride >= (long long)a.l.rows1 * WL * WAVE &&
            a.ckpt && a.ckpt_stride >= 2ll * (a.l.S - 1) * a.l.rows1 && a.walk;
@@ -290,20 +211,20 @@ static bool geometry_ok(const GapXLongArgs& a) {
 const char* launch_gap_ckpt_long(const GapXLongArgs& a, int nreads, int kind, hipStream_t s) {
     if (!geometry_ok(a)) return nullptr;
     const dim3 grid(nreads);
-    RG_GAP_XLONG_DISPATCH(k_gap_ckpt_long, grid, a)
+    RG_GAP_SWITCH_KIND(k_gap_ckpt_long, grid, a);
     return nullptr;
 }
 const char* launch_gap_redo_long(const GapXLongArgs& a, int nreads, int kind, int round, hipStream_t s) {
     if (!geometry_ok(a) || round < 0 || round >= a.l.S) return nullptr;
     const dim3 grid(nreads);
-    RG_GAP_XLONG_DISPATCH(k_gap_redo_long, grid, a, round)
+    RG_GAP_SWITCH_KIND(k_gap_redo_long, grid, a, round);
     return nullptr;
 }
 const char* launch_gap_walk_long(const GapXLongArgs& a, int nreads, int kind, int round, hipStream_t s) {
     if (!geometry_ok(a) || round < 0 || round >= a.l.S) return nullptr;
-    if (kind == GAP_LONG_LOCAL) RG_LAUNCH0(k_gap_walk_local_long, dim3(nreads), dim3(WAVE), 0, s, a, round);
-    if (kind != GAP_LONG_GLOBAL && kind != GAP_LONG_SEMI) return nullptr;
-    RG_LAUNCH0(k_gap_walk_long, dim3(nreads), dim3(WAVE), 0, s, a, kind == GAP_LONG_SEMI ? 1 : 0, round);
+    if (kind == GAP_LOCAL) RG_LAUNCH0(k_gap_walk_local_long, dim3(nreads), dim3(WAVE), 0, s, a, round);
+    if (kind != GAP_GLOBAL && kind != GAP_SEMI) return nullptr;
+    RG_LAUNCH0(k_gap_walk_long, dim3(nreads), dim3(WAVE), 0, s, a, kind == GAP_SEMI ? 1 : 0, round);
 }
 
 }  // namespace rg

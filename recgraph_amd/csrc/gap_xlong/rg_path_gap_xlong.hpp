@@ -27,7 +27,7 @@ struct GapXLongArgs {
     GapWalkState* walk;           // [reads]
 };
 
-// kind: GapLongKind (56: global, 57: semi, 62: local); round: the stripe the launch works on, l.S - 1 down to 0
+// kind: GapKind (56: global, 57: semi, 62: local); round: the stripe the launch works on, l.S - 1 down to 0
 const char* launch_gap_ckpt_long(const GapXLongArgs& a, int nreads, int kind, hipStream_t s);
 const char* launch_gap_redo_long(const GapXLongArgs& a, int nreads, int kind, int round, hipStream_t s);
 const char* launch_gap_walk_long(const GapXLongArgs& a, int nreads, int kind, int round, hipStream_t s);

@@ -251,50 +251,52 @@ int Run::enqueue_pathwise_gap() {
     ga.P = h.P; ga.o = p.gap_open; ga.e = p.gap_ext; ga.state = w.state.p; ga.dirs = w.gdirs.p; ga.dirs_stride = plan.gdirs_stride;
     ga.cells = d_cells; ga.rec = d_rec + done; ga.ops = d_ops + (long long)done * ops_stride; ga.ops_stride = ops_stride;
     const int C = plan.C;
-    const bool semi = plan.semi;
-    if (plan.nwv > 1) {
-        // column stripes (a long mode with a read over 2047 bases): the pick kernels are the base modes', told the striped width
-        GapLongArgs la;
-        memset(&la, 0, sizeof la);
-        la.g = ga; la.S = plan.nwv; la.rows1 = h.max_path_rows + 1;
-        la.bnd = w.gbnd.p; la.bnd_stride = plan.gbnd_stride; la.dbnd = w.gdbnd.p;
-        const int kind = plan.local ? GAP_LONG_LOCAL : semi ? GAP_LONG_SEMI : GAP_LONG_GLOBAL;
-        if (plan.gap_xlong) {
-            // one stripe of direction words: checkpoints first, then per stripe, last to first, the rebuild and the walk (no read-back
-            // in between: a read whose walk is elsewhere returns at once).  The score pass is the long modes', its stripe cap lifted
-            static_assert(sizeof(GapWalkState) == 32, "the plan counts 32 bytes of walk state per read");
-            GapXLongArgs xa;
-            memset(&xa, 0, sizeof xa);
-            la.dbnd = nullptr;
-            xa.l = la; xa.ckpt = w.gckpt.p; xa.ckpt_stride = plan.gckpt_stride; xa.walk = w.gwalk.p;
-            RG_TRY(T.run("k_gap_score_long", [&] { return launch_gap_score_long(la, chunk, kind, stream, GAP_XLONG_MAX_STRIPES); }));
-            if (plan.local) RG_TRY(T.run("k_gap_pick_local", [&] { return launch_gap_pick_local(ga, chunk, plan.nwv * C, stream); }));
-            else RG_TRY(T.run("k_gap_pick", [&] { return launch_gap_pick(ga, chunk, plan.nwv * C, semi, stream); }));
-            RG_TRY(T.run("k_gap_ckpt_long", [&] { return launch_gap_ckpt_long(xa, chunk, kind, stream); }));
-            for (int round = plan.nwv - 1; round >= 0; --round) {
-                RG_TRY(T.run("k_gap_redo_long", [&] { return launch_gap_redo_long(xa, chunk, kind, round, stream); }));
-                RG_TRY(T.run(plan.local ? "k_gap_walk_local_long" : "k_gap_walk_long", [&] { return launch_gap_walk_long(xa, chunk, kind, round, stream); }));
-            }
-            return read_back();
-        }
-        RG_TRY(T.run("k_gap_score_long", [&] { return launch_gap_score_long(la, chunk, kind, stream); }));
-        if (plan.local) RG_TRY(T.run("k_gap_pick_local", [&] { return launch_gap_pick_local(ga, chunk, plan.nwv * C, stream); }));
-        else RG_TRY(T.run("k_gap_pick", [&] { return launch_gap_pick(ga, chunk, plan.nwv * C, semi, stream); }));
+    const bool semi = plan.semi, local = plan.local;
+    const int kind = local ? GAP_LOCAL : semi ? GAP_SEMI : GAP_GLOBAL;
+    // a step whose local kind has a kernel of its own: (label, launch) of the global / semi kinds, then of the local kind
+    auto step = [&](const char* name, auto&& launch, const char* name_local, auto&& launch_local) {
+        return local ? T.run(name_local, launch_local) : T.run(name, launch);
+    };
+    // (the pick kernels are the base modes' in every pipeline: a striped batch tells them the striped width)
+    auto pick = [&] {
+        return step("k_gap_pick", [&] { return launch_gap_pick(ga, chunk, plan.nwv * C, semi, stream); },
+                    "k_gap_pick_local", [&] { return launch_gap_pick_local(ga, chunk, plan.nwv * C, stream); });
+    };
+    if (plan.nwv == 1) {
+        // single wave: the whole row in one wave's registers
+        RG_TRY(step("k_gap_score", [&] { return launch_gap_score(ga, chunk, C, semi, stream); },
+                    "k_gap_score_local", [&] { return launch_gap_score_local(ga, chunk, C, stream); }));
+        RG_TRY(pick());
+        RG_TRY(step("k_gap_dirs", [&] { return launch_gap_dirs(ga, chunk, C, semi, stream); },
+                    "k_gap_dirs_local", [&] { return launch_gap_dirs_local(ga, chunk, C, stream); }));
+        RG_TRY(step("k_gap_trace", [&] { return launch_gap_trace(ga, chunk, C, semi, stream); },
+                    "k_gap_trace_local", [&] { return launch_gap_trace_local(ga, chunk, C, stream); }));
+        return read_back();
+    }
+    // column stripes (a long mode with a read over 2047 bases); with checkpoints (gap_xlong) the score pass is the same, its stripe cap lifted
+    GapLongArgs la;
+    memset(&la, 0, sizeof la);
+    la.g = ga; la.S = plan.nwv; la.rows1 = h.max_path_rows + 1;
+    la.bnd = w.gbnd.p; la.bnd_stride = plan.gbnd_stride; la.dbnd = plan.gap_xlong ? nullptr : w.gdbnd.p;
+    RG_TRY(T.run("k_gap_score_long", [&] { return launch_gap_score_long(la, chunk, kind, stream, plan.gap_xlong ? GAP_XLONG_MAX_STRIPES : GAP_LONG_MAX_STRIPES); }));
+    RG_TRY(pick());
+    if (!plan.gap_xlong) {
+        // striped: the direction words of every stripe, one walk
         RG_TRY(T.run("k_gap_dirs_long", [&] { return launch_gap_dirs_long(la, chunk, kind, stream); }));
-        RG_TRY(T.run(plan.local ? "k_gap_trace_local_long" : "k_gap_trace_long", [&] { return launch_gap_trace_long(la, chunk, kind, stream); }));
+        RG_TRY(T.run(local ? "k_gap_trace_local_long" : "k_gap_trace_long", [&] { return launch_gap_trace_long(la, chunk, kind, stream); }));
         return read_back();
     }
-    if (plan.local) {
-        RG_TRY(T.run("k_gap_score_local", [&] { return launch_gap_score_local(ga, chunk, C, stream); }));
-        RG_TRY(T.run("k_gap_pick_local", [&] { return launch_gap_pick_local(ga, chunk, C, stream); }));
-        RG_TRY(T.run("k_gap_dirs_local", [&] { return launch_gap_dirs_local(ga, chunk, C, stream); }));
-        RG_TRY(T.run("k_gap_trace_local", [&] { return launch_gap_trace_local(ga, chunk, C, stream); }));
-        return read_back();
+    // striped with checkpoints: one stripe of direction words: checkpoints first, then per stripe, last to first, the rebuild and the
+    // walk (no read-back in between: a read whose walk is elsewhere returns at once)
+    static_assert(sizeof(GapWalkState) == 32, "the plan counts 32 bytes of walk state per read");
+    GapXLongArgs xa;
+    memset(&xa, 0, sizeof xa);
+    xa.l = la; xa.ckpt = w.gckpt.p; xa.ckpt_stride = plan.gckpt_stride; xa.walk = w.gwalk.p;
+    RG_TRY(T.run("k_gap_ckpt_long", [&] { return launch_gap_ckpt_long(xa, chunk, kind, stream); }));
+    for (int round = plan.nwv - 1; round >= 0; --round) {
+        RG_TRY(T.run("k_gap_redo_long", [&] { return launch_gap_redo_long(xa, chunk, kind, round, stream); }));
+        RG_TRY(T.run(local ? "k_gap_walk_local_long" : "k_gap_walk_long", [&] { return launch_gap_walk_long(xa, chunk, kind, round, stream); }));
     }
-    RG_TRY(T.run("k_gap_score", [&] { return launch_gap_score(ga, chunk, C, semi, stream); }));
-    RG_TRY(T.run("k_gap_pick", [&] { return launch_gap_pick(ga, chunk, C, semi, stream); }));
-    RG_TRY(T.run("k_gap_dirs", [&] { return launch_gap_dirs(ga, chunk, C, semi, stream); }));
-    RG_TRY(T.run("k_gap_trace", [&] { return launch_gap_trace(ga, chunk, C, semi, stream); }));
     return read_back();
 }
 

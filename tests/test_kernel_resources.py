@@ -78,6 +78,35 @@ def test_no_valu_write_into_a_wide_buffer_store_in_flight():
     assert len(kernel_resources.scan_store_hazards(listing, want64=True)[0]) == 4
 
 
+def test_gap_family_kernels_keep_their_registers():
+    """Every instantiation of the four affine-gap pathwise kernel files shares one row step, one walk and one record writer
+    (gap/rg_path_gap_common.hpp): none may use scratch or spill a VGPR, and none may fall below the occupancy it had while each
+    file carried its own copy (profiles/gap_family_notes.md has the table; SGPR spills exist in k_gap_score_long and are not
+    asserted)."""
+    import re
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import kernel_resources
+    by_c = {"k_gap_score": {4: 8, 8: 8, 16: 6, 32: 3}, "k_gap_score_local": {4: 8, 8: 8, 16: 6, 32: 3},
+            "k_gap_dirs": {4: 8, 8: 8, 16: 4, 32: 2}, "k_gap_dirs_local": {4: 8, 8: 8, 16: 5, 32: 2}}
+    seen = 0
+    for src in ("gap/rg_path_gap.hip", "gap_local/rg_path_gap_local.hip", "gap_long/rg_path_gap_long.hip", "gap_xlong/rg_path_gap_xlong.hip"):
+        for k in kernel_resources.report(src):
+            m = re.fullmatch(r"rg::(k_gap_\w+?)(?:<(\d+)(?:, \w+)?>)?", k["name"])
+            assert m, k["name"]
+            kernel, arg = m.group(1), m.group(2)
+            if kernel in by_c:
+                floor = by_c[kernel][int(arg)]                   # columns per lane
+            elif kernel.endswith("_long") and arg is not None:
+                floor = 3                                        # the striped row loops, 32 columns per lane, per kind
+            else:
+                assert arg is None and re.fullmatch(r"k_gap_(pick|trace|walk)(_local)?(_long)?", kernel), k["name"]
+                floor = 8                                        # pick and walk kernels
+            assert k["ScratchSize [bytes/lane]"] == 0 and k["VGPRs Spill"] == 0, (k["name"], k)
+            assert k["Occupancy [waves/SIMD]"] >= floor, (k["name"], floor, k)
+            seen += 1
+    assert seen == 18 + 10 + 8 + 8
+
+
 def test_poa_kernels_use_no_scratch():
     """`k_m0_simd` and `k_poa_banded` keep the previous row's chunks in registers — the compiler once fused the select chains
     that pick a chunk into a dynamically indexed vector it kept in scratch (32 / 48 bytes per lane, dependent scratch loads in
