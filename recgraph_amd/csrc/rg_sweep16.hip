@@ -277,11 +277,8 @@ constexpr int SWEEP16_WAVES = 2;
 // forward sweep (37.4 vs 37.5 ms, and the variant spills 48 registers with them) and 0.7 ms SLOWER in the reverse one (34.3 vs
 // 33.6): their runs end in tails, whose epilogue separates the loads from the stores anyway (profiles/r04_notes.md)
 //
-// Register runs: the next row's score profile read from LDS a row ahead, behind this row's member steps.  Measured SLOWER (it
-// spills: 98.9 k against 114.3 k reads/s at config 5, profiles/r06_notes.md).  The code stays, switched off (kAhead in the kernel):
-// taking it out changes the capture order of the run loop's closure, and the compiler then schedules a few scalar instructions of
-// most variants differently — no longer the same kernels
-constexpr bool PROFILE_AHEAD = false;
+// Register runs: the next row's score profile read from LDS a row ahead, behind this row's member steps, measured SLOWER twice (it
+// spills: 98.9 k against 114.3 k reads/s at config 5, profiles/r05_notes.md, r06_notes.md) and is gone with the counted row loop.
 //
 // Gather runs (see k_sweep16 and the GATHER RUN comment) are compiled into every variant, also the record variants at 32 columns
 // per lane (round 6 — 32 spilled registers, and still 21.4 k -> 24.9 k reads/s at 1.5 kbp).
@@ -1323,31 +1320,36 @@ __global__ __launch_bounds__(64, SWEEP16_WAVES) void k_sweep16(SweepArgs a) {
                 for (int kk = 0; kk < KRUN; ++kk) { mk[kk] = tm ? kbase + __builtin_ctzll(tm) : 0; tm = tm ? (tm & (tm - 1)) : 0; }
             }
             int rr[KRUN > 0 ? KRUN : 1][H];
+            // Where runs do not chain, the run's rows are loaded and stored INSIDE the loop body of the run's member count (run_rows).
+            // Loaded in front of the dispatch and stored behind it, the rows of every count had to meet in one set of registers on
+            // either side: the compiler moved them there and back with ~50 v_mov per run and held copies of rows across the
+            // 4-member loop (the headline variant: 224 -> 176 VGPRs).  Chained runs hand the next run's rows over around the
+            // dispatch and keep that form; so do the wide variants (kRowsInBody below; see the WIDE comment in run_rows).
+            auto ld_run = [&](int nrun) {
 #pragma unroll
-            for (int kk = 0; kk < KRUN; ++kk)
-                if (kk < rnm) ld_row(mk[kk], rr[kk]);
-            // wait for the run's rows HERE: otherwise the compiler's wait sits at the top of the row loop as vmcnt(0) (one
-            // counter for loads and stores on gfx9) and every row also waits for the direction-word store of the row before
-            {
+                for (int kk = 0; kk < KRUN; ++kk)
+                    if (kk < nrun) ld_row(mk[kk], rr[kk]);
+                // wait for the run's rows HERE: otherwise the compiler's wait sits at the top of the row loop as vmcnt(0) (one
+                // counter for loads and stores on gfx9) and every row also waits for the direction-word store of the row before
                 RG_STALL_BEGIN();
                 __builtin_amdgcn_s_waitcnt(0x0F70);
 #if defined(RG_SWEEP16_STALLSTAT) && RG_SWEEP16_STALLSTAT == 1
                 RG_STALL_END(st_run); ++st_nrun;
 #endif
-            }
+            };
+            auto st_run = [&](int nrun) {
+#pragma unroll
+                for (int kk = 0; kk < KRUN; ++kk)
+                    if (kk < nrun) st_row(mk[kk], rr[kk]);
+            };
+            constexpr bool kRowsInBody = !kChain && !kWide;
+            if constexpr (!kRowsInBody) ld_run(rnm);
 #if defined(RG_SWEEP16_STALLSTAT) && RG_SWEEP16_STALLSTAT == 3
             const unsigned long long st_rb = __builtin_amdgcn_s_memtime();
 #endif
             int ri = i, rli = li, rslot = slot, rw1 = w1, rfl = 7;
             int rleft = run_left;               // rows left in the counted run, this one included (the record's run field)
             bool tail = false;
-            // The row's score profile (two 16-byte LDS reads per lane, ~100 cycles before the diagonal step can use them) can be
-            // fetched a row AHEAD: a record whose run field counts more rows than itself is followed by the next inner row of
-            // its run, so its profile row is known — and `s` is dead — as soon as the members have their steps.  Off: see
-            // PROFILE_AHEAD.  (not at 32 columns per lane: a row is 16 registers there and the variant is out of them)
-            constexpr bool kAhead = PROFILE_AHEAD && C <= 16;
-            int s[H];
-            if (kAhead) load_steps(rli, s);
             for (;;) {          // (chained runs)
             tail = false; rfl = 7;
             // ONE LOOP BODY PER GROUP SIZE (round 6): the rows of a run with RN members, RN a compile-time constant.  With the
@@ -1363,15 +1365,39 @@ __global__ __launch_bounds__(64, SWEEP16_WAVES) void k_sweep16(SweepArgs a) {
             // (every row of the run — and its tail — has the run's members; wide runs: a member of any page may be a picked path)
             const unsigned long long run_sel = kWide ? (wide_sel ? ~0ull : 0ull) : rgm;
             const int run_page = 0;
+            // (RN == rnm.  run_dispatch_from clamps its count to 1 .. KRUN, so this rests on 1 <= rnm <= KRUN: a register run is
+            // entered with nme <= KRUN members — nm <= KRUN, or thinned to that by retirement —, and a record none of whose members is
+            // computed, gm == 0, is skipped at the top of the record loop.  With another count the body would load and store the
+            // rows of mk[] entries that name no member.)
+            if constexpr (kRowsInBody) ld_run(RN);
             unsigned nrows = 0;                 // rows of this run: the cell counters move once per run, not once per row
+            // TWO LEVELS.  The inner loop is COUNTED: a record whose run field counts rleft rows is followed by rleft - 1 inner rows
+            // of the same segment — same group, flags 7 (rg_steps.cpp builds the field that way and moves runs whole; a capped
+            // field, 63, says "at least 63") — so the rows from record t on that also lie in the 64-record block `recs` holds run
+            // on a down-counter alone: no block test, no run-field test, no end-of-table test, `tail` does not change, `recs`, `blk`
+            // and `live` are not assigned, and a row's fields come from readlanes at an index that advances by one.  The outer loop
+            // turns once per block switch, capped field, tail or run end and does everything else.  (As one loop with four exits a
+            // continuing lean one-member row issued ~46 instructions between the alpha's last one and the back edge — exit tests
+            // materialised as lane masks, phi copies of `recs`, the block switch twice —, counted it issues 10:
+            // profiles/run_loop_notes.md.)
             while (true) {
+                // (record t is in the block `recs` holds: fetch / to_block below brought it there.  A tail is one row; wide runs
+                // step over continuation entries, which may lie in the next block already: one row per turn of the outer loop)
+                int cnt = 1;
+                if constexpr (!kWide) {
+                    if (!tail) cnt = max(min(min(rleft, WAVE - (t & (WAVE - 1))), nsteps - t), 1);     // (>= 1 by the tables; a counter of 0 would never end)
+                }
+                nrows += (unsigned)cnt;
+                int idx = t & (WAVE - 1);
+                for (int left = cnt;;) {
                 const int g_i = gcost;
                 const int g0 = kSemi ? 0 : g_i;
                 int XU[H], XL[H];
 #if defined(RG_SWEEP16_STALLSTAT) && RG_SWEEP16_STALLSTAT == 3
                 ++st_nrun;
 #endif
-                if (!kAhead) load_steps(rli, s);
+                int s[H];
+                load_steps(rli, s);
                 int lmax;
                 RowOps16<C>::alpha(rr[0], s, g_i, g0, lane, XU, XL, lmax);
                 if constexpr (!kLean) {
@@ -1394,12 +1420,6 @@ __global__ __launch_bounds__(64, SWEEP16_WAVES) void k_sweep16(SweepArgs a) {
                     for (int kk = 1; kk < KRUN; ++kk)
                         if (kk < RN) RowOps16<C>::member_p2(rr[kk], ML, lmask, zl[kk], vlo[kk]);
                 }
-                if (kAhead && !tail && rleft > 1) {
-                    const int tn = t + 1;
-                    if ((tn >> 6) != blk) to_block(tn >> 6);
-                    load_steps((__builtin_amdgcn_readlane(recs.x, tn & (WAVE - 1)) >> 20) & 7, s);
-                }
-                ++nrows;
                 if (kRec && kColmax == 0 && tail) {
                     if (track) {
                         if (rfl & F_FIRST) row_open = false;
@@ -1408,8 +1428,12 @@ __global__ __launch_bounds__(64, SWEEP16_WAVES) void k_sweep16(SweepArgs a) {
 #pragma unroll
                         for (int kk = 1; kk < KRUN; ++kk) if (kk < RN) fold_keys(key, rr[kk], mk[kk]);
                         row_open = true;
-                        // the tail's row: its epilogue when this was its last group
-                        if (rfl & F_LAST) { row_end(ri, ((rw1 >> 20) & 511) - 1, key); row_open = false; }
+                        // the tail's row: its epilogue when this was its last group.  (Opaque copies of its row and knm: in the lean
+                        // form both are invariant in the counted loop, and the compiler computed the epilogue's per-lane
+                        // thresholds in front of it — nine registers held across every row of the 4-member loop for its one tail)
+                        int tri = ri, tw1 = rw1;
+                        if constexpr (kLean) asm volatile("" : "+s"(tri), "+s"(tw1));
+                        if (rfl & F_LAST) { row_end(tri, ((tw1 >> 20) & 511) - 1, key); row_open = false; }
                         else keys_st(key);
                     }
                 } else if constexpr (kLean) {
@@ -1487,39 +1511,66 @@ __global__ __launch_bounds__(64, SWEEP16_WAVES) void k_sweep16(SweepArgs a) {
                     for (int kk = 0; kk < KRUN; ++kk) if (kk < RN) end_fold(mk[kk], ri, rr[kk]);
                     end_row_done(ri);
                 }
-                t += kWide ? went : 1;                          // (wide runs: over the row's continuation entries)
+                if (--left == 0) break;
+                // the next row of the counted stretch: neither its flags nor its members are looked at, and only the words a row
+                // of this form uses are fetched (lean: the base code.  A tail behind the run fetches its own row, slot and knm below)
+                ++idx;
+                const int nw0 = __builtin_amdgcn_readlane(recs.x, idx);
+                rli = (nw0 >> 20) & 7;
+                if constexpr (!kLean) {
+                    const int nw1 = __builtin_amdgcn_readlane(recs.y, idx);
+                    ri = nw0 & 0xfffff; rslot = nw1 & 0xfffff; rw1 = nw1;
+                }
+                }
+                t += kWide ? went : cnt;                        // (wide runs: over the row's continuation entries)
                 if (tail || t >= nsteps) break;                 // (a tail ends its run)
-                if (rleft > 1) {
-                    // the run goes on: a record whose run field counts more rows than itself is followed by the next inner row
-                    // of the same segment — same group, flags 7 (rg_steps.cpp builds the field that way and moves runs whole) —
-                    // so neither its flags nor its members are looked at, and only two of its four words are fetched
-                    if ((t >> 6) != blk) to_block(t >> 6);
-                    if constexpr (kLean) {
-                        // (a tail behind the run fetches its own row, slot and knm below)
-                        const int nw0 = __builtin_amdgcn_readlane(recs.x, t & (WAVE - 1));
-                        rli = (nw0 >> 20) & 7;
+                if constexpr (kWide) {
+                    // WIDE variants: one row per turn (cnt == 1, the counted loop above folds away), and behind the row the code
+                    // of the loop as it was before it was counted — the run's next row first, the look at a foreign record behind
+                    // it.  These variants sit at 256 registers with spills; with the non-wide code below (and the rows loaded in
+                    // the body) their sweeps of the 128-path region case measured slower in every pair of runs
+                    // (profiles/run_loop_notes.md, section 6), so they keep what they had.
+                    if (rleft > 1) {
+                        if ((t >> 6) != blk) to_block(t >> 6);
+                        const int nw0 = __builtin_amdgcn_readlane(recs.x, t & (WAVE - 1)), nw1 = __builtin_amdgcn_readlane(recs.y, t & (WAVE - 1));
+                        ri = nw0 & 0xfffff; rli = (nw0 >> 20) & 7; rslot = nw1 & 0xfffff; rw1 = nw1;
                         rleft = (nw0 >> 26) & 63;
                         continue;
                     }
-                    const int nw0 = __builtin_amdgcn_readlane(recs.x, t & (WAVE - 1)), nw1 = __builtin_amdgcn_readlane(recs.y, t & (WAVE - 1));
+                    const int pw = peek_w0(t);
+                    const int nf = (pw >> 23) & 7;
+                    const bool to_tail = kRec && kColmax == 0 && (nf & F_INNER) && ((pw >> 26) & 63) == 0;
+                    if (!to_tail && (nf != 7 || ((pw >> 26) & 63) == 0)) break;
+                    if (peek_gm(t) != rgm) break;
+                    int nw0, nw1;
+                    unsigned long long ngm;
+                    fetch(t, nw0, nw1, ngm);
                     ri = nw0 & 0xfffff; rli = (nw0 >> 20) & 7; rslot = nw1 & 0xfffff; rw1 = nw1;
-                    rleft = (nw0 >> 26) & 63;
-                    continue;
+                    tail = to_tail; rfl = nf;
+                    rleft = to_tail ? 0 : (nw0 >> 26) & 63;
+                } else {
+                // NOT wide.  `last`, the run field of the row just done (its record is the one before t, in the block `recs` still
+                // holds): above 1, the run goes on in the next block or behind a capped field
+                const int last = (__builtin_amdgcn_readlane(recs.x, (t - 1) & (WAVE - 1)) >> 26) & 63;
+                const int nw0 = peek_w0(t);                     // (the one place of the loop that moves `recs` to the next block)
+                const int nf = (nw0 >> 23) & 7, nfield = (nw0 >> 26) & 63;
+                const bool to_tail = kRec && kColmax == 0 && last <= 1 && (nf & F_INNER) && nfield == 0;
+                if (last <= 1) {
+                    if (!to_tail && (nf != 7 || nfield == 0)) break;    // next record starts another segment (a HEAD or a general row)
+                    // ... or is an inner row of ANOTHER segment: in a split table the rows of a segment whose first row had all
+                    // its groups moved away as tails can follow an unrelated run (found by test_random_dag_graphs)
+                    const int idt = t & (WAVE - 1);
+                    if ((((unsigned long long)(unsigned)__builtin_amdgcn_readlane(recs.w, idt) << 32) | (unsigned)__builtin_amdgcn_readlane(recs.z, idt)) != rgm) break;
+                    rfl = nf;
                 }
-                const int pw = peek_w0(t);
-                const int nf = (pw >> 23) & 7;
-                const bool to_tail = kRec && kColmax == 0 && (nf & F_INNER) && ((pw >> 26) & 63) == 0;
-                if (!to_tail && (nf != 7 || ((pw >> 26) & 63) == 0)) break;   // next record starts another segment (a HEAD or a general row)
-                // ... or is an inner row of ANOTHER segment: in a split table the rows of a segment whose first row had all
-                // its groups moved away as tails can follow an unrelated run (found by test_random_dag_graphs)
-                if (peek_gm(t) != rgm) break;
-                int nw0, nw1;
-                unsigned long long ngm;
-                fetch(t, nw0, nw1, ngm);
-                ri = nw0 & 0xfffff; rli = (nw0 >> 20) & 7; rslot = nw1 & 0xfffff; rw1 = nw1;
-                tail = to_tail; rfl = nf;
-                rleft = to_tail ? 0 : (nw0 >> 26) & 63;
-                if (kAhead) load_steps(rli, s);
+                rli = (nw0 >> 20) & 7;
+                tail = to_tail;
+                rleft = nfield;                                 // (a tail: 0)
+                if (!kLean || to_tail) {
+                    const int nw1 = __builtin_amdgcn_readlane(recs.y, t & (WAVE - 1));
+                    ri = nw0 & 0xfffff; rslot = nw1 & 0xfffff; rw1 = nw1;
+                }
+                }
             }
             cells += (unsigned long long)nrows * (unsigned long long)(kWide ? wide_total : __popcll(rgm));
             done += (unsigned long long)nrows * (unsigned long long)RN;
@@ -1527,6 +1578,7 @@ __global__ __launch_bounds__(64, SWEEP16_WAVES) void k_sweep16(SweepArgs a) {
                 sil[3] += (int)nrows;          // (every lane the same word, the same value)
                 if constexpr (kLean) sil[2] += (int)(nrows - (tail ? 1u : 0u));
             }
+            if constexpr (kRowsInBody) st_run(RN);
             };
             auto run_rows_full = [&](auto rn_tag) __attribute__((always_inline)) { run_rows(rn_tag, std::false_type{}); };
             if constexpr (kSilent) {
@@ -1569,9 +1621,7 @@ __global__ __launch_bounds__(64, SWEEP16_WAVES) void k_sweep16(SweepArgs a) {
                     if (kk < __popcll(gm2)) ld_row(mk2[kk], rn[kk]);
             }
             __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0): the next run's rows (every older store is long done)
-#pragma unroll
-            for (int kk = 0; kk < KRUN; ++kk)
-                if (kk < rnm) st_row(mk[kk], rr[kk]);
+            st_run(rnm);
             rnm = __popcll(gm2);
             rgm = gm2;
 #pragma unroll
@@ -1586,12 +1636,9 @@ __global__ __launch_bounds__(64, SWEEP16_WAVES) void k_sweep16(SweepArgs a) {
                 fetch(t, nw0, nw1, ngm);
                 ri = nw0 & 0xfffff; rli = (nw0 >> 20) & 7; rslot = nw1 & 0xfffff; rw1 = nw1;
                 rleft = (nw0 >> 26) & 63;
-                if (kAhead) load_steps(rli, s);
             }
             }                   // (chained runs)
-#pragma unroll
-            for (int kk = 0; kk < KRUN; ++kk)
-                if (kk < rnm) st_row(mk[kk], rr[kk]);
+            if constexpr (!kRowsInBody) st_run(rnm);
 #if defined(RG_SWEEP16_STALLSTAT) && RG_SWEEP16_STALLSTAT == 3
             st_gen += __builtin_amdgcn_s_memtime() - st_rb;
 #endif
