@@ -400,16 +400,7 @@ __device__ __forceinline__ void gap_trace_wave(const GapArgs& a, int semi, int C
 // ---- launchers: the two dispatches (inside a launcher with `C` / `kind`, `s` and the kernel's arguments behind the grid; every case
 // returns the launched instantiation's name, an unknown C / kind returns null) -------------------------------------------------------
 // TAIL: the template arguments behind C, in parentheses: (, true) / ()
-#define RG_GAP_SWITCH_C(K, TAIL, grid, ...)                                                     \
-    do {                                                                                        \
-        switch (C) {                                                                            \
-            case 4: RG_LAUNCH(K, (4 RG_TARGS_ TAIL), grid, dim3(WAVE), 0, s, __VA_ARGS__);      \
-            case 8: RG_LAUNCH(K, (8 RG_TARGS_ TAIL), grid, dim3(WAVE), 0, s, __VA_ARGS__);      \
-            case 16: RG_LAUNCH(K, (16 RG_TARGS_ TAIL), grid, dim3(WAVE), 0, s, __VA_ARGS__);    \
-            case 32: RG_LAUNCH(K, (32 RG_TARGS_ TAIL), grid, dim3(WAVE), 0, s, __VA_ARGS__);    \
-            default: return nullptr;                                                            \
-        }                                                                                       \
-    } while (0)
+#define RG_GAP_SWITCH_C(K, TAIL, grid, ...) RG_SWITCH_C((4, 8, 16, 32), K, TAIL, grid, dim3(WAVE), 0, s, __VA_ARGS__)
 #define RG_GAP_SWITCH_KIND(K, grid, ...)                                                        \
     do {                                                                                        \
         switch (kind) {                                                                         \

@@ -23,6 +23,7 @@
 #include "rg_layer_window.hpp"
 
 #include "../rg_path_kernels.hpp"
+#include "../rg_pk16.hpp"
 
 namespace rg {
 
@@ -31,34 +32,7 @@ namespace {
 constexpr int UNK = LAYER_WINDOW_UNKNOWN;
 constexpr int UNKPAIR = (int)(((unsigned)(UNK & 0xffff) << 16) | (unsigned)(UNK & 0xffff));
 constexpr int KNOWNPAIR = (int)(((unsigned)(LAYER_WINDOW_KNOWN & 0xffff) << 16) | (unsigned)(LAYER_WINDOW_KNOWN & 0xffff));
-constexpr int ONE2 = 0x00010001;
 
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ int pk_add(int a, int b) {
-    return __builtin_bit_cast(int, (s16x2)(__builtin_bit_cast(s16x2, a) + __builtin_bit_cast(s16x2, b)));
-}
-__device__ __forceinline__ int pk_sub(int a, int b) {
-    return __builtin_bit_cast(int, (s16x2)(__builtin_bit_cast(s16x2, a) - __builtin_bit_cast(s16x2, b)));
-}
-__device__ __forceinline__ int pk_max(int a, int b) {
-    return __builtin_bit_cast(int, __builtin_elementwise_max(__builtin_bit_cast(s16x2, a), __builtin_bit_cast(s16x2, b)));
-}
-__device__ __forceinline__ int pk_min(int a, int b) {
-    return __builtin_bit_cast(int, __builtin_elementwise_min(__builtin_bit_cast(s16x2, a), __builtin_bit_cast(s16x2, b)));
-}
-__device__ __forceinline__ int pk_sub_sat(int a, int b) {
-    return __builtin_bit_cast(int, __builtin_elementwise_sub_sat(__builtin_bit_cast(s16x2, a), __builtin_bit_cast(s16x2, b)));
-}
-// per half: 0xffff where the half of `v` is negative, else 0
-__device__ __forceinline__ int pk_sign(int v) {
-    return __builtin_bit_cast(int, (s16x2)(__builtin_bit_cast(s16x2, v) >> (s16x2)(15)));
-}
-__device__ __forceinline__ int pack16(int lo, int hi) { return (int)(((unsigned)hi << 16) | ((unsigned)lo & 0xffffu)); }
-__device__ __forceinline__ int lo16(int v) { return (int)(short)(v & 0xffff); }
-__device__ __forceinline__ int hi16(int v) { return v >> 16; }
-// per half: mask ? a : b
-__device__ __forceinline__ int bfi(int mask, int a, int b) { return __builtin_amdgcn_bitop3_b32(mask, a, b, 0xCA); }
 // Value of lane - 1 (lane 0 reads lane 63: wave_ror:1), `fill` in the lanes where `edge` is all ones.  The fill goes in through a
 // v_bitop3, not a select: a select on the result of a DPP move is turned into a branch around the move, and the lanes the branch
 // disables are then read by their neighbours (the hazard dpp_shr1 of rg_device.hpp describes; its empty asm was sunk into the
@@ -84,16 +58,12 @@ __global__ __launch_bounds__(64, 8) void k_layer_win(LayerArgs a) {
     const int rd = blockIdx.x;
     const int lane = threadIdx.x;
     const PathGraphDev& g = a.g;
-    ReadState* rs = a.state + rd;
-    if (rs->status & (ST_BAD_BASE | ST_WOULD_PANIC | ST_OVERFLOW | ST_RETRY | ST_LAYER_FULL)) return;
+    LayerJob job;
+    if (!job.open(a, rd, ST_BAD_BASE | ST_WOULD_PANIC | ST_OVERFLOW | ST_RETRY | ST_LAYER_FULL, false)) return;
+    ReadState* rs = job.rs;
     const bool rev = a.rev;
-    const int path = rev ? rs->rev_path : rs->fwd_path;
-    const bool recomb = rs->fwd_path != rs->rev_path;
-    if (rev && !recomb) return;  // no recombination: reverse layer not needed
-    const long long ro = a.read_off[rd];
-    const int n = (int)(a.read_off[rd + 1] - ro);
-    const uint8_t* read = a.reads + ro - 1;
-    const int ncols = rev ? n : n + 1;
+    const int path = job.path, n = job.n, ncols = job.ncols;
+    const uint8_t* read = job.read;
     const int GAP = 5;
     __shared__ int sct[64];              // [36]
     __shared__ int s2[5 * 64];           // packed (s - g) pairs by row base and (code_lo | code_hi << 3)
@@ -101,10 +71,7 @@ __global__ __launch_bounds__(64, 8) void k_layer_win(LayerArgs a) {
     if (lane < 36) sct[lane] = a.sc.t[lane];
     __syncthreads();
     const int gcost = __builtin_amdgcn_readfirstlane(sct[GAP]);
-    for (int e = lane; e < 5 * 64; e += WAVE) {
-        const int li = e >> 6, cl = e & 7, ch = (e >> 3) & 7;
-        s2[e] = (cl < 6 && ch < 6) ? pack16(sct[li * 6 + cl] - gcost, sct[li * 6 + ch] - gcost) : 0;
-    }
+    pair_table(s2, sct, gcost, lane);
     auto code = [&](int c) -> int { return (c >= 1 && c < ncols) ? (int)(rev ? read[n - c + 1] : read[c]) : 4; };
     for (int b = lane; b < NBLK; b += WAVE) {
         int kk = 0;
@@ -113,15 +80,9 @@ __global__ __launch_bounds__(64, 8) void k_layer_win(LayerArgs a) {
         kkp[b] = kk;
     }
     __syncthreads();
-    const int* prow = rev ? a.rprow : a.fprow;
-    const int* pslot = rev ? a.rpslot : a.fpslot;
-    const int* poff = rev ? a.rpoff : a.fpoff;
-    const int pbase = poff[path];
-    const int nrows = poff[path + 1] - pbase;
-    // the walk's start cell (k_trace): forward (fen | end row, rec_col | n), reverse (rsn, mirrored rec_col)
-    const int start_row = rev ? rs->rsn : (recomb ? rs->fen : rs->end_row);
-    const int start_col = rev ? n - rs->rec_col : (recomb ? rs->rec_col : n);
-    const int sidx = __builtin_amdgcn_readfirstlane(layer_row_index(prow + pbase, nrows, start_row, rev));
+    // the walk's start cell (k_trace)
+    const int start_col = job.start_col;
+    const int sidx = __builtin_amdgcn_readfirstlane(layer_row_index(job.prow + job.pbase, job.nrows, job.start_row, rev));
     if (sidx < 0) return;                // (k_trace reports it)
     const int t_start = sidx + 1;
     uint8_t* tdir = reinterpret_cast<uint8_t*>(reinterpret_cast<uint32_t*>(a.layer) + (long long)rd * a.layer_stride);
@@ -137,22 +98,17 @@ __global__ __launch_bounds__(64, 8) void k_layer_win(LayerArgs a) {
         const int c0 = blk * CW + r, c1 = c0 + H;
         cur[r] = pack16(c0 < ncols ? 0 : UNK, c1 < ncols ? 0 : UNK);
     }
-    // two-stage look-ahead as in k_layer16: the list entries of row t + PF + 1 are loaded while row t is computed, the loads
-    // they address one iteration later
+    // two-stage look-ahead as in k_layer16 (LayerJob::fetch_idx), over the rows up to the walk's start row
     constexpr int PF = 2;
     int pf_li[PF];
     uint32_t pf_w[PF];
-    int nx_row = -1, nx_slot = 0;
-    auto fetch_idx = [&](int tt) {
-        nx_row = -1; nx_slot = 0;
-        if (tt <= sidx) { nx_row = prow[pbase + tt]; nx_slot = pslot[pbase + tt]; }
-    };
+    auto fetch_idx = [&](int tt) { job.fetch_idx(tt, sidx + 1); };
     auto prefetch = [&](int tt, int& li_o, uint32_t& w_o) {       // row tt, whose list entries are in nx_row / nx_slot
         li_o = 4; w_o = 0;
-        if (nx_row >= 0) {
+        if (job.nx_row >= 0) {
             const int b = block_of(layer_window_left(start_col, t_start, tt + 1, W, WPAD) / CW);
-            li_o = g.lnz[nx_row];
-            w_o = dirs[(long long)nx_slot * a.dir_words + (b * CW) / C];
+            li_o = g.lnz[job.nx_row];
+            w_o = dirs[(long long)job.nx_slot * a.dir_words + (b * CW) / C];
         }
     };
 #pragma unroll
@@ -251,12 +207,8 @@ __global__ __launch_bounds__(64, 8) void k_layer_win(LayerArgs a) {
         for (int r = 0; r < H; ++r) {
             const int d = pk_add(o1, s[r]);
             const int u = pk_add(old[r], GI);
-            const int mx = pk_max(pk_max(d, u), nl);
             const int unk = pk_sign(pk_sub_sat(pk_min(pk_min(d, u), nl), KNOWNPAIR));     // 0xffff where an input is unknown
-            const int nd = pk_sign(pk_sub_sat(d, mx));                  // 0xffff where D does not attain the maximum
-            const int nu = pk_sign(pk_sub_sat(u, mx));
-            const int b0 = __builtin_amdgcn_bitop3_b32(nd, nu, ONE2, 0x8A);           // (~nd | nu) & 1
-            const unsigned code2 = (unsigned)((b0 | (nd & 0x00020002)) & ~unk);
+            const unsigned code2 = decide16(d, u, nl) & ~(unsigned)unk;
             tw |= code2 << (2 * r);
             o1 = old[r];
             nl = cur[r];
@@ -288,18 +240,8 @@ __global__ __launch_bounds__(64, 8) void k_layer_win(LayerArgs a) {
 }
 
 const char* launch_layer_window(const LayerArgs& a, int nreads, int C, int window, hipStream_t s) {
-    if (window == LAYER_WINDOW_NARROW) {
-        switch (C) {
-            case 4: RG_LAUNCH(k_layer_win, (4, 2), dim3(nreads), dim3(64), 0, s, a);
-            case 8: RG_LAUNCH(k_layer_win, (8, 2), dim3(nreads), dim3(64), 0, s, a);
-            default: RG_LAUNCH(k_layer_win, (16, 2), dim3(nreads), dim3(64), 0, s, a);
-        }
-    }
-    switch (C) {
-        case 4: RG_LAUNCH(k_layer_win, (4, 4), dim3(nreads), dim3(64), 0, s, a);
-        case 8: RG_LAUNCH(k_layer_win, (8, 4), dim3(nreads), dim3(64), 0, s, a);
-        default: RG_LAUNCH(k_layer_win, (16, 4), dim3(nreads), dim3(64), 0, s, a);
-    }
+    if (window == LAYER_WINDOW_NARROW) RG_SWITCH_C((4, 8, 16), k_layer_win, (, 2), dim3(nreads), dim3(64), 0, s, a);
+    RG_SWITCH_C((4, 8, 16), k_layer_win, (, 4), dim3(nreads), dim3(64), 0, s, a);
 }
 
 }  // namespace rg

@@ -51,4 +51,24 @@ const char* inst_label(const char* kernel) {
         return ::rg::inst_label<&K>("rg::" #K);                                      \
     } while (0)
 
+// RG_SWITCH_C((4, 8, 16, 32), k_layer, (, false), grid, block, lds bytes, stream, kernel arguments...): the dispatch on the columns per
+// lane, inside a launcher whose parameter `C` holds them.  One RG_LAUNCH per listed value (three or four of them) with that value as
+// the kernel's first template argument and TAIL — in parentheses, with its leading comma: (, true) / () — behind it; a C outside the
+// list launches nothing and returns null (the timer then reports RG_ERR_ARG).  The plan only produces listed values (plan_pathwise).
+#define RG_SWITCH_C_CASE_(K, TAIL, c, ...) case c: RG_LAUNCH(K, (c RG_TARGS_ TAIL), __VA_ARGS__);
+#define RG_SWITCH_C_3_(K, TAIL, c0, c1, c2, ...) \
+    RG_SWITCH_C_CASE_(K, TAIL, c0, __VA_ARGS__) RG_SWITCH_C_CASE_(K, TAIL, c1, __VA_ARGS__) RG_SWITCH_C_CASE_(K, TAIL, c2, __VA_ARGS__)
+#define RG_SWITCH_C_4_(K, TAIL, c0, c1, c2, c3, ...) \
+    RG_SWITCH_C_3_(K, TAIL, c0, c1, c2, __VA_ARGS__) RG_SWITCH_C_CASE_(K, TAIL, c3, __VA_ARGS__)
+#define RG_SWITCH_C_COUNT_(a, b, c, d, N, ...) N
+#define RG_SWITCH_C_PICK_(...) RG_SWITCH_C_COUNT_(__VA_ARGS__, RG_SWITCH_C_4_, RG_SWITCH_C_3_, , )
+#define RG_SWITCH_C_APPLY_(M, ...) M(__VA_ARGS__)
+#define RG_SWITCH_C(CS, K, TAIL, ...)                                                                  \
+    do {                                                                                               \
+        switch (C) {                                                                                   \
+            RG_SWITCH_C_APPLY_(RG_SWITCH_C_PICK_ CS, K, TAIL, RG_TARGS_ CS, __VA_ARGS__)               \
+            default: return nullptr;                                                                   \
+        }                                                                                              \
+    } while (0)
+
 }  // namespace rg

@@ -155,6 +155,40 @@ struct Opt0Args {
     int rec_pen;               // what a two-path bound pays for its switch: base recombination cost + displacement allowance
 };
 
+// The rows the bound kernels walk for one read (k_opt0, k_opt0_striped; k_opt0_16 states the same walk with a two-stage look-ahead), and the bound they write: the rows of the picked
+// path — path 0 without picks: only its score is a provable bound (PickArgs) — or, for a two-path pick, p1's rows up to X followed by
+// p2's rows above X (both lists ascending; every wave of a striped read takes the same rows).  A walk is
+//     for (int t = 0; t < pr.cnt; ++t) { if (!pr.row(t, i)) continue; ... }
+// row() returns false for the one iteration that switches to p2's list and moves t in front of its first row above X.
+struct PickedRows {
+    const int* fpoff; const int* fprow;
+    int pk, pk2, X, beg, cnt;
+    bool second;
+    __device__ __forceinline__ PickedRows(const Opt0Args& a, int rd) : fpoff(a.fpoff), fprow(a.fprow), second(false) {
+        pk = a.pick ? a.pick[rd] : 0;
+        pk2 = (a.pick && a.pick2) ? a.pick2[2 * rd] : -1;
+        X = pk2 >= 0 ? a.pick2[2 * rd + 1] : INT32_MAX;
+        beg = fpoff[pk]; cnt = fpoff[pk + 1] - beg;
+    }
+    // p2's list; -> index of its first row above X
+    __device__ __forceinline__ int switch_lists() {
+        second = true;
+        beg = fpoff[pk2]; cnt = fpoff[pk2 + 1] - beg;
+        int lo = 0, hi = cnt;
+        while (lo < hi) { const int mid = (lo + hi) >> 1; if (fprow[beg + mid] <= X) lo = mid + 1; else hi = mid; }
+        return lo;
+    }
+    __device__ __forceinline__ bool row(int& t, int& i) {
+        i = fprow[beg + t];
+        if (i > X && !second) { t = switch_lists() - 1; return false; }
+        return true;
+    }
+    // lb[rd] from the walk's score: minus the margin of a speculative bound and what a two-path bound pays for its switch
+    __device__ __forceinline__ void write_bound(const Opt0Args& a, int rd, int score) const {
+        a.lb[rd] = score - (a.pick ? a.margin : 0) - (pk2 >= 0 ? a.rec_pen : 0);
+    }
+};
+
 // Speculative lower bound of the -m 8 search maximum.  The forward sweep of the two-sweep pipeline emits every cell that
 // could still pair up to `lb`; the only PROVABLE lb before the sweep is the alignment of the read against path 0 (the one
 // path that is the alpha of all its groups), which lies ~1500 below the seed at config 5 and lets 40 000 records per read
@@ -215,6 +249,52 @@ struct LayerArgs {
     const int* rpoff; const int* rprow; const int* rpslot;   // rows of every path, reverse order
     int nwv;                   // column stripes per read (see SweepArgs)
     int only_full;             // 1: only the reads k_trace flagged ST_LAYER_FULL (the fallback behind the windowed kernels, layer_window/)
+};
+
+// What the three layer kernels (k_layer, k_layer16, k_layer_win) settle for a read before their row loop: which path and which of
+// its row lists (forward / reverse program order), the read and its (mirrored) columns, and the cell the traceback starts from —
+// forward (fen | end row, rec_col | n), reverse (rsn, mirrored rec_col).  open() is false where there is nothing to rebuild: a read
+// with one of the `skip` status bits (ST_RETRY: it is aligned again and its direction words may not exist), a reverse layer without a
+// recombination, and — `heed_only_full`, the fallback launches behind the windowed kernel — a read k_trace did not flag.
+struct LayerJob {
+    ReadState* rs;
+    int path;
+    bool recomb;
+    int n, ncols;
+    const uint8_t* read;       // read[1 .. n]
+    const int* prow; const int* pslot;
+    int pbase, nrows;
+    int start_row, start_col;
+    int nx_row, nx_slot;       // look-ahead, stage one: the list entries of the next row to be fetched (-1: none)
+    __device__ __forceinline__ bool open(const LayerArgs& a, int rd, uint32_t skip, bool heed_only_full) {
+        rs = a.state + rd;
+        if (rs->status & skip) return false;
+        if (heed_only_full && a.only_full && !(rs->status & ST_LAYER_FULL)) return false;
+        const bool rev = a.rev;
+        path = rev ? rs->rev_path : rs->fwd_path;
+        recomb = rs->fwd_path != rs->rev_path;
+        if (rev && !recomb) return false;
+        const long long ro = a.read_off[rd];
+        n = (int)(a.read_off[rd + 1] - ro);
+        read = a.reads + ro - 1;
+        ncols = rev ? n : n + 1;
+        prow = rev ? a.rprow : a.fprow;
+        pslot = rev ? a.rpslot : a.fpslot;
+        const int* poff = rev ? a.rpoff : a.fpoff;
+        pbase = poff[path];
+        nrows = poff[path + 1] - pbase;
+        start_row = rev ? rs->rsn : (recomb ? rs->fen : rs->end_row);
+        start_col = rev ? n - rs->rec_col : (recomb ? rs->rec_col : n);
+        nx_row = -1; nx_slot = 0;
+        return true;
+    }
+    // TWO-STAGE look-ahead.  A row needs its base code and its direction word, and their addresses come from the path's row / slot
+    // lists: two DEPENDENT loads.  The list entries of row tt (of the first `upto` rows) are loaded here, while an earlier row is
+    // computed; the loads they address are issued by the kernel one iteration later, when they have landed.
+    __device__ __forceinline__ void fetch_idx(int tt, int upto) {
+        nx_row = -1; nx_slot = 0;
+        if (tt < upto) { nx_row = prow[pbase + tt]; nx_slot = pslot[pbase + tt]; }
+    }
 };
 
 struct TraceArgs {

@@ -72,6 +72,15 @@ struct StripeFifo {
         v1 = __builtin_amdgcn_readfirstlane(b);
     }
 };
+// The FIFO pair of stripe wv of nwv in fifo_lds (nwv queues of FIFO_WORDS + 2 words: buffer, head, tail): queue w carries wave
+// w - 1 -> wave w, so `fin` is queue wv and `fout` queue wv + 1.  Zeroes the counters; the caller's barrier makes them visible.
+__device__ __forceinline__ void stripe_fifos(int* fifo_lds, int wv, int nwv, int lane, StripeFifo& fin, StripeFifo& fout) {
+    constexpr int QW = FIFO_WORDS + 2;
+    if (lane < nwv) { fifo_lds[lane * QW + FIFO_WORDS] = 0; fifo_lds[lane * QW + FIFO_WORDS + 1] = 0; }
+    fin = StripeFifo{fifo_lds + wv * QW, (unsigned*)(fifo_lds + wv * QW + FIFO_WORDS), (unsigned*)(fifo_lds + wv * QW + FIFO_WORDS + 1), 0u};
+    const int nx = wv + 1 < nwv ? wv + 1 : 0;
+    fout = StripeFifo{fifo_lds + nx * QW, (unsigned*)(fifo_lds + nx * QW + FIFO_WORDS), (unsigned*)(fifo_lds + nx * QW + FIFO_WORDS + 1), 0u};
+}
 struct StripeIO {            // carries of one row update: in from the stripe on the left, out to the stripe on the right
     int in_prev, in_carry;   // old value of the left stripe's last column; alpha: its running maximum (z-space), member: its last non-L value
     int out_prev, out_carry;
@@ -195,13 +204,7 @@ __global__ __launch_bounds__(kStripes ? 512 : 64, kStripes ? 1 : RG_SWEEP_WAVES)
     // stripe FIFOs (after the score table and the semiglobal end arrays): queue w carries wave w - 1 -> wave w
     int* fifo_lds = g_lds + 64 + 2 * RG_MAXP;
     StripeFifo fin{}, fout{};
-    if (kStripes) {
-        constexpr int QW = FIFO_WORDS + 2;
-        if (lane < nwv) { fifo_lds[lane * QW + FIFO_WORDS] = 0; fifo_lds[lane * QW + FIFO_WORDS + 1] = 0; }
-        fin = StripeFifo{fifo_lds + wv * QW, (unsigned*)(fifo_lds + wv * QW + FIFO_WORDS), (unsigned*)(fifo_lds + wv * QW + FIFO_WORDS + 1), 0u};
-        const int nx = wv + 1 < nwv ? wv + 1 : 0;
-        fout = StripeFifo{fifo_lds + nx * QW, (unsigned*)(fifo_lds + nx * QW + FIFO_WORDS), (unsigned*)(fifo_lds + nx * QW + FIFO_WORDS + 1), 0u};
-    }
+    if (kStripes) stripe_fifos(fifo_lds, wv, nwv, lane, fin, fout);
     __syncthreads();
 
     // rolling rows of this stripe: [P][wpadw], stripes of a read back to back
@@ -672,26 +675,15 @@ __global__ __launch_bounds__(64) void k_opt0(Opt0Args a) {
 #pragma unroll
         for (int q = 0; q < C; ++q) { GP[q] += pre; row[q] = lane * C + q < ncols ? GP[q] : NEG; }
     }
-    const int pk = a.pick ? a.pick[rd] : 0;      // (only path 0's score is a provable bound: see PickArgs)
-    // (two-path pick: p1's rows <= X, then p2's rows > X)
-    const int pk2 = (a.pick && a.pick2) ? a.pick2[2 * rd] : -1;
-    const int X = pk2 >= 0 ? a.pick2[2 * rd + 1] : INT32_MAX;
-    int beg = a.fpoff[pk], cnt = a.fpoff[pk + 1] - beg;
+    PickedRows pr(a, rd);
     int semibest = NEG;
-    bool second = false;
-    for (int t = 0; t < cnt; ++t) {
-        const int i = a.fprow[beg + t];
-        if (i > X && !second) {
-            // switch lists: first row of p2 above X (its list is ascending)
-            second = true;
-            beg = a.fpoff[pk2]; cnt = a.fpoff[pk2 + 1] - beg;
-            int lo = 0, hi = cnt;
-            while (lo < hi) { const int mid = (lo + hi) >> 1; if (a.fprow[beg + mid] <= X) lo = mid + 1; else hi = mid; }
-            t = lo - 1;
-            continue;
-        }
+    for (int t = 0; t < pr.cnt; ++t) {
+        int i;
+        if (!pr.row(t, i)) continue;
         const int li = g.lnz[i];
         const int g_i = sct[li * 6 + GAP];
+        // (RowOps<C, false, false>::alpha without its masks, restated: through alpha k_opt0<16> takes 90 registers for 58 and loses
+        // two waves of occupancy, profiles/pathwise_side_notes.md)
         int prev_old = dpp_shr1(row[C - 1], NEG);
         int runmax = NEG;
 #pragma unroll
@@ -725,7 +717,7 @@ __global__ __launch_bounds__(64) void k_opt0(Opt0Args a) {
     int v = NEG;
 #pragma unroll
     for (int q = 0; q < C; ++q) if (q == ql) v = row[q];
-    if (lane == ln) a.lb[rd] = (a.semi ? semibest : v) - (a.pick ? a.margin : 0) - (pk2 >= 0 ? a.rec_pen : 0);
+    if (lane == ln) pr.write_bound(a, rd, a.semi ? semibest : v);
 }
 
 // The same for reads longer than 2047 bases: a.nwv waves per read, wave w owns columns [w * 64 * C, (w + 1) * 64 * C) and runs
@@ -747,11 +739,8 @@ __global__ __launch_bounds__(512) void k_opt0_striped(Opt0Args a) {
     __shared__ int sct[36];
     __shared__ int fifo_lds[8 * (FIFO_WORDS + 2)];
     if (lane < 36) sct[lane] = a.sc.t[lane];
-    constexpr int QW = FIFO_WORDS + 2;
-    if (lane < nwv) { fifo_lds[lane * QW + FIFO_WORDS] = 0; fifo_lds[lane * QW + FIFO_WORDS + 1] = 0; }
-    StripeFifo fin{fifo_lds + wv * QW, (unsigned*)(fifo_lds + wv * QW + FIFO_WORDS), (unsigned*)(fifo_lds + wv * QW + FIFO_WORDS + 1), 0u};
-    const int nx = wv + 1 < nwv ? wv + 1 : 0;
-    StripeFifo fout{fifo_lds + nx * QW, (unsigned*)(fifo_lds + nx * QW + FIFO_WORDS), (unsigned*)(fifo_lds + nx * QW + FIFO_WORDS + 1), 0u};
+    StripeFifo fin{}, fout{};
+    stripe_fifos(fifo_lds, wv, nwv, lane, fin, fout);
     __syncthreads();
     const int gcost = sct[GAP];
     int er[C], row[C], s[C];
@@ -762,24 +751,12 @@ __global__ __launch_bounds__(512) void k_opt0_striped(Opt0Args a) {
         er[q] = (c >= 1 && c < ncols) ? read[c] : 4;
         row[q] = c < ncols ? c * gcost : NEG;               // the gap-only start row
     }
-    const int pk = a.pick ? a.pick[rd] : 0;      // (only path 0's score is a provable bound: see PickArgs)
-    // (two-path pick: p1's rows <= X, then p2's rows > X — every wave of the block takes the same rows)
-    const int pk2 = (a.pick && a.pick2) ? a.pick2[2 * rd] : -1;
-    const int X = pk2 >= 0 ? a.pick2[2 * rd + 1] : INT32_MAX;
-    int beg = a.fpoff[pk], cnt = a.fpoff[pk + 1] - beg;
+    PickedRows pr(a, rd);
     int semibest = NEG;
-    bool second = false;
     StripeIO io{NEG, NEG, NEG, NEG};
-    for (int t = 0; t < cnt; ++t) {
-        const int i = a.fprow[beg + t];
-        if (i > X && !second) {
-            second = true;
-            beg = a.fpoff[pk2]; cnt = a.fpoff[pk2 + 1] - beg;
-            int lo = 0, hi = cnt;
-            while (lo < hi) { const int mid = (lo + hi) >> 1; if (a.fprow[beg + mid] <= X) lo = mid + 1; else hi = mid; }
-            t = lo - 1;
-            continue;
-        }
+    for (int t = 0; t < pr.cnt; ++t) {
+        int i;
+        if (!pr.row(t, i)) continue;
         const int li = g.lnz[i];
         const int g_i = sct[li * 6 + GAP];
 #pragma unroll
@@ -800,7 +777,7 @@ __global__ __launch_bounds__(512) void k_opt0_striped(Opt0Args a) {
     int v = NEG;
 #pragma unroll
     for (int q = 0; q < C; ++q) if (q == n % C) v = row[q];
-    if (lane == n / C) a.lb[rd] = (a.semi ? semibest : v) - (a.pick ? a.margin : 0) - (pk2 >= 0 ? a.rec_pen : 0);
+    if (lane == n / C) pr.write_bound(a, rd, a.semi ? semibest : v);
 }
 
 // ---------------------------------------------------------------------------------
@@ -1204,6 +1181,8 @@ __global__ __launch_bounds__(kStripes ? 512 : 64) void k_layer(LayerArgs a) {
     const int lane = wv * WAVE + wl;                                                   // global lane: column = lane * C + q
     const int dww = WAVE * (C <= 16 ? 1 : 2);                                          // words of one stripe per row
     const PathGraphDev& g = a.g;
+    // (the prologue of LayerJob, restated: through LayerJob every instantiation at 16 and 32 columns per lane spills more SGPRs — <16, true>
+    // 56 for 43 — and <32, true> two more VGPRs, profiles/pathwise_side_notes.md)
     ReadState* rs = a.state + rd;
     if (rs->status & (ST_BAD_BASE | ST_WOULD_PANIC | ST_OVERFLOW | ST_RETRY)) return;      // (ST_RETRY: aligned again; its direction words may not exist)
     const bool rev = a.rev;
@@ -1219,13 +1198,7 @@ __global__ __launch_bounds__(kStripes ? 512 : 64) void k_layer(LayerArgs a) {
     __shared__ int fifo_lds[kStripes ? 8 * (FIFO_WORDS + 2) : 1];
     if (lane < 36) sct[lane] = a.sc.t[lane];
     StripeFifo fin{}, fout{};
-    if (kStripes) {
-        constexpr int QW = FIFO_WORDS + 2;
-        if (lane < nwv) { fifo_lds[lane * QW + FIFO_WORDS] = 0; fifo_lds[lane * QW + FIFO_WORDS + 1] = 0; }
-        fin = StripeFifo{fifo_lds + wv * QW, (unsigned*)(fifo_lds + wv * QW + FIFO_WORDS), (unsigned*)(fifo_lds + wv * QW + FIFO_WORDS + 1), 0u};
-        const int nx = wv + 1 < nwv ? wv + 1 : 0;
-        fout = StripeFifo{fifo_lds + nx * QW, (unsigned*)(fifo_lds + nx * QW + FIFO_WORDS), (unsigned*)(fifo_lds + nx * QW + FIFO_WORDS + 1), 0u};
-    }
+    if (kStripes) stripe_fifos(fifo_lds, wv, nwv, lane, fin, fout);
     __syncthreads();
     int er[C], GP[C];
     bool act[C];
@@ -1420,50 +1393,39 @@ __global__ __launch_bounds__(64) void k_trace(TraceArgs a) {
         }
         return (td[(long long)idx * dw + (gl / WAVE) * dww + (q / 16) * WAVE + gl % WAVE] >> (2 * (q % 16))) & 3u;
     };
-    const uint32_t* fl = reinterpret_cast<const uint32_t*>(a.flayer) + (long long)rd * a.layer_stride;
+    // One walk over the decisions of layer `td` from layer row t (0 = the gap-only start row) at column c towards row 0 and column 0; the
+    // reverse walk hands in mirrored columns c' = n - j.  `cont` tags the gap runs behind the walk proper.  False: the window cannot serve it.
+    auto walk = [&](const uint32_t* td, int t, int c, uint8_t cont) -> bool {
+        const int t0 = t, c0 = c;
+        while (t > 0 && c > 0) {
+            const uint32_t mv = move(td, t, c, t0, c0);
+            if (mv == 1u) { ops[nops++] = OP_D; t -= 1; c -= 1; }
+            else if (mv == 2u) { ops[nops++] = OP_U; t -= 1; }
+            else if (mv == 3u || !a.window) { ops[nops++] = OP_L; c -= 1; }
+            else return false;
+        }
+        while (c > 0) { ops[nops++] = OP_L | cont; c -= 1; }
+        while (!a.semi && t > 0) { ops[nops++] = OP_U | cont; t -= 1; }   // semiglobal: the alignment may start inside the graph
+        return true;
+    };
     // ---- forward walk from (row, j) back to the source on path fp ----
     const int fp = rs->fwd_path;
-    const int fbeg = a.fpoff[fp], fnr = a.fpoff[fp + 1] - fbeg;
-    int start_row = recomb ? rs->fen : rs->end_row;
-    int j = recomb ? rs->rec_col : n;
-    // index of start_row among the rows of path fp (binary search; rows ascending)
-    int lo = 0, hi = fnr - 1, idx = -1;
-    while (lo <= hi) { int mid = (lo + hi) >> 1; int r = a.fprow[fbeg + mid]; if (r == start_row) { idx = mid; break; } if (r < start_row) lo = mid + 1; else hi = mid - 1; }
+    const int fbeg = a.fpoff[fp];
+    const int start_row = recomb ? rs->fen : rs->end_row;
+    const int idx = layer_row_index(a.fprow + fbeg, a.fpoff[fp + 1] - fbeg, start_row, false);
     if (idx < 0) { rec->status = ST_WOULD_PANIC; rec->n_ops = 0; return; }
-    int t = idx + 1;  // layer index of the current row (0 = row 0)
     const int score = rs->trace_score;
-    const int ft0 = t, fc0 = j;
-    while (t > 0 && j > 0) {
-        const uint32_t mv = move(fl, t, j, ft0, fc0);
-        if (mv == 1u) { ops[nops++] = OP_D; t -= 1; j -= 1; }
-        else if (mv == 2u) { ops[nops++] = OP_U; t -= 1; }
-        else if (mv == 3u || !a.window) { ops[nops++] = OP_L; j -= 1; }
-        else { give_up(); return; }
-    }
-    while (j > 0) { ops[nops++] = OP_L; j -= 1; }
-    while (!a.semi && t > 0) { ops[nops++] = OP_U; t -= 1; }   // semiglobal: the alignment may start inside the graph
+    const uint32_t* fl = reinterpret_cast<const uint32_t*>(a.flayer) + (long long)rd * a.layer_stride;
+    if (!walk(fl, idx + 1, recomb ? rs->rec_col : n, 0)) { give_up(); return; }
     const int nfwd = nops;
     if (recomb) {
-        // ---- reverse walk from (rsn, rec_col) forward to the sink on path rp (mirrored columns c' = n - jj) ----
+        // ---- reverse walk from (rsn, rec_col) forward to the sink on path rp (rows of the reverse program are descending) ----
         const int rp = rs->rev_path;
-        const uint32_t* rl = reinterpret_cast<const uint32_t*>(a.rlayer) + (long long)rd * a.layer_stride;
-        const int rbeg = a.rpoff[rp], rnr = a.rpoff[rp + 1] - rbeg;
-        // rows of the reverse program are descending
-        int lo2 = 0, hi2 = rnr - 1, ridx = -1;
-        while (lo2 <= hi2) { int mid = (lo2 + hi2) >> 1; int r = a.rprow[rbeg + mid]; if (r == rs->rsn) { ridx = mid; break; } if (r > rs->rsn) lo2 = mid + 1; else hi2 = mid - 1; }
+        const int rbeg = a.rpoff[rp];
+        const int ridx = layer_row_index(a.rprow + rbeg, a.rpoff[rp + 1] - rbeg, rs->rsn, true);
         if (ridx < 0) { rec->status = ST_WOULD_PANIC; rec->n_ops = 0; return; }
-        int tt = ridx + 1;          // layer index (0 = row L-1)
-        int jj = rs->rec_col;       // real column
-        const int rt0 = tt, rc0 = n - jj;
-        while (tt > 0 && jj < n) {
-            const uint32_t mv = move(rl, tt, n - jj, rt0, rc0);
-            if (mv == 1u) { ops[nops++] = OP_D; tt -= 1; jj += 1; }
-            else if (mv == 2u) { ops[nops++] = OP_U; tt -= 1; }
-            else if (mv == 3u || !a.window) { ops[nops++] = OP_L; jj += 1; }
-            else { give_up(); return; }
-        }
-        while (jj < n) { ops[nops++] = OP_L | OP_CONT; jj += 1; }
-        while (!a.semi && tt > 0) { ops[nops++] = OP_U | OP_CONT; tt -= 1; }
+        const uint32_t* rl = reinterpret_cast<const uint32_t*>(a.rlayer) + (long long)rd * a.layer_stride;
+        if (!walk(rl, ridx + 1, n - rs->rec_col, OP_CONT)) { give_up(); return; }
     }
     rec->status = rs->status & ~ST_LAYER_FULL;
     rec->score = score;
@@ -1502,15 +1464,6 @@ const char* launch_need(const ReadState* st, const unsigned* nf, const unsigned*
 
 // ---------------------------------------------------------------------------------
 // launchers
-template <int C>
-static const char* launch_sweep_c(const SweepArgs& a, int nreads, hipStream_t s) {
-    // uniform read-gap cost: every (base, '-') entry equal (reads hold ACGTN only)
-    bool uni = true;
-    for (int b = 1; b < 5; ++b) uni = uni && a.sc.t[b * 6 + 5] == a.sc.t[5];
-    const size_t sct_bytes = (64 + 2 * RG_MAXP + C * WAVE) * sizeof(int);       // (+ the path-retirement constants)
-    if (uni) RG_LAUNCH(k_sweep, (C, true, false), dim3(nreads), dim3(64), sct_bytes, s, a);
-    else RG_LAUNCH(k_sweep, (C, false, false), dim3(nreads), dim3(64), sct_bytes, s, a);
-}
 const char* launch_sweep(const SweepArgs& a, int nreads, int C, hipStream_t s) {
     if (a.nwv > 1) {
         // striped long reads: a.nwv waves per read, C columns per lane (16: the rows and keys fit the registers; 32 spills
@@ -1519,36 +1472,21 @@ const char* launch_sweep(const SweepArgs& a, int nreads, int C, hipStream_t s) {
         // maxima, C x 64 constants per stripe)
         // (the 32-column stripes do not retire paths and get no constants: eight of them would pass the 64 KB a launch may ask for)
         const size_t bytes = (64 + 2 * RG_MAXP + 8 * (FIFO_WORDS + 2) + 16 + 4 * 8 * WAVE + (C <= 16 ? (size_t)a.nwv * C * WAVE : 0)) * sizeof(int);
-        switch (C) {
-            case 8: RG_LAUNCH(k_sweep, (8, true, true), dim3(nreads), dim3(64 * a.nwv), bytes, s, a);
-            case 16: RG_LAUNCH(k_sweep, (16, true, true), dim3(nreads), dim3(64 * a.nwv), bytes, s, a);
-            default: RG_LAUNCH(k_sweep, (32, true, true), dim3(nreads), dim3(64 * a.nwv), bytes, s, a);
-        }
+        RG_SWITCH_C((8, 16, 32), k_sweep, (, true, true), dim3(nreads), dim3(64 * a.nwv), bytes, s, a);
     }
-    switch (C) {
-        case 4: return launch_sweep_c<4>(a, nreads, s);
-        case 8: return launch_sweep_c<8>(a, nreads, s);
-        case 16: return launch_sweep_c<16>(a, nreads, s);
-        default: return launch_sweep_c<32>(a, nreads, s);
-    }
+    // uniform read-gap cost: every (base, '-') entry equal (reads hold ACGTN only)
+    bool uni = true;
+    for (int b = 1; b < 5; ++b) uni = uni && a.sc.t[b * 6 + 5] == a.sc.t[5];
+    const size_t sct_bytes = (64 + 2 * RG_MAXP + C * WAVE) * sizeof(int);       // (+ the path-retirement constants)
+    if (uni) RG_SWITCH_C((4, 8, 16, 32), k_sweep, (, true, false), dim3(nreads), dim3(64), sct_bytes, s, a);
+    RG_SWITCH_C((4, 8, 16, 32), k_sweep, (, false, false), dim3(nreads), dim3(64), sct_bytes, s, a);
 }
 const char* launch_seed(const SeedArgs& a, hipStream_t s) {
     RG_LAUNCH0(k_seed, dim3((a.nreads + 63) / 64), dim3(64), 0, s, a);
 }
 const char* launch_opt0(const Opt0Args& a, int nreads, int C, hipStream_t s) {
-    if (a.nwv > 1) {
-        switch (C) {
-            case 8: RG_LAUNCH(k_opt0_striped, (8), dim3(nreads), dim3(64 * a.nwv), 0, s, a);
-            case 16: RG_LAUNCH(k_opt0_striped, (16), dim3(nreads), dim3(64 * a.nwv), 0, s, a);
-            default: RG_LAUNCH(k_opt0_striped, (32), dim3(nreads), dim3(64 * a.nwv), 0, s, a);
-        }
-    }
-    switch (C) {
-        case 4: RG_LAUNCH(k_opt0, (4), dim3(nreads), dim3(64), 0, s, a);
-        case 8: RG_LAUNCH(k_opt0, (8), dim3(nreads), dim3(64), 0, s, a);
-        case 16: RG_LAUNCH(k_opt0, (16), dim3(nreads), dim3(64), 0, s, a);
-        default: RG_LAUNCH(k_opt0, (32), dim3(nreads), dim3(64), 0, s, a);
-    }
+    if (a.nwv > 1) RG_SWITCH_C((8, 16, 32), k_opt0_striped, (), dim3(nreads), dim3(64 * a.nwv), 0, s, a);
+    RG_SWITCH_C((4, 8, 16, 32), k_opt0, (), dim3(nreads), dim3(64), 0, s, a);
 }
 const char* launch_pick(const PickArgs& a, int nreads, hipStream_t s) { RG_LAUNCH0(k_pick, dim3(nreads), dim3(64), 0, s, a); }
 __global__ __launch_bounds__(1024) void k_order(const int* pick, const int* pick2, int* order, int nreads) {
@@ -1594,28 +1532,11 @@ const char* launch_search(const SearchArgs& a, int nreads, hipStream_t s) {
     RG_LAUNCH0(k_search, dim3(nreads), dim3(64), bytes, s, a);
 }
 const char* launch_layer(const LayerArgs& a, int nreads, int C, hipStream_t s) {
-    if (a.nwv > 1) {
-        switch (C) {
-            case 8: RG_LAUNCH(k_layer, (8, true), dim3(nreads), dim3(64 * a.nwv), 0, s, a);
-            case 16: RG_LAUNCH(k_layer, (16, true), dim3(nreads), dim3(64 * a.nwv), 0, s, a);
-            default: RG_LAUNCH(k_layer, (32, true), dim3(nreads), dim3(64 * a.nwv), 0, s, a);
-        }
-    }
-    switch (C) {
-        case 4: RG_LAUNCH(k_layer, (4, false), dim3(nreads), dim3(64), 0, s, a);
-        case 8: RG_LAUNCH(k_layer, (8, false), dim3(nreads), dim3(64), 0, s, a);
-        case 16: RG_LAUNCH(k_layer, (16, false), dim3(nreads), dim3(64), 0, s, a);
-        default: RG_LAUNCH(k_layer, (32, false), dim3(nreads), dim3(64), 0, s, a);
-    }
+    if (a.nwv > 1) RG_SWITCH_C((8, 16, 32), k_layer, (, true), dim3(nreads), dim3(64 * a.nwv), 0, s, a);
+    RG_SWITCH_C((4, 8, 16, 32), k_layer, (, false), dim3(nreads), dim3(64), 0, s, a);
 }
 const char* launch_trace(const TraceArgs& a, int C, hipStream_t s) {
-    const dim3 grid((a.nreads + 63) / 64), blk(64);
-    switch (C) {
-        case 4: RG_LAUNCH(k_trace, (4), grid, blk, 0, s, a);
-        case 8: RG_LAUNCH(k_trace, (8), grid, blk, 0, s, a);
-        case 16: RG_LAUNCH(k_trace, (16), grid, blk, 0, s, a);
-        default: RG_LAUNCH(k_trace, (32), grid, blk, 0, s, a);
-    }
+    RG_SWITCH_C((4, 8, 16, 32), k_trace, (), dim3((a.nreads + 63) / 64), dim3(64), 0, s, a);
 }
 
 }  // namespace rg

@@ -25,16 +25,13 @@
 #include <type_traits>
 
 #include "rg_path_kernels.hpp"
+#include "rg_pk16.hpp"
 
 namespace rg {
 
 namespace {
 
 constexpr int NEG32 = INT32_MIN / 4;
-constexpr int NEG16 = -30000;                               // "minus infinity" of a 16-bit lane; real values stay > -24000
-constexpr int NEGPAIR = (int)(((unsigned)(NEG16 & 0xffff) << 16) | (unsigned)(NEG16 & 0xffff));
-constexpr int ONE2 = 0x00010001;
-
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 // buffer resource over [base, base + bytes) built from wave-uniform values only (the halves of the pointer go through
@@ -44,42 +41,6 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t uniform_rsrc(const void* base,
     const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)u), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(u >> 32));
     void* p = (void*)(((unsigned long long)hi << 32) | lo);
     return __builtin_amdgcn_make_buffer_rsrc(p, 0, (int)__builtin_amdgcn_readfirstlane((int)bytes), 0x00020000);
-}
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ int pk_add(int a, int b) {
-    return __builtin_bit_cast(int, (s16x2)(__builtin_bit_cast(s16x2, a) + __builtin_bit_cast(s16x2, b)));
-}
-__device__ __forceinline__ int pk_sub(int a, int b) {
-    return __builtin_bit_cast(int, (s16x2)(__builtin_bit_cast(s16x2, a) - __builtin_bit_cast(s16x2, b)));
-}
-__device__ __forceinline__ int pk_max(int a, int b) {
-    return __builtin_bit_cast(int, __builtin_elementwise_max(__builtin_bit_cast(s16x2, a), __builtin_bit_cast(s16x2, b)));
-}
-__device__ __forceinline__ int pk_min(int a, int b) {
-    return __builtin_bit_cast(int, __builtin_elementwise_min(__builtin_bit_cast(s16x2, a), __builtin_bit_cast(s16x2, b)));
-}
-__device__ __forceinline__ int pk_minu(int a, int b) {
-    return __builtin_bit_cast(int, __builtin_elementwise_min(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b)));
-}
-// saturating packed difference (v_pk_sub_i16 ... clamp): the sign of each half is the sign of the true difference
-__device__ __forceinline__ int pk_sub_sat(int a, int b) {
-    return __builtin_bit_cast(int, __builtin_elementwise_sub_sat(__builtin_bit_cast(s16x2, a), __builtin_bit_cast(s16x2, b)));
-}
-__device__ __forceinline__ int pk_add_sat(int a, int b) {
-    return __builtin_bit_cast(int, __builtin_elementwise_add_sat(__builtin_bit_cast(s16x2, a), __builtin_bit_cast(s16x2, b)));
-}
-// per half: 0xffff where the half of `v` is negative, else 0  (v_pk_ashrrev_i16)
-__device__ __forceinline__ int pk_sign(int v) {
-    return __builtin_bit_cast(int, (s16x2)(__builtin_bit_cast(s16x2, v) >> (s16x2)(15)));
-}
-__device__ __forceinline__ int pack16(int lo, int hi) { return (int)(((unsigned)hi << 16) | ((unsigned)lo & 0xffffu)); }
-__device__ __forceinline__ int lo16(int v) { return (int)(short)(v & 0xffff); }
-__device__ __forceinline__ int hi16(int v) { return v >> 16; }
-// per half: mask ? a : b   (mask halves are 0 or 0xffff)
-__device__ __forceinline__ int bfi(int mask, int a, int b) {
-    return __builtin_amdgcn_bitop3_b32(mask, a, b, 0xCA);   // (mask & a) | (~mask & b) in ONE v_bitop3_b32
 }
 
 // Row operators on packed z-space rows.  MU / ML: per register, 0xffff in the halves whose column took U (not D) / L.
@@ -395,10 +356,7 @@ __global__ __launch_bounds__(64, SWEEP16_WAVES) void k_sweep16(SweepArgs a) {
     // uniform gap cost (checked by the driver's plan, sweep16_admissible in rg_path_plan.cpp: score(b, '-') is the same for b = A, C, G, T, N): the
     // z-space slope — and, being the same table column, what a U move adds in EVERY row (g_i below): no per-row lookup
     const int gcost = __builtin_amdgcn_readfirstlane(sct[GAP]);
-    for (int e = lane; e < 5 * 64; e += WAVE) {
-        const int li = e >> 6, cl = e & 7, ch = (e >> 3) & 7;
-        s2[e] = (cl < 6 && ch < 6) ? pack16(sct[li * 6 + cl] - gcost, sct[li * 6 + ch] - gcost) : 0;   // diagonal step in z-space
-    }
+    pair_table(s2, sct, gcost, lane);      // diagonal step in z-space
     int* rows = a.roll + (long long)rd * (P + 2) * wrow;
     // rolling rows in HBM: [path][lane][r] — the H packed words of a lane are contiguous, so a row moves as 16-byte
     // accesses (two per lane at C = 16; the wave covers the row's 2 KB contiguously) instead of one 4-byte access per word
@@ -1820,12 +1778,7 @@ __global__ __launch_bounds__(256) void k_expand(ExpandArgs a) {
 }
 
 const char* launch_expand(const ExpandArgs& a, int nreads, int C, hipStream_t s) {
-    switch (C) {
-        case 4: RG_LAUNCH(k_expand, (4), dim3(nreads), dim3(256), 0, s, a);
-        case 8: RG_LAUNCH(k_expand, (8), dim3(nreads), dim3(256), 0, s, a);
-        case 16: RG_LAUNCH(k_expand, (16), dim3(nreads), dim3(256), 0, s, a);
-        default: RG_LAUNCH(k_expand, (32), dim3(nreads), dim3(256), 0, s, a);
-    }
+    RG_SWITCH_C((4, 8, 16, 32), k_expand, (), dim3(nreads), dim3(256), 0, s, a);
 }
 
 // Column maxima of a sweep and the cells attaining them, from the sweep's own records: per column the best member-winner
@@ -1871,12 +1824,7 @@ __global__ __launch_bounds__(256) void k_colmax_rec(ExpandArgs a, int* colmax_ou
 
 const char* launch_colmax_rec(const ExpandArgs& a, int* colmax_out, int* colarg_out, int nreads, int C, hipStream_t s) {
     const size_t bytes = (size_t)a.wpad * sizeof(unsigned long long);
-    switch (C) {
-        case 4: RG_LAUNCH(k_colmax_rec, (4), dim3(nreads), dim3(256), bytes, s, a, colmax_out, colarg_out);
-        case 8: RG_LAUNCH(k_colmax_rec, (8), dim3(nreads), dim3(256), bytes, s, a, colmax_out, colarg_out);
-        case 16: RG_LAUNCH(k_colmax_rec, (16), dim3(nreads), dim3(256), bytes, s, a, colmax_out, colarg_out);
-        default: RG_LAUNCH(k_colmax_rec, (32), dim3(nreads), dim3(256), bytes, s, a, colmax_out, colarg_out);
-    }
+    RG_SWITCH_C((4, 8, 16, 32), k_colmax_rec, (), dim3(nreads), dim3(256), bytes, s, a, colmax_out, colarg_out);
 }
 
 
@@ -1898,17 +1846,12 @@ __global__ __launch_bounds__(64, C <= 16 ? LAYER16_WAVES : 1) void k_layer16(Lay
     const int rd = blockIdx.x;
     const int lane = threadIdx.x;
     const PathGraphDev& g = a.g;
-    ReadState* rs = a.state + rd;
-    if (rs->status & (ST_BAD_BASE | ST_WOULD_PANIC | ST_OVERFLOW | ST_RETRY)) return;
-    if (a.only_full && !(rs->status & ST_LAYER_FULL)) return;      // the fallback behind the windowed kernels: flagged reads only
-    const bool rev = a.rev;
-    const int path = rev ? rs->rev_path : rs->fwd_path;
-    const bool recomb = rs->fwd_path != rs->rev_path;
-    if (rev && !recomb) return;  // no recombination: reverse layer not needed
-    const long long ro = a.read_off[rd];
-    const int n = (int)(a.read_off[rd + 1] - ro);
-    const uint8_t* read = a.reads + ro - 1;
-    const int ncols = rev ? n : n + 1;
+    LayerJob job;
+    if (!job.open(a, rd, ST_BAD_BASE | ST_WOULD_PANIC | ST_OVERFLOW | ST_RETRY, true)) return;
+    ReadState* rs = job.rs;
+    const bool rev = a.rev, recomb = job.recomb;
+    const int path = job.path, n = job.n, ncols = job.ncols, nrows = job.nrows;
+    const uint8_t* read = job.read;
     const int GAP = 5;
     extern __shared__ __attribute__((aligned(16))) int lds16[];
     int* sct = lds16;                    // [36]
@@ -1917,53 +1860,28 @@ __global__ __launch_bounds__(64, C <= 16 ? LAYER16_WAVES : 1) void k_layer16(Lay
     if (lane < 36) sct[lane] = a.sc.t[lane];
     __syncthreads();
     const int gcost = __builtin_amdgcn_readfirstlane(sct[GAP]);      // (= score(b, '-') of every row base b: see k_sweep16)
-    for (int e = lane; e < 5 * 64; e += WAVE) {
-        const int li = e >> 6, cl = e & 7, ch = (e >> 3) & 7;
-        s2[e] = (cl < 6 && ch < 6) ? pack16(sct[li * 6 + cl] - gcost, sct[li * 6 + ch] - gcost) : 0;
-    }
+    pair_table(s2, sct, gcost, lane);
     __syncthreads();
     int cur[H];
-#pragma unroll
-    for (int r = 0; r < H; ++r) {
-        const int c0 = lane * C + r, c1 = c0 + H;
-        int k0 = 4, k1 = 4;
-        if (c0 >= 1 && c0 < ncols) k0 = rev ? read[n - c0 + 1] : read[c0];
-        if (c1 >= 1 && c1 < ncols) k1 = rev ? read[n - c1 + 1] : read[c1];
-#pragma unroll
-        for (int li = 0; li < 5; ++li) sprof[(li * WAVE + lane) * H + r] = s2[li * 64 + (k0 | (k1 << 3))];
-        cur[r] = pack16(c0 < ncols ? 0 : NEG16, c1 < ncols ? 0 : NEG16);       // the gap-only start row: z = 0
-    }
+    stage_profile<H>(sprof, s2, read, n, ncols, rev, lane, cur);      // (and the gap-only start row: z = 0)
     __syncthreads();
     uint32_t* tdir = reinterpret_cast<uint32_t*>(a.layer) + (long long)rd * a.layer_stride;
-    const int* prow = rev ? a.rprow : a.fprow;
-    const int* pslot = rev ? a.rpslot : a.fpslot;
-    const int* poff = rev ? a.rpoff : a.fpoff;
     const uint32_t* dirs = a.dirs + (long long)rd * a.dirs_stride;
-    const int nrows = poff[path + 1] - poff[path];
-    const int start_row = recomb ? rs->fen : rs->end_row;
-    const int start_col = recomb ? rs->rec_col : n;
+    const int start_row = job.start_row, start_col = job.start_col;
     constexpr unsigned FULL = RowOps16<C>::FULL;
     constexpr unsigned LOWH = H >= 16 ? 0xffffu : ((1u << H) - 1u);
     constexpr int PF = LAYER16_PF;       // (rows fetched ahead)
     int pf_li[PF], pf_row[PF];
     uint32_t pf_w0[PF], pf_w1[PF];
-    // TWO-STAGE look-ahead (round 6).  A row needs its base code and its direction word, and their addresses come from the path's
-    // row / slot lists: two DEPENDENT loads.  Until round 6 both were issued in one step — `poff[path]` (loop-invariant) was even
-    // reloaded in front of them — and the row loop opened with two full memory round trips every iteration (the ISA: three loads
-    // behind three `s_waitcnt vmcnt(0)`; 2.7 us per row, all of it latency).  Now the list entries of row t + PF + 1 are loaded
-    // while row t is computed, and the loads they address are issued one iteration later, when they have landed.
-    const int pbase = poff[path];
-    int nx_row = -1, nx_slot = 0;               // list entries of the NEXT row to be fetched (index nx_t)
-    auto fetch_idx = [&](int tt) {
-        nx_row = -1; nx_slot = 0;
-        if (tt < nrows) { nx_row = prow[pbase + tt]; nx_slot = pslot[pbase + tt]; }
-    };
+    // two-stage look-ahead (LayerJob::fetch_idx; until round 6 both loads were issued in one step and the row loop opened with two full
+    // memory round trips every iteration: 2.7 us per row, all of it latency)
+    auto fetch_idx = [&](int tt) { job.fetch_idx(tt, nrows); };
     auto prefetch = [&](int& li_o, int& row_o, uint32_t& w0_o, uint32_t& w1_o) {       // the row whose list entries are in nx_row / nx_slot
-        li_o = 4; row_o = nx_row; w0_o = 0; w1_o = 0;
-        if (nx_row >= 0) {
-            li_o = g.lnz[nx_row];
-            w0_o = dirs[(long long)nx_slot * a.dir_words + lane];
-            if (C > 16) w1_o = dirs[(long long)nx_slot * a.dir_words + WAVE + lane];
+        li_o = 4; row_o = job.nx_row; w0_o = 0; w1_o = 0;
+        if (job.nx_row >= 0) {
+            li_o = g.lnz[job.nx_row];
+            w0_o = dirs[(long long)job.nx_slot * a.dir_words + lane];
+            if (C > 16) w1_o = dirs[(long long)job.nx_slot * a.dir_words + WAVE + lane];
         }
     };
 #pragma unroll
@@ -2026,12 +1944,7 @@ __global__ __launch_bounds__(64, C <= 16 ? LAYER16_WAVES : 1) void k_layer16(Lay
         for (int r = 0; r < H; ++r) {
             const int d = pk_add(o1, s[r]);
             const int u = pk_add(old[r], GI);                           // (the walkers add the row's gap cost in column 0 too, semiglobal or not)
-            const int mx = pk_max(pk_max(d, u), nl);
-            const int nd = pk_sign(pk_sub_sat(d, mx));                  // 0xffff where D does not attain the maximum
-            const int nu = pk_sign(pk_sub_sat(u, mx));
-            // 1 = D, 2 = U, 3 = L per half: bit 1 = nd, bit 0 = ~nd | nu
-            const int b0 = __builtin_amdgcn_bitop3_b32(nd, nu, ONE2, 0x8A);           // (~nd | nu) & 1
-            const unsigned code2 = (unsigned)(b0 | (nd & 0x00020002));
+            const unsigned code2 = decide16(d, u, nl);                  // 1 = D, 2 = U, 3 = L per half
             if (H <= 8) tw0 |= code2 << (2 * r);
             else { tw0 |= (code2 & 3u) << (2 * r); tw1 |= (code2 >> 16) << (2 * r); }
             o1 = old[r];
@@ -2059,12 +1972,7 @@ __global__ __launch_bounds__(64, C <= 16 ? LAYER16_WAVES : 1) void k_layer16(Lay
 
 const char* launch_layer16(const LayerArgs& a, int nreads, int C, hipStream_t s) {
     const size_t bytes = (size_t)(64 + 5 * 64 + 5 * WAVE * (C / 2)) * sizeof(int);
-    switch (C) {
-        case 4: RG_LAUNCH(k_layer16, (4), dim3(nreads), dim3(64), bytes, s, a);
-        case 8: RG_LAUNCH(k_layer16, (8), dim3(nreads), dim3(64), bytes, s, a);
-        case 16: RG_LAUNCH(k_layer16, (16), dim3(nreads), dim3(64), bytes, s, a);
-        default: RG_LAUNCH(k_layer16, (32), dim3(nreads), dim3(64), bytes, s, a);
-    }
+    RG_SWITCH_C((4, 8, 16, 32), k_layer16, (), dim3(nreads), dim3(64), bytes, s, a);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -2091,25 +1999,15 @@ __global__ __launch_bounds__(64) void k_opt0_16(Opt0Args a) {
     if (lane < 36) sct[lane] = a.sc.t[lane];
     __syncthreads();
     const int gcost = __builtin_amdgcn_readfirstlane(sct[GAP]);
-    for (int e = lane; e < 5 * 64; e += WAVE) {
-        const int li = e >> 6, cl = e & 7, ch = (e >> 3) & 7;
-        s2[e] = (cl < 6 && ch < 6) ? pack16(sct[li * 6 + cl] - gcost, sct[li * 6 + ch] - gcost) : 0;
-    }
+    pair_table(s2, sct, gcost, lane);
     __syncthreads();
     int row[H];
-#pragma unroll
-    for (int r = 0; r < H; ++r) {
-        const int c0 = lane * C + r, c1 = c0 + H;
-        int k0 = 4, k1 = 4;
-        if (c0 >= 1 && c0 < ncols) k0 = read[c0];
-        if (c1 >= 1 && c1 < ncols) k1 = read[c1];
-#pragma unroll
-        for (int li = 0; li < 5; ++li) sprof[(li * WAVE + lane) * H + r] = s2[li * 64 + (k0 | (k1 << 3))];
-        row[r] = pack16(c0 < ncols ? 0 : NEG16, c1 < ncols ? 0 : NEG16);       // the gap-only start row: z = 0
-    }
+    stage_profile<H>(sprof, s2, read, n, ncols, false, lane, row);    // (and the gap-only start row: z = 0)
     __syncthreads();
     const int GI = pack16(gcost, gcost);
     const int GI0 = lane == 0 ? pack16(a.semi ? 0 : gcost, gcost) : GI;        // border column 0 (semiglobal: stays 0)
+    // (the walk of PickedRows in its look-ahead form, restated: through the struct this kernel measured 0.80 ms for 0.75 per 4096 reads,
+    // profiles/pathwise_side_notes.md)
     const int pk = a.pick ? a.pick[rd] : 0;
     const int pk2 = (a.pick && a.pick2) ? a.pick2[2 * rd] : -1;
     const int X = pk2 >= 0 ? a.pick2[2 * rd + 1] : INT32_MAX;
@@ -2180,23 +2078,13 @@ __global__ __launch_bounds__(64) void k_opt0_16(Opt0Args a) {
 
 const char* launch_opt0_16(const Opt0Args& a, int nreads, int C, hipStream_t s) {
     const size_t bytes = (size_t)(64 + 5 * 64 + 5 * WAVE * (C / 2)) * sizeof(int);
-    switch (C) {
-        case 4: RG_LAUNCH(k_opt0_16, (4), dim3(nreads), dim3(64), bytes, s, a);
-        case 8: RG_LAUNCH(k_opt0_16, (8), dim3(nreads), dim3(64), bytes, s, a);
-        case 16: RG_LAUNCH(k_opt0_16, (16), dim3(nreads), dim3(64), bytes, s, a);
-        default: RG_LAUNCH(k_opt0_16, (32), dim3(nreads), dim3(64), bytes, s, a);
-    }
+    RG_SWITCH_C((4, 8, 16, 32), k_opt0_16, (), dim3(nreads), dim3(64), bytes, s, a);
 }
 
 template <int kColmax, bool kRec, bool kWide, bool kSemi>
 static const char* launch_sweep16_s(const SweepArgs& a, int nreads, int C, hipStream_t s) {
     const size_t bytes = (size_t)(64 + 2 * (kWide ? RG_MAXP : 64) + std::max(C * WAVE, 5 * 64) + 4 * WAVE * (C / 2)) * sizeof(int) + (size_t)options().lds_pad;
-    switch (C) {
-        case 4: RG_LAUNCH(k_sweep16, (4, kColmax, kRec, kWide, kSemi), dim3(nreads), dim3(64), bytes, s, a);
-        case 8: RG_LAUNCH(k_sweep16, (8, kColmax, kRec, kWide, kSemi), dim3(nreads), dim3(64), bytes, s, a);
-        case 16: RG_LAUNCH(k_sweep16, (16, kColmax, kRec, kWide, kSemi), dim3(nreads), dim3(64), bytes, s, a);
-        default: RG_LAUNCH(k_sweep16, (32, kColmax, kRec, kWide, kSemi), dim3(nreads), dim3(64), bytes, s, a);
-    }
+    RG_SWITCH_C((4, 8, 16, 32), k_sweep16, (, kColmax, kRec, kWide, kSemi), dim3(nreads), dim3(64), bytes, s, a);
 }
 template <int kColmax, bool kRec, bool kWide>
 static const char* launch_sweep16_w(const SweepArgs& a, int nreads, int C, hipStream_t s) {
