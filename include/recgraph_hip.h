@@ -177,6 +177,43 @@ typedef enum rg_status {
 #define RG_MODE_PATHWISE_GAP_XLONG 56
 #define RG_MODE_PATHWISE_GAP_SEMI_XLONG 57
 #define RG_MODE_PATHWISE_GAP_LOCAL_XLONG 62
+/*
+ * RG_MODE_PATHWISE_GAP_XSTRANDS (76), RG_MODE_PATHWISE_GAP_SEMI_XSTRANDS (77), RG_MODE_PATHWISE_GAP_LOCAL_XSTRANDS (82): modes 6, 7
+ * and 12 on BOTH STRANDS for reads of 1 to 131071 bases, numbered `mode + 70`.  Write "pipeline m" for mode 56, 57 or 62 of the base
+ * mode.  THERE IS NO NEW RECURRENCE, CHOICE, TIE ORDER, TRACEBACK, RECORD OR LINE; what is new is which strand is reported, and that
+ * rule is mode m + 20's, restated on the PICKED scores.  A read's PICK on a strand is (status, score, path, end row) as the score
+ * pass and the pick of pipeline m leave it: the score that decides between the strands is that integer, which no traceback changes.
+ *   MODES 76 AND 77, amb_mode 0 or 4 (bit 2 is implied and accepted as redundant): every read is picked forward; a read whose
+ *     forward pick has neither RG_READ_BAD_BASE nor RG_READ_WOULD_PANIC and a score < 0 is also picked as its reverse complement;
+ *     the reverse strand wins only when its pick has a record and a STRICTLY greater score.
+ *   MODES 76 AND 77, amb_mode 12: rules 1 to 7 of RG_AMB_STRAND_VOTE with "pass" read as "pick": the first strand by the 12-mer
+ *     vote, a read goes to the second pick iff its first score is < 0, reverse wins only if strictly greater, whichever went first.
+ *   MODE 82, amb_mode 0 or 4: every read without RG_READ_BAD_BASE is picked on both strands, and reverse wins only if strictly
+ *     greater.  An RG_READ_UNALIGNED pick scores 0: forward unaligned and reverse aligned — reverse, status 0; both unaligned —
+ *     RG_READ_UNALIGNED, strand '+', no line; ties and reverse-palindromic reads — forward.  amb_mode 12 is RG_ERR_ARG, for mode
+ *     32's reason: no score of a local pass says "hopeless", so a vote would have no rule for a second pass.
+ *   REPORTING.  The winning strand ALONE is traced.  The read is reported exactly as that strand's sequence would be had it been
+ *     submitted by itself in mode m + 50, except for strand column '-' of a reverse winner; query coordinates of mode 82 are in the
+ *     reverse complement's coordinates.  Every accessor, rg_batch_format_all and a stream's text describe the chosen record.
+ *   WHERE THE WORDING DIFFERS FROM MODES 26 / 27 / 32.  There a read qualifies by the status of its finished RECORD, here by that of
+ *     its PICK: an RG_READ_WOULD_PANIC that only the walk could raise can no longer keep a read from its reverse pick.  For a batch
+ *     the plan admits the walk cannot raise one: it starts on the pick's end row, which is a row of the picked path (its index + 1
+ *     is at most the rows of the longest path, the geometry every buffer is sized for); every emitted op moves one row up or one
+ *     column left from at most (rows of the path, n), so a walk has at most rows + n ops, below the op area of a read, min(rows of the
+ *     graph + longest read + 8, 2 (rows of the longest path + longest read) + 16); its iteration cap 3 (rows + n) + 3 covers every
+ *     valid walk; and the local kind's end column is the one the same integer row step found in the score pass.  CONSEQUENCE: for every
+ *     read of at most 16383 bases, mode m + 70 returns the bytes, statuses and scores of mode m + 20 with the same amb_mode.
+ *   REFUSALS.  amb_mode bits 0 and 1, bit 3 alone, any higher bit, positive gap costs, a read over 131071 bases: RG_ERR_ARG.  The
+ *     2^28 budget of modes 56, 57, 62: RG_ERR_CAPACITY.  All answered by rg_batch_create before a device is needed.  Modes 56, 57 and
+ *     62 keep refusing every amb_mode bit; modes 26, 27 and 32 keep their limit of 16383 bases.
+ *   COUNTERS.  rg_batch_cell_updates = rows_k * n summed over the paths, for every (read, strand) that was picked.
+ *     rg_batch_cell_updates_performed adds the traceback cells of the traced strand only: mode m + 50's formula for that strand.
+ * k_gap_pick_out, k_gap_seed_pick, k_gap_xstrands_duel and k_gap_xstrands_mark (gap_xstrands/) appear in the kernel statistics
+ * under their own names beside the gate, k_revcomp and k_strand_orient; there is no k_strand_merge and no second op area.
+ */
+#define RG_MODE_PATHWISE_GAP_XSTRANDS 76
+#define RG_MODE_PATHWISE_GAP_SEMI_XSTRANDS 77
+#define RG_MODE_PATHWISE_GAP_LOCAL_XSTRANDS 82
 
 /*
  * Scoring and banding parameters.  Replaces the HashMap<(char,char),i32|f32> score matrix arguments

@@ -56,6 +56,10 @@ MODE_PATHWISE_GAP_LOCAL_STRANDS = 32
 MODE_PATHWISE_GAP_XLONG = 56
 MODE_PATHWISE_GAP_SEMI_XLONG = 57
 MODE_PATHWISE_GAP_LOCAL_XLONG = 62
+# RG_MODE_PATHWISE_GAP_XSTRANDS / _SEMI_XSTRANDS / _LOCAL_XSTRANDS: those on both strands, the traceback run once (`mode + 70`)
+MODE_PATHWISE_GAP_XSTRANDS = 76
+MODE_PATHWISE_GAP_SEMI_XSTRANDS = 77
+MODE_PATHWISE_GAP_LOCAL_XSTRANDS = 82
 READ_UNALIGNED = 16     # RG_READ_UNALIGNED: status bit of that mode — the read has no local alignment, and no record
 
 

@@ -61,6 +61,11 @@ MODE_PATHWISE_GAP_LOCAL_STRANDS = _lib.MODE_PATHWISE_GAP_LOCAL_STRANDS
 MODE_PATHWISE_GAP_XLONG = _lib.MODE_PATHWISE_GAP_XLONG
 MODE_PATHWISE_GAP_SEMI_XLONG = _lib.MODE_PATHWISE_GAP_SEMI_XLONG
 MODE_PATHWISE_GAP_LOCAL_XLONG = _lib.MODE_PATHWISE_GAP_LOCAL_XLONG
+# ... and those on both strands (RG_MODE_PATHWISE_GAP_XSTRANDS ...: `mode + 70`, the strand rule of `mode + 20` on the picked scores of
+# `mode + 50`, the winning strand alone traced)
+MODE_PATHWISE_GAP_XSTRANDS = _lib.MODE_PATHWISE_GAP_XSTRANDS
+MODE_PATHWISE_GAP_SEMI_XSTRANDS = _lib.MODE_PATHWISE_GAP_SEMI_XSTRANDS
+MODE_PATHWISE_GAP_LOCAL_XSTRANDS = _lib.MODE_PATHWISE_GAP_LOCAL_XSTRANDS
 
 READ_BAND_WARNING, READ_BAND_NOT_ENOUGH, READ_WOULD_PANIC, READ_BAD_BASE = 1, 2, 4, 8
 READ_UNALIGNED = _lib.READ_UNALIGNED
@@ -77,6 +82,8 @@ PATHWISE_GAP_MODES = (MODE_PATHWISE_GAP, MODE_PATHWISE_GAP_SEMI, MODE_PATHWISE_G
 PATHWISE_GAP_STRANDS_MODES = (MODE_PATHWISE_GAP_STRANDS, MODE_PATHWISE_GAP_SEMI_STRANDS, MODE_PATHWISE_GAP_LOCAL_STRANDS)
 # reads of up to 131071 bases, as given: both strands at this length is not offered
 PATHWISE_GAP_XLONG_MODES = (MODE_PATHWISE_GAP_XLONG, MODE_PATHWISE_GAP_SEMI_XLONG, MODE_PATHWISE_GAP_LOCAL_XLONG)
+# ... except through these: both strands is the mode itself again, so ``both_strands=True`` is redundant there
+PATHWISE_GAP_XSTRANDS_MODES = (MODE_PATHWISE_GAP_XSTRANDS, MODE_PATHWISE_GAP_SEMI_XSTRANDS, MODE_PATHWISE_GAP_LOCAL_XSTRANDS)
 
 
 def _both_strands_kw(mode, both_strands, kw, strand_vote=False):
@@ -84,10 +91,10 @@ def _both_strands_kw(mode, both_strands, kw, strand_vote=False):
     outside the pathwise modes, where ``amb_strand`` (``-s true``) is the way."""
     if not both_strands and not strand_vote:
         return kw
-    if mode in PATHWISE_GAP_STRANDS_MODES:
-        if strand_vote and mode == MODE_PATHWISE_GAP_LOCAL_STRANDS:
-            raise _lib.RecGraphError(-1, "strand_vote is not available in mode 32: no score of a local pass says \"hopeless\", so a vote "
-                                         "would have no rule for a second pass")
+    if mode in PATHWISE_GAP_STRANDS_MODES or mode in PATHWISE_GAP_XSTRANDS_MODES:
+        if strand_vote and mode in (MODE_PATHWISE_GAP_LOCAL_STRANDS, MODE_PATHWISE_GAP_LOCAL_XSTRANDS):
+            raise _lib.RecGraphError(-1, "strand_vote is not available in mode %d: no score of a local pass says \"hopeless\", so a vote "
+                                         "would have no rule for a second pass" % mode)
         return dict(kw, amb=(kw.get("amb") or 0) | AMB_BOTH_STRANDS | (AMB_STRAND_VOTE if strand_vote else 0))
     if mode in PATHWISE_GAP_XLONG_MODES:
         raise _lib.RecGraphError(-1, "%s is not available in the affine-gap pathwise modes for reads of up to 131071 bases (56, 57, 62): they "
@@ -875,9 +882,12 @@ def pathwise_alignment_semiglobal_exec(sequence, graph, score_matrix=None):
     return GAFStruct.from_line(text.rstrip("\n"))
 
 
-def _gap_exec_mode(mode, long_reads, both_strands, very_long_reads=False):
+def _gap_exec_mode(mode, long_reads, both_strands, very_long_reads=False, very_long_both_strands=False):
     """The value of rg_params.mode behind the three wrappers below: ``mode + 20`` on both strands (which takes long reads
-    anyway), ``mode + 10`` for long reads alone, ``mode + 50`` for very long reads (which are aligned as given)."""
+    anyway), ``mode + 10`` for long reads alone, ``mode + 50`` for very long reads (which are aligned as given), ``mode + 70``
+    for very long reads on both strands (a keyword of its own: it says both, whatever the others say)."""
+    if very_long_both_strands:
+        return mode + 70
     if very_long_reads:
         if both_strands:
             raise _lib.RecGraphError(-1, "very_long_reads (modes 56, 57, 62) aligns the reads as given: both_strands is not available at this length")
@@ -885,28 +895,29 @@ def _gap_exec_mode(mode, long_reads, both_strands, very_long_reads=False):
     return mode + 20 if both_strands else mode + 10 if long_reads else mode
 
 
-def pathwise_alignment_gap_exec(sequence, graph, score_matrix=None, o=-4, e=-2, long_reads=False, both_strands=False, very_long_reads=False):
+def pathwise_alignment_gap_exec(sequence, graph, score_matrix=None, o=-4, e=-2, long_reads=False, both_strands=False, very_long_reads=False, very_long_both_strands=False):
     """-m 6: global pathwise alignment with affine gaps (a gap of length g costs o + g * e; the rule: RG_MODE_PATHWISE_GAP in
     include/recgraph_hip.h).  The reference's pathwise_alignment_gap::exec returns the index of the best path only; here that
     index is the "best path" of the GAFStruct's comments.  ``sequence`` carries the leading '$' like the reference's read arrays.
     ``long_reads=True`` (here and in the two wrappers below): the long-read flavour of the mode, reads of up to 16383 bases.
     ``both_strands=True`` (likewise): ``mode + 20``, the read on both strands — the strand of the chosen record is the GAFStruct's.
-    ``very_long_reads=True`` (likewise): ``mode + 50``, reads of up to 131071 bases as given; not together with ``both_strands``."""
-    _, text = _single(graph, "".join(sequence[1:]), "Temp", _gap_exec_mode(MODE_PATHWISE_GAP, long_reads, both_strands, very_long_reads), 1, score_matrix=score_matrix, o=o, e=e)
+    ``very_long_reads=True`` (likewise): ``mode + 50``, reads of up to 131071 bases as given; not together with ``both_strands``.
+    ``very_long_both_strands=True`` (likewise): ``mode + 70``, reads of up to 131071 bases on both strands, the winning strand alone traced."""
+    _, text = _single(graph, "".join(sequence[1:]), "Temp", _gap_exec_mode(MODE_PATHWISE_GAP, long_reads, both_strands, very_long_reads, very_long_both_strands), 1, score_matrix=score_matrix, o=o, e=e)
     return GAFStruct.from_line(text.rstrip("\n"))
 
 
-def pathwise_alignment_gap_semi_exec(sequence, graph, score_matrix=None, o=-4, e=-2, long_reads=False, both_strands=False, very_long_reads=False):
+def pathwise_alignment_gap_semi_exec(sequence, graph, score_matrix=None, o=-4, e=-2, long_reads=False, both_strands=False, very_long_reads=False, very_long_both_strands=False):
     """-m 7: the semiglobal twin of ``pathwise_alignment_gap_exec`` (the alignment may start and end inside a path)."""
-    _, text = _single(graph, "".join(sequence[1:]), "Temp", _gap_exec_mode(MODE_PATHWISE_GAP_SEMI, long_reads, both_strands, very_long_reads), 1, score_matrix=score_matrix, o=o, e=e)
+    _, text = _single(graph, "".join(sequence[1:]), "Temp", _gap_exec_mode(MODE_PATHWISE_GAP_SEMI, long_reads, both_strands, very_long_reads, very_long_both_strands), 1, score_matrix=score_matrix, o=o, e=e)
     return GAFStruct.from_line(text.rstrip("\n"))
 
 
-def pathwise_alignment_gap_local_exec(sequence, graph, score_matrix=None, o=-4, e=-2, long_reads=False, both_strands=False, very_long_reads=False):
+def pathwise_alignment_gap_local_exec(sequence, graph, score_matrix=None, o=-4, e=-2, long_reads=False, both_strands=False, very_long_reads=False, very_long_both_strands=False):
     """-m 12: the local member of the family (RG_MODE_PATHWISE_GAP_LOCAL in include/recgraph_hip.h): the best-scoring piece of the
     read against a piece of one path; query_start / query_end of the GAFStruct say which piece of the read.  A read without a
     local alignment (READ_UNALIGNED) raises, like a read with a bad base."""
-    _, text = _single(graph, "".join(sequence[1:]), "Temp", _gap_exec_mode(MODE_PATHWISE_GAP_LOCAL, long_reads, both_strands, very_long_reads), 1, score_matrix=score_matrix, o=o, e=e)
+    _, text = _single(graph, "".join(sequence[1:]), "Temp", _gap_exec_mode(MODE_PATHWISE_GAP_LOCAL, long_reads, both_strands, very_long_reads, very_long_both_strands), 1, score_matrix=score_matrix, o=o, e=e)
     return GAFStruct.from_line(text.rstrip("\n"))
 
 

@@ -47,7 +47,8 @@ def build_parser():
     p.add_argument("-o", "--out_file", default="standard output")
     p.add_argument("-m", "--aln-mode", type=int, default=0, dest="alignment_mode",
                    help="0 to 9 as in the reference; 12: local affine-gap pathwise; 16, 17, 22: modes 6, 7, 12 for reads of up to 16383 bases; "
-                        "26, 27, 32: those on both strands (--strand-vote: 26 and 27 only); 56, 57, 62: modes 6, 7, 12 for reads of up to 131071 bases")
+                        "26, 27, 32: those on both strands (--strand-vote: 26 and 27 only); 56, 57, 62: modes 6, 7, 12 for reads of up to 131071 bases; "
+                        "76, 77, 82: those on both strands, the traceback run once, on the strand that won (--strand-vote: 76 and 77 only)")
     p.add_argument("-M", "--match", type=int, default=2, dest="match_score")
     p.add_argument("-X", "--mismatch", type=int, default=4, dest="mismatch_score")
     p.add_argument("-t", "--matrix", default="none")
@@ -60,10 +61,10 @@ def build_parser():
     p.add_argument("-b", "--extra-b", type=int, default=1)
     p.add_argument("-f", "--extra-f", type=float, default=0.01)
     p.add_argument("--both-strands", action="store_true", dest="both_strands",
-                   help="modes 4, 5, 8, 9 (not a flag of the reference; refused in 6 and 7; redundant in 26, 27, 32): reads that score below 0 are aligned again as their reverse "
+                   help="modes 4, 5, 8, 9 (not a flag of the reference; refused in 6 and 7; redundant in 26, 27, 32, 76, 77, 82): reads that score below 0 are aligned again as their reverse "
                         "complement; a strictly better reverse record is written with strand '-'")
     p.add_argument("--strand-vote", action="store_true", dest="strand_vote",
-                   help="modes 4, 5, 8, 9, 26, 27 (not a flag of the reference; implies --both-strands): the strand that is aligned first is "
+                   help="modes 4, 5, 8, 9, 26, 27, 76, 77 (not a flag of the reference; implies --both-strands): the strand that is aligned first is "
                         "picked per read by a vote of its 12-mers against the paths'")
     p.add_argument("--scalar", action="store_true", help="-m 0 / -m 1 with the non-AVX2 path of the reference")
     p.add_argument("--devices", default="", help="comma-separated HIP device ids (default: every visible device)")
@@ -88,7 +89,8 @@ def main(argv=None):
     # 16, 17, 22: the long-read flavours of 6, 7, 12 (reads of up to 16383 bases), admitted beside the modes the message names
     # 26, 27, 32: the same three on both strands; --both-strands is redundant there, --strand-vote the vote rule of 26 and 27
     # 56, 57, 62: 6, 7, 12 for reads of up to 131071 bases, as given
-    if a.alignment_mode not in (0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 12, 16, 17, 22, 26, 27, 32, 56, 57, 62):
+    # 76, 77, 82: those on both strands; --both-strands is redundant there, --strand-vote the vote rule of 76 and 77
+    if a.alignment_mode not in (0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 12, 16, 17, 22, 26, 27, 32, 56, 57, 62, 76, 77, 82):
         raise SystemExit("Alignment mode must be in [0..9], or 12")   # main.rs:315-317; 12: local affine-gap pathwise, this project's own
     if a.alignment_mode in (6, 7) and (a.both_strands or a.strand_vote):
         raise SystemExit("--both-strands / --strand-vote are not available in modes 6 and 7: they align the reads as given")
@@ -98,8 +100,8 @@ def main(argv=None):
         raise SystemExit("--both-strands / --strand-vote are not available in modes 16, 17 and 22: they align the reads as given")
     if a.alignment_mode in (56, 57, 62) and (a.both_strands or a.strand_vote):
         raise SystemExit("--both-strands / --strand-vote are not available in modes 56, 57 and 62: they align the reads as given")
-    if a.alignment_mode == 32 and a.strand_vote:
-        raise SystemExit("--strand-vote is not available in mode 32: no score of a local pass says \"hopeless\", so a vote would have no rule for a second pass")
+    if a.alignment_mode in (32, 82) and a.strand_vote:
+        raise SystemExit("--strand-vote is not available in mode %d: no score of a local pass says \"hopeless\", so a vote would have no rule for a second pass" % a.alignment_mode)
     amb = a.amb_strand == "true" and a.alignment_mode in (0, 1, 2, 3)     # modes 4+ ignore -s (main.rs:254-313)
     if a.strand_vote and a.alignment_mode in (0, 1, 2, 3):
         raise SystemExit("--strand-vote applies to modes 4, 5, 8 and 9: for modes 0-3 use `-s true`")
@@ -118,7 +120,8 @@ def main(argv=None):
             9: api.MODE_RECOMBINATION_SEMI, 12: api.MODE_PATHWISE_GAP_LOCAL, 16: api.MODE_PATHWISE_GAP_LONG,
             17: api.MODE_PATHWISE_GAP_SEMI_LONG, 22: api.MODE_PATHWISE_GAP_LOCAL_LONG, 26: api.MODE_PATHWISE_GAP_STRANDS,
             27: api.MODE_PATHWISE_GAP_SEMI_STRANDS, 32: api.MODE_PATHWISE_GAP_LOCAL_STRANDS, 56: api.MODE_PATHWISE_GAP_XLONG,
-            57: api.MODE_PATHWISE_GAP_SEMI_XLONG, 62: api.MODE_PATHWISE_GAP_LOCAL_XLONG}[a.alignment_mode]
+            57: api.MODE_PATHWISE_GAP_SEMI_XLONG, 62: api.MODE_PATHWISE_GAP_LOCAL_XLONG, 76: api.MODE_PATHWISE_GAP_XSTRANDS,
+            77: api.MODE_PATHWISE_GAP_SEMI_XSTRANDS, 82: api.MODE_PATHWISE_GAP_LOCAL_XSTRANDS}[a.alignment_mode]
     kw = dict(score_matrix=scores, o=-a.gap_open, e=-a.gap_extension, b=float(a.extra_b), f=a.extra_f,
               R=a.base_rec_cost, r=a.multi_rec_cost, B=a.rec_band_width)
     to_file = a.out_file != "standard output"
@@ -133,7 +136,7 @@ def main(argv=None):
         records, numbers = [], []
         # warning lines are println!'d by the exec functions whatever -o says; only the record goes through write_gaf
         for k, t in enumerate(texts):
-            if not t and a.alignment_mode in (12, 22, 32, 62):       # a read without a local alignment (RG_READ_UNALIGNED) has no record
+            if not t and a.alignment_mode in (12, 22, 32, 62, 82):      # a read without a local alignment (RG_READ_UNALIGNED) has no record
                 continue
             lines = t.split("\n")[:-1]
             sys.stdout.write("".join(ln + "\n" for ln in lines[:-1]))

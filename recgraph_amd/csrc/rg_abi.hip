@@ -332,7 +332,8 @@ static int load_reads(rg_batch* b, const char* reads, const int64_t* read_off, i
     b->ops_stride = is_poa(mode) ? (long long)h.L + b->max_n + 8
                                  : std::min<long long>((long long)h.L + b->max_n + 8, 2ll * (h.max_path_rows + b->max_n) + 16);
     const bool both = !is_poa(mode) && (p->amb_mode & RG_AMB_BOTH_STRANDS);
-    if (both) b->ops_stride = (b->ops_stride + 15) & ~15ll;      // k_strand_merge moves op bytes in 16-byte pieces
+    // k_strand_merge moves op bytes in 16-byte pieces (-m 76 / -m 77 / -m 82 trace the chosen strand alone: no merge, the op area of -m 56 / -m 57 / -m 62)
+    if (both && !path_gap_xstrands_mode(mode)) b->ops_stride = (b->ops_stride + 15) & ~15ll;
     if ((rc = b->d_ops.alloc((size_t)nreads * b->ops_stride))) return rc;
     if (both && (rc = size_strand_buffers(b, total))) return rc;
     if (is_poa(mode)) {
@@ -359,7 +360,7 @@ int32_t rg_batch_create(const rg_graph* gc, const rg_params* p, const char* read
     if (!gc || !p || !reads || !read_off || !out || nreads < 1) return fail(RG_ERR_ARG, "null/empty argument");
     const rg_graph* g = gc;
     const int mode = p->mode;
-    const int gbase = path_gap_base_mode(mode);       // (-m 16 / -m 17 / -m 22: the long-read flavours of 6, 7, 12; -m 26 / -m 27 / -m 32: those on both strands; -m 56 / -m 57 / -m 62: reads of up to 131071 bases)
+    const int gbase = path_gap_base_mode(mode);       // (-m 16 / -m 17 / -m 22: the long-read flavours of 6, 7, 12; -m 26 / -m 27 / -m 32: those on both strands; -m 56 / -m 57 / -m 62: reads of up to 131071 bases; -m 76 / -m 77 / -m 82: those on both strands)
     const bool path_gap = gbase == RG_MODE_PATHWISE_GAP || gbase == RG_MODE_PATHWISE_GAP_SEMI || gbase == RG_MODE_PATHWISE_GAP_LOCAL;
     if (!(is_poa(mode) || mode == RG_MODE_PATHWISE || mode == RG_MODE_RECOMBINATION || mode == RG_MODE_PATHWISE_SEMI ||
           mode == RG_MODE_RECOMBINATION_SEMI || path_gap))
@@ -405,7 +406,7 @@ int32_t rg_batch_create(const rg_graph* gc, const rg_params* p, const char* read
     b->p = *p;
     // -m 26 / -m 27 / -m 32 align both strands whatever the bit says: from here on the handle IS a both-strands handle (the 16-byte
     // ops_stride, the strand buffers, the strand of a record)
-    if (path_gap_strands_mode(mode)) b->p.amb_mode |= RG_AMB_BOTH_STRANDS;
+    if (path_gap_strands_mode(mode) || path_gap_xstrands_mode(mode)) b->p.amb_mode |= RG_AMB_BOTH_STRANDS;      // (-m 76 / -m 77 / -m 82 likewise)
     HIPCHK(hipGetDevice(&b->dev));
     {
         // the handle's stream at the highest priority: it carries the small kernels; the pathwise sweeps run on a low-priority

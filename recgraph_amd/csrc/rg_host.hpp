@@ -90,8 +90,13 @@ inline bool path_gap_long_mode(int mode) {
 inline bool path_gap_xlong_mode(int mode) {
     return mode == RG_MODE_PATHWISE_GAP_XLONG || mode == RG_MODE_PATHWISE_GAP_SEMI_XLONG || mode == RG_MODE_PATHWISE_GAP_LOCAL_XLONG;
 }
+// ... and those on both strands `mode + 70` (76, 77, 82): the strand rule of `mode + 20` on the PICKED scores of pipeline `mode + 50`,
+// the traceback run once per read, on the strand that won (gap_xstrands/).  amb_mode 0, 4 or (76 / 77) 12
+inline bool path_gap_xstrands_mode(int mode) {
+    return mode == RG_MODE_PATHWISE_GAP_XSTRANDS || mode == RG_MODE_PATHWISE_GAP_SEMI_XSTRANDS || mode == RG_MODE_PATHWISE_GAP_LOCAL_XSTRANDS;
+}
 inline int path_gap_base_mode(int mode) {
-    return path_gap_xlong_mode(mode) ? mode - 50 : path_gap_strands_mode(mode) ? mode - 20 : path_gap_long_mode(mode) ? mode - 10 : mode;
+    return path_gap_xstrands_mode(mode) ? mode - 70 : path_gap_xlong_mode(mode) ? mode - 50 : path_gap_strands_mode(mode) ? mode - 20 : path_gap_long_mode(mode) ? mode - 10 : mode;
 }
 
 // Reads per launch when `n` reads go through launches of at most `maxchunk` (both >= 1): as few launches as that allows, and

@@ -145,6 +145,10 @@ struct PathJob {
     DevRecord* rec;                 // out [nreads]
     uint8_t* ops;                   // out [nreads][ops_stride]
     long long ops_stride;
+    // which part of the pipeline runs (PATH_STAGE_*, rg_path_plan.hpp): the whole of it, or — affine-gap pipelines, -m 76 / -m 77 /
+    // -m 82 — the PICK stage (score pass + pick: `rec` gets status, score, path and end row, `ops` is not touched and may be null) or
+    // the TRACE stage (`rec` holds such picks on entry, and the records and ops of the traceback on return)
+    int stage = 0;
 };
 // cells [2]: the job's cell updates, counted | performed, are ADDED
 int path_driver_run(const PathCtx& c, const PathJob& j, unsigned long long* cells);

@@ -8,6 +8,9 @@
 //   -m 16, 17, 22: the rules of -m 6, 7, 12; a batch with a read over 2047 bases runs the striped kernels    (gap_long/rg_path_gap_long.hip)
 //   -m 56, 57, 62: gap_score_long -> gap_pick -> gap_ckpt_long -> (gap_redo_long -> gap_walk_long) per stripe, last to first     (gap_xlong/rg_path_gap_xlong.hip)
 //   -m 26, 27, 32: two passes of -m 16, 17, 22, each planned here by its own longest read (the passes: rg_strand_driver.hip)
+//   -m 76, 77, 82: the pipeline of -m 56, 57, 62 in STAGES (PathJob::stage): PICK = gap_score[_long] -> gap_pick -> gap_pick_out, run per
+//          strand; TRACE = gap_seed_pick -> the rest of the pipeline, run once (gap_xstrands/rg_gap_xstrands.hip; the stages of a batch:
+//          rg_strand_driver.hip)
 //   -m 8:  sweep(F1: column maxima) -> seed -> thr -> sweep(R: dirs, candidates, column maxima)
 //          -> thr -> sweep(F2: dirs, candidates) -> search -> layer(F) -> layer(R) -> trace
 #include <algorithm>
@@ -20,6 +23,7 @@
 #include "gap_local/rg_path_gap_local.hpp"
 #include "gap_long/rg_path_gap_long.hpp"
 #include "gap_xlong/rg_path_gap_xlong.hpp"
+#include "gap_xstrands/rg_gap_xstrands.hpp"
 #include "rg_kernel_timer.hpp"
 #include "rg_path_kernels.hpp"
 #include "rg_path_plan.hpp"
@@ -158,9 +162,12 @@ int Run::alloc_chunk(bool* oom) {
     const size_t n = (size_t)chunk, wpad = (size_t)plan.wpad;
     int rc;
     if (plan.gap) {
-        if ((rc = w.state.alloc(n, oom)) || (rc = w.gdirs.alloc(n * (size_t)plan.gdirs_stride, oom))) return rc;
+        // (a stage allocates what its kernels touch: plan_gap_stage counted the same buffers)
+        const bool score = plan.stage != PATH_STAGE_TRACE, trace = plan.stage != PATH_STAGE_PICK;
+        if ((rc = w.state.alloc(n, oom)) || (trace && (rc = w.gdirs.alloc(n * (size_t)plan.gdirs_stride, oom)))) return rc;
         if (plan.gap_xlong) {
-            if ((rc = w.gbnd.alloc(n * (size_t)plan.gbnd_stride, oom)) || (rc = w.gckpt.alloc(n * (size_t)plan.gckpt_stride, oom)) || (rc = w.gwalk.alloc(n, oom))) return rc;
+            if (score && (rc = w.gbnd.alloc(n * (size_t)plan.gbnd_stride, oom))) return rc;
+            if (trace && ((rc = w.gckpt.alloc(n * (size_t)plan.gckpt_stride, oom)) || (rc = w.gwalk.alloc(n, oom)))) return rc;
             return RG_OK;
         }
         if (plan.nwv > 1 && ((rc = w.gbnd.alloc(n * (size_t)plan.gbnd_stride, oom)) || (rc = w.gdbnd.alloc(n * (size_t)plan.gdbnd_stride, oom)))) return rc;
@@ -249,7 +256,7 @@ int Run::enqueue_pathwise_gap() {
     memset(&ga, 0, sizeof ga);
     ga.sc = sc; ga.lnz = gd.lnz; ga.reads = d_reads; ga.read_off = off(); ga.bad = bad(); ga.poff = w.fpoff.p; ga.prow = w.fprow.p;
     ga.P = h.P; ga.o = p.gap_open; ga.e = p.gap_ext; ga.state = w.state.p; ga.dirs = w.gdirs.p; ga.dirs_stride = plan.gdirs_stride;
-    ga.cells = d_cells; ga.rec = d_rec + done; ga.ops = d_ops + (long long)done * ops_stride; ga.ops_stride = ops_stride;
+    ga.cells = d_cells; ga.rec = d_rec + done; ga.ops = d_ops ? d_ops + (long long)done * ops_stride : nullptr; ga.ops_stride = ops_stride;
     const int C = plan.C;
     const bool semi = plan.semi, local = plan.local;
     const int kind = local ? GAP_LOCAL : semi ? GAP_SEMI : GAP_GLOBAL;
@@ -262,11 +269,23 @@ int Run::enqueue_pathwise_gap() {
         return step("k_gap_pick", [&] { return launch_gap_pick(ga, chunk, plan.nwv * C, semi, stream); },
                     "k_gap_pick_local", [&] { return launch_gap_pick_local(ga, chunk, plan.nwv * C, stream); });
     };
+    // the stages of -m 76 / -m 77 / -m 82: a PICK stage ends behind the pick, which goes out into the job's records; a TRACE stage
+    // begins there, with the picks of the records (the whole pipeline runs score, pick and the rest without either)
+    const bool score = plan.stage != PATH_STAGE_TRACE;
+    auto pick_out = [&] {
+        RG_TRY(T.run("k_gap_pick_out", [&] { return launch_gap_pick_out(w.state.p, ga.rec, chunk, stream); }));
+        return read_back();
+    };
+    auto seed_pick = [&] { return T.run("k_gap_seed_pick", [&] { return launch_gap_seed_pick(ga.rec, w.state.p, chunk, stream); }); };
     if (plan.nwv == 1) {
         // single wave: the whole row in one wave's registers
-        RG_TRY(step("k_gap_score", [&] { return launch_gap_score(ga, chunk, C, semi, stream); },
-                    "k_gap_score_local", [&] { return launch_gap_score_local(ga, chunk, C, stream); }));
-        RG_TRY(pick());
+        if (score) {
+            RG_TRY(step("k_gap_score", [&] { return launch_gap_score(ga, chunk, C, semi, stream); },
+                        "k_gap_score_local", [&] { return launch_gap_score_local(ga, chunk, C, stream); }));
+            RG_TRY(pick());
+        }
+        if (plan.stage == PATH_STAGE_PICK) return pick_out();
+        if (plan.stage == PATH_STAGE_TRACE) RG_TRY(seed_pick());
         RG_TRY(step("k_gap_dirs", [&] { return launch_gap_dirs(ga, chunk, C, semi, stream); },
                     "k_gap_dirs_local", [&] { return launch_gap_dirs_local(ga, chunk, C, stream); }));
         RG_TRY(step("k_gap_trace", [&] { return launch_gap_trace(ga, chunk, C, semi, stream); },
@@ -277,9 +296,13 @@ int Run::enqueue_pathwise_gap() {
     GapLongArgs la;
     memset(&la, 0, sizeof la);
     la.g = ga; la.S = plan.nwv; la.rows1 = h.max_path_rows + 1;
-    la.bnd = w.gbnd.p; la.bnd_stride = plan.gbnd_stride; la.dbnd = plan.gap_xlong ? nullptr : w.gdbnd.p;
-    RG_TRY(T.run("k_gap_score_long", [&] { return launch_gap_score_long(la, chunk, kind, stream, plan.gap_xlong ? GAP_XLONG_MAX_STRIPES : GAP_LONG_MAX_STRIPES); }));
-    RG_TRY(pick());
+    la.bnd = score ? w.gbnd.p : nullptr; la.bnd_stride = plan.gbnd_stride; la.dbnd = plan.gap_xlong ? nullptr : w.gdbnd.p;
+    if (score) {
+        RG_TRY(T.run("k_gap_score_long", [&] { return launch_gap_score_long(la, chunk, kind, stream, plan.gap_xlong ? GAP_XLONG_MAX_STRIPES : GAP_LONG_MAX_STRIPES); }));
+        RG_TRY(pick());
+    }
+    if (plan.stage == PATH_STAGE_PICK) return pick_out();
+    if (plan.stage == PATH_STAGE_TRACE) RG_TRY(seed_pick());
     if (!plan.gap_xlong) {
         // striped: the direction words of every stripe, one walk
         RG_TRY(T.run("k_gap_dirs_long", [&] { return launch_gap_dirs_long(la, chunk, kind, stream); }));
@@ -631,7 +654,7 @@ int path_driver_run(const PathCtx& c, const PathJob& j, unsigned long long* cell
     const Options& opt = options();
     PathPlan plan;
     int rc = plan_pathwise(p, PathPlanInput{h.P, h.L, h.fslots, h.rslots, h.max_path_rows, j.max_n}, opt, c.spec_level, plan);
-    if (rc) return rc;
+    if (rc || (rc = plan_gap_stage(plan, j.stage))) return rc;
     Run r{h, c.gd, p, w, plan, j.reads, j.off, j.bad, j.max_n, j.rec, j.ops, j.ops_stride, d_cells, stream, stats, c.spec_level, c.T, opt.debug != 0};
     for (int i = 0; i < 36; ++i) r.sc.t[i] = p.scores[i];
     if (!w.h_sum) HIPCHK(hipHostMalloc((void**)&w.h_sum, 8 * sizeof(unsigned long long), hipHostMallocDefault));

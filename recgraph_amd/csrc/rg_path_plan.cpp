@@ -81,24 +81,27 @@ bool sweep16_admissible(const DevScores& sc, int max_path_rows, int max_n, int C
 static int plan_pathwise_gap(const rg_params& p, const PathPlanInput& in, PathPlan& o) {
     if (p.gap_open > 0 || p.gap_ext > 0) return fail(RG_ERR_ARG, "gap penalties must be <= 0");
     const bool lng = path_gap_long_mode(p.mode);
-    const bool xlng = path_gap_xlong_mode(p.mode);
+    const bool xstr = path_gap_xstrands_mode(p.mode);
+    const bool xlng = path_gap_xlong_mode(p.mode) || xstr;      // (-m 76 / -m 77 / -m 82: every stage is one of pipeline 56 / 57 / 62)
     const int base = path_gap_base_mode(p.mode);
     const bool local = base == RG_MODE_PATHWISE_GAP_LOCAL;
-    if (path_gap_strands_mode(p.mode)) {
-        // -m 26 / -m 27 / -m 32: both strands is what the mode does (bit 2 is redundant); the vote is a rule of the two modes whose
-        // scores can be negative.  Every pass of such a batch is planned here, with the pass's own longest read
+    if (xstr || path_gap_strands_mode(p.mode)) {
+        // -m 26 / -m 27 / -m 32 and -m 76 / -m 77 / -m 82: both strands is what the mode does (bit 2 is redundant); the vote is a rule
+        // of the two modes whose scores can be negative.  Every pass (every stage) of such a batch is planned here, with its own longest read
         if (local && p.amb_mode == (RG_AMB_BOTH_STRANDS | RG_AMB_STRAND_VOTE))
-            return fail(RG_ERR_ARG, "RG_AMB_STRAND_VOTE is not available in the local both-strands mode (-m 32): no score of a local pass says "
-                                    "\"hopeless\", so a vote would have no rule for a second pass");
+            return fail(RG_ERR_ARG, "RG_AMB_STRAND_VOTE is not available in the local both-strands mode (-m " + std::to_string(p.mode) +
+                                    "): no score of a local pass says \"hopeless\", so a vote would have no rule for a second pass");
         if (p.amb_mode != 0 && p.amb_mode != RG_AMB_BOTH_STRANDS && p.amb_mode != (RG_AMB_BOTH_STRANDS | RG_AMB_STRAND_VOTE))
-            return fail(RG_ERR_ARG, "amb_mode must be 0, 4 or 12 in the both-strands affine-gap pathwise modes (-m 26 / -m 27), 0 or 4 in -m 32");
+            return fail(RG_ERR_ARG, std::string("amb_mode must be 0, 4 or 12 in the both-strands affine-gap pathwise modes ") +
+                                    (xstr ? "for reads of up to 131071 bases (-m 76 / -m 77), 0 or 4 in -m 82" : "(-m 26 / -m 27), 0 or 4 in -m 32"));
     } else if (p.amb_mode)
         return fail(RG_ERR_ARG, xlng    ? "amb_mode must be 0 in the affine-gap pathwise modes for reads of up to 131071 bases (-m 56 / -m 57 / -m 62): they align the reads as given"
                                 : lng   ? "amb_mode must be 0 in the long-read affine-gap pathwise modes (-m 16 / -m 17 / -m 22): they align the reads as given"
                                 : local ? "amb_mode must be 0 in the local affine-gap pathwise mode (-m 12): it aligns the reads as given"
                                         : "amb_mode must be 0 in the affine-gap pathwise modes (-m 6 / -m 7): they align the reads as given");
     if (xlng && in.max_n > 64 * 32 * WAVE - 1)
-        return fail(RG_ERR_ARG, "reads longer than 131071 bases are not supported by the affine-gap pathwise modes -m 56 / -m 57 / -m 62");
+        return fail(RG_ERR_ARG, xstr ? "reads longer than 131071 bases are not supported by the both-strands affine-gap pathwise modes -m 76 / -m 77 / -m 82"
+                                     : "reads longer than 131071 bases are not supported by the affine-gap pathwise modes -m 56 / -m 57 / -m 62");
     if (lng && in.max_n > 8 * 32 * WAVE - 1)
         return fail(RG_ERR_ARG, "reads longer than 16383 bases are not supported by the long-read affine-gap pathwise modes (-m 16 / -m 17 / -m 22, and -m 26 / -m 27 / -m 32 on both strands)");
     if (!lng && !xlng && in.max_n > 32 * WAVE - 1)
@@ -142,6 +145,17 @@ static int plan_pathwise_gap(const rg_params& p, const PathPlanInput& in, PathPl
     }
     for (int x = 0; x < 5; ++x)
         for (int y = 0; y < 5; ++y) o.maxmatch = std::max(o.maxmatch, p.scores[x * 6 + y]);
+    return RG_OK;
+}
+
+int plan_gap_stage(PathPlan& o, int stage) {
+    if (stage == PATH_STAGE_ALL) return RG_OK;
+    if ((stage != PATH_STAGE_PICK && stage != PATH_STAGE_TRACE) || !o.gap || (o.nwv > 1 && !o.gap_xlong))
+        return fail(RG_ERR_ARG, "a pick or trace stage needs an affine-gap plan of one wave or of the checkpointed stripes");
+    // (only the score pass reads and writes the boundary ints: gap_xlong/ exchanges its stripes through the checkpoint slots)
+    const size_t bnd = o.nwv > 1 ? (size_t)o.gbnd_stride * 4 : 0;
+    o.stage = stage;
+    o.per_read = stage == PATH_STAGE_PICK ? sizeof(ReadState) + bnd : o.per_read - bnd;
     return RG_OK;
 }
 

@@ -72,6 +72,9 @@ struct PathPlan {
     bool gap_xlong;
     long long gckpt_stride;
     size_t gwalk_bytes;
+    // -m 76 / -m 77 / -m 82 (rg_strand_driver.hip): which part of the affine-gap pipeline a job runs (PATH_STAGE_*, plan_gap_stage);
+    // PATH_STAGE_ALL in every plan plan_pathwise returns
+    int stage;
 
     // ... with candidate lists of fcap / rcap entries and record lists of frec_cap / rrec_cap records
     size_t per_read_all(unsigned fcap_, unsigned rcap_, unsigned frec_cap_, unsigned rrec_cap_) const {
@@ -84,6 +87,16 @@ struct PathPlan {
 // spec_level: 0 = the batch itself; 1 = the reads whose speculation failed, once more with a generous margin; 2 = what fails
 // even that, with the provable bound.  RG_ERR_ARG / RG_ERR_CAPACITY (through fail()) for batches the kernels cannot take.
 int plan_pathwise(const rg_params& p, const PathPlanInput& in, const Options& opt, int spec_level, PathPlan& out);
+
+// The stages of an affine-gap pipeline (PathJob::stage, rg_path_args.hpp).  PICK: score pass + pick, and the pick goes out into the
+// job's records (status, score, path, end row; no ops).  TRACE: the picks come back in from the job's records, then the direction
+// pass and the walk as they are.
+enum { PATH_STAGE_ALL = 0, PATH_STAGE_PICK = 1, PATH_STAGE_TRACE = 2 };
+// Narrows a plan of plan_pathwise to one stage: `stage`, and `per_read` = what the stage's kernels touch.  PICK: ReadState and, when
+// striped, the score pass's P * 2 * (rows + 1) boundary ints; TRACE: the whole pipeline's minus those ints.  Geometry, strides and
+// kernels are untouched.  RG_ERR_ARG for a plan that is no affine-gap plan, and for the striped plan of -m 16 / -m 17 / -m 22, whose
+// direction pass has no caller that runs it alone.
+int plan_gap_stage(PathPlan& plan, int stage);
 
 bool sweep16_admissible(const DevScores& sc, int max_path_rows, int max_n, int C);
 

@@ -10,7 +10,10 @@
 // affine-gap modes each pass is planned by its own longest read, so one may run the striped kernels and the other the base ones.
 // Every pass is path_driver_run on the same context; the passes differ in their PathJob alone.  The work buffers are owned by
 // PathWork, the strand buffers by the handle (size_strand_buffers).
+//
+// -m 76, 77, 82 (both strands at up to 131071 bases) are not two passes but two PICK stages and one TRACE stage: run_gap_xstrands below.
 #include "gap_strands/rg_gap_strands.hpp"
+#include "gap_xstrands/rg_gap_xstrands.hpp"
 #include "rg_batch_impl.hpp"
 
 int size_strand_buffers(rg_batch* b, size_t total) {
@@ -22,16 +25,86 @@ int size_strand_buffers(rg_batch* b, size_t total) {
     RG_TRY(b->d_rc.alloc(total + 64));
     RG_TRY(b->d_rcbad.alloc(n));
     RG_TRY(b->d_rec2.alloc(n));
-    RG_TRY(b->d_ops2.alloc(n * b->ops_stride));
+    // (-m 76 / -m 77 / -m 82 trace one strand per read, into d_ops: no second op area — at 131071 bases it would be the largest
+    // buffer of the handle; their strand byte and their trace input take the vote's two buffers, vote or not)
+    const bool xstrands = path_gap_xstrands_mode(b->p.mode);
+    if (!xstrands) RG_TRY(b->d_ops2.alloc(n * b->ops_stride));
     RG_TRY(b->h_ssum.alloc(2));
-    if (b->p.amb_mode & RG_AMB_STRAND_VOTE) {
+    if (xstrands || (b->p.amb_mode & RG_AMB_STRAND_VOTE)) {
         RG_TRY(b->d_first_rev.alloc(n));
         RG_TRY(b->d_pa.alloc(total + 64));
     }
     return RG_OK;
 }
 
+// -m 76 / -m 77 / -m 82: both strands on pipeline 56 / 57 / 62, the traceback run once per read (include/recgraph_hip.h,
+// RG_MODE_PATHWISE_GAP_XSTRANDS).  The strand rule of -m 26 / -m 27 / -m 32 needs the SCORES of the two strands, and
+// those are final after the pick: two PICK stages and one TRACE stage of path_driver_run, each planned by its own longest read,
+// joined by the gate and k_revcomp as they are and by the kernels of gap_xstrands/:
+//
+//   [k_strand_vote -> k_strand_orient ->]  PICK(first strand, all reads) -> d_rec  ->  k_strand_gate | k_gap_strands_gate  ->  k_revcomp
+//   ->  {count, max_len} to the host  [->  PICK(other strand, qualifying reads) -> d_rec2  ->  k_gap_xstrands_duel]
+//   ->  k_strand_orient(the strand that won)  ->  TRACE(all reads) -> d_rec, d_ops  ->  k_gap_xstrands_mark
+//
+// The strand byte of a read lives in d_first_rev (the vote's answer, or zeros), flipped by the duel where the other strand wins;
+// d_pa is the first PICK's input under the vote and the TRACE's input always (every kernel that read the first is through by then:
+// one stream).  The walk's record writer clears DevRecord.pad, so the strand flag goes on behind the TRACE stage.
+static int run_gap_xstrands(rg_batch* b) {
+    const HostGraph& h = b->g->h;
+    const int n = (int)b->nreads;
+    const bool vote = (b->p.amb_mode & RG_AMB_STRAND_VOTE) != 0;
+    KernelTimer& T = b->timer;
+    const PathCtx cx{h, b->gt->pgd, b->p, b->pw, b->stream, b->d_cells.p, b->mem_budget, T, b->stats, 0};
+    unsigned long long cells[2] = {0, 0};
+    auto counters = [&] { b->cells = cells[0]; b->cells_performed = cells[1]; };
+    PathJob a{b->in.reads, b->in.off, b->in.bad, n, b->max_n, b->d_rec.p, nullptr, b->ops_stride, PATH_STAGE_PICK};
+    StrandOrientArgs oa{b->in.reads, b->in.off, b->d_first_rev.p, b->d_pa.p};
+    if (vote) {
+        const uint32_t* keys = nullptr;
+        unsigned table_mask = 0;
+        RG_TRY(path_driver_vote_table(h, b->pw, &keys, &table_mask));
+        StrandVoteArgs va{b->in.reads, b->in.off, b->in.bad, keys, table_mask, b->d_first_rev.p};
+        RG_TRY(T.run("k_strand_vote", [&] { return launch_strand_vote(va, n, b->stream); }));
+        RG_TRY(T.run("k_strand_orient", [&] { return launch_strand_orient(oa, n, b->stream); }));
+        a.reads = b->d_pa.p;
+    } else {
+        HIPCHK(hipMemsetAsync(b->d_first_rev.p, 0, (size_t)n, b->stream));
+    }
+    const int rc_a = path_driver_run(cx, a, cells);
+    counters();
+    if (rc_a) return rc_a;
+    // the gates of -m 26 / -m 27 and of -m 32 on the picks: both read status and score only
+    StrandGateArgs ga{b->d_rec.p, b->in.off, n, 0, b->d_sidx.p, b->d_rcoff.p, b->d_ssum.p, vote ? b->d_first_rev.p : nullptr};
+    if (b->p.mode == RG_MODE_PATHWISE_GAP_LOCAL_XSTRANDS) RG_TRY(T.run("k_gap_strands_gate", [&] { return launch_gap_strands_gate(ga, b->stream); }));
+    else RG_TRY(T.run("k_strand_gate", [&] { return launch_strand_gate(ga, b->stream); }));
+    RevcompArgs ra{a.reads, b->in.off, b->d_sidx.p, b->d_rcoff.p, b->d_ssum.p, b->d_rc.p};
+    RG_TRY(T.run("k_revcomp", [&] { return launch_revcomp(ra, n, b->stream); }));
+    HIPCHK(hipMemcpyAsync(b->h_ssum.p, b->d_ssum.p, 2 * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+    RG_TRY(T.collect(b->stats));
+    const int count = b->h_ssum.p[0], max_len = b->h_ssum.p[1];
+    if (count < 0 || count > n || (count > 0 && (max_len < 1 || max_len > b->max_n)))
+        return fail(RG_ERR_HIP, "k_strand_gate returned an impossible read count / length");
+    if (count > 0) {
+        HIPCHK(hipMemsetAsync(b->d_rcbad.p, 0, (size_t)count, b->stream));
+        const PathJob other{b->d_rc.p, b->d_rcoff.p, b->d_rcbad.p, count, max_len, b->d_rec2.p, nullptr, b->ops_stride, PATH_STAGE_PICK};
+        const int rc_b = path_driver_run(cx, other, cells);
+        counters();
+        if (rc_b) return rc_b;
+        GapXStrandsDuelArgs da{b->d_rec.p, b->d_rec2.p, b->d_sidx.p, count, b->d_first_rev.p};
+        RG_TRY(T.run("k_gap_xstrands_duel", [&] { return launch_gap_xstrands_duel(da, b->stream); }));
+    }
+    // every read on the strand that won, at the input's own offsets, and the traceback of those
+    RG_TRY(T.run("k_strand_orient", [&] { return launch_strand_orient(oa, n, b->stream); }));
+    const PathJob trace{b->d_pa.p, b->in.off, b->in.bad, n, b->max_n, b->d_rec.p, b->d_ops.p, b->ops_stride, PATH_STAGE_TRACE};
+    const int rc_t = path_driver_run(cx, trace, cells);
+    counters();
+    if (rc_t) return rc_t;
+    RG_TRY(T.run("k_gap_xstrands_mark", [&] { return launch_gap_xstrands_mark(b->d_rec.p, b->d_first_rev.p, n, b->stream); }));
+    return T.collect(b->stats);
+}
+
 int rg_run_pathwise(rg_batch* b) {
+    if (path_gap_xstrands_mode(b->p.mode)) return run_gap_xstrands(b);
     const HostGraph& h = b->g->h;
     const int n = (int)b->nreads;
     const bool vote = (b->p.amb_mode & RG_AMB_STRAND_VOTE) != 0;

@@ -3,7 +3,7 @@
 engine on other read lengths, score parameters and path counts, with the sweep kernel that ran and a parity check of a
 few reads against the oracle.  One JSON line per case.
 
-    python tools/region_bench.py [case ...]        cases: c5 x6 m3x5 hoxd70 len1500 p128 len600 gap gap_local gap_long gap_strands gap_xlong (default: all but the strand cases and the five `gap` cases)
+    python tools/region_bench.py [case ...]        cases: c5 x6 m3x5 hoxd70 len1500 p128 len600 gap gap_local gap_long gap_strands gap_xlong gap_xstrands (default: all but the strand cases and the six `gap` cases)
 
 The strand cases (RG_AMB_BOTH_STRANDS, config-5 shape; `reads_per_s` counts SOURCE reads): `both_strands_fwd` — option on, every
 read forward (what the option costs when nothing qualifies: compare with `c5`); `both_strands` — option on, half of the reads
@@ -42,6 +42,14 @@ read of both.  (b) one batch no earlier mode accepts: 32 reads of 50 000 bases o
 counted cell update, the work bytes per read beside what the layout of -m 16 would have needed.  Two reads of each part are checked
 against the rule (tests/pathwise_gap_rule.py): the printed score is the rule's (part (b): the rule's score of the printed path), and
 the printed CIGAR re-scores to it and consumes the read.  One JSON line per part.
+
+`gap_xstrands` (only when named): -m 76 / 77 / 82 beside -m 56 / 57 / 62 OF THE SAME BUILD on the reads of `gap_xlong`'s two parts, in
+one process, in alternating rounds: all-forward reads, and half of them reverse-complemented (synth.reverse_complement_share, seed
+5678) under the exact rule and, in modes 76 and 77, under the vote.  Every ratio is relative to the as-given mode on the all-forward
+reads; beside mode 82's stands the prediction (2 S + T) / (S + T) from this run's own kernel times of mode 62 (S: score pass and
+pick, T: the traceback).  Every read of every both-strands batch is compared with the as-given mode's line of its source read and
+with the flip; reads spread over the batch are checked against the numpy rules.  Two JSON lines per part (the first before the
+rule check, which takes minutes at 50 000 bases); RG_REGION_PART=a or b runs one part.
 
 Every case: TILES tiles of TILE reads through one rg_stream (3 handles), timed after one warm-up tile per handle."""
 import json
@@ -303,6 +311,102 @@ def gap_xlong_case():
     print(json.dumps(out), flush=True)
 
 
+def gap_xstrands_case():
+    """-m 76 / -m 77 / -m 82 beside -m 56 / -m 57 / -m 62 of the same build on the same reads, one process, alternating rounds: all
+    forward, and half of the reads reverse-complemented (seed 5678), under the exact rule and (76 / 77) under the vote.  Shapes (a)
+    and (b) of gap_xlong (RG_REGION_PART=a or b runs one of them).  Per both-strands batch, reads spread over the batch are checked:
+    the strand against the flip, the line against the as-given mode's line of the source read (column 5 apart), the score against the
+    numpy rule over all paths ((a); (b): over the printed path) and the re-scored CIGAR."""
+    from recgraph_amd import api, synth
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import pathwise_gap_local_rule as L
+    import pathwise_gap_rule as R
+    import strand_vote_rule as V
+    part = os.environ.get("RG_REGION_PART", "ab")
+    paths = 16
+    for tag, rounds, plen, nreads, seed in (("a", 5, 4000, 512, 900), ("b", 2, 50000, 32, 901)):
+        if tag not in part:
+            continue
+        g = synth.haplotype_graph(3 * plen, paths, path_len=plen, seed=1234)
+        gg = api.Graph.from_gfa_text(g.gfa())
+        fwd = synth.haplotype_reads(g, nreads, length=plen, seed=seed, mosaic_frac=0.0)
+        half, flipped = synth.reverse_complement_share(fwd, 0.5, seed=5678)
+        runs = {"m62_fwd": (62, 0, fwd), "m82_fwd": (82, 0, fwd), "m82_half": (82, 0, half),
+                "m56_fwd": (56, 0, fwd), "m76_fwd": (76, 0, fwd), "m76_half_exact": (76, 0, half), "m76_half_vote": (76, 12, half),
+                "m57_fwd": (57, 0, fwd), "m77_fwd": (77, 0, fwd), "m77_half_exact": (77, 0, half), "m77_half_vote": (77, 12, half)}
+        batch = {k: api.Batch(gg, rd, api.make_params(m, amb=amb or None)) for k, (m, amb, rd) in runs.items()}
+        times = {k: [] for k in runs}
+        ks = {k: {} for k in runs}
+        for k in runs:
+            batch[k].run()                       # warm-up: code objects, work buffers of every stage
+        for _ in range(rounds):
+            for k in runs:                       # alternating: every run sees the same machine
+                t0 = time.perf_counter()
+                batch[k].run()
+                times[k].append(time.perf_counter() - t0)
+                for name, v in batch[k].kernel_stats().items():
+                    if not name.startswith(("host:", "mem:", "inst:")):
+                        ks[k][name] = ks[k].get(name, 0.0) + v[0] / rounds
+        for k in runs:
+            batch[k].fetch()
+        med = {k: sorted(times[k])[rounds // 2] for k in runs}
+        out = {"case": "gap_xstrands", "part": tag, "rows": gg.rows, "paths": paths, "read_len": plen, "reads": nreads, "rounds": rounds,
+               "reads_reverse_complemented": int(flipped.sum()), "seed": 5678}
+        for k in runs:
+            b = batch[k]
+            out[k] = {"ms_per_batch_median": round(med[k] * 1e3, 2), "ms_per_batch_min": round(min(times[k]) * 1e3, 2),
+                      "counted_cell_updates": b.cell_updates, "performed_over_counted": round(b.cell_updates_performed / b.cell_updates, 3),
+                      "minus_records": sum(1 for i in range(nreads) if b.gaf_text(i, "r", 1).split("\t")[4:5] == ["-"]),
+                      "work_bytes_per_read_summed_over_chunks": int(b.kernel_stats().get("mem:work_bytes_per_read", (0, 1))[0]),
+                      "kernel_ms_per_batch": {name: round(v, 3) for name, v in ks[k].items()}}
+        for num, den in (("m82_fwd", "m62_fwd"), ("m82_half", "m62_fwd"), ("m76_fwd", "m56_fwd"), ("m76_half_exact", "m56_fwd"), ("m76_half_vote", "m56_fwd"),
+                         ("m77_fwd", "m57_fwd"), ("m77_half_exact", "m57_fwd"), ("m77_half_vote", "m57_fwd")):
+            out["%s_over_%s" % (num, den)] = {"median": round(med[num] / med[den], 3), "min": round(min(times[num]) / min(times[den]), 3)}
+        # the prediction for mode 82 from this run's own kernel times of mode 62: S the score pass and pick, T everything behind them
+        k62 = ks["m62_fwd"]
+        s = sum(v for name, v in k62.items() if name.startswith(("k_gap_score", "k_gap_pick")))
+        t = sum(k62.values()) - s
+        out["m82_predicted_from_m62_kernels"] = round((2 * s + t) / (s + t), 3) if s + t > 0 else None
+        print(json.dumps(dict(out, rule_checked="pending")), flush=True)
+        lnz, prow = R.graph_paths(gg)
+        picks = sorted({0, nreads - 1} if tag == "a" else {nreads // 2})
+        ok = True
+        for k, (m, amb, rd) in runs.items():
+            if m not in (76, 77, 82):
+                continue
+            b, base = batch[k], batch["m%d_fwd" % (m - 20)]
+            for i in range(nreads):
+                f = b.gaf_text(i, "r", 1).split("\t")
+                want = base.gaf_text(i, "r", 1).split("\t")
+                minus = bool(rd is half and flipped[i])
+                # the line of the source read in the as-given mode, column 5 apart; the strand is the flip
+                ok = ok and f[4] == ("-" if minus else "+") and f[:4] + f[5:] == want[:4] + want[5:] and b.status(i) == base.status(i)
+            if tag == "b" and k not in ("m82_half", "m76_half_exact"):
+                continue                             # (a numpy pass over 50 000 x 50 000 cells takes a minute: two batches stand for the eight)
+            for i in picks:
+                f = b.gaf_text(i, "r", 1)[:-1].split("\t")
+                mm = re.fullmatch(r"([0-9MXID]+), best path: (\d+), score: (-?\d+)", f[12])
+                chosen = V.rc(rd[i]) if f[4] == "-" else rd[i]
+                ok = ok and mm is not None
+                if not ok:
+                    break
+                score, q = int(mm.group(3)), int(mm.group(2))
+                rows = prow if tag == "a" else [prow[q]]
+                if m == 82:
+                    best, _ = L.all_paths_best(lnz, rows, chosen, R.default_scores(), -4, -2)      # (no matrix is kept)
+                    ok = ok and int(max(best)) == score and int(best[q if tag == "a" else 0]) == score
+                    ok = ok and L.rescore(mm.group(1), f[13], chosen, int(f[2]), int(f[3]))[0] == score
+                else:
+                    last, lens = R.all_paths_last(lnz, rows, chosen, R.default_scores(), -4, -2, m == 77)
+                    if m == 76:
+                        best = max((int(last[p, lens[p]]), -p) for p in range(len(rows)))
+                        ok = ok and best[0] == score and (tag != "a" or -best[1] == q)
+                    ok = ok and R.rescore(mm.group(1), f[13], chosen)[:2] == (score, len(chosen))
+        out["rule_checked"] = "FAILED" if not ok else len(picks)
+        print(json.dumps(out), flush=True)
+        del batch
+
+
 def gap_strands_case():
     from recgraph_amd import api, synth
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -375,6 +479,11 @@ def main():
     if "gap_xlong" in sys.argv[1:]:
         gap_xlong_case()
         sys.argv = [a for a in sys.argv if a != "gap_xlong"]
+        if len(sys.argv) == 1:
+            return
+    if "gap_xstrands" in sys.argv[1:]:
+        gap_xstrands_case()
+        sys.argv = [a for a in sys.argv if a != "gap_xstrands"]
         if len(sys.argv) == 1:
             return
     if "gap_strands" in sys.argv[1:]:
