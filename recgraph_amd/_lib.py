@@ -1,4 +1,5 @@
 """ctypes binding of librecgraph_hip.so (the C ABI declared in include/recgraph_hip.h)."""
+import collections
 import ctypes as C
 import os
 import subprocess
@@ -43,23 +44,54 @@ class Params(C.Structure):
 
 AMB_BOTH_STRANDS = 4     # RG_AMB_BOTH_STRANDS (include/recgraph_hip.h): bit 2 of Params.amb_mode, pathwise modes
 AMB_STRAND_VOTE = 8      # RG_AMB_STRAND_VOTE: bit 3, only together with bit 2 — the first strand by a 12-mer vote
-MODE_PATHWISE_GAP_LOCAL = 12    # RG_MODE_PATHWISE_GAP_LOCAL: a value of Params.mode, no entry point of its own
-# RG_MODE_PATHWISE_GAP_LONG / _SEMI_LONG / _LOCAL_LONG: modes 6, 7, 12 for reads of up to 16383 bases (`mode + 10`)
-MODE_PATHWISE_GAP_LONG = 16
-MODE_PATHWISE_GAP_SEMI_LONG = 17
-MODE_PATHWISE_GAP_LOCAL_LONG = 22
-# RG_MODE_PATHWISE_GAP_STRANDS / _SEMI_STRANDS / _LOCAL_STRANDS: modes 6, 7, 12 on both strands (`mode + 20`), reads of up to 16383 bases
-MODE_PATHWISE_GAP_STRANDS = 26
-MODE_PATHWISE_GAP_SEMI_STRANDS = 27
-MODE_PATHWISE_GAP_LOCAL_STRANDS = 32
-# RG_MODE_PATHWISE_GAP_XLONG / _SEMI_XLONG / _LOCAL_XLONG: modes 6, 7, 12 for reads of up to 131071 bases (`mode + 50`)
-MODE_PATHWISE_GAP_XLONG = 56
-MODE_PATHWISE_GAP_SEMI_XLONG = 57
-MODE_PATHWISE_GAP_LOCAL_XLONG = 62
-# RG_MODE_PATHWISE_GAP_XSTRANDS / _SEMI_XSTRANDS / _LOCAL_XSTRANDS: those on both strands, the traceback run once (`mode + 70`)
-MODE_PATHWISE_GAP_XSTRANDS = 76
-MODE_PATHWISE_GAP_SEMI_XSTRANDS = 77
-MODE_PATHWISE_GAP_LOCAL_XSTRANDS = 82
+
+# The affine-gap pathwise modes (values of Params.mode, no entry points of their own): a rule in a family, `mode = the rule's base mode +
+# the family's offset`.  The rows of csrc/rg_gap_modes.hpp once more, with the fixed text of the Python side's refusals; DESIGN 4.8 has
+# the table in words.  From it come the MODE_PATHWISE_GAP_* names here and in api, api's tuples and flag rules, and the CLI's.
+GAP_RULES = (("", 6), ("_SEMI", 7), ("_LOCAL", 12))      # (infix of the name, base mode): global, semiglobal, local
+GAP_GLOBAL, GAP_SEMI, GAP_LOCAL = 0, 1, 2                # indices into GAP_RULES
+GapFamily = collections.namedtuple("GapFamily", "suffix offset max_stripes both_strands one_stripe_dirs staged api_refusal cli_refusal "
+                                                "cli_refusal_local cli_help")
+# max_stripes: the longest read is max_stripes * 2048 - 1 bases; both_strands: the mode itself says both strands (the flag is redundant,
+# the vote a rule of the global and semiglobal modes), otherwise the reads are aligned as given and both flags are refused: api_refusal
+# (%s: the flag), cli_refusal (cli_refusal_local: what the local mode says instead); one_stripe_dirs: the checkpointed traceback;
+# staged: two PICK stages and one TRACE stage instead of two passes
+_AS_GIVEN = "%s is not available in the affine-gap pathwise modes (6, 7, 12 and their long-read flavours 16, 17, 22)"
+_CLI_AS_GIVEN = "--both-strands / --strand-vote are not available in mode%s: %s the reads as given"
+GAP_FAMILIES = (
+    GapFamily("", 0, 1, False, False, False, _AS_GIVEN, _CLI_AS_GIVEN % ("s 6 and 7", "they align"), _CLI_AS_GIVEN % (" 12", "it aligns"),
+              "12: local affine-gap pathwise"),
+    GapFamily("_LONG", 10, 8, False, False, False, _AS_GIVEN, _CLI_AS_GIVEN % ("s 16, 17 and 22", "they align"), None,
+              "16, 17, 22: modes 6, 7, 12 for reads of up to 16383 bases"),
+    GapFamily("_STRANDS", 20, 8, True, False, False, None, None, None,
+              "26, 27, 32: those on both strands (--strand-vote: 26 and 27 only)"),
+    GapFamily("_XLONG", 50, 64, False, True, False,
+              "%s is not available in the affine-gap pathwise modes for reads of up to 131071 bases (56, 57, 62): they align the reads as given",
+              _CLI_AS_GIVEN % ("s 56, 57 and 62", "they align"), None,
+              "56, 57, 62: modes 6, 7, 12 for reads of up to 131071 bases"),
+    GapFamily("_XSTRANDS", 70, 64, True, True, True, None, None, None,
+              "76, 77, 82: those on both strands, the traceback run once, on the strand that won (--strand-vote: 76 and 77 only)"),
+)
+GapMode = collections.namedtuple("GapMode", "rule family")      # rule: GAP_GLOBAL / GAP_SEMI / GAP_LOCAL
+_GAP_MODES = {base + f.offset: GapMode(r, f) for f in GAP_FAMILIES for r, (_, base) in enumerate(GAP_RULES)}
+GAP_MODE_NAMES = {"MODE_PATHWISE_GAP%s%s" % (GAP_RULES[m.rule][0], m.family.suffix): mode for mode, m in _GAP_MODES.items()}
+globals().update(GAP_MODE_NAMES)      # MODE_PATHWISE_GAP = 6 ... MODE_PATHWISE_GAP_LOCAL_XSTRANDS = 82 (RG_MODE_* in include/recgraph_hip.h)
+
+
+def gap_mode(mode):
+    """GapMode(rule, family) of an affine-gap pathwise mode, None for every other value."""
+    return _GAP_MODES.get(mode)
+
+
+def gap_family(suffix):
+    return next(f for f in GAP_FAMILIES if f.suffix == suffix)
+
+
+def gap_family_modes(*suffixes):
+    """The modes of the named families, family by family, each in the order global, semiglobal, local."""
+    return tuple(base + gap_family(s).offset for s in suffixes for _, base in GAP_RULES)
+
+
 READ_UNALIGNED = 16     # RG_READ_UNALIGNED: status bit of that mode — the read has no local alignment, and no record
 
 

@@ -43,29 +43,11 @@ MODE_RECOMBINATION_SEMI = 9
 MODE_LOCAL_POA = 1
 MODE_LOCAL_POA_SCALAR = 11
 MODE_GAP_LOCAL_POA = 3
-# pathwise alignment with affine gaps, global / semiglobal: a definition of this project's own (RG_MODE_PATHWISE_GAP in
-# include/recgraph_hip.h), GAF in the -m 4 format
-MODE_PATHWISE_GAP = 6
-MODE_PATHWISE_GAP_SEMI = 7
-# ... and local (RG_MODE_PATHWISE_GAP_LOCAL): soft-clipped reads; a read without a local alignment has READ_UNALIGNED and no line
-MODE_PATHWISE_GAP_LOCAL = _lib.MODE_PATHWISE_GAP_LOCAL
-# ... and the three again for reads of up to 16383 bases (RG_MODE_PATHWISE_GAP_LONG ...: `mode + 10`, the same rule and the same bytes)
-MODE_PATHWISE_GAP_LONG = _lib.MODE_PATHWISE_GAP_LONG
-MODE_PATHWISE_GAP_SEMI_LONG = _lib.MODE_PATHWISE_GAP_SEMI_LONG
-MODE_PATHWISE_GAP_LOCAL_LONG = _lib.MODE_PATHWISE_GAP_LOCAL_LONG
-# ... and on both strands (RG_MODE_PATHWISE_GAP_STRANDS ...: `mode + 20`, every pass one of the long flavour's; the rule: include/recgraph_hip.h)
-MODE_PATHWISE_GAP_STRANDS = _lib.MODE_PATHWISE_GAP_STRANDS
-MODE_PATHWISE_GAP_SEMI_STRANDS = _lib.MODE_PATHWISE_GAP_SEMI_STRANDS
-MODE_PATHWISE_GAP_LOCAL_STRANDS = _lib.MODE_PATHWISE_GAP_LOCAL_STRANDS
-# ... and for reads of up to 131071 bases (RG_MODE_PATHWISE_GAP_XLONG ...: `mode + 50`, the same rule and bytes, one stripe of direction words)
-MODE_PATHWISE_GAP_XLONG = _lib.MODE_PATHWISE_GAP_XLONG
-MODE_PATHWISE_GAP_SEMI_XLONG = _lib.MODE_PATHWISE_GAP_SEMI_XLONG
-MODE_PATHWISE_GAP_LOCAL_XLONG = _lib.MODE_PATHWISE_GAP_LOCAL_XLONG
-# ... and those on both strands (RG_MODE_PATHWISE_GAP_XSTRANDS ...: `mode + 70`, the strand rule of `mode + 20` on the picked scores of
-# `mode + 50`, the winning strand alone traced)
-MODE_PATHWISE_GAP_XSTRANDS = _lib.MODE_PATHWISE_GAP_XSTRANDS
-MODE_PATHWISE_GAP_SEMI_XSTRANDS = _lib.MODE_PATHWISE_GAP_SEMI_XSTRANDS
-MODE_PATHWISE_GAP_LOCAL_XSTRANDS = _lib.MODE_PATHWISE_GAP_LOCAL_XSTRANDS
+# pathwise alignment with affine gaps: a definition of this project's own (RG_MODE_PATHWISE_GAP ... in include/recgraph_hip.h), GAF in
+# the -m 4 format.  MODE_PATHWISE_GAP (global), MODE_PATHWISE_GAP_SEMI, MODE_PATHWISE_GAP_LOCAL (soft-clipped reads; a read without a
+# local alignment has READ_UNALIGNED and no line), and the three again in every family of _lib.GAP_FAMILIES: _LONG, _STRANDS, _XLONG,
+# _XSTRANDS
+globals().update(_lib.GAP_MODE_NAMES)
 
 READ_BAND_WARNING, READ_BAND_NOT_ENOUGH, READ_WOULD_PANIC, READ_BAD_BASE = 1, 2, 4, 8
 READ_UNALIGNED = _lib.READ_UNALIGNED
@@ -76,34 +58,31 @@ AMB_BOTH_STRANDS = _lib.AMB_BOTH_STRANDS
 # bit 3 (RG_AMB_STRAND_VOTE), only together with bit 2: the strand that is aligned first is picked per read by a 12-mer vote
 AMB_STRAND_VOTE = _lib.AMB_STRAND_VOTE
 PATHWISE_MODES = (MODE_PATHWISE, MODE_PATHWISE_SEMI, MODE_RECOMBINATION, MODE_RECOMBINATION_SEMI)
-PATHWISE_GAP_MODES = (MODE_PATHWISE_GAP, MODE_PATHWISE_GAP_SEMI, MODE_PATHWISE_GAP_LOCAL,
-                      MODE_PATHWISE_GAP_LONG, MODE_PATHWISE_GAP_SEMI_LONG, MODE_PATHWISE_GAP_LOCAL_LONG)      # (they align the reads as given: no both_strands)
+PATHWISE_GAP_MODES = _lib.gap_family_modes("", "_LONG")      # (they align the reads as given: no both_strands)
 # ... which is what these are for: both strands is the mode itself, so ``both_strands=True`` is redundant there
-PATHWISE_GAP_STRANDS_MODES = (MODE_PATHWISE_GAP_STRANDS, MODE_PATHWISE_GAP_SEMI_STRANDS, MODE_PATHWISE_GAP_LOCAL_STRANDS)
+PATHWISE_GAP_STRANDS_MODES = _lib.gap_family_modes("_STRANDS")
 # reads of up to 131071 bases, as given: both strands at this length is not offered
-PATHWISE_GAP_XLONG_MODES = (MODE_PATHWISE_GAP_XLONG, MODE_PATHWISE_GAP_SEMI_XLONG, MODE_PATHWISE_GAP_LOCAL_XLONG)
+PATHWISE_GAP_XLONG_MODES = _lib.gap_family_modes("_XLONG")
 # ... except through these: both strands is the mode itself again, so ``both_strands=True`` is redundant there
-PATHWISE_GAP_XSTRANDS_MODES = (MODE_PATHWISE_GAP_XSTRANDS, MODE_PATHWISE_GAP_SEMI_XSTRANDS, MODE_PATHWISE_GAP_LOCAL_XSTRANDS)
+PATHWISE_GAP_XSTRANDS_MODES = _lib.gap_family_modes("_XSTRANDS")
 
 
 def _both_strands_kw(mode, both_strands, kw, strand_vote=False):
     """``both_strands=True`` / ``strand_vote=True`` (which implies it) as the ``amb`` keyword of ``make_params``; refused
-    outside the pathwise modes, where ``amb_strand`` (``-s true``) is the way."""
+    outside the pathwise modes, where ``amb_strand`` (``-s true``) is the way, and in the affine-gap families that align the
+    reads as given."""
     if not both_strands and not strand_vote:
         return kw
-    if mode in PATHWISE_GAP_STRANDS_MODES or mode in PATHWISE_GAP_XSTRANDS_MODES:
-        if strand_vote and mode in (MODE_PATHWISE_GAP_LOCAL_STRANDS, MODE_PATHWISE_GAP_LOCAL_XSTRANDS):
-            raise _lib.RecGraphError(-1, "strand_vote is not available in mode %d: no score of a local pass says \"hopeless\", so a vote "
-                                         "would have no rule for a second pass" % mode)
-        return dict(kw, amb=(kw.get("amb") or 0) | AMB_BOTH_STRANDS | (AMB_STRAND_VOTE if strand_vote else 0))
-    if mode in PATHWISE_GAP_XLONG_MODES:
-        raise _lib.RecGraphError(-1, "%s is not available in the affine-gap pathwise modes for reads of up to 131071 bases (56, 57, 62): they "
-                                     "align the reads as given" % ("strand_vote" if strand_vote else "both_strands"))
-    if mode in PATHWISE_GAP_MODES:
-        raise _lib.RecGraphError(-1, "%s is not available in the affine-gap pathwise modes (6, 7, 12 and their long-read flavours 16, 17, 22)" % ("strand_vote" if strand_vote else "both_strands"))
-    if mode not in PATHWISE_MODES:
+    flag = "strand_vote" if strand_vote else "both_strands"
+    gm = _lib.gap_mode(mode)
+    if gm and not gm.family.both_strands:
+        raise _lib.RecGraphError(-1, gm.family.api_refusal % flag)
+    if gm and strand_vote and gm.rule == _lib.GAP_LOCAL:
+        raise _lib.RecGraphError(-1, "strand_vote is not available in mode %d: no score of a local pass says \"hopeless\", so a vote "
+                                     "would have no rule for a second pass" % mode)
+    if not gm and mode not in PATHWISE_MODES:
         raise _lib.RecGraphError(-1, "%s applies to the pathwise modes (4, 5, 8, 9) only: the POA modes align both "
-                                     "strands with amb_strand (`-s true`)" % ("strand_vote" if strand_vote else "both_strands"))
+                                     "strands with amb_strand (`-s true`)" % flag)
     return dict(kw, amb=(kw.get("amb") or 0) | AMB_BOTH_STRANDS | (AMB_STRAND_VOTE if strand_vote else 0))
 
 
@@ -883,16 +862,14 @@ def pathwise_alignment_semiglobal_exec(sequence, graph, score_matrix=None):
 
 
 def _gap_exec_mode(mode, long_reads, both_strands, very_long_reads=False, very_long_both_strands=False):
-    """The value of rg_params.mode behind the three wrappers below: ``mode + 20`` on both strands (which takes long reads
-    anyway), ``mode + 10`` for long reads alone, ``mode + 50`` for very long reads (which are aligned as given), ``mode + 70``
-    for very long reads on both strands (a keyword of its own: it says both, whatever the others say)."""
-    if very_long_both_strands:
-        return mode + 70
-    if very_long_reads:
-        if both_strands:
-            raise _lib.RecGraphError(-1, "very_long_reads (modes 56, 57, 62) aligns the reads as given: both_strands is not available at this length")
-        return mode + 50
-    return mode + 20 if both_strands else mode + 10 if long_reads else mode
+    """The value of rg_params.mode behind the three wrappers below: base mode ``mode`` in the family the keywords name (_lib.GAP_FAMILIES).
+    Both strands takes long reads anyway; very long reads are aligned as given; very long reads on both strands is a keyword of its own:
+    it says both, whatever the others say."""
+    if very_long_reads and both_strands and not very_long_both_strands:
+        raise _lib.RecGraphError(-1, "very_long_reads (modes %s) aligns the reads as given: both_strands is not available at this length"
+                                 % ", ".join(map(str, PATHWISE_GAP_XLONG_MODES)))
+    suffix = "_XSTRANDS" if very_long_both_strands else "_XLONG" if very_long_reads else "_STRANDS" if both_strands else "_LONG" if long_reads else ""
+    return mode + _lib.gap_family(suffix).offset
 
 
 def pathwise_alignment_gap_exec(sequence, graph, score_matrix=None, o=-4, e=-2, long_reads=False, both_strands=False, very_long_reads=False, very_long_both_strands=False):
@@ -900,9 +877,9 @@ def pathwise_alignment_gap_exec(sequence, graph, score_matrix=None, o=-4, e=-2, 
     include/recgraph_hip.h).  The reference's pathwise_alignment_gap::exec returns the index of the best path only; here that
     index is the "best path" of the GAFStruct's comments.  ``sequence`` carries the leading '$' like the reference's read arrays.
     ``long_reads=True`` (here and in the two wrappers below): the long-read flavour of the mode, reads of up to 16383 bases.
-    ``both_strands=True`` (likewise): ``mode + 20``, the read on both strands — the strand of the chosen record is the GAFStruct's.
-    ``very_long_reads=True`` (likewise): ``mode + 50``, reads of up to 131071 bases as given; not together with ``both_strands``.
-    ``very_long_both_strands=True`` (likewise): ``mode + 70``, reads of up to 131071 bases on both strands, the winning strand alone traced."""
+    ``both_strands=True`` (likewise): the both-strands family, the read on both strands — the strand of the chosen record is the GAFStruct's.
+    ``very_long_reads=True`` (likewise): reads of up to 131071 bases as given; not together with ``both_strands``.
+    ``very_long_both_strands=True`` (likewise): reads of up to 131071 bases on both strands, the winning strand alone traced."""
     _, text = _single(graph, "".join(sequence[1:]), "Temp", _gap_exec_mode(MODE_PATHWISE_GAP, long_reads, both_strands, very_long_reads, very_long_both_strands), 1, score_matrix=score_matrix, o=o, e=e)
     return GAFStruct.from_line(text.rstrip("\n"))
 

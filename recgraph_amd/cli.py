@@ -9,6 +9,10 @@ import argparse
 import sys
 import time
 
+from . import _lib
+
+POA_MODES = (0, 1, 2, 3)
+
 
 def get_sequences(path):
     """sequences::get_sequences (sequences.rs:5-45) through the library (rg_reads_from_fasta): (sequences, names)."""
@@ -40,15 +44,37 @@ def write_gaf_records(out_file, records, numbers):
             f.write("".join(r + "\n" for r in buf))
 
 
+# the modes of the both-strands families: --both-strands is redundant there, --strand-vote a rule of their global and semiglobal modes
+_STRAND_MODES = [m for m in sorted(_lib.GAP_MODE_NAMES.values()) if _lib.gap_mode(m).family.both_strands]
+
+
+def check_mode_flags(alignment_mode, both_strands, strand_vote, amb_strand):
+    """What main refuses before it opens a file: a mode that is neither 0 to 9 nor an affine-gap pathwise mode (_lib.GAP_FAMILIES), and
+    --both-strands / --strand-vote where the mode has no such rule.  Returns whether ``-s true`` counts."""
+    gm = _lib.gap_mode(alignment_mode)
+    if alignment_mode not in range(10) and not gm:
+        raise SystemExit("Alignment mode must be in [0..9], or 12")   # main.rs:315-317; 12: local affine-gap pathwise, this project's own
+    if gm and (both_strands or strand_vote):
+        local = gm.rule == _lib.GAP_LOCAL
+        if not gm.family.both_strands:
+            raise SystemExit(gm.family.cli_refusal_local if local and gm.family.cli_refusal_local else gm.family.cli_refusal)
+        if strand_vote and local:
+            raise SystemExit("--strand-vote is not available in mode %d: no score of a local pass says \"hopeless\", so a vote would have no rule for a second pass" % alignment_mode)
+    amb = amb_strand == "true" and alignment_mode in POA_MODES     # modes 4+ ignore -s (main.rs:254-313)
+    if strand_vote and alignment_mode in POA_MODES:
+        raise SystemExit("--strand-vote applies to modes 4, 5, 8 and 9: for modes 0-3 use `-s true`")
+    if both_strands and alignment_mode in POA_MODES:
+        raise SystemExit("--both-strands applies to modes 4, 5, 8 and 9: for modes 0-3 use `-s true`")
+    return amb
+
+
 def build_parser():
     p = argparse.ArgumentParser(prog="recgraph-hip", description="RecGraph DP hot path on MI355X")
     p.add_argument("sequence_path")
     p.add_argument("graph_path")
     p.add_argument("-o", "--out_file", default="standard output")
     p.add_argument("-m", "--aln-mode", type=int, default=0, dest="alignment_mode",
-                   help="0 to 9 as in the reference; 12: local affine-gap pathwise; 16, 17, 22: modes 6, 7, 12 for reads of up to 16383 bases; "
-                        "26, 27, 32: those on both strands (--strand-vote: 26 and 27 only); 56, 57, 62: modes 6, 7, 12 for reads of up to 131071 bases; "
-                        "76, 77, 82: those on both strands, the traceback run once, on the strand that won (--strand-vote: 76 and 77 only)")
+                   help="0 to 9 as in the reference; " + "; ".join(f.cli_help for f in _lib.GAP_FAMILIES))
     p.add_argument("-M", "--match", type=int, default=2, dest="match_score")
     p.add_argument("-X", "--mismatch", type=int, default=4, dest="mismatch_score")
     p.add_argument("-t", "--matrix", default="none")
@@ -61,11 +87,11 @@ def build_parser():
     p.add_argument("-b", "--extra-b", type=int, default=1)
     p.add_argument("-f", "--extra-f", type=float, default=0.01)
     p.add_argument("--both-strands", action="store_true", dest="both_strands",
-                   help="modes 4, 5, 8, 9 (not a flag of the reference; refused in 6 and 7; redundant in 26, 27, 32, 76, 77, 82): reads that score below 0 are aligned again as their reverse "
-                        "complement; a strictly better reverse record is written with strand '-'")
+                   help="modes 4, 5, 8, 9 (not a flag of the reference; refused in 6 and 7; redundant in %s): reads that score below 0 are aligned again as their reverse "
+                        "complement; a strictly better reverse record is written with strand '-'" % ", ".join(str(m) for m in _STRAND_MODES))
     p.add_argument("--strand-vote", action="store_true", dest="strand_vote",
-                   help="modes 4, 5, 8, 9, 26, 27, 76, 77 (not a flag of the reference; implies --both-strands): the strand that is aligned first is "
-                        "picked per read by a vote of its 12-mers against the paths'")
+                   help="modes 4, 5, 8, 9, %s (not a flag of the reference; implies --both-strands): the strand that is aligned first is "
+                        "picked per read by a vote of its 12-mers against the paths'" % ", ".join(str(m) for m in _STRAND_MODES if _lib.gap_mode(m).rule != _lib.GAP_LOCAL))
     p.add_argument("--scalar", action="store_true", help="-m 0 / -m 1 with the non-AVX2 path of the reference")
     p.add_argument("--devices", default="", help="comma-separated HIP device ids (default: every visible device)")
     p.add_argument("--handles", type=int, default=0, help="batch handles per device (default 3)")
@@ -86,27 +112,7 @@ def main(argv=None):
         return time.time()
     from . import api
     tp = mark("import", t0)
-    # 16, 17, 22: the long-read flavours of 6, 7, 12 (reads of up to 16383 bases), admitted beside the modes the message names
-    # 26, 27, 32: the same three on both strands; --both-strands is redundant there, --strand-vote the vote rule of 26 and 27
-    # 56, 57, 62: 6, 7, 12 for reads of up to 131071 bases, as given
-    # 76, 77, 82: those on both strands; --both-strands is redundant there, --strand-vote the vote rule of 76 and 77
-    if a.alignment_mode not in (0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 12, 16, 17, 22, 26, 27, 32, 56, 57, 62, 76, 77, 82):
-        raise SystemExit("Alignment mode must be in [0..9], or 12")   # main.rs:315-317; 12: local affine-gap pathwise, this project's own
-    if a.alignment_mode in (6, 7) and (a.both_strands or a.strand_vote):
-        raise SystemExit("--both-strands / --strand-vote are not available in modes 6 and 7: they align the reads as given")
-    if a.alignment_mode == 12 and (a.both_strands or a.strand_vote):
-        raise SystemExit("--both-strands / --strand-vote are not available in mode 12: it aligns the reads as given")
-    if a.alignment_mode in (16, 17, 22) and (a.both_strands or a.strand_vote):
-        raise SystemExit("--both-strands / --strand-vote are not available in modes 16, 17 and 22: they align the reads as given")
-    if a.alignment_mode in (56, 57, 62) and (a.both_strands or a.strand_vote):
-        raise SystemExit("--both-strands / --strand-vote are not available in modes 56, 57 and 62: they align the reads as given")
-    if a.alignment_mode in (32, 82) and a.strand_vote:
-        raise SystemExit("--strand-vote is not available in mode %d: no score of a local pass says \"hopeless\", so a vote would have no rule for a second pass" % a.alignment_mode)
-    amb = a.amb_strand == "true" and a.alignment_mode in (0, 1, 2, 3)     # modes 4+ ignore -s (main.rs:254-313)
-    if a.strand_vote and a.alignment_mode in (0, 1, 2, 3):
-        raise SystemExit("--strand-vote applies to modes 4, 5, 8 and 9: for modes 0-3 use `-s true`")
-    if a.both_strands and a.alignment_mode in (0, 1, 2, 3):
-        raise SystemExit("--both-strands applies to modes 4, 5, 8 and 9: for modes 0-3 use `-s true`")
+    amb = check_mode_flags(a.alignment_mode, a.both_strands, a.strand_vote, a.amb_strand)
     a.both_strands = a.both_strands or a.strand_vote
     if a.matrix in ("none",):
         scores = api.create_score_matrix_i32(a.match_score, -a.mismatch_score)   # args_parser.rs:155
@@ -114,17 +120,12 @@ def main(argv=None):
         scores = api.create_score_matrix_i32(matrix_file_path=a.matrix if a.matrix.endswith(".mtx") else a.matrix + ".mtx")
     g = api.Graph.from_gfa(a.graph_path)
     tp = mark("graph", tp)
-    mode = {0: api.MODE_GLOBAL_POA_SCALAR if a.scalar else api.MODE_GLOBAL_POA, 2: api.MODE_GAP_POA,
-            1: api.MODE_LOCAL_POA_SCALAR if a.scalar else api.MODE_LOCAL_POA, 3: api.MODE_GAP_LOCAL_POA,
-            4: api.MODE_PATHWISE, 5: api.MODE_PATHWISE_SEMI, 6: api.MODE_PATHWISE_GAP, 7: api.MODE_PATHWISE_GAP_SEMI, 8: api.MODE_RECOMBINATION,
-            9: api.MODE_RECOMBINATION_SEMI, 12: api.MODE_PATHWISE_GAP_LOCAL, 16: api.MODE_PATHWISE_GAP_LONG,
-            17: api.MODE_PATHWISE_GAP_SEMI_LONG, 22: api.MODE_PATHWISE_GAP_LOCAL_LONG, 26: api.MODE_PATHWISE_GAP_STRANDS,
-            27: api.MODE_PATHWISE_GAP_SEMI_STRANDS, 32: api.MODE_PATHWISE_GAP_LOCAL_STRANDS, 56: api.MODE_PATHWISE_GAP_XLONG,
-            57: api.MODE_PATHWISE_GAP_SEMI_XLONG, 62: api.MODE_PATHWISE_GAP_LOCAL_XLONG, 76: api.MODE_PATHWISE_GAP_XSTRANDS,
-            77: api.MODE_PATHWISE_GAP_SEMI_XSTRANDS, 82: api.MODE_PATHWISE_GAP_LOCAL_XSTRANDS}[a.alignment_mode]
+    # -m IS the value of rg_params.mode, but for --scalar
+    mode = {0: api.MODE_GLOBAL_POA_SCALAR, 1: api.MODE_LOCAL_POA_SCALAR}.get(a.alignment_mode, a.alignment_mode) if a.scalar else a.alignment_mode
     kw = dict(score_matrix=scores, o=-a.gap_open, e=-a.gap_extension, b=float(a.extra_b), f=a.extra_f,
               R=a.base_rec_cost, r=a.multi_rec_cost, B=a.rec_band_width)
     to_file = a.out_file != "standard output"
+    local_gap = bool(_lib.gap_mode(a.alignment_mode)) and _lib.gap_mode(a.alignment_mode).rule == _lib.GAP_LOCAL
 
     def emit(first, texts):
         """texts: the stdout text of consecutive reads starting at read `first`.  With -o the records of the tile go
@@ -136,14 +137,14 @@ def main(argv=None):
         records, numbers = [], []
         # warning lines are println!'d by the exec functions whatever -o says; only the record goes through write_gaf
         for k, t in enumerate(texts):
-            if not t and a.alignment_mode in (12, 22, 32, 62, 82):      # a read without a local alignment (RG_READ_UNALIGNED) has no record
+            if not t and local_gap:      # a read without a local alignment (RG_READ_UNALIGNED) has no record
                 continue
             lines = t.split("\n")[:-1]
             sys.stdout.write("".join(ln + "\n" for ln in lines[:-1]))
             records.append(lines[-1])
             # main.rs passes i + 1 in modes 0-3 (:98-103, :161-166, :206-211, :246-251) and the 0-based i in modes
             # 4, 5, 8, 9 (:260, :268, :311)
-            numbers.append(first + k + 1 if a.alignment_mode in (0, 1, 2, 3) else first + k)
+            numbers.append(first + k + 1 if a.alignment_mode in POA_MODES else first + k)
         write_gaf_records(a.out_file, records, numbers)
 
     # The reference's read loop (main.rs:56,174,257,297) has no order dependence: the streaming engine cuts the reads into

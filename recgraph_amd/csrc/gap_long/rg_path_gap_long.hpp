@@ -8,7 +8,7 @@ namespace rg {
 
 constexpr int GAP_LONG_C = 32;                        // columns per lane
 constexpr int GAP_LONG_STRIPE = GAP_LONG_C * WAVE;    // columns per stripe: 2048
-constexpr int GAP_LONG_MAX_STRIPES = 8;               // reads of up to 8 * 2048 - 1 = 16383 bases
+// (GAP_LONG_MAX_STRIPES, the most stripes of a read here: rg_gap_modes.hpp, beside the families that use it)
 
 struct GapLongArgs {
     GapArgs g;                    // g.dirs: [reads][dirs_stride], stripe s, row t of the picked path at ((s * rows1 + t + 1) * 4 + w) * 64 + lane

@@ -7,7 +7,7 @@
 
 namespace rg {
 
-constexpr int GAP_XLONG_MAX_STRIPES = 64;             // reads of up to 64 * 2048 - 1 = 131071 bases
+// (GAP_XLONG_MAX_STRIPES: rg_gap_modes.hpp)
 
 // where the walk of a read stands between two rounds (written by k_gap_ckpt_long, then by the walk kernels)
 struct GapWalkState {

@@ -56,7 +56,7 @@ static void fill_record(const rg_batch* b, int64_t i, ReadRecord& r) {
     r.ops = b->ops.data() + (size_t)i * b->ops_stride;
     r.rows = is_poa(b->p.mode) ? b->oprows.data() + (size_t)i * b->ops_stride : nullptr;
 }
-// RG_AMB_BOTH_STRANDS (set by rg_batch_create on every handle of -m 26 / -m 27 / -m 32): the record of read i came from the
+// RG_AMB_BOTH_STRANDS (set by rg_batch_create on every handle of a both-strands family): the record of read i came from the
 // reverse-complement pass (DevRecord.pad is written by that mode's kernels only)
 static bool reverse_won(const rg_batch* b, int64_t i) {
     return (b->p.amb_mode & RG_AMB_BOTH_STRANDS) && !is_poa(b->p.mode) && (b->rec[i].pad & REC_REVERSE_STRAND);
@@ -332,8 +332,8 @@ static int load_reads(rg_batch* b, const char* reads, const int64_t* read_off, i
     b->ops_stride = is_poa(mode) ? (long long)h.L + b->max_n + 8
                                  : std::min<long long>((long long)h.L + b->max_n + 8, 2ll * (h.max_path_rows + b->max_n) + 16);
     const bool both = !is_poa(mode) && (p->amb_mode & RG_AMB_BOTH_STRANDS);
-    // k_strand_merge moves op bytes in 16-byte pieces (-m 76 / -m 77 / -m 82 trace the chosen strand alone: no merge, the op area of -m 56 / -m 57 / -m 62)
-    if (both && !path_gap_xstrands_mode(mode)) b->ops_stride = (b->ops_stride + 15) & ~15ll;
+    // k_strand_merge moves op bytes in 16-byte pieces (a staged family traces the chosen strand alone: no merge, the op area of one pass)
+    if (both && !gap_mode(mode).family->staged) b->ops_stride = (b->ops_stride + 15) & ~15ll;
     if ((rc = b->d_ops.alloc((size_t)nreads * b->ops_stride))) return rc;
     if (both && (rc = size_strand_buffers(b, total))) return rc;
     if (is_poa(mode)) {
@@ -360,8 +360,7 @@ int32_t rg_batch_create(const rg_graph* gc, const rg_params* p, const char* read
     if (!gc || !p || !reads || !read_off || !out || nreads < 1) return fail(RG_ERR_ARG, "null/empty argument");
     const rg_graph* g = gc;
     const int mode = p->mode;
-    const int gbase = path_gap_base_mode(mode);       // (-m 16 / -m 17 / -m 22: the long-read flavours of 6, 7, 12; -m 26 / -m 27 / -m 32: those on both strands; -m 56 / -m 57 / -m 62: reads of up to 131071 bases; -m 76 / -m 77 / -m 82: those on both strands)
-    const bool path_gap = gbase == RG_MODE_PATHWISE_GAP || gbase == RG_MODE_PATHWISE_GAP_SEMI || gbase == RG_MODE_PATHWISE_GAP_LOCAL;
+    const bool path_gap = gap_mode(mode).valid;       // (every rule in every family of rg_gap_modes.hpp)
     if (!(is_poa(mode) || mode == RG_MODE_PATHWISE || mode == RG_MODE_RECOMBINATION || mode == RG_MODE_PATHWISE_SEMI ||
           mode == RG_MODE_RECOMBINATION_SEMI || path_gap))
         return fail(RG_ERR_ARG, "unsupported mode");
@@ -387,7 +386,7 @@ int32_t rg_batch_create(const rg_graph* gc, const rg_params* p, const char* read
                                 "rg_stream_opts.amb_strand (`-s true`, main.rs:82,132,188,229)");
     if ((p->amb_mode & 3) && !is_poa(mode)) return fail(RG_ERR_ARG, "amb_mode bits 0 and 1 apply to the POA modes only (main.rs:82,132,188,229)");
     if (path_gap) {
-        // what the plan of -m 6 / -m 7 / -m 12 refuses (amb_mode bits, reads over 2047 bases (16383 in the long modes, 131071 in -m 56 / -m 57 / -m 62), scores outside the i32 budget) is host
+        // what the plan of these modes refuses (amb_mode bits, reads over the family's limit, scores outside the i32 budget) is host
         // arithmetic on the longest read: answered here, before a device is needed
         int64_t longest = 0;
         for (int64_t r = 0; r < nreads; ++r) longest = std::max<int64_t>(longest, read_off[r + 1] - read_off[r]);
@@ -404,9 +403,9 @@ int32_t rg_batch_create(const rg_graph* gc, const rg_params* p, const char* read
     b->g = g;
     b->gt = gt;
     b->p = *p;
-    // -m 26 / -m 27 / -m 32 align both strands whatever the bit says: from here on the handle IS a both-strands handle (the 16-byte
+    // a both-strands family aligns both strands whatever the bit says: from here on the handle IS a both-strands handle (the
     // ops_stride, the strand buffers, the strand of a record)
-    if (path_gap_strands_mode(mode) || path_gap_xstrands_mode(mode)) b->p.amb_mode |= RG_AMB_BOTH_STRANDS;      // (-m 76 / -m 77 / -m 82 likewise)
+    if (gap_mode(mode).family->both_strands) b->p.amb_mode |= RG_AMB_BOTH_STRANDS;
     HIPCHK(hipGetDevice(&b->dev));
     {
         // the handle's stream at the highest priority: it carries the small kernels; the pathwise sweeps run on a low-priority

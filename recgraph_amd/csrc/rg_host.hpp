@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/recgraph_hip.h"
+#include "rg_gap_modes.hpp"      // gap_mode(): rule and family of an affine-gap pathwise mode
 
 namespace rg {
 
@@ -75,29 +76,6 @@ Options& options();
 int wait_stream_sleeping(void* stream, void* ev, bool spin = false);   // spin: this handle asked for hipStreamSynchronize (rg_stream_opts.spin_wait)
 
 int fail(int code, const std::string& msg);
-
-// the long-read flavours of the affine-gap pathwise modes are `mode + 10` (16, 17, 22): the rule, the record and the line of `mode`
-// ... and their both-strands flavours `mode + 20` (26, 27, 32): every pass is one of the long flavour's, so they share its read limit
-inline bool path_gap_strands_mode(int mode) {
-    return mode == RG_MODE_PATHWISE_GAP_STRANDS || mode == RG_MODE_PATHWISE_GAP_SEMI_STRANDS || mode == RG_MODE_PATHWISE_GAP_LOCAL_STRANDS;
-}
-inline bool path_gap_long_mode(int mode) {
-    return mode == RG_MODE_PATHWISE_GAP_LONG || mode == RG_MODE_PATHWISE_GAP_SEMI_LONG || mode == RG_MODE_PATHWISE_GAP_LOCAL_LONG ||
-           path_gap_strands_mode(mode);
-}
-// ... and the flavours for reads of up to 131071 bases `mode + 50` (56, 57, 62): the long flavour's rule and bytes once more, with a
-// traceback that keeps one stripe of direction words (gap_xlong/); no amb_mode bit
-inline bool path_gap_xlong_mode(int mode) {
-    return mode == RG_MODE_PATHWISE_GAP_XLONG || mode == RG_MODE_PATHWISE_GAP_SEMI_XLONG || mode == RG_MODE_PATHWISE_GAP_LOCAL_XLONG;
-}
-// ... and those on both strands `mode + 70` (76, 77, 82): the strand rule of `mode + 20` on the PICKED scores of pipeline `mode + 50`,
-// the traceback run once per read, on the strand that won (gap_xstrands/).  amb_mode 0, 4 or (76 / 77) 12
-inline bool path_gap_xstrands_mode(int mode) {
-    return mode == RG_MODE_PATHWISE_GAP_XSTRANDS || mode == RG_MODE_PATHWISE_GAP_SEMI_XSTRANDS || mode == RG_MODE_PATHWISE_GAP_LOCAL_XSTRANDS;
-}
-inline int path_gap_base_mode(int mode) {
-    return path_gap_xstrands_mode(mode) ? mode - 70 : path_gap_xlong_mode(mode) ? mode - 50 : path_gap_strands_mode(mode) ? mode - 20 : path_gap_long_mode(mode) ? mode - 10 : mode;
-}
 
 // Reads per launch when `n` reads go through launches of at most `maxchunk` (both >= 1): as few launches as that allows, and
 // those even, so no short tail launch.  Every launch but the last takes the result, the last what is left (at least one read).

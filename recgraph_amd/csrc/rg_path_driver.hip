@@ -5,10 +5,11 @@
 //   -m 4:  sweep(F, dirs) -> seed -> layer(F) -> trace
 //   -m 6:  gap_score(every path) -> gap_pick -> gap_dirs(picked path) -> gap_trace          (gap/rg_path_gap.hip; -m 7 likewise)
 //   -m 12: the same four steps with the local kernels                                       (gap_local/rg_path_gap_local.hip)
-//   -m 16, 17, 22: the rules of -m 6, 7, 12; a batch with a read over 2047 bases runs the striped kernels    (gap_long/rg_path_gap_long.hip)
-//   -m 56, 57, 62: gap_score_long -> gap_pick -> gap_ckpt_long -> (gap_redo_long -> gap_walk_long) per stripe, last to first     (gap_xlong/rg_path_gap_xlong.hip)
-//   -m 26, 27, 32: two passes of -m 16, 17, 22, each planned here by its own longest read (the passes: rg_strand_driver.hip)
-//   -m 76, 77, 82: the pipeline of -m 56, 57, 62 in STAGES (PathJob::stage): PICK = gap_score[_long] -> gap_pick -> gap_pick_out, run per
+//   the families of these three rules (rg_gap_modes.hpp):
+//     long:     the same rules; a batch with a read over 2047 bases runs the striped kernels    (gap_long/rg_path_gap_long.hip)
+//     xlong:    gap_score_long -> gap_pick -> gap_ckpt_long -> (gap_redo_long -> gap_walk_long) per stripe, last to first     (gap_xlong/rg_path_gap_xlong.hip)
+//     strands:  two passes of the long family, each planned here by its own longest read (the passes: rg_strand_driver.hip)
+//     xstrands: the pipeline of the xlong family in STAGES (PathJob::stage): PICK = gap_score[_long] -> gap_pick -> gap_pick_out, run per
 //          strand; TRACE = gap_seed_pick -> the rest of the pipeline, run once (gap_xstrands/rg_gap_xstrands.hip; the stages of a batch:
 //          rg_strand_driver.hip)
 //   -m 8:  sweep(F1: column maxima) -> seed -> thr -> sweep(R: dirs, candidates, column maxima)
@@ -36,8 +37,8 @@ struct PathWorkImpl {
     DevBuf<ReadState> state;
     DevBuf<int> roll, mf, wr, mfarg, wrarg, thr, flayer, rlayer;
     DevBuf<uint32_t> fdirs, rdirs, gdirs;
-    DevBuf<int> gbnd, gdbnd;            // -m 16 / 17 / 22: the stripe boundaries of the score pass and of the direction pass
-    DevBuf<int> gckpt;                  // -m 56 / 57 / 62: per stripe but the last, what it leaves to its right neighbour (picked path)
+    DevBuf<int> gbnd, gdbnd;            // the long family: the stripe boundaries of the score pass and of the direction pass
+    DevBuf<int> gckpt;                  // the xlong family: per stripe but the last, what it leaves to its right neighbour (picked path)
     DevBuf<GapWalkState> gwalk;         // ... and where each read's walk stands between two rounds
     DevBuf<Cand> fcand, rcand;
     DevBuf<unsigned> nf, nr, ridx, nrec, nrrec;
@@ -269,7 +270,7 @@ int Run::enqueue_pathwise_gap() {
         return step("k_gap_pick", [&] { return launch_gap_pick(ga, chunk, plan.nwv * C, semi, stream); },
                     "k_gap_pick_local", [&] { return launch_gap_pick_local(ga, chunk, plan.nwv * C, stream); });
     };
-    // the stages of -m 76 / -m 77 / -m 82: a PICK stage ends behind the pick, which goes out into the job's records; a TRACE stage
+    // the stages of the xstrands family: a PICK stage ends behind the pick, which goes out into the job's records; a TRACE stage
     // begins there, with the picks of the records (the whole pipeline runs score, pick and the rest without either)
     const bool score = plan.stage != PATH_STAGE_TRACE;
     auto pick_out = [&] {

@@ -76,37 +76,21 @@ bool sweep16_admissible(const DevScores& sc, int max_path_rows, int max_n, int C
     return true;
 }
 
-// -m 6 / -m 7 / -m 12: one wave per (read, path) keeps H and Y of the current row in registers, C columns per lane (n + 1 <= 64 C), so a
-// read must fit one wave (-m 16 / -m 17 / -m 22: up to 8 column stripes of 2048, walked by that one wave, gap_long/rg_path_gap_long.hip; -m 56 / -m 57 / -m 62: up to 64, gap_xlong/); the only HBM work buffer beside ReadState holds the 4-bit directions of the picked path.
-static int plan_pathwise_gap(const rg_params& p, const PathPlanInput& in, PathPlan& o) {
+// The affine-gap pathwise modes (the table: rg_gap_modes.hpp): one wave per (read, path) keeps H and Y of the current row in registers,
+// C columns per lane (n + 1 <= 64 C), so a read must fit one wave, or as many column stripes of 2048, walked by that one wave, as the
+// mode's family allows (gap_long/, gap_xlong/); the only HBM work buffer beside ReadState holds the 4-bit directions of the picked path.
+static int plan_pathwise_gap(const rg_params& p, const GapMode& gm, const PathPlanInput& in, PathPlan& o) {
     if (p.gap_open > 0 || p.gap_ext > 0) return fail(RG_ERR_ARG, "gap penalties must be <= 0");
-    const bool lng = path_gap_long_mode(p.mode);
-    const bool xstr = path_gap_xstrands_mode(p.mode);
-    const bool xlng = path_gap_xlong_mode(p.mode) || xstr;      // (-m 76 / -m 77 / -m 82: every stage is one of pipeline 56 / 57 / 62)
-    const int base = path_gap_base_mode(p.mode);
-    const bool local = base == RG_MODE_PATHWISE_GAP_LOCAL;
-    if (xstr || path_gap_strands_mode(p.mode)) {
-        // -m 26 / -m 27 / -m 32 and -m 76 / -m 77 / -m 82: both strands is what the mode does (bit 2 is redundant); the vote is a rule
-        // of the two modes whose scores can be negative.  Every pass (every stage) of such a batch is planned here, with its own longest read
-        if (local && p.amb_mode == (RG_AMB_BOTH_STRANDS | RG_AMB_STRAND_VOTE))
-            return fail(RG_ERR_ARG, "RG_AMB_STRAND_VOTE is not available in the local both-strands mode (-m " + std::to_string(p.mode) +
-                                    "): no score of a local pass says \"hopeless\", so a vote would have no rule for a second pass");
-        if (p.amb_mode != 0 && p.amb_mode != RG_AMB_BOTH_STRANDS && p.amb_mode != (RG_AMB_BOTH_STRANDS | RG_AMB_STRAND_VOTE))
-            return fail(RG_ERR_ARG, std::string("amb_mode must be 0, 4 or 12 in the both-strands affine-gap pathwise modes ") +
-                                    (xstr ? "for reads of up to 131071 bases (-m 76 / -m 77), 0 or 4 in -m 82" : "(-m 26 / -m 27), 0 or 4 in -m 32"));
-    } else if (p.amb_mode)
-        return fail(RG_ERR_ARG, xlng    ? "amb_mode must be 0 in the affine-gap pathwise modes for reads of up to 131071 bases (-m 56 / -m 57 / -m 62): they align the reads as given"
-                                : lng   ? "amb_mode must be 0 in the long-read affine-gap pathwise modes (-m 16 / -m 17 / -m 22): they align the reads as given"
-                                : local ? "amb_mode must be 0 in the local affine-gap pathwise mode (-m 12): it aligns the reads as given"
-                                        : "amb_mode must be 0 in the affine-gap pathwise modes (-m 6 / -m 7): they align the reads as given");
-    if (xlng && in.max_n > 64 * 32 * WAVE - 1)
-        return fail(RG_ERR_ARG, xstr ? "reads longer than 131071 bases are not supported by the both-strands affine-gap pathwise modes -m 76 / -m 77 / -m 82"
-                                     : "reads longer than 131071 bases are not supported by the affine-gap pathwise modes -m 56 / -m 57 / -m 62");
-    if (lng && in.max_n > 8 * 32 * WAVE - 1)
-        return fail(RG_ERR_ARG, "reads longer than 16383 bases are not supported by the long-read affine-gap pathwise modes (-m 16 / -m 17 / -m 22, and -m 26 / -m 27 / -m 32 on both strands)");
-    if (!lng && !xlng && in.max_n > 32 * WAVE - 1)
-        return fail(RG_ERR_ARG, local ? "reads longer than 2047 bases are not supported by the local affine-gap pathwise mode (-m 12)"
-                                      : "reads longer than 2047 bases are not supported by the affine-gap pathwise modes (-m 6 / -m 7)");
+    const GapFamily& f = *gm.family;
+    const bool local = gm.rule == GAP_RULE_LOCAL;
+    // a both-strands family: both strands is what the mode does (bit 2 is redundant); the vote is a rule of the two modes whose scores
+    // can be negative.  Every pass (every stage) of such a batch is planned here, with its own longest read
+    if (f.both_strands && local && p.amb_mode == (RG_AMB_BOTH_STRANDS | RG_AMB_STRAND_VOTE))
+        return fail(RG_ERR_ARG, "RG_AMB_STRAND_VOTE is not available in the local both-strands mode (-m " + std::to_string(p.mode) +
+                                "): no score of a local pass says \"hopeless\", so a vote would have no rule for a second pass");
+    if (p.amb_mode != 0 && !(f.both_strands && (p.amb_mode == RG_AMB_BOTH_STRANDS || p.amb_mode == (RG_AMB_BOTH_STRANDS | RG_AMB_STRAND_VOTE))))
+        return fail(RG_ERR_ARG, f.amb_text(local));
+    if (in.max_n > f.max_read()) return fail(RG_ERR_ARG, f.len_text(local));
     // every value of H, X, Y is a sum of at most (rows + n) steps of at most max(|sc|, |o + e|) each: kept inside +-2^28, so that
     // the NEG sentinel (-2^29) plus any such sum can neither win nor wrap (the striped kernels' z in global columns: their header)
     long long maxabs = std::llabs((long long)p.gap_open + (long long)p.gap_ext);
@@ -117,8 +101,8 @@ static int plan_pathwise_gap(const rg_params& p, const PathPlanInput& in, PathPl
         return fail(RG_ERR_CAPACITY, "scores of this batch can reach 2^28 in magnitude: outside the i32 range of the affine-gap pathwise kernels");
     o.gap = true;
     o.mode = RG_MODE_PATHWISE_GAP;
-    o.semi = base == RG_MODE_PATHWISE_GAP_SEMI;
-    o.local = local;          // (-m 12: neither end is pinned; `semi` stays false)
+    o.semi = gm.rule == GAP_RULE_SEMI;
+    o.local = local;          // (neither end is pinned; `semi` stays false)
     int C = 4;
     while (C * WAVE < in.max_n + 1 && C < 32) C *= 2;
     o.C = C;
@@ -128,8 +112,8 @@ static int plan_pathwise_gap(const rg_params& p, const PathPlanInput& in, PathPl
     o.gap_words = std::max(1, C / 8);
     o.gdirs_stride = (long long)o.nwv * (in.max_path_rows + 1) * o.gap_words * WAVE;
     o.per_read = (size_t)o.gdirs_stride * 4 + sizeof(ReadState);
-    if (o.nwv > 1 && xlng) {
-        // -m 56 / -m 57 / -m 62 (gap_xlong/rg_path_gap_xlong.hip), whatever the stripe count: direction words of ONE stripe, a checkpoint
+    if (o.nwv > 1 && f.one_stripe_dirs) {
+        // gap_xlong/rg_path_gap_xlong.hip, whatever the stripe count: direction words of ONE stripe, a checkpoint
         // slot of two ints per row for every stripe but the last, the score pass's boundary buffer and the walk state
         const long long rows1 = in.max_path_rows + 1;
         o.gap_xlong = true;
@@ -161,8 +145,8 @@ int plan_gap_stage(PathPlan& o, int stage) {
 
 int plan_pathwise(const rg_params& p, const PathPlanInput& in, const Options& opt, int spec_level, PathPlan& o) {
     o = PathPlan{};
-    const int gbase = path_gap_base_mode(p.mode);
-    if (gbase == RG_MODE_PATHWISE_GAP || gbase == RG_MODE_PATHWISE_GAP_SEMI || gbase == RG_MODE_PATHWISE_GAP_LOCAL) return plan_pathwise_gap(p, in, o);
+    const GapMode gm = gap_mode(p.mode);
+    if (gm.valid) return plan_pathwise_gap(p, gm, in, o);
     const int P = in.P, L = in.L, max_n = in.max_n;
     o.semi = p.mode == RG_MODE_PATHWISE_SEMI || p.mode == RG_MODE_RECOMBINATION_SEMI;
     o.mode = p.mode == RG_MODE_PATHWISE_SEMI ? RG_MODE_PATHWISE : p.mode == RG_MODE_RECOMBINATION_SEMI ? RG_MODE_RECOMBINATION : p.mode;

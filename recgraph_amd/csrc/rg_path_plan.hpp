@@ -62,17 +62,17 @@ struct PathPlan {
     bool local;                   // -m 12 (gap_local/rg_path_gap_local.hip): the same geometry and buffers, the local kernels
     int gap_words;
     long long gdirs_stride;       // words per read: (rows of the longest path + 1) * gap_words * 64
-    // -m 16 / -m 17 / -m 22 (gap_long/rg_path_gap_long.hip) when the longest read has more than 2047 bases — otherwise the plan IS the
+    // the long family (gap_long/rg_path_gap_long.hip) when the longest read has more than 2047 bases — otherwise the plan IS the
     // base mode's: C = 32, nwv = S = ceil((max_n + 1) / 2048) column stripes walked by ONE wave, gdirs_stride = S * (rows + 1) * 4 * 64,
     // and two boundary buffers (ints per read): 2 * (rows + 1) per path for the score pass, 2 * (rows + 1) for the direction pass
     long long gbnd_stride, gdbnd_stride;
-    // -m 56 / -m 57 / -m 62 (gap_xlong/rg_path_gap_xlong.hip) when the longest read has more than 2047 bases — otherwise the plan IS the
+    // the xlong family (gap_xlong/rg_path_gap_xlong.hip) when the longest read has more than 2047 bases — otherwise the plan IS the
     // base mode's: C = 32, nwv = S = ceil((max_n + 1) / 2048) <= 64, gdirs_stride = (rows + 1) * 4 * 64 (ONE stripe), gbnd_stride as
     // above, gdbnd_stride = 0, and (ints per read) (S - 1) * 2 * (rows + 1) of checkpoints; gwalk_bytes: the walk state of a read
     bool gap_xlong;
     long long gckpt_stride;
     size_t gwalk_bytes;
-    // -m 76 / -m 77 / -m 82 (rg_strand_driver.hip): which part of the affine-gap pipeline a job runs (PATH_STAGE_*, plan_gap_stage);
+    // the xstrands family (rg_strand_driver.hip): which part of the affine-gap pipeline a job runs (PATH_STAGE_*, plan_gap_stage);
     // PATH_STAGE_ALL in every plan plan_pathwise returns
     int stage;
 
@@ -94,7 +94,7 @@ int plan_pathwise(const rg_params& p, const PathPlanInput& in, const Options& op
 enum { PATH_STAGE_ALL = 0, PATH_STAGE_PICK = 1, PATH_STAGE_TRACE = 2 };
 // Narrows a plan of plan_pathwise to one stage: `stage`, and `per_read` = what the stage's kernels touch.  PICK: ReadState and, when
 // striped, the score pass's P * 2 * (rows + 1) boundary ints; TRACE: the whole pipeline's minus those ints.  Geometry, strides and
-// kernels are untouched.  RG_ERR_ARG for a plan that is no affine-gap plan, and for the striped plan of -m 16 / -m 17 / -m 22, whose
+// kernels are untouched.  RG_ERR_ARG for a plan that is no affine-gap plan, and for the striped plan of the long family, whose
 // direction pass has no caller that runs it alone.
 int plan_gap_stage(PathPlan& plan, int stage);
 

@@ -102,8 +102,7 @@ int usable_cpus() {
 
 bool mode_is_pathwise(int mode) {
     return mode == RG_MODE_PATHWISE || mode == RG_MODE_RECOMBINATION || mode == RG_MODE_PATHWISE_SEMI || mode == RG_MODE_RECOMBINATION_SEMI ||
-           mode == RG_MODE_PATHWISE_GAP || mode == RG_MODE_PATHWISE_GAP_SEMI || mode == RG_MODE_PATHWISE_GAP_LOCAL || path_gap_long_mode(mode) ||
-           path_gap_xlong_mode(mode) || path_gap_xstrands_mode(mode);
+           gap_mode(mode).valid;
 }
 bool mode_is_local(int mode) { return mode == RG_MODE_LOCAL_POA || mode == RG_MODE_LOCAL_POA_SCALAR || mode == RG_MODE_GAP_LOCAL_POA; }
 
@@ -401,8 +400,8 @@ int32_t rg_stream_create(const rg_graph* g, const rg_params* p, const int32_t* d
     // extension; no second handle, and the kept record is the chosen one)
     if ((s->o.amb_strand == 2 || s->o.amb_strand == 3) && mode_is_pathwise(p->mode)) s->p.amb_mode |= RG_AMB_BOTH_STRANDS;
     if (s->o.amb_strand == 3 && mode_is_pathwise(p->mode)) s->p.amb_mode |= RG_AMB_STRAND_VOTE;      // (the first strand by a 12-mer vote)
-    // -m 32 and -m 82 have no vote (include/recgraph_hip.h); said here, before a worker meets it on its first tile
-    if ((p->mode == RG_MODE_PATHWISE_GAP_LOCAL_STRANDS || p->mode == RG_MODE_PATHWISE_GAP_LOCAL_XSTRANDS) && (s->p.amb_mode & RG_AMB_STRAND_VOTE))
+    // the local rule of a both-strands family has no vote (include/recgraph_hip.h); said here, before a worker meets it on its first tile
+    if (gap_mode(p->mode).rule == GAP_RULE_LOCAL && gap_mode(p->mode).family->both_strands && (s->p.amb_mode & RG_AMB_STRAND_VOTE))
         return fail(RG_ERR_ARG, "amb_strand = 3 (the strand vote) is not available in the local both-strands mode (-m " + std::to_string(p->mode) +
                                 "): no score of a local pass says \"hopeless\", so a vote would have no rule for a second pass");
     if (s->amb && s->o.keep_records) return fail(RG_ERR_ARG, "amb_strand and keep_records exclude each other (the kept record would be the forward one)");

@@ -2,14 +2,10 @@
 // arithmetic only):   forward_bound_plan <rows of the graph> <longest read> [option=value ...]
 // prints "C nwv use16 opt16 spec dsel spec_margin" — the fields that decide which bound kernel the batch launches and whether k_verify
 // looks at the bound alone.
-#include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <string>
 
-#include "rg_path_plan.hpp"
-
-using namespace rg;
+#include "plan_check_common.hpp"
 
 int main(int argc, char** argv) {
     if (argc < 3) return 2;
@@ -22,14 +18,8 @@ int main(int argc, char** argv) {
         if (!d) { fprintf(stderr, "no option %s\n", argv[k]); return 2; }
         store_option(o, *d, atoi(eq + 1));
     }
-    rg_params p;
-    memset(&p, 0, sizeof p);
-    p.mode = RG_MODE_RECOMBINATION;
     // the default scores (score_matrix.rs:35-66: match 2, mismatch -4, any pairing with '-' twice the mismatch)
-    for (int i = 0; i < 6; ++i)
-        for (int j = 0; j < 6; ++j) p.scores[i * 6 + j] = i == j ? 2 : (i == 5 || j == 5) ? -8 : -4;
-    p.scores[4 * 6 + 4] = -4;
-    p.scores[5 * 6 + 5] = RG_SCORE_MISSING;
+    rg_params p = score_params(RG_MODE_RECOMBINATION);
     p.base_rec_cost = 4;
     p.multi_rec_cost = 0.1f;
     p.rec_band_width = 1.0f;

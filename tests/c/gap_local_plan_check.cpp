@@ -1,36 +1,9 @@
 // CPU check of the plan of the local affine-gap pathwise mode (-m 12; recgraph_amd/csrc/rg_path_plan.cpp: plan_pathwise): the gap
 // route with the `local` flag, columns per lane on both sides of every boundary, the refusals, the bytes per read — and that modes 6
 // and 7 keep `local` off.  Built and run by tests/test_pathwise_gap_local_cpu.py.
-#include <cstdio>
-#include <cstring>
+#include "plan_check_common.hpp"
 
-#include "rg_path_plan.hpp"
-
-using namespace rg;
-
-static int failures = 0;
-#define CHECK(c)                                                                        \
-    do {                                                                                \
-        if (!(c)) { ++failures; fprintf(stderr, "gap_local_plan_check.cpp:%d: %s\n", __LINE__, #c); } \
-    } while (0)
-
-static rg_params params(int mode, int o = -4, int e = -2) {
-    rg_params p;
-    memset(&p, 0, sizeof p);
-    p.mode = mode;
-    for (int i = 0; i < 6; ++i)
-        for (int j = 0; j < 6; ++j) p.scores[i * 6 + j] = i == j ? 2 : (i == 5 || j == 5) ? -8 : -4;
-    p.scores[4 * 6 + 4] = -4;
-    p.scores[5 * 6 + 5] = RG_SCORE_MISSING;
-    p.gap_open = o;
-    p.gap_ext = e;
-    return p;
-}
-static PathPlanInput shape(int max_n, int rows = 1000) { return PathPlanInput{6, rows + 2, 1400, 1400, rows, max_n}; }
-static int run(const rg_params& p, const PathPlanInput& in, PathPlan& q) {
-    Options o;
-    return plan_pathwise(p, in, o, 0, q);
-}
+using namespace gap_check;
 
 int main() {
     PathPlan q;
@@ -80,7 +53,5 @@ int main() {
         CHECK(run(p, shape(1000), q) == RG_OK);
     }
     CHECK(run(params(RG_MODE_PATHWISE), shape(150), q) == RG_OK && !q.gap && !q.local);
-    if (failures) { fprintf(stderr, "%d failures\n", failures); return 1; }
-    puts("gap local plan ok");
-    return 0;
+    return finish("gap local plan ok");
 }

@@ -2,43 +2,16 @@
 // plan_pathwise): up to 2047 bases the plan IS the base mode's; beyond, C = 32 and S = ceil((n + 1) / 2048) column stripes walked by
 // one wave, with the direction words and the two boundary buffers counted per read; the refusals at the new lengths.  Built and run by
 // tests/test_pathwise_gap_long_cpu.py.
-#include <cstdio>
-#include <cstring>
+#include "gap_mode_check.hpp"
 
-#include "rg_path_plan.hpp"
-
-using namespace rg;
-
-static int failures = 0;
-#define CHECK(c)                                                                        \
-    do {                                                                                \
-        if (!(c)) { ++failures; fprintf(stderr, "gap_long_plan_check.cpp:%d: %s\n", __LINE__, #c); } \
-    } while (0)
-
-static rg_params params(int mode, int o = -4, int e = -2) {
-    rg_params p;
-    memset(&p, 0, sizeof p);
-    p.mode = mode;
-    for (int i = 0; i < 6; ++i)
-        for (int j = 0; j < 6; ++j) p.scores[i * 6 + j] = i == j ? 2 : (i == 5 || j == 5) ? -8 : -4;
-    p.scores[4 * 6 + 4] = -4;
-    p.scores[5 * 6 + 5] = RG_SCORE_MISSING;
-    p.gap_open = o;
-    p.gap_ext = e;
-    return p;
-}
-static const int kPaths = 6;
-static PathPlanInput shape(int max_n, int rows = 1000) { return PathPlanInput{kPaths, rows + 2, 1400, 1400, rows, max_n}; }
-static int run(const rg_params& p, const PathPlanInput& in, PathPlan& q) {
-    Options o;
-    return plan_pathwise(p, in, o, 0, q);
-}
+using namespace gap_check;
 
 int main() {
     CHECK(RG_MODE_PATHWISE_GAP_LONG == 16 && RG_MODE_PATHWISE_GAP_SEMI_LONG == 17 && RG_MODE_PATHWISE_GAP_LOCAL_LONG == 22);
     const int longs[] = {RG_MODE_PATHWISE_GAP_LONG, RG_MODE_PATHWISE_GAP_SEMI_LONG, RG_MODE_PATHWISE_GAP_LOCAL_LONG};
     for (int M : longs) {
-        const int base = M - 10;
+        const int base = path_gap_base_mode(M);
+        CHECK(is_family(M, GAP_FAM_LONG) && in_family(base, GAP_FAM_LONG) == M);
         PathPlan q, g;
         // up to 2047 bases: exactly the base mode's plan, and its kernels (nwv = 1)
         for (int n : {1, 255, 256, 1023, 1024, 2047}) {
@@ -97,7 +70,5 @@ int main() {
     }
     PathPlan q;
     CHECK(run(params(RG_MODE_PATHWISE), shape(5000), q) == RG_OK && !q.gap && q.gbnd_stride == 0);
-    if (failures) { fprintf(stderr, "%d failures\n", failures); return 1; }
-    puts("gap long plan ok");
-    return 0;
+    return finish("gap long plan ok");
 }

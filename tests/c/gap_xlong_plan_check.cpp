@@ -3,44 +3,17 @@
 // S = ceil((n + 1) / 2048) <= 64 column stripes with the direction words of ONE stripe, a checkpoint slot for every stripe but the
 // last, the score pass's boundary buffer and the walk state counted per read — for S <= 8 too, where modes 16 / 17 / 22 would keep S
 // stripes of words; the refusals at the new lengths.  Built and run by tests/test_pathwise_gap_xlong_cpu.py.
-#include <cstdio>
-#include <cstring>
+#include "gap_mode_check.hpp"
 
-#include "rg_path_plan.hpp"
-
-using namespace rg;
-
-static int failures = 0;
-#define CHECK(c)                                                                        \
-    do {                                                                                \
-        if (!(c)) { ++failures; fprintf(stderr, "gap_xlong_plan_check.cpp:%d: %s\n", __LINE__, #c); } \
-    } while (0)
-
-static rg_params params(int mode, int o = -4, int e = -2) {
-    rg_params p;
-    memset(&p, 0, sizeof p);
-    p.mode = mode;
-    for (int i = 0; i < 6; ++i)
-        for (int j = 0; j < 6; ++j) p.scores[i * 6 + j] = i == j ? 2 : (i == 5 || j == 5) ? -8 : -4;
-    p.scores[4 * 6 + 4] = -4;
-    p.scores[5 * 6 + 5] = RG_SCORE_MISSING;
-    p.gap_open = o;
-    p.gap_ext = e;
-    return p;
-}
-static PathPlanInput shape(int max_n, int rows = 1000, int paths = 6) { return PathPlanInput{paths, rows + 2, 1400, 1400, rows, max_n}; }
-static int run(const rg_params& p, const PathPlanInput& in, PathPlan& q) {
-    Options o;
-    return plan_pathwise(p, in, o, 0, q);
-}
+using namespace gap_check;
 
 int main() {
     CHECK(RG_MODE_PATHWISE_GAP_XLONG == 56 && RG_MODE_PATHWISE_GAP_SEMI_XLONG == 57 && RG_MODE_PATHWISE_GAP_LOCAL_XLONG == 62);
     const int xlongs[] = {RG_MODE_PATHWISE_GAP_XLONG, RG_MODE_PATHWISE_GAP_SEMI_XLONG, RG_MODE_PATHWISE_GAP_LOCAL_XLONG};
     for (int M : xlongs) {
-        const int base = M - 50;
-        CHECK(path_gap_xlong_mode(M) && path_gap_base_mode(M) == base && !path_gap_long_mode(M) && !path_gap_strands_mode(M));
-        CHECK(!path_gap_xlong_mode(base) && !path_gap_xlong_mode(M - 40) && !path_gap_xlong_mode(M - 30));
+        const int base = kGapRuleBase[gap_mode(M).rule], lng = in_family(M, GAP_FAM_LONG), str = in_family(M, GAP_FAM_STRANDS);
+        CHECK(is_family(M, GAP_FAM_XLONG) && path_gap_base_mode(M) == base && !long_limit(M) && !is_family(M, GAP_FAM_STRANDS) && in_family(base, GAP_FAM_XLONG) == M);
+        CHECK(!is_family(base, GAP_FAM_XLONG) && !is_family(lng, GAP_FAM_XLONG) && !is_family(str, GAP_FAM_XLONG));
         PathPlan q, g;
         // up to 2047 bases: exactly the base mode's plan, and its kernels (nwv = 1)
         for (int n : {1, 255, 256, 1023, 1024, 2047}) {
@@ -69,11 +42,11 @@ int main() {
             CHECK(!q.use16 && !q.spec && !q.spec4 && !q.two_sweep && !q.use_rec && !q.retire && !q.dsel && !q.dsel4);
         }
         // the long modes on the same batch keep S stripes of words and no checkpoint
-        CHECK(run(params(M - 40), shape(8192), g) == RG_OK);
+        CHECK(run(params(lng), shape(8192), g) == RG_OK);
         CHECK(!g.gap_xlong && g.nwv == 5 && g.gdirs_stride == 5ll * 1001 * 4 * 64 && g.gckpt_stride == 0 && g.gdbnd_stride == 2ll * 1001);
         // one 16383-base read on 17000 rows and 16 paths: direction words and checkpoints of mode 56 against the words of mode 16
         CHECK(run(params(M), shape(16383, 17000, 16), q) == RG_OK);
-        CHECK(run(params(M - 40), shape(16383, 17000, 16), g) == RG_OK);
+        CHECK(run(params(lng), shape(16383, 17000, 16), g) == RG_OK);
         CHECK(q.gdirs_stride * 4 + q.gckpt_stride * 4 == 17001ll * 1024 + 7ll * 8 * 17001);
         CHECK(g.gdirs_stride * 4 == 8ll * 17001 * 1024);
         CHECK(q.gbnd_stride == g.gbnd_stride && q.gbnd_stride == 16ll * 2 * 17001);
@@ -108,12 +81,10 @@ int main() {
         // the earlier modes keep their limits
         CHECK(run(params(base), shape(2048), q) == RG_ERR_ARG);
         CHECK(g_last_error.find("2047") != std::string::npos);
-        CHECK(run(params(M - 40), shape(16384), q) == RG_ERR_ARG);
+        CHECK(run(params(lng), shape(16384), q) == RG_ERR_ARG);
         CHECK(g_last_error.find("16383") != std::string::npos);
-        CHECK(run(params(M - 30), shape(16384), q) == RG_ERR_ARG);
+        CHECK(run(params(str), shape(16384), q) == RG_ERR_ARG);
         CHECK(g_last_error.find("16383") != std::string::npos);
     }
-    if (failures) { fprintf(stderr, "%d failures\n", failures); return 1; }
-    puts("gap xlong plan ok");
-    return 0;
+    return finish("gap xlong plan ok");
 }

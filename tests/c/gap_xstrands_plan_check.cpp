@@ -4,38 +4,10 @@
 // (and, striped, the score pass's P * 2 * (rows + 1) boundary ints) per read, a TRACE plan mode m + 50's bytes minus those ints;
 // plan_gap_stage leaves every plan of an existing mode as it is; the amb_mode rule and the refusals.  Built and run by
 // tests/test_pathwise_gap_xstrands_cpu.py.
-#include <cstdio>
-#include <cstring>
+#include "gap_mode_check.hpp"
 
-#include "rg_path_plan.hpp"
+using namespace gap_check;
 
-using namespace rg;
-
-static int failures = 0;
-#define CHECK(c)                                                                        \
-    do {                                                                                \
-        if (!(c)) { ++failures; fprintf(stderr, "gap_xstrands_plan_check.cpp:%d: %s\n", __LINE__, #c); } \
-    } while (0)
-
-static rg_params params(int mode, int o = -4, int e = -2, int amb = 0) {
-    rg_params p;
-    memset(&p, 0, sizeof p);
-    p.mode = mode;
-    for (int i = 0; i < 6; ++i)
-        for (int j = 0; j < 6; ++j) p.scores[i * 6 + j] = i == j ? 2 : (i == 5 || j == 5) ? -8 : -4;
-    p.scores[4 * 6 + 4] = -4;
-    p.scores[5 * 6 + 5] = RG_SCORE_MISSING;
-    p.gap_open = o;
-    p.gap_ext = e;
-    p.amb_mode = amb;
-    return p;
-}
-constexpr int kRows = 1000, kPaths = 6;
-static PathPlanInput shape(int max_n, int rows = kRows, int paths = kPaths) { return PathPlanInput{paths, rows + 2, 1400, 1400, rows, max_n}; }
-static int run(const rg_params& p, const PathPlanInput& in, PathPlan& q) {
-    Options o;
-    return plan_pathwise(p, in, o, 0, q);
-}
 // everything of a plan but per_read and stage
 static bool same_geometry(const PathPlan& a, const PathPlan& b) {
     return a.C == b.C && a.nwv == b.nwv && a.wpad == b.wpad && a.gap_words == b.gap_words && a.gdirs_stride == b.gdirs_stride &&
@@ -48,14 +20,15 @@ int main() {
     CHECK(PATH_STAGE_ALL == 0 && PATH_STAGE_PICK != PATH_STAGE_TRACE);
     const int modes[] = {RG_MODE_PATHWISE_GAP_XSTRANDS, RG_MODE_PATHWISE_GAP_SEMI_XSTRANDS, RG_MODE_PATHWISE_GAP_LOCAL_XSTRANDS};
     for (int M : modes) {
-        const int base = M - 70, xl = M - 20;
-        CHECK(path_gap_xstrands_mode(M) && path_gap_base_mode(M) == base);
-        // the existing predicates keep their values: for the new modes (false) and for every existing mode
-        CHECK(!path_gap_xlong_mode(M) && !path_gap_long_mode(M) && !path_gap_strands_mode(M));
-        for (int other : {base, base + 10, base + 20, base + 50}) CHECK(!path_gap_xstrands_mode(other) && path_gap_base_mode(other) == base);
-        CHECK(path_gap_xlong_mode(xl) && path_gap_strands_mode(base + 20) && path_gap_long_mode(base + 10) && path_gap_long_mode(base + 20));
+        const int base = kGapRuleBase[gap_mode(M).rule], xl = in_family(M, GAP_FAM_XLONG);
+        const int lng = in_family(M, GAP_FAM_LONG), str = in_family(M, GAP_FAM_STRANDS);
+        CHECK(is_family(M, GAP_FAM_XSTRANDS) && path_gap_base_mode(M) == base && in_family(base, GAP_FAM_XSTRANDS) == M);
+        // the other families keep their members: not the new modes, and every existing mode
+        CHECK(!is_family(M, GAP_FAM_XLONG) && !long_limit(M) && !is_family(M, GAP_FAM_STRANDS));
+        for (int other : {base, lng, str, xl}) CHECK(!is_family(other, GAP_FAM_XSTRANDS) && path_gap_base_mode(other) == base);
+        CHECK(is_family(xl, GAP_FAM_XLONG) && is_family(str, GAP_FAM_STRANDS) && long_limit(lng) && long_limit(str));
         for (int m = 0; m < 128; ++m)
-            if (m != 76 && m != 77 && m != 82) CHECK(!path_gap_xstrands_mode(m));
+            if (m != modes[0] && m != modes[1] && m != modes[2]) CHECK(!is_family(m, GAP_FAM_XSTRANDS));
         PathPlan q, g, pick, trace;
         // the whole-pipeline plan of a stage's reads IS mode m + 50's, at every length class
         for (int n : {1, 255, 1024, 2047, 2048, 4096, 16383, 16384, 40000, 131071}) {
@@ -116,7 +89,7 @@ int main() {
         CHECK(run(params(M, -2047, -2), shape(130000), q) == RG_OK);
         CHECK(run(params(M, -2048, -2), shape(130000), q) == RG_ERR_CAPACITY);
         // modes 26 / 27 / 32 keep their limit
-        CHECK(run(params(base + 20), shape(16384), q) == RG_ERR_ARG);
+        CHECK(run(params(str), shape(16384), q) == RG_ERR_ARG);
         CHECK(g_last_error.find("16383") != std::string::npos);
     }
     // plan_gap_stage on the plans of the existing modes: no stage for a plan that is no affine-gap plan, none for the striped plan of
@@ -130,24 +103,22 @@ int main() {
             CHECK(q.per_read == before.per_read && q.stage == PATH_STAGE_ALL);
             CHECK(plan_gap_stage(q, PATH_STAGE_ALL) == RG_OK && q.per_read == before.per_read);
         }
-        for (int m : {16, 17, 22, 26, 27, 32}) {
+        for (int m : family_modes({GAP_FAM_LONG, GAP_FAM_STRANDS})) {
             CHECK(run(params(m), shape(5000), q) == RG_OK && q.gap && q.nwv == 3 && !q.gap_xlong && q.stage == PATH_STAGE_ALL);
             before = q;
             CHECK(plan_gap_stage(q, PATH_STAGE_TRACE) == RG_ERR_ARG && q.per_read == before.per_read && q.stage == PATH_STAGE_ALL);
             CHECK(q.per_read == (size_t)q.gdirs_stride * 4 + (size_t)(q.gbnd_stride + q.gdbnd_stride) * 4 + sizeof(ReadState));
         }
-        for (int m : {6, 7, 12, 16, 17, 22, 26, 27, 32, 56, 57, 62}) {
+        for (int m : family_modes({GAP_FAM_BASE, GAP_FAM_LONG, GAP_FAM_STRANDS, GAP_FAM_XLONG})) {
             CHECK(run(params(m), shape(700), q) == RG_OK && q.stage == PATH_STAGE_ALL && q.nwv == 1);
             CHECK(q.per_read == (size_t)q.gdirs_stride * 4 + sizeof(ReadState));
         }
-        for (int m : {56, 57, 62}) {
+        for (int m : family_modes({GAP_FAM_XLONG})) {
             CHECK(run(params(m), shape(8192), q) == RG_OK && q.stage == PATH_STAGE_ALL);
             CHECK(q.per_read == (size_t)q.gdirs_stride * 4 + (size_t)(q.gbnd_stride + q.gckpt_stride) * 4 + q.gwalk_bytes + sizeof(ReadState));
         }
         PathPlan z;
-        CHECK(run(params(76), shape(700), z) == RG_OK && plan_gap_stage(z, 3) == RG_ERR_ARG && plan_gap_stage(z, -1) == RG_ERR_ARG);
+        CHECK(run(params(RG_MODE_PATHWISE_GAP_XSTRANDS), shape(700), z) == RG_OK && plan_gap_stage(z, 3) == RG_ERR_ARG && plan_gap_stage(z, -1) == RG_ERR_ARG);
     }
-    if (failures) { fprintf(stderr, "%d failures\n", failures); return 1; }
-    puts("gap xstrands plan ok");
-    return 0;
+    return finish("gap xstrands plan ok");
 }

@@ -2,31 +2,15 @@
 // arithmetic that the GPU tests only see through byte parity — a wrong decision is usually still correct, only slower.  Every
 // expected value is read off the driver as it was before the plan was split out of it; "drv:N" names the line of
 // rg_path_driver.hip in that commit (0343416) the value comes from.  Built and run by tests/test_path_plan_cpu.py.
-#include <cstdio>
-#include <cstring>
 #include <map>
 #include <set>
 #include <string>
 
-#include "rg_path_plan.hpp"
+#include "plan_check_common.hpp"
 
-using namespace rg;
-
-static int failures = 0;
-#define CHECK(c)                                                                    \
-    do {                                                                            \
-        if (!(c)) { ++failures; fprintf(stderr, "plan_check.cpp:%d: %s\n", __LINE__, #c); } \
-    } while (0)
-
-// score_matrix.rs:35-66 as rg_scores_match_mis builds it (any pairing with '-' = 2x)
+// score_matrix.rs:35-66 as rg_scores_match_mis builds it (any pairing with '-' = 2x), and the CLI's recombination costs
 static rg_params params(int mode, int m = 2, int x = -4) {
-    rg_params p;
-    memset(&p, 0, sizeof p);
-    p.mode = mode;
-    for (int i = 0; i < 6; ++i)
-        for (int j = 0; j < 6; ++j) p.scores[i * 6 + j] = i == j ? m : (i == 5 || j == 5) ? 2 * x : x;
-    p.scores[4 * 6 + 4] = x;
-    p.scores[5 * 6 + 5] = RG_SCORE_MISSING;
+    rg_params p = score_params(mode, m, x);
     p.base_rec_cost = 4;
     p.multi_rec_cost = 0.1f;
     p.rec_band_width = 1.0f;
@@ -275,7 +259,5 @@ int main() {
     score_matrices();
     long_reads();
     second_pass_levels();
-    if (failures) { fprintf(stderr, "%d plan checks failed\n", failures); return 1; }
-    puts("plan ok");
-    return 0;
+    return finish("plan ok");
 }

@@ -18,13 +18,12 @@ with `stripe_c` 8 and plain for k_opt0_striped<8> / <16>; the defaults with `no_
 shape: the path itself, five substitutions, one inserted base, one deleted base.  The CPU half asks plan_pathwise (tests/c/
 forward_bound_plan.cpp) that these shapes and options give the geometry, `spec` on and `dsel` off: a plan change cannot empty the GPU
 half silently."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import plan_check_build
 
 # id -> (bases of the longest read, options, instantiation of the bound kernel, (C, nwv, use16 / opt16), lb - score at spec_margin -1)
 CASES = {
@@ -111,12 +110,7 @@ def test_bound_is_the_exact_score(oracle, case):
 
 @pytest.fixture(scope="module")
 def plan_exe(tmp_path_factory):
-    csrc = os.path.join(ROOT, "recgraph_amd", "csrc")
-    exe = tmp_path_factory.mktemp("forward_bound") / "forward_bound_plan"
-    srcs = [os.path.join(csrc, f) for f in ("rg_path_plan.cpp", "rg_steps.cpp", "rg_graph.cpp", "rg_gaf.cpp", "rg_reads.cpp")]
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-I", csrc, "-o", str(exe), os.path.join(ROOT, "tests", "c", "forward_bound_plan.cpp")]
-                          + srcs + ["-lpthread"])
-    return str(exe)
+    return plan_check_build.build("forward_bound_plan", tmp_path_factory.mktemp("forward_bound"))
 
 
 @pytest.mark.parametrize("case", sorted(CASES))

@@ -6,42 +6,14 @@ launched the entry's instantiation.  Cases that several entries share run once."
 import pytest
 
 import kernel_matrix_gap_xlong as KX
-import pathwise_gap_rule as R
-from test_gpu_pathwise_gap_long import check_long
+from test_gpu_pathwise_gap_long import run_matrix_case
 
 pytestmark = pytest.mark.gpu
 _RESULTS = {}
 
 
 def _run_case(cid):
-    if cid in _RESULTS:
-        return _RESULTS[cid]
-    from recgraph_amd import api
-    case = KX.CASES[cid]
-    g, batches = KX.build(case)
-    gg = api.Graph.from_gfa_text(g.gfa())
-    lnz, rows = R.graph_paths(gg)
-    graph = (g, gg, lnz, rows, R.graph_node_ids(gg))
-    per_batch, coarse = [], set()
-    try:
-        api.set_option("launch_log", 1)
-        for reads in batches:
-            b = api.Batch(gg, reads, api.make_params(case.mode, **case.kw))
-            b.run()
-            b.fetch()
-            status = [b.status(i) for i in range(len(reads))]
-            assert status == [0] * len(reads), cid
-            texts = [b.gaf_text(i, "r%d" % i, i + 1) for i in range(len(reads))]
-            stats = b.kernel_stats()
-            per_batch.append({k[5:]: v[1] for k, v in stats.items() if k.startswith("inst:")})
-            coarse |= {k for k in stats if not k.startswith("inst:")}
-            api.set_option("launch_log", 0)
-            check_long(graph, reads, case.mode - 40, texts=texts, status=status, **case.kw)
-            api.set_option("launch_log", 1)
-    finally:
-        api.set_option("launch_log", 0)
-    _RESULTS[cid] = (per_batch, coarse)
-    return _RESULTS[cid]
+    return run_matrix_case(KX, cid, _RESULTS)
 
 
 @pytest.mark.parametrize("name", sorted(KX.MATRIX))

@@ -78,6 +78,41 @@ def check_long(graph, reads, mode, scores=None, o=-4, e=-2, texts=None, status=N
     return texts, status
 
 
+def run_matrix_case(K, cid, results):
+    """One case of a kernel matrix K (kernel_matrix_gap_long, kernel_matrix_gap_xlong) with the launch log on, cached in `results`: every
+    read checked by check_long as a read of the case's rule in the long family (the same rule and bytes); returns (the instantiations
+    each batch launched, the coarse kernel names of all batches)."""
+    if cid in results:
+        return results[cid]
+    from recgraph_amd import api
+    case = K.CASES[cid]
+    long_mode = case.mode - api._lib.gap_mode(case.mode).family.offset + api._lib.gap_family("_LONG").offset
+    g, batches = K.build(case)
+    gg = api.Graph.from_gfa_text(g.gfa())
+    lnz, rows = R.graph_paths(gg)
+    graph = (g, gg, lnz, rows, R.graph_node_ids(gg))
+    per_batch, coarse = [], set()
+    try:
+        api.set_option("launch_log", 1)
+        for reads in batches:
+            b = api.Batch(gg, reads, api.make_params(case.mode, **case.kw))
+            b.run()
+            b.fetch()
+            status = [b.status(i) for i in range(len(reads))]
+            assert status == [0] * len(reads), cid
+            texts = [b.gaf_text(i, "r%d" % i, i + 1) for i in range(len(reads))]
+            stats = b.kernel_stats()
+            per_batch.append({k[5:]: v[1] for k, v in stats.items() if k.startswith("inst:")})
+            coarse |= {k for k in stats if not k.startswith("inst:")}
+            api.set_option("launch_log", 0)
+            check_long(graph, reads, long_mode, texts=texts, status=status, **case.kw)
+            api.set_option("launch_log", 1)
+    finally:
+        api.set_option("launch_log", 0)
+    results[cid] = (per_batch, coarse)
+    return results[cid]
+
+
 def _noisy(rng, s, every=97):
     """`s` with a substitution every `every` bases (the length is kept)."""
     s = list(s)

@@ -2,11 +2,12 @@
 admission and the refusals of rg_batch_create (answered before a device is needed), the plan's routes
 (tests/c/gap_local_plan_check.cpp), the CLI's parser and the registers of the new kernels."""
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
+
+import plan_check_build
 
 import pathwise_gap_local_rule as L
 import pathwise_gap_rule as R
@@ -129,13 +130,7 @@ def test_the_cli_takes_the_mode():
 
 
 def test_gap_local_plan_routes(tmp_path):
-    csrc = os.path.join(ROOT, "recgraph_amd", "csrc")
-    exe = tmp_path / "gap_local_plan_check"
-    srcs = [os.path.join(csrc, f) for f in ("rg_path_plan.cpp", "rg_steps.cpp", "rg_graph.cpp", "rg_gaf.cpp", "rg_reads.cpp")]
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-I", csrc, "-o", str(exe), os.path.join(ROOT, "tests", "c", "gap_local_plan_check.cpp")]
-                          + srcs + ["-lpthread"])
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and r.stdout.strip() == "gap local plan ok", (r.stdout, r.stderr[-4000:])
+    plan_check_build.run_ok("gap_local_plan_check", tmp_path, "gap local plan ok")
 
 
 def test_the_kernels_keep_their_rows_in_registers():

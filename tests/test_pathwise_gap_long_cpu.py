@@ -2,25 +2,16 @@
 bases): admission and refusals of rg_batch_create (answered before a device is needed), the plan's routes
 (tests/c/gap_long_plan_check.cpp), the API and CLI surface and the registers of the new kernels."""
 import os
-import subprocess
 import sys
 
 import pytest
+
+import plan_check_build
 
 from test_pathwise_gap_cpu import TWO_BUBBLES, _create, _no_device
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LONG = {16: 6, 17: 7, 22: 12}
-
-
-def test_the_constants():
-    from recgraph_amd import api
-    assert (api.MODE_PATHWISE_GAP_LONG, api.MODE_PATHWISE_GAP_SEMI_LONG, api.MODE_PATHWISE_GAP_LOCAL_LONG) == (16, 17, 22)
-    assert (api._lib.MODE_PATHWISE_GAP_LONG, api._lib.MODE_PATHWISE_GAP_SEMI_LONG, api._lib.MODE_PATHWISE_GAP_LOCAL_LONG) == (16, 17, 22)
-    assert (api.MODE_PATHWISE_GAP + 10, api.MODE_PATHWISE_GAP_SEMI + 10, api.MODE_PATHWISE_GAP_LOCAL + 10) == (16, 17, 22)
-    header = open(os.path.join(ROOT, "include", "recgraph_hip.h")).read()
-    for name, v in (("RG_MODE_PATHWISE_GAP_LONG", 16), ("RG_MODE_PATHWISE_GAP_SEMI_LONG", 17), ("RG_MODE_PATHWISE_GAP_LOCAL_LONG", 22)):
-        assert "#define %s %d\n" % (name, v) in header
 
 
 @pytest.mark.parametrize("mode", sorted(LONG))
@@ -95,13 +86,7 @@ def test_the_cli_takes_the_modes():
 
 
 def test_gap_long_plan_routes(tmp_path):
-    csrc = os.path.join(ROOT, "recgraph_amd", "csrc")
-    exe = tmp_path / "gap_long_plan_check"
-    srcs = [os.path.join(csrc, f) for f in ("rg_path_plan.cpp", "rg_steps.cpp", "rg_graph.cpp", "rg_gaf.cpp", "rg_reads.cpp")]
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-I", csrc, "-o", str(exe), os.path.join(ROOT, "tests", "c", "gap_long_plan_check.cpp")]
-                          + srcs + ["-lpthread"])
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and r.stdout.strip() == "gap long plan ok", (r.stdout, r.stderr[-4000:])
+    plan_check_build.run_ok("gap_long_plan_check", tmp_path, "gap long plan ok")
 
 
 def test_the_kernels_keep_their_rows_in_registers():

@@ -5,10 +5,11 @@ tests/pathwise_gap_strands_rule.py on hand cases and in the score regimes the GP
 import functools
 import inspect
 import os
-import subprocess
 import sys
 
 import pytest
+
+import plan_check_build
 
 import pathwise_gap_local_rule as L
 import pathwise_gap_rule as R
@@ -18,19 +19,6 @@ from test_pathwise_gap_cpu import TWO_BUBBLES, _create, _no_device
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STRANDS = {26: 6, 27: 7, 32: 12}
-
-
-def test_the_constants():
-    from recgraph_amd import api
-    assert (api.MODE_PATHWISE_GAP_STRANDS, api.MODE_PATHWISE_GAP_SEMI_STRANDS, api.MODE_PATHWISE_GAP_LOCAL_STRANDS) == (26, 27, 32)
-    assert (api._lib.MODE_PATHWISE_GAP_STRANDS, api._lib.MODE_PATHWISE_GAP_SEMI_STRANDS, api._lib.MODE_PATHWISE_GAP_LOCAL_STRANDS) == (26, 27, 32)
-    assert (api.MODE_PATHWISE_GAP + 20, api.MODE_PATHWISE_GAP_SEMI + 20, api.MODE_PATHWISE_GAP_LOCAL + 20) == (26, 27, 32)
-    assert api.PATHWISE_GAP_STRANDS_MODES == (26, 27, 32) and not set(api.PATHWISE_GAP_STRANDS_MODES) & set(api.PATHWISE_GAP_MODES)
-    header = open(os.path.join(ROOT, "include", "recgraph_hip.h")).read()
-    ffi = open(os.path.join(ROOT, "shim", "src", "hip_ffi.rs")).read()
-    for name, v in (("RG_MODE_PATHWISE_GAP_STRANDS", 26), ("RG_MODE_PATHWISE_GAP_SEMI_STRANDS", 27), ("RG_MODE_PATHWISE_GAP_LOCAL_STRANDS", 32)):
-        assert "#define %s %d\n" % (name, v) in header
-        assert "pub const %s: i32 = %d;\n" % (name, v) in ffi
 
 
 @pytest.mark.parametrize("mode", sorted(STRANDS))
@@ -140,13 +128,7 @@ def test_the_cli_takes_the_modes():
 
 
 def test_gap_strands_plan_routes(tmp_path):
-    csrc = os.path.join(ROOT, "recgraph_amd", "csrc")
-    exe = tmp_path / "gap_strands_plan_check"
-    srcs = [os.path.join(csrc, f) for f in ("rg_path_plan.cpp", "rg_steps.cpp", "rg_graph.cpp", "rg_gaf.cpp", "rg_reads.cpp")]
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-I", csrc, "-o", str(exe), os.path.join(ROOT, "tests", "c", "gap_strands_plan_check.cpp")]
-                          + srcs + ["-lpthread"])
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and r.stdout.strip() == "gap strands plan ok", (r.stdout, r.stderr[-4000:])
+    plan_check_build.run_ok("gap_strands_plan_check", tmp_path, "gap strands plan ok")
 
 
 def test_the_gate_kernel_is_small():

@@ -3,10 +3,11 @@ and refusals of rg_batch_create (answered before a device is needed), the plan's
 and CLI surface and the registers of the new kernels."""
 import inspect
 import os
-import subprocess
 import sys
 
 import pytest
+
+import plan_check_build
 
 from test_pathwise_gap_cpu import TWO_BUBBLES, _create, _no_device
 
@@ -14,20 +15,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 XLONG = {56: 6, 57: 7, 62: 12}
 KERNELS = (["rg::k_gap_ckpt_long<%d>" % k for k in range(3)] + ["rg::k_gap_redo_long<%d>" % k for k in range(3)] +
            ["rg::k_gap_walk_long", "rg::k_gap_walk_local_long"])
-
-
-def test_the_constants():
-    from recgraph_amd import api
-    assert (api.MODE_PATHWISE_GAP_XLONG, api.MODE_PATHWISE_GAP_SEMI_XLONG, api.MODE_PATHWISE_GAP_LOCAL_XLONG) == (56, 57, 62)
-    assert (api._lib.MODE_PATHWISE_GAP_XLONG, api._lib.MODE_PATHWISE_GAP_SEMI_XLONG, api._lib.MODE_PATHWISE_GAP_LOCAL_XLONG) == (56, 57, 62)
-    assert (api.MODE_PATHWISE_GAP + 50, api.MODE_PATHWISE_GAP_SEMI + 50, api.MODE_PATHWISE_GAP_LOCAL + 50) == (56, 57, 62)
-    assert api.PATHWISE_GAP_XLONG_MODES == (56, 57, 62)
-    assert not set(api.PATHWISE_GAP_XLONG_MODES) & (set(api.PATHWISE_GAP_MODES) | set(api.PATHWISE_GAP_STRANDS_MODES))
-    header = open(os.path.join(ROOT, "include", "recgraph_hip.h")).read()
-    for name, v in (("RG_MODE_PATHWISE_GAP_XLONG", 56), ("RG_MODE_PATHWISE_GAP_SEMI_XLONG", 57), ("RG_MODE_PATHWISE_GAP_LOCAL_XLONG", 62)):
-        assert "#define %s %d\n" % (name, v) in header
-    ffi = open(os.path.join(ROOT, "shim", "src", "hip_ffi.rs")).read()
-    assert "pub const RG_MODE_PATHWISE_GAP_LOCAL_XLONG: i32 = 62;" in ffi
 
 
 @pytest.mark.parametrize("mode", sorted(XLONG))
@@ -123,13 +110,7 @@ def api_error():
 
 
 def test_gap_xlong_plan_routes(tmp_path):
-    csrc = os.path.join(ROOT, "recgraph_amd", "csrc")
-    exe = tmp_path / "gap_xlong_plan_check"
-    srcs = [os.path.join(csrc, f) for f in ("rg_path_plan.cpp", "rg_steps.cpp", "rg_graph.cpp", "rg_gaf.cpp", "rg_reads.cpp")]
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-I", csrc, "-o", str(exe), os.path.join(ROOT, "tests", "c", "gap_xlong_plan_check.cpp")]
-                          + srcs + ["-lpthread"])
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and r.stdout.strip() == "gap xlong plan ok", (r.stdout, r.stderr[-4000:])
+    plan_check_build.run_ok("gap_xlong_plan_check", tmp_path, "gap xlong plan ok")
 
 
 def test_the_kernels_keep_their_rows_in_registers():

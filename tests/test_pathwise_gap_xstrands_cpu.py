@@ -4,10 +4,11 @@
 tests/pathwise_gap_xstrands_rule.py on hand cases."""
 import inspect
 import os
-import subprocess
 import sys
 
 import pytest
+
+import plan_check_build
 
 import pathwise_gap_rule as R
 import pathwise_gap_xstrands_rule as X
@@ -18,20 +19,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 XSTRANDS = {76: 6, 77: 7, 82: 12}
 KERNELS = ["rg::k_gap_pick_out", "rg::k_gap_seed_pick", "rg::k_gap_xstrands_duel", "rg::k_gap_xstrands_mark"]
 LENGTHS = (5, 30000, 131072)
-
-
-def test_the_constants():
-    from recgraph_amd import api
-    assert (api.MODE_PATHWISE_GAP_XSTRANDS, api.MODE_PATHWISE_GAP_SEMI_XSTRANDS, api.MODE_PATHWISE_GAP_LOCAL_XSTRANDS) == (76, 77, 82)
-    assert (api._lib.MODE_PATHWISE_GAP_XSTRANDS, api._lib.MODE_PATHWISE_GAP_SEMI_XSTRANDS, api._lib.MODE_PATHWISE_GAP_LOCAL_XSTRANDS) == (76, 77, 82)
-    assert (api.MODE_PATHWISE_GAP + 70, api.MODE_PATHWISE_GAP_SEMI + 70, api.MODE_PATHWISE_GAP_LOCAL + 70) == (76, 77, 82)
-    assert api.PATHWISE_GAP_XSTRANDS_MODES == (76, 77, 82)
-    assert not set(api.PATHWISE_GAP_XSTRANDS_MODES) & (set(api.PATHWISE_GAP_MODES) | set(api.PATHWISE_GAP_STRANDS_MODES) | set(api.PATHWISE_GAP_XLONG_MODES))
-    header = open(os.path.join(ROOT, "include", "recgraph_hip.h")).read()
-    ffi = open(os.path.join(ROOT, "shim", "src", "hip_ffi.rs")).read()
-    for name, v in (("RG_MODE_PATHWISE_GAP_XSTRANDS", 76), ("RG_MODE_PATHWISE_GAP_SEMI_XSTRANDS", 77), ("RG_MODE_PATHWISE_GAP_LOCAL_XSTRANDS", 82)):
-        assert "#define %s %d\n" % (name, v) in header
-        assert "pub const %s: i32 = %d;\n" % (name, v) in ffi
 
 
 @pytest.mark.parametrize("mode", sorted(XSTRANDS))
@@ -172,13 +159,7 @@ def test_the_cli_takes_the_modes():
 
 
 def test_gap_xstrands_plan_routes(tmp_path):
-    csrc = os.path.join(ROOT, "recgraph_amd", "csrc")
-    exe = tmp_path / "gap_xstrands_plan_check"
-    srcs = [os.path.join(csrc, f) for f in ("rg_path_plan.cpp", "rg_steps.cpp", "rg_graph.cpp", "rg_gaf.cpp", "rg_reads.cpp")]
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-I", csrc, "-o", str(exe), os.path.join(ROOT, "tests", "c", "gap_xstrands_plan_check.cpp")]
-                          + srcs + ["-lpthread"])
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and r.stdout.strip() == "gap xstrands plan ok", (r.stdout, r.stderr[-4000:])
+    plan_check_build.run_ok("gap_xstrands_plan_check", tmp_path, "gap xstrands plan ok")
 
 
 def test_the_new_kernels_are_small():
