@@ -214,6 +214,30 @@ typedef enum rg_status {
 #define RG_MODE_PATHWISE_GAP_XSTRANDS 76
 #define RG_MODE_PATHWISE_GAP_SEMI_XSTRANDS 77
 #define RG_MODE_PATHWISE_GAP_LOCAL_XSTRANDS 82
+/*
+ * RG_MODE_PATHWISE_EDIT (44), RG_MODE_PATHWISE_EDIT_SEMI (45): modes 16 and 17 RESTRICTED TO UNIT COSTS (match 0; mismatch, inserted
+ * and deleted base 1: edit distance against every path), computed with Myers' bit-vector recurrence: one cell per bit instead of one
+ * per register, a read of up to 16383 bases whole in one wave.  THERE IS NO NEW RULE: for every batch they admit, mode 44 returns the
+ * bytes, statuses, scores and both cell counters that mode 16 returns for the same rg_params, mode 45 those of mode 17 (recurrence,
+ * choice, tie order, traceback, record, line and RG_READ_BAD_BASE reads included).  The modes are values of rg_params.mode only: no
+ * entry point, no struct field, and no row of the affine-gap family table.
+ *   ADMISSION.  gap_open == 0 and gap_ext == -1, and every entry scores[a * 6 + b] with a, b < 5 (the ACGTN x ACGTN block) is 0 or
+ *     -1: `-M 0 -X 1 -O 0 -E 1`, or any 0 / -1 matrix (an N that matches N, for one).  The '-' entries are not looked at.
+ *   REFUSALS.  Other gap costs or block entries (the message names `-M 0 -X 1 -O 0 -E 1`), any amb_mode bit (the reads are aligned as
+ *     given), a read longer than 16383 bases, and whatever else mode 16 refuses: RG_ERR_ARG (the 2^28 budget of mode 16:
+ *     RG_ERR_CAPACITY).  All answered by rg_batch_create before a device is needed.
+ *   WHY THE BYTES AGREE.  With costs in {0, 1} every difference between neighbouring cells of the distance matrix is -1, 0 or +1, so
+ *     a row is two bit vectors and a row step a handful of word operations with one wide addition; with o = 0 every gap state of the
+ *     rule of mode 6 equals H, and its traceback reads: D if H == H[i-1][j-1] + sc, else U if H == H[i-1][j] - 1, else L.  The
+ *     direction pass keeps two bits per cell from which the walk decides exactly that ("the diagonal is equal", "the vertical
+ *     difference is +1"); whether the two bases match is recomputed from the bases.
+ *   COST.  The direction bits of the chosen path take (rows of the longest path + 1) * W * 512 bytes per read of the batch, W = 1, 2,
+ *     4 or 8 the smallest with longest read <= 2048 W: about 70 MB for one 16383-base read on 17000 rows, half of mode 16's.
+ * k_edit_score, k_edit_dirs and k_edit_trace (edit/rg_path_edit.hip) appear in the kernel statistics under their own names beside
+ * k_gap_pick, which is the kernel of modes 6 and 7.
+ */
+#define RG_MODE_PATHWISE_EDIT 44
+#define RG_MODE_PATHWISE_EDIT_SEMI 45
 
 /*
  * Scoring and banding parameters.  Replaces the HashMap<(char,char),i32|f32> score matrix arguments

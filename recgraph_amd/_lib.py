@@ -92,6 +92,25 @@ def gap_family_modes(*suffixes):
     return tuple(base + gap_family(s).offset for s in suffixes for _, base in GAP_RULES)
 
 
+# The bit-vector edit-distance pathwise modes (RG_MODE_PATHWISE_EDIT / RG_MODE_PATHWISE_EDIT_SEMI in include/recgraph_hip.h, the lookup of
+# csrc/rg_edit_modes.hpp once more): modes 16 / 17 restricted to unit costs.  No rows of the table above: gap_mode(44) is None.
+MODE_PATHWISE_EDIT, MODE_PATHWISE_EDIT_SEMI = 44, 45
+EDIT_MAX_READ = 16383
+EDIT_SCORE_REFUSAL = ("the edit-distance pathwise modes (-m 44 / -m 45) take unit costs only: -M 0 -X 1 -O 0 -E 1, or a -t matrix whose ACGTN x ACGTN "
+                      "entries are all 0 or -1 with -O 0 -E 1; every other scoring is what -m 16 / -m 17 are for")
+EDIT_STRANDS_REFUSAL = "%s is not available in the edit-distance pathwise modes (44, 45): they align the reads as given"
+
+
+def edit_mode(mode):
+    """{"semi": bool} of an edit-distance pathwise mode, None for every other value."""
+    return {MODE_PATHWISE_EDIT: {"semi": False}, MODE_PATHWISE_EDIT_SEMI: {"semi": True}}.get(mode)
+
+
+def unit_costs(table, gap_open, gap_ext):
+    """What modes 44 / 45 admit: gap_open 0, gap_ext -1 and a 36-entry score table whose ACGTN x ACGTN block holds 0 and -1 only."""
+    return gap_open == 0 and gap_ext == -1 and all(table[a * 6 + b] in (0, -1) for a in range(5) for b in range(5))
+
+
 READ_UNALIGNED = 16     # RG_READ_UNALIGNED: status bit of that mode — the read has no local alignment, and no record
 
 

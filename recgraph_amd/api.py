@@ -49,6 +49,11 @@ MODE_GAP_LOCAL_POA = 3
 # _XSTRANDS
 globals().update(_lib.GAP_MODE_NAMES)
 
+# pathwise alignment at unit costs by Myers' bit-vector recurrence (RG_MODE_PATHWISE_EDIT / RG_MODE_PATHWISE_EDIT_SEMI): the bytes of
+# MODE_PATHWISE_GAP_LONG / MODE_PATHWISE_GAP_SEMI_LONG for gap costs (0, -1) and a 0 / -1 matrix, anything else is refused
+MODE_PATHWISE_EDIT = _lib.MODE_PATHWISE_EDIT
+MODE_PATHWISE_EDIT_SEMI = _lib.MODE_PATHWISE_EDIT_SEMI
+
 READ_BAND_WARNING, READ_BAND_NOT_ENOUGH, READ_WOULD_PANIC, READ_BAD_BASE = 1, 2, 4, 8
 READ_UNALIGNED = _lib.READ_UNALIGNED
 
@@ -65,6 +70,8 @@ PATHWISE_GAP_STRANDS_MODES = _lib.gap_family_modes("_STRANDS")
 PATHWISE_GAP_XLONG_MODES = _lib.gap_family_modes("_XLONG")
 # ... except through these: both strands is the mode itself again, so ``both_strands=True`` is redundant there
 PATHWISE_GAP_XSTRANDS_MODES = _lib.gap_family_modes("_XSTRANDS")
+# unit costs, the reads as given, up to 16383 bases
+PATHWISE_EDIT_MODES = (MODE_PATHWISE_EDIT, MODE_PATHWISE_EDIT_SEMI)
 
 
 def _both_strands_kw(mode, both_strands, kw, strand_vote=False):
@@ -74,6 +81,8 @@ def _both_strands_kw(mode, both_strands, kw, strand_vote=False):
     if not both_strands and not strand_vote:
         return kw
     flag = "strand_vote" if strand_vote else "both_strands"
+    if _lib.edit_mode(mode):
+        raise _lib.RecGraphError(-1, _lib.EDIT_STRANDS_REFUSAL % flag)
     gm = _lib.gap_mode(mode)
     if gm and not gm.family.both_strands:
         raise _lib.RecGraphError(-1, gm.family.api_refusal % flag)
@@ -895,6 +904,15 @@ def pathwise_alignment_gap_local_exec(sequence, graph, score_matrix=None, o=-4, 
     read against a piece of one path; query_start / query_end of the GAFStruct say which piece of the read.  A read without a
     local alignment (READ_UNALIGNED) raises, like a read with a bad base."""
     _, text = _single(graph, "".join(sequence[1:]), "Temp", _gap_exec_mode(MODE_PATHWISE_GAP_LOCAL, long_reads, both_strands, very_long_reads, very_long_both_strands), 1, score_matrix=score_matrix, o=o, e=e)
+    return GAFStruct.from_line(text.rstrip("\n"))
+
+
+def pathwise_alignment_edit_exec(sequence, graph, semi=False, score_matrix=None):
+    """-m 44 (``semi=True``: -m 45): ``pathwise_alignment_gap_exec(..., o=0, e=-1, long_reads=True)`` (``..._semi_exec``) for a 0 / -1
+    matrix, computed by the bit-vector kernels: one cell per bit, reads of up to 16383 bases.  The default matrix is match 0, mismatch -1;
+    any matrix whose ACGTN x ACGTN entries are 0 or -1 is taken (an N that matches N, for one), every other one is refused."""
+    sm = score_matrix if score_matrix is not None else create_score_matrix_i32(0, -1)
+    _, text = _single(graph, "".join(sequence[1:]), "Temp", MODE_PATHWISE_EDIT_SEMI if semi else MODE_PATHWISE_EDIT, 1, score_matrix=sm, o=0, e=-1)
     return GAFStruct.from_line(text.rstrip("\n"))
 
 

@@ -52,6 +52,10 @@ def check_mode_flags(alignment_mode, both_strands, strand_vote, amb_strand):
     """What main refuses before it opens a file: a mode that is neither 0 to 9 nor an affine-gap pathwise mode (_lib.GAP_FAMILIES), and
     --both-strands / --strand-vote where the mode has no such rule.  Returns whether ``-s true`` counts."""
     gm = _lib.gap_mode(alignment_mode)
+    if _lib.edit_mode(alignment_mode):
+        if both_strands or strand_vote:
+            raise SystemExit("--both-strands / --strand-vote are not available in modes 44 and 45: they align the reads as given")
+        return False
     if alignment_mode not in range(10) and not gm:
         raise SystemExit("Alignment mode must be in [0..9], or 12")   # main.rs:315-317; 12: local affine-gap pathwise, this project's own
     if gm and (both_strands or strand_vote):
@@ -68,13 +72,24 @@ def check_mode_flags(alignment_mode, both_strands, strand_vote, amb_strand):
     return amb
 
 
+def check_edit_scores(alignment_mode, scores, gap_open, gap_extension):
+    """Modes 44 and 45 take unit costs only: what main refuses once the score matrix is built, before it opens the graph.  ``scores``: the
+    matrix as a dict; ``gap_open`` / ``gap_extension``: -O / -E as given (positive)."""
+    if not _lib.edit_mode(alignment_mode):
+        return
+    table = [scores.get((a, b), 0) for a in "ACGTN-" for b in "ACGTN-"]
+    if not _lib.unit_costs(table, -gap_open, -gap_extension):
+        raise SystemExit(_lib.EDIT_SCORE_REFUSAL)
+
+
 def build_parser():
     p = argparse.ArgumentParser(prog="recgraph-hip", description="RecGraph DP hot path on MI355X")
     p.add_argument("sequence_path")
     p.add_argument("graph_path")
     p.add_argument("-o", "--out_file", default="standard output")
     p.add_argument("-m", "--aln-mode", type=int, default=0, dest="alignment_mode",
-                   help="0 to 9 as in the reference; " + "; ".join(f.cli_help for f in _lib.GAP_FAMILIES))
+                   help="0 to 9 as in the reference; " + "; ".join(f.cli_help for f in _lib.GAP_FAMILIES) +
+                        "; 44, 45: modes 16, 17 at unit costs (-M 0 -X 1 -O 0 -E 1 must be given) on the bit-vector kernels")
     p.add_argument("-M", "--match", type=int, default=2, dest="match_score")
     p.add_argument("-X", "--mismatch", type=int, default=4, dest="mismatch_score")
     p.add_argument("-t", "--matrix", default="none")
@@ -118,6 +133,7 @@ def main(argv=None):
         scores = api.create_score_matrix_i32(a.match_score, -a.mismatch_score)   # args_parser.rs:155
     else:
         scores = api.create_score_matrix_i32(matrix_file_path=a.matrix if a.matrix.endswith(".mtx") else a.matrix + ".mtx")
+    check_edit_scores(a.alignment_mode, scores, a.gap_open, a.gap_extension)
     g = api.Graph.from_gfa(a.graph_path)
     tp = mark("graph", tp)
     # -m IS the value of rg_params.mode, but for --scalar

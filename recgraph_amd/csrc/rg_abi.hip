@@ -361,10 +361,11 @@ int32_t rg_batch_create(const rg_graph* gc, const rg_params* p, const char* read
     const rg_graph* g = gc;
     const int mode = p->mode;
     const bool path_gap = gap_mode(mode).valid;       // (every rule in every family of rg_gap_modes.hpp)
+    const bool path_edit = edit_mode(mode).valid;     // (-m 44 / -m 45: rg_edit_modes.hpp)
     if (!(is_poa(mode) || mode == RG_MODE_PATHWISE || mode == RG_MODE_RECOMBINATION || mode == RG_MODE_PATHWISE_SEMI ||
-          mode == RG_MODE_RECOMBINATION_SEMI || path_gap))
+          mode == RG_MODE_RECOMBINATION_SEMI || path_gap || path_edit))
         return fail(RG_ERR_ARG, "unsupported mode");
-    if ((mode == RG_MODE_GAP_POA || mode == RG_MODE_GAP_LOCAL_POA || path_gap) && (p->gap_open > 0 || p->gap_ext > 0))
+    if ((mode == RG_MODE_GAP_POA || mode == RG_MODE_GAP_LOCAL_POA || path_gap || path_edit) && (p->gap_open > 0 || p->gap_ext > 0))
         return fail(RG_ERR_ARG, "gap penalties must be <= 0");
     if (is_poa(mode) && !g->h.has_lnz) return fail(RG_ERR_ARG, "graph has no LnzGraph view");
     if (!is_poa(mode) && !g->h.has_path)
@@ -385,9 +386,9 @@ int32_t rg_batch_create(const rg_graph* gc, const rg_params* p, const char* read
         return fail(RG_ERR_ARG, "RG_AMB_BOTH_STRANDS applies to the pathwise modes only: the POA modes align both strands through "
                                 "rg_stream_opts.amb_strand (`-s true`, main.rs:82,132,188,229)");
     if ((p->amb_mode & 3) && !is_poa(mode)) return fail(RG_ERR_ARG, "amb_mode bits 0 and 1 apply to the POA modes only (main.rs:82,132,188,229)");
-    if (path_gap) {
-        // what the plan of these modes refuses (amb_mode bits, reads over the family's limit, scores outside the i32 budget) is host
-        // arithmetic on the longest read: answered here, before a device is needed
+    if (path_gap || path_edit) {
+        // what the plan of these modes refuses (amb_mode bits, reads over the family's limit, scores outside the i32 budget; the
+        // edit-distance modes: anything but unit costs) is host arithmetic on the longest read: answered here, before a device is needed
         int64_t longest = 0;
         for (int64_t r = 0; r < nreads; ++r) longest = std::max<int64_t>(longest, read_off[r + 1] - read_off[r]);
         PathPlan plan;

@@ -12,6 +12,7 @@
 //     xstrands: the pipeline of the xlong family in STAGES (PathJob::stage): PICK = gap_score[_long] -> gap_pick -> gap_pick_out, run per
 //          strand; TRACE = gap_seed_pick -> the rest of the pipeline, run once (gap_xstrands/rg_gap_xstrands.hip; the stages of a batch:
 //          rg_strand_driver.hip)
+//   -m 44: edit_score(every path) -> gap_pick -> edit_dirs(picked path) -> edit_trace        (edit/rg_path_edit.hip; -m 45 likewise)
 //   -m 8:  sweep(F1: column maxima) -> seed -> thr -> sweep(R: dirs, candidates, column maxima)
 //          -> thr -> sweep(F2: dirs, candidates) -> search -> layer(F) -> layer(R) -> trace
 #include <algorithm>
@@ -25,6 +26,7 @@
 #include "gap_long/rg_path_gap_long.hpp"
 #include "gap_xlong/rg_path_gap_xlong.hpp"
 #include "gap_xstrands/rg_gap_xstrands.hpp"
+#include "edit/rg_path_edit.hpp"
 #include "rg_kernel_timer.hpp"
 #include "rg_path_kernels.hpp"
 #include "rg_path_plan.hpp"
@@ -108,6 +110,7 @@ struct Run {
     const char* sweep(const SweepArgs& sa);     // (what it launched, like the launchers: rg_launch_log.hpp)
     int enqueue_pathwise(const SweepArgs& sa, const SeedArgs& se);
     int enqueue_pathwise_gap();
+    int enqueue_pathwise_edit();
     int read_back();
     int enqueue_recombination(SweepArgs& sa, const SeedArgs& se);
     int enqueue_forward_bounded(SweepArgs& sa, const SeedArgs& se);
@@ -162,6 +165,10 @@ int ensure_tables(const HostGraph& h, PathWorkImpl& w) {
 int Run::alloc_chunk(bool* oom) {
     const size_t n = (size_t)chunk, wpad = (size_t)plan.wpad;
     int rc;
+    if (plan.edit) {
+        if ((rc = w.state.alloc(n, oom)) || (rc = w.gdirs.alloc(n * (size_t)plan.gdirs_stride, oom))) return rc;
+        return RG_OK;
+    }
     if (plan.gap) {
         // (a stage allocates what its kernels touch: plan_gap_stage counted the same buffers)
         const bool score = plan.stage != PATH_STAGE_TRACE, trace = plan.stage != PATH_STAGE_PICK;
@@ -321,6 +328,24 @@ int Run::enqueue_pathwise_gap() {
         RG_TRY(T.run("k_gap_redo_long", [&] { return launch_gap_redo_long(xa, chunk, kind, round, stream); }));
         RG_TRY(T.run(local ? "k_gap_walk_local_long" : "k_gap_walk_long", [&] { return launch_gap_walk_long(xa, chunk, kind, round, stream); }));
     }
+    return read_back();
+}
+
+// -m 44 / -m 45:  edit_score(every path) -> gap_pick -> edit_dirs(picked path) -> edit_trace -> the chunk's one read-back
+int Run::enqueue_pathwise_edit() {
+    GapArgs ga;
+    memset(&ga, 0, sizeof ga);
+    ga.sc = sc; ga.lnz = gd.lnz; ga.reads = d_reads; ga.read_off = off(); ga.bad = bad(); ga.poff = w.fpoff.p; ga.prow = w.fprow.p;
+    ga.P = h.P; ga.o = p.gap_open; ga.e = p.gap_ext; ga.state = w.state.p; ga.dirs = w.gdirs.p; ga.dirs_stride = plan.gdirs_stride;
+    ga.cells = d_cells; ga.rec = d_rec + done; ga.ops = d_ops ? d_ops + (long long)done * ops_stride : nullptr; ga.ops_stride = ops_stride;
+    const int W = plan.edit_words;
+    const bool semi = plan.semi;
+    RG_TRY(T.run("k_edit_score", [&] { return launch_edit_score(ga, chunk, W, semi, stream); }));
+    // (the pick kernel of modes 6 / 7 refuses a read of more than its width - 1 bases, a width it takes in 64s: 4096 W covers the
+    // 2048 W bases of a lane layout that has no column 0; the direction pass reports a read beyond those itself)
+    RG_TRY(T.run("k_gap_pick", [&] { return launch_gap_pick(ga, chunk, 64 * W, semi, stream); }));
+    RG_TRY(T.run("k_edit_dirs", [&] { return launch_edit_dirs(ga, chunk, W, semi, stream); }));
+    RG_TRY(T.run("k_edit_trace", [&] { return launch_edit_trace(ga, chunk, W, semi, stream); }));
     return read_back();
 }
 
@@ -504,6 +529,7 @@ int Run::read_back() {
 int Run::enqueue_chunk() {
     HIPCHK(hipMemsetAsync(w.state.p, 0, sizeof(ReadState) * chunk, stream));
     if (plan.gap) return enqueue_pathwise_gap();
+    if (plan.edit) return enqueue_pathwise_edit();
     SweepArgs sa = sweep_args();
     SeedArgs se;
     se.g = gd; se.state = w.state.p; se.nreads = chunk; se.mode = p.mode; se.sc = sc; se.reads = d_reads; se.read_off = off();

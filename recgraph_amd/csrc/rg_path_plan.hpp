@@ -75,6 +75,12 @@ struct PathPlan {
     // the xstrands family (rg_strand_driver.hip): which part of the affine-gap pipeline a job runs (PATH_STAGE_*, plan_gap_stage);
     // PATH_STAGE_ALL in every plan plan_pathwise returns
     int stage;
+    // -m 44 / -m 45 (bit-vector edit distance, edit/rg_path_edit.hip): `semi` says -m 45; one wave per (read, path) holds the whole read,
+    // edit_words (W = 1, 2, 4, 8: the smallest with max_n <= 2048 W) dwords of 32 columns per lane and bit vector; the direction pass
+    // stores 2 W dwords per lane and row (2 bits per cell) for the picked path: gdirs_stride = (rows of the longest path + 1) * 2 W * 64
+    // words, the only work buffer beside ReadState.  `gap` stays false: none of the affine-gap kernels but the pick runs
+    bool edit;
+    int edit_words;
 
     // ... with candidate lists of fcap / rcap entries and record lists of frec_cap / rrec_cap records
     size_t per_read_all(unsigned fcap_, unsigned rcap_, unsigned frec_cap_, unsigned rrec_cap_) const {
@@ -87,6 +93,10 @@ struct PathPlan {
 // spec_level: 0 = the batch itself; 1 = the reads whose speculation failed, once more with a generous margin; 2 = what fails
 // even that, with the provable bound.  RG_ERR_ARG / RG_ERR_CAPACITY (through fail()) for batches the kernels cannot take.
 int plan_pathwise(const rg_params& p, const PathPlanInput& in, const Options& opt, int spec_level, PathPlan& out);
+// The plan of the edit-distance modes (what plan_pathwise returns for -m 44 / -m 45), with every refusal of theirs: gap costs other than
+// (0, -1) or an ACGTN x ACGTN entry other than 0 / -1, an amb_mode bit, a read over 16383 bases (RG_ERR_ARG), mode 16's 2^28 budget
+// (RG_ERR_CAPACITY).  `out` must be a cleared plan
+int plan_pathwise_edit(const rg_params& p, const PathPlanInput& in, PathPlan& out);
 
 // The stages of an affine-gap pipeline (PathJob::stage, rg_path_args.hpp).  PICK: score pass + pick, and the pick goes out into the
 // job's records (status, score, path, end row; no ops).  TRACE: the picks come back in from the job's records, then the direction

@@ -3,7 +3,7 @@
 engine on other read lengths, score parameters and path counts, with the sweep kernel that ran and a parity check of a
 few reads against the oracle.  One JSON line per case.
 
-    python tools/region_bench.py [case ...]        cases: c5 x6 m3x5 hoxd70 len1500 p128 len600 gap gap_local gap_long gap_strands gap_xlong gap_xstrands (default: all but the strand cases and the six `gap` cases)
+    python tools/region_bench.py [case ...]        cases: c5 x6 m3x5 hoxd70 len1500 p128 len600 gap gap_local gap_long gap_strands gap_xlong gap_xstrands edit (default: all but the strand cases, the six `gap` cases and `edit`)
 
 The strand cases (RG_AMB_BOTH_STRANDS, config-5 shape; `reads_per_s` counts SOURCE reads): `both_strands_fwd` — option on, every
 read forward (what the option costs when nothing qualifies: compare with `c5`); `both_strands` — option on, half of the reads
@@ -50,6 +50,14 @@ reads; beside mode 82's stands the prediction (2 S + T) / (S + T) from this run'
 pick, T: the traceback).  Every read of every both-strands batch is compared with the as-given mode's line of its source read and
 with the flip; reads spread over the batch are checked against the numpy rules.  Two JSON lines per part (the first before the
 rule check, which takes minutes at 50 000 bases); RG_REGION_PART=a or b runs one part.
+
+`edit` (only when named): the bit-vector modes beside the affine-gap modes OF THE SAME BUILD at unit costs (match 0, mismatch -1, o = 0,
+e = -1 on both sides), by the protocol of `gap_long` — one process, warm-up, alternating rounds, whole rg_batch_run calls, the handle's
+kernel timer.  (a) -m 44 beside -m 16 on the 512 reads of 4000 bases and the 16-path graph of 4000-row paths of `gap_long`; (b), (c)
+-m 44 beside -m 6 on 1000-base reads at the C4 / C5 graph shapes (16 paths on 5 000 rows, 32 on 10 000).  Per part: the same texts
+(compared), time per batch, time per counted cell update, the time of every kernel, the score pass of -m 44 as a ratio to the other
+mode's per counted cell, and the work bytes per read.  Two reads of each part are checked against the rule
+(tests/pathwise_gap_rule.py at unit costs): the printed score is the rule's and the printed CIGAR re-scores to it.  One JSON line per part.
 
 Every case: TILES tiles of TILE reads through one rg_stream (3 handles), timed after one warm-up tile per handle."""
 import json
@@ -224,6 +232,67 @@ def gap_long_case():
     out["m16_over_m6_time_per_cell_median"] = round(out["m16"]["ps_per_counted_cell_update"] / out["m6"]["ps_per_counted_cell_update"], 3)
     out["rule_checked"] = 2 if ok else "FAILED"
     print(json.dumps(out), flush=True)
+
+
+def edit_case():
+    from recgraph_amd import api, synth
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import pathwise_gap_rule as R
+    unit = api.create_score_matrix_i32(0, -1)
+    table = R.default_scores(0, -1)
+    rounds = 5
+    # (part, other mode, its score kernel, rows of the graph, paths, rows of a path = read length, reads)
+    parts = (("a", api.MODE_PATHWISE_GAP_LONG, "k_gap_score_long", 12000, 16, 4000, 512), ("b", api.MODE_PATHWISE_GAP, "k_gap_score", 5000, 16, 1000, 2048),
+             ("c", api.MODE_PATHWISE_GAP, "k_gap_score", 10000, 32, 1000, 2048))
+    for part, other, other_score, grows, paths, plen, nreads in parts:
+        if os.environ.get("RG_REGION_PART", part) != part:
+            continue
+        g = synth.haplotype_graph(grows, paths, path_len=plen, seed=1234)
+        gg = api.Graph.from_gfa_text(g.gfa())
+        reads = synth.haplotype_reads(g, nreads, length=plen, seed=900, mosaic_frac=0.0)
+        modes = (api.MODE_PATHWISE_EDIT, other)
+        batch = {m: api.Batch(gg, reads, api.make_params(m, score_matrix=unit, o=0, e=-1)) for m in modes}
+        times = {m: [] for m in modes}
+        ks = {m: {} for m in modes}
+        mem = {}
+        for m in modes:
+            batch[m].run()                       # warm-up: code objects, work buffers
+        for _ in range(rounds):
+            for m in modes:                      # alternating: both modes see the same machine
+                t0 = time.perf_counter()
+                batch[m].run()
+                times[m].append(time.perf_counter() - t0)
+                for k, v in batch[m].kernel_stats().items():
+                    if k == "mem:work_bytes_per_read":
+                        mem[m] = v[0] / max(1, v[1])
+                    if not k.startswith(("host:", "mem:", "inst:")):
+                        ks[m][k] = ks[m].get(k, 0.0) + v[0] / rounds
+        for m in modes:
+            batch[m].fetch()
+        b = batch[api.MODE_PATHWISE_EDIT]
+        same = all(b.gaf_text(i, "r", 1) == batch[other].gaf_text(i, "r", 1) for i in range(nreads))
+        same = same and (b.cell_updates, b.cell_updates_performed) == (batch[other].cell_updates, batch[other].cell_updates_performed)
+        lnz, prow = R.graph_paths(gg)
+        ok = True
+        for i in (0, nreads - 1):
+            f = b.gaf_text(i, "r", 1)[:-1].split("\t")
+            mm = re.fullmatch(r"([0-9MXID]+), best path: (\d+), score: (-?\d+)", f[12])
+            last, lens = R.all_paths_last(lnz, prow, reads[i], table, 0, -1, False)
+            best = max((int(last[k, lens[k]]), -k) for k in range(paths))
+            ok = ok and mm is not None and (int(mm.group(3)), -int(mm.group(2))) == best
+            ok = ok and R.rescore(mm.group(1), f[13], reads[i], table, 0, -1)[:2] == (best[0], len(reads[i]))
+        med = {m: sorted(times[m])[rounds // 2] for m in modes}
+        out = {"case": "edit", "part": part, "rows": gg.rows, "paths": paths, "path_rows": max(len(r) for r in prow), "reads": nreads, "read_len": plen, "rounds": rounds}
+        for m in modes:
+            bm = batch[m]
+            out["m%d" % m] = {"ms_per_batch_median": round(med[m] * 1e3, 2), "ms_per_batch_min": round(min(times[m]) * 1e3, 2),
+                              "counted_cell_updates": bm.cell_updates, "ps_per_counted_cell_update": round(med[m] / bm.cell_updates * 1e12, 3),
+                              "kernel_ms_per_batch": {k: round(v, 3) for k, v in ks[m].items()}, "work_bytes_per_read": int(mem.get(m, 0))}
+        out["m44_over_m%d_time_per_batch_median" % other] = round(med[api.MODE_PATHWISE_EDIT] / med[other], 3)
+        out["k_edit_score_over_%s" % other_score] = round(ks[api.MODE_PATHWISE_EDIT]["k_edit_score"] / ks[other][other_score], 3)
+        out["same_texts_and_counters"] = bool(same)
+        out["rule_checked"] = 2 if ok else "FAILED"
+        print(json.dumps(out), flush=True)
 
 
 def gap_xlong_case():
@@ -476,6 +545,11 @@ def gap_strands_case():
 def main():
     from recgraph_amd import api, synth
     from oracle import oracle as O
+    if "edit" in sys.argv[1:]:
+        edit_case()
+        sys.argv = [a for a in sys.argv if a != "edit"]
+        if len(sys.argv) == 1:
+            return
     if "gap_xlong" in sys.argv[1:]:
         gap_xlong_case()
         sys.argv = [a for a in sys.argv if a != "gap_xlong"]
