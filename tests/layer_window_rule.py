@@ -1,6 +1,6 @@
 """What the windowed layer rebuild (recgraph_amd/csrc/layer_window/: k_layer_win<C, CW>, walked by k_trace of rg_pathwise.hip) owes,
-stated in numpy for tests/test_layer_window_rule_cpu.py and tests/test_gpu_layer_window_walks.py.  Nothing here asks the device or the
-library anything.
+stated in numpy for tests/test_layer_window_rule_cpu.py and tests/test_gpu_layer_window_walks.py.  Nothing of the rule asks the device
+or the library anything; the three names at the end are what the two GPU test modules of the window share to run a batch.
 
 The contract is the one of the kernel's header comment and of rg_layer_window.hpp, restated for the one case where the walked path
 is the alpha of every row it visits: a graph with exactly ONE path.  There the rebuilt values are plain linear-gap Needleman-Wunsch
@@ -398,3 +398,27 @@ def shape_census(scores, n, W):
                 ok += not r["falls_back"]
                 wide += (not r["falls_back"]) and r["excursion"] >= W // 4
     return fb, ok, wide
+
+
+# ---- shared by tests/test_gpu_layer_window.py and tests/test_gpu_layer_window_walks.py ----
+
+LOG = "mem:layer_window:"      # the pseudo-statistic that names the windowed kernel ("inst:" belongs to tests/kernel_matrix.py)
+
+
+def oracle_mode(oracle, mode):
+    return {4: oracle.M4_ABS, 5: oracle.M5_ABS, 8: oracle.M8_ABS, 9: oracle.M9_ABS}[mode]
+
+
+def align_windowed(gg, reads, mode, window):
+    """(texts, kernel statistics) of one batch under layer_window = `window` (0: the full-width kernels); the default is put back."""
+    from recgraph_amd import api
+    try:
+        api.set_option("layer_window", window)
+        b = api.Batch(gg, reads, api.make_params(mode))
+        b.run()
+        b.fetch()
+        texts = [b.gaf_text(i, "r", 1) for i in range(len(reads))]
+        stats = b.kernel_stats()
+    finally:
+        api.set_option("layer_window", 256)
+    return texts, stats

@@ -3,7 +3,7 @@ import random
 
 import pytest
 
-from test_ingestion_cpu import odd_gfa, renumbered
+from pathwise_support import odd_gfa, renumbered
 
 pytestmark = pytest.mark.gpu
 

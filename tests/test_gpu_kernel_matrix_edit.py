@@ -1,13 +1,14 @@
 """GPU: every instantiation of the edit-distance kernels (tests/kernel_matrix_edit.py) ran and was right.
 
-One test per entry: the entry's case is aligned with the launch log on, every read is checked against the rule (check_edit of
-tests/test_gpu_pathwise_edit.py: whole line, re-scored CIGAR, status), and EVERY batch of the case — one per side of the width's
-boundary — must have launched the entry's instantiation, and nothing but the four kernels of its (mode, W).  Cases that several entries
-share run once."""
+One test per entry: the entry's case is aligned with the launch log on (run_case of tests/kernel_matrix_checks.py), every read is
+checked against the rule (check_edit of tests/pathwise_support.py: whole line, re-scored CIGAR, status), and EVERY batch of the case —
+one per side of the width's boundary — must have launched the entry's instantiation, and nothing but the four kernels of its (mode, W).
+Cases that several entries share run once."""
 import pytest
 
 import kernel_matrix_edit as KE
-from test_gpu_pathwise_edit import EDIT_KERNELS, run_matrix_case
+from kernel_matrix_checks import run_case
+from pathwise_support import EDIT_KERNELS, check_edit, run_batch_unit
 
 pytestmark = pytest.mark.gpu
 _RESULTS = {}
@@ -17,7 +18,8 @@ _RESULTS = {}
 def test_instantiation_ran_and_matched_the_rule(name):
     cid = KE.MATRIX[name]
     case = KE.CASES[cid]
-    per_batch, coarse = run_matrix_case(cid, _RESULTS)
+    per_batch, coarse = run_case(KE, cid, _RESULTS, lambda gg, reads, case: run_batch_unit(gg, reads, case.mode),
+                                 lambda graph, reads, case, run: check_edit(graph, reads, case.mode, out=run))
     assert len(per_batch) == len(case.batches) == 2
     for b in per_batch:
         assert b.get(name, 0) >= 1, (name, cid, sorted(b.items()))

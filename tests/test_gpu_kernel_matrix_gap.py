@@ -1,47 +1,26 @@
 """GPU: every instantiation of the gap kernels (tests/kernel_matrix_gap.py) ran and was right.
 
-One test per entry: the entry's case is aligned with the launch log on, every read is checked against the rule (check_batch of
-tests/test_gpu_pathwise_gap.py: comments column, re-scored CIGAR, status), and EVERY batch of the case — one per boundary length —
-must have launched the entry's instantiation.  Cases that several entries share run once."""
+One test per entry: the entry's case is aligned with the launch log on (run_case of tests/kernel_matrix_checks.py), every read is
+checked against the rule (check_base of tests/pathwise_support.py: whole line, comments column, re-scored CIGAR, status), and EVERY
+batch of the case — one per boundary length — must have launched the entry's instantiation.  Cases that several entries share run once."""
 import pytest
 
 import kernel_matrix_gap as KG
-from test_gpu_pathwise_gap import check_batch
+from kernel_matrix_checks import run_case
+from pathwise_support import check_base
 
 pytestmark = pytest.mark.gpu
 _RESULTS = {}
 
 
-def _run_case(cid):
-    if cid in _RESULTS:
-        return _RESULTS[cid]
-    from recgraph_amd import api
-    case = KG.CASES[cid]
-    g, batches = KG.build(case)
-    gg = api.Graph.from_gfa_text(g.gfa())
-    per_batch, coarse = [], set()
-    try:
-        api.set_option("launch_log", 1)
-        for reads in batches:
-            b = api.Batch(gg, reads, api.make_params(case.mode, **case.kw))
-            b.run()
-            b.fetch()
-            assert [b.status(i) for i in range(len(reads))] == [0] * len(reads), cid
-            texts = [b.gaf_text(i, "r%d" % i, i + 1) for i in range(len(reads))]
-            stats = b.kernel_stats()
-            per_batch.append({k[5:]: v[1] for k, v in stats.items() if k.startswith("inst:")})
-            coarse |= {k for k in stats if not k.startswith("inst:")}
-            check_batch(g.gfa(), reads, case.mode == 7, texts=texts, **case.kw)
-    finally:
-        api.set_option("launch_log", 0)
-    _RESULTS[cid] = (per_batch, coarse)
-    return _RESULTS[cid]
+def _check(graph, reads, case, run):
+    check_base(graph, reads, case.mode == 7, texts=run.texts, status=run.status, **case.kw)
 
 
 @pytest.mark.parametrize("name", sorted(KG.MATRIX))
 def test_instantiation_ran_and_matched_the_rule(name):
     cid = KG.MATRIX[name]
-    per_batch, coarse = _run_case(cid)
+    per_batch, coarse = run_case(KG, cid, _RESULTS, check=_check)
     assert len(per_batch) == len(KG.CASES[cid].batches)
     for b in per_batch:
         assert b.get(name, 0) >= 1, (name, cid, sorted(b.items()))

@@ -1,19 +1,15 @@
 """GPU: every instantiation of the long-read gap kernels (tests/kernel_matrix_gap_long.py) ran and was right.
 
-One test per entry: the entry's case is aligned with the launch log on, every read is checked against the rule (check_long of
-tests/test_gpu_pathwise_gap_long.py: whole line, re-scored CIGAR, status), and EVERY batch of the case — one per boundary length —
-must have launched the entry's instantiation.  Cases that several entries share run once."""
+One test per entry: the entry's case is aligned with the launch log on (run_case of tests/kernel_matrix_checks.py), every read is
+checked against the rule (check_reads of tests/pathwise_support.py: whole line, re-scored CIGAR, status), and EVERY batch of the case —
+one per boundary length — must have launched the entry's instantiation.  Cases that several entries share run once."""
 import pytest
 
 import kernel_matrix_gap_long as KG
-from test_gpu_pathwise_gap_long import run_matrix_case
+from kernel_matrix_checks import run_case
 
 pytestmark = pytest.mark.gpu
 _RESULTS = {}
-
-
-def _run_case(cid):
-    return run_matrix_case(KG, cid, _RESULTS)
 
 
 @pytest.mark.parametrize("name", sorted(KG.MATRIX))
@@ -21,7 +17,7 @@ def test_instantiation_ran_and_matched_the_rule(name):
     cid = KG.MATRIX[name]
     mode = KG.CASES[cid].mode
     kind = (16, 17, 22).index(mode)
-    per_batch, coarse = _run_case(cid)
+    per_batch, coarse = run_case(KG, cid, _RESULTS)
     assert len(per_batch) == len(KG.CASES[cid].batches)
     for b in per_batch:
         assert b.get(name, 0) >= 1, (name, cid, sorted(b.items()))

@@ -2,13 +2,12 @@
 right.
 
 One test per entry: the entry's case is aligned with the launch log on, every read is checked against the composed rule
-(check_strands of tests/test_gpu_pathwise_gap_strands.py: whole line, status, strand and score accessors, re-scored CIGAR on the
+(check_strands of tests/pathwise_support.py: whole line, status, strand and score accessors, re-scored CIGAR on the
 chosen strand), and EVERY batch of the case must have launched the entry's instantiation — and not the gate of the other modes."""
 import pytest
 
 import kernel_matrix_gap_strands as KS
-import pathwise_gap_rule as R
-from test_gpu_pathwise_gap_strands import check_strands, run_batch
+from pathwise_support import check_strands, graph_tuple, run_batch_strands
 
 pytestmark = pytest.mark.gpu
 _RESULTS = {}
@@ -17,15 +16,12 @@ _RESULTS = {}
 def _run_case(cid):
     if cid in _RESULTS:
         return _RESULTS[cid]
-    from recgraph_amd import api
     case = KS.CASES[cid]
     g, batches = KS.build(case)
-    gg = api.Graph.from_gfa_text(g.gfa())
-    lnz, rows = R.graph_paths(gg)
-    graph = (g, gg, lnz, rows, R.graph_node_ids(gg))
+    graph = graph_tuple(g)
     per_batch = []
     for reads in batches:
-        res = run_batch(gg, reads, case.mode, log=True, **case.kw)
+        res = run_batch_strands(graph[1], reads, case.mode, log=True, **case.kw)
         check_strands(graph, reads, case.mode, res)
         per_batch.append(res)
     _RESULTS[cid] = per_batch

@@ -2,15 +2,13 @@
 right.
 
 One test per entry: the entry's case is aligned with the launch log on, every read is checked against the composed rule (check_x of
-tests/test_gpu_pathwise_gap_xstrands.py: whole line, status, strand and score accessors, re-scored CIGAR on the chosen strand, both
+tests/pathwise_support.py: whole line, status, strand and score accessors, re-scored CIGAR on the chosen strand, both
 counters), and EVERY batch of the case must have launched the entry's instantiation — the pick twice out and once in, the duel and
 the marks once — and no merge."""
 import pytest
 
 import kernel_matrix_gap_xstrands as KX
-import pathwise_gap_rule as R
-from test_gpu_pathwise_gap_strands import run_batch
-from test_gpu_pathwise_gap_xstrands import check_x
+from pathwise_support import check_x, graph_tuple, run_batch_strands
 
 pytestmark = pytest.mark.gpu
 _RESULTS = {}
@@ -20,15 +18,12 @@ LAUNCHES = {"rg::k_gap_pick_out": 2, "rg::k_gap_seed_pick": 1, "rg::k_gap_xstran
 def _run_case(cid):
     if cid in _RESULTS:
         return _RESULTS[cid]
-    from recgraph_amd import api
     case = KX.CASES[cid]
     g, batches = KX.build(case)
-    gg = api.Graph.from_gfa_text(g.gfa())
-    lnz, rows = R.graph_paths(gg)
-    graph = (g, gg, lnz, rows, R.graph_node_ids(gg))
+    graph = graph_tuple(g)
     per_batch = []
     for reads in batches:
-        res = run_batch(gg, reads, case.mode, log=True, **case.kw)
+        res = run_batch_strands(graph[1], reads, case.mode, log=True, **case.kw)
         check_x(graph, reads, case.mode, res)
         per_batch.append(res)
     _RESULTS[cid] = per_batch

@@ -17,9 +17,9 @@ import numpy as np
 import pytest
 
 import kernel_matrix_layer_window as KW
+from layer_window_rule import LOG, align_windowed as _gpu, oracle_mode as _omode
 
 pytestmark = pytest.mark.gpu
-LOG = "mem:layer_window:"      # the pseudo-statistic that names the windowed kernel ("inst:" belongs to tests/kernel_matrix.py)
 _ORACLE = {}      # (graph key, oracle mode, read) -> text with name "r", index 1
 _RESULTS = {}
 
@@ -28,10 +28,6 @@ def _graph(key):
     from recgraph_amd import synth
     rows, paths, plen, seed = key
     return synth.haplotype_graph(rows, paths, path_len=plen, seed=seed)
-
-
-def _omode(oracle, mode):
-    return {4: oracle.M4_ABS, 5: oracle.M5_ABS, 8: oracle.M8_ABS, 9: oracle.M9_ABS}[mode]
 
 
 def _subst(rng, s, rate=0.01):
@@ -74,20 +70,6 @@ def indel_reads(g, count, length, seed, indel=100):
         s = p[:cut] + (p[cut + indel:] if i % 2 == 0 else _rand(rng, indel) + p[cut:])
         out.append(_subst(rng, _fit(rng, s, length), 0.005))
     return out
-
-
-def _gpu(gg, reads, mode, window):
-    from recgraph_amd import api
-    try:
-        api.set_option("layer_window", window)
-        b = api.Batch(gg, reads, api.make_params(mode))
-        b.run()
-        b.fetch()
-        texts = [b.gaf_text(i, "r", 1) for i in range(len(reads))]
-        stats = b.kernel_stats()
-    finally:
-        api.set_option("layer_window", 256)
-    return texts, stats
 
 
 def _check(oracle, gkey, reads, mode, window, want_full=None):

@@ -18,7 +18,7 @@ import numpy as np
 import pytest
 
 import layer_window_rule as R
-from test_gpu_layer_window import LOG, _gpu, _omode
+from layer_window_rule import LOG, align_windowed as _gpu, oracle_mode as _omode
 
 pytestmark = pytest.mark.gpu
 FULL = "mem:layer_full_reads"

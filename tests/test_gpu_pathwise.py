@@ -4,6 +4,8 @@ import os
 
 import pytest
 
+from pathwise_support import DIAMOND, TWO_BUBBLES
+
 pytestmark = pytest.mark.gpu
 SLOW = os.environ.get("RG_SLOW_TESTS", "0") not in ("", "0")      # the long variants of the trimmed tests
 
@@ -16,13 +18,6 @@ def _switch(var, on):
     from recgraph_amd import api
     api.set_option({"RG_SWEEP_I32": "sweep_i32", "RG_NO_FREC": "no_frec", "RG_THREE_SWEEPS": "three_sweeps", "RG_LAYER_I32": "layer_i32"}[var], on)
 
-
-
-DIAMOND = ("H\tVN:Z:1.0\nS\t1\tA\nS\t2\tT\nS\t3\tC\nS\t4\tG\nL\t1\t+\t2\t+\t0M\nL\t1\t+\t3\t+\t0M\nL\t2\t+\t4\t+\t0M\n"
-           "L\t3\t+\t4\t+\t0M\nP\tp0\t1+,2+,4+\t*\nP\tp1\t1+,3+,4+\t*\n")
-TWO_BUBBLES = ("S\t1\tA\nS\t2\tT\nS\t3\tC\nS\t4\tG\nS\t5\tA\nS\t6\tC\nS\t7\tT\n" +
-               "".join(f"L\t{a}\t+\t{b}\t+\t0M\n" for a, b in [(1, 2), (1, 3), (2, 4), (3, 4), (4, 5), (4, 6), (5, 7), (6, 7)]) +
-               "P\tp0\t1+,2+,4+,5+,7+\t*\nP\tp1\t1+,3+,4+,6+,7+\t*\n")
 
 
 def _check(oracle, gfa, reads, mode, omode, names=None, **kw):

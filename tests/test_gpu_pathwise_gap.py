@@ -1,8 +1,8 @@
 """-m 6 / -m 7 (pathwise alignment with affine gaps) on the GPU against the rule of tests/pathwise_gap_rule.py.
 
-Every read is checked three ways (check_batch): (a) the whole line equals the line built from the rule's record — path string, path
-length, start and end derived from (best path, end row, ops) as the walkers do — and, where -m 4 walks the same rows (same CIGAR,
-path and bases), also -m 4's line with the comments column replaced;
+Every read is checked three ways (check_base of tests/pathwise_support.py): (a) the whole line equals the line built from the rule's
+record — path string, path length, start and end derived from (best path, end row, ops) as the walkers do — and, where -m 4 walks the
+same rows (same CIGAR, path and bases), also -m 4's line with the comments column replaced;
 (b) the printed CIGAR, re-scored against the printed path bases with o, e and the matrix, gives exactly the printed score and
 consumes the whole read (and, in -m 6, the whole path) — true whatever the tie rules; (c) the status is 0."""
 import os
@@ -11,62 +11,19 @@ import re
 import numpy as np
 import pytest
 
-import pathwise_gap_rule as R
-from test_gpu_pathwise import DIAMOND, TWO_BUBBLES
+from pathwise_support import DIAMOND, TWO_BUBBLES, check_base, rand_bases
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _rand(rng, n, alphabet="ACGT"):
-    return "".join(alphabet[int(x)] for x in rng.integers(0, len(alphabet), size=n))
-
-
-def check_batch(gfa, reads, semi, scores=None, o=-4, e=-2, texts=None):
-    """Aligns `reads` in -m 6 / -m 7 (or takes `texts`) and checks every read; returns the texts."""
-    from recgraph_amd import api
-    g = api.Graph.from_gfa_text(gfa)
-    lnz, rows = R.graph_paths(g)
-    node_ids = R.graph_node_ids(g)
-    names = ["r%d" % i for i in range(len(reads))]
-    mode = api.MODE_PATHWISE_GAP_SEMI if semi else api.MODE_PATHWISE_GAP
-    table = None if scores is None else api._table_from_dict(scores)
-    if texts is None:
-        texts, status = api.align_batch(g, reads, names, mode=mode, score_matrix=scores, o=o, e=e)
-        assert status == [0] * len(reads), status                                                   # (c)
-    m4, _ = api.align_batch(g, reads, names, mode=api.MODE_PATHWISE_SEMI if semi else api.MODE_PATHWISE, score_matrix=scores)
-    whole = 0
-    for i, rd in enumerate(reads):
-        n = len(rd)
-        assert texts[i].endswith("\n"), (i, texts[i][-100:])
-        f = texts[i][:-1].split("\t")
-        assert f[:5] == ["r%d" % i, str(n), "0", str(n - 1), "+"] and f[9:12] == ["0", "*", "*"], (i, f[:12])
-        exp = R.comments(lnz, rows, rd, table, o, e, semi)
-        assert "\t".join(f[12:]) == exp, (i, rd[:60], "\t".join(f[12:])[-300:], exp[-300:])          # (a)
-        whole_exp = R.line(lnz, rows, node_ids, "r%d" % i, rd, table, o, e, semi)
-        assert texts[i] == whole_exp, (i, rd[:60], f[:12], whole_exp.split("\t")[:12])
-        mm = re.fullmatch(r"([0-9MXID]+), best path: (\d+), score: (-?\d+)", f[12])
-        cigar, k, score, pseq = mm.group(1), int(mm.group(2)), int(mm.group(3)), f[13]
-        f4 = m4[i][:-1].split("\t")
-        if f4[12].split(", score")[0] == f[12].split(", score")[0] and f4[13] == pseq:
-            assert f[:12] == f4[:12], (i, f[:12], f4[:12])
-            whole += 1
-        got, ri, pi = R.rescore(cigar, pseq, rd, table, o, e)                                        # (b)
-        assert (got, ri) == (score, n), (i, got, score, ri, n)
-        if not semi:
-            assert pseq == "".join(lnz[r] for r in rows[k]), (i, k)
-        else:
-            assert pseq in "".join(lnz[r] for r in rows[k]) and pi == len(pseq)
-    return texts, whole
-
-
 def test_hand_checked_results():
-    t, _ = check_batch(DIAMOND, ["ATG"], False)
+    t, _ = check_base(DIAMOND, ["ATG"], False)
     assert t[0] == "r0\t3\t0\t2\t+\t>1>2>4\t3\t0\t2\t0\t*\t*\t3M, best path: 0, score: 6\tATG\n"
-    t, _ = check_batch(TWO_BUBBLES, ["ATGCT", "ATGGGAT"], False)
+    t, _ = check_base(TWO_BUBBLES, ["ATGCT", "ATGGGAT"], False)
     assert t[0] == "r0\t5\t0\t4\t+\t>1>2>4>5>7\t5\t0\t4\t0\t*\t*\t3M1X1M, best path: 0, score: 4\tATGAT\n"
     assert t[1].split("\t")[12:] == ["2M2D3M, best path: 0, score: 2", "ATGAT\n"]
-    t, _ = check_batch(TWO_BUBBLES, ["T"], True)
+    t, _ = check_base(TWO_BUBBLES, ["T"], True)
     assert t[0].split("\t")[5] == ">2" and t[0].split("\t")[12:] == ["1M, best path: 0, score: 2", "T\n"]
 
 
@@ -74,14 +31,14 @@ def test_hand_checked_results():
 def test_small_graphs(semi):
     rng = np.random.default_rng(3)
     for gfa in (DIAMOND, TWO_BUBBLES):
-        reads = [_rand(rng, int(rng.integers(1, 9))) for _ in range(40)] + ["A", "N", "ANG", "TTTTTTTT"]
-        _, whole = check_batch(gfa, reads, semi)
+        reads = [rand_bases(rng, int(rng.integers(1, 9))) for _ in range(40)] + ["A", "N", "ANG", "TTTTTTTT"]
+        _, whole = check_base(gfa, reads, semi)
         assert whole >= 1
 
 
 @pytest.mark.parametrize("semi", [False, True])
 def test_example_data(example_gfa, example_reads, semi):
-    check_batch(example_gfa, example_reads[1], semi)
+    check_base(example_gfa, example_reads[1], semi)
 
 
 @pytest.mark.parametrize("P", [1, 2, 64, 65, 256])
@@ -99,15 +56,15 @@ def test_path_counts_and_identical_paths(P):
     rng = np.random.default_rng(P)
     picks = sorted({0, P - 1, 3 % P, 40 % P, 17 % P})
     walks = [g.path_sequence(k) for k in picks]
-    reads = walks + [w[:len(w) // 2] + _rand(rng, 5) + w[len(w) // 2 + 3:] for w in walks]
-    texts, _ = check_batch(g.gfa(), reads, False)
+    reads = walks + [w[:len(w) // 2] + rand_bases(rng, 5) + w[len(w) // 2 + 3:] for w in walks]
+    texts, _ = check_base(g.gfa(), reads, False)
     for k, t in zip(picks, texts):
         best = int(re.search(r"best path: (\d+)", t).group(1))
         seqs = [g.path_sequence(q) for q in range(P)]
         assert best == seqs.index(seqs[k]), (k, best)
     # -m 7: substrings from the middle of a walk
     mids = [w[len(w) // 3: len(w) // 3 + 25] for w in walks] + [w[-12:] for w in walks]
-    check_batch(g.gfa(), mids, True)
+    check_base(g.gfa(), mids, True)
 
 
 def _haplotype():
@@ -122,7 +79,7 @@ def test_both_sides_of_every_column_count(semi):
     g = _haplotype()
     for n in (63, 64, 255, 256, 511, 512, 1023, 1024, 2047):
         k = n % 4
-        check_batch(g.gfa(), [(g.path_sequence(k) * (n // 100 + 1))[:n]], semi)
+        check_base(g.gfa(), [(g.path_sequence(k) * (n // 100 + 1))[:n]], semi)
 
 
 def test_mixed_lengths_long_runs_and_flat_reads():
@@ -130,16 +87,16 @@ def test_mixed_lengths_long_runs_and_flat_reads():
     rng = np.random.default_rng(8)
     w = g.path_sequence(2)
     reads = [w[:5], (w * 8)[:1000],                                      # 5 and 1000 bases in one batch
-             w[:70] + _rand(rng, 200) + w[70:],                          # 200 inserted bases: an L run that crosses lanes
+             w[:70] + rand_bases(rng, 200) + w[70:],                          # 200 inserted bases: an L run that crosses lanes
              "A" * 90, "N" * 40, "T", w[:40] + "N" * 10 + w[50:]]
-    check_batch(g.gfa(), reads, False)
-    check_batch(g.gfa(), reads, True)
+    check_base(g.gfa(), reads, False)
+    check_base(g.gfa(), reads, True)
     # a read that lacks 200 path rows (a U run): on a graph whose paths are longer than that
     from recgraph_amd import synth
     big = synth.haplotype_graph(1200, 3, path_len=400, seed=22)
     v = big.path_sequence(1)
-    check_batch(big.gfa(), [v[:100] + v[300:], v[:100] + v[300:350]], False)
-    check_batch(big.gfa(), [v[:100] + v[300:350]], True)
+    check_base(big.gfa(), [v[:100] + v[300:], v[:100] + v[300:350]], False)
+    check_base(big.gfa(), [v[:100] + v[300:350]], True)
 
 
 @pytest.mark.parametrize("oe", [(-4, -2), (0, -2), (-6, 0), (-40, -1)])
@@ -147,9 +104,9 @@ def test_gap_costs(oe):
     g = _haplotype()
     rng = np.random.default_rng(5)
     w = g.path_sequence(1)
-    reads = [w, w[:30] + w[45:], w[:60] + _rand(rng, 12) + w[60:], w[:20] + w[22:90] + "ACG" + w[90:], _rand(rng, 50)]
+    reads = [w, w[:30] + w[45:], w[:60] + rand_bases(rng, 12) + w[60:], w[:20] + w[22:90] + "ACG" + w[90:], rand_bases(rng, 50)]
     for semi in (False, True):
-        check_batch(g.gfa(), reads, semi, o=oe[0], e=oe[1])
+        check_base(g.gfa(), reads, semi, o=oe[0], e=oe[1])
 
 
 def test_hoxd70():
@@ -158,9 +115,9 @@ def test_hoxd70():
     g = _haplotype()
     rng = np.random.default_rng(6)
     w = g.path_sequence(3)
-    reads = [w, w[:50] + w[70:], w[:80] + _rand(rng, 9) + w[80:], _rand(rng, 130), w[:30] + "N" + w[31:]]
+    reads = [w, w[:50] + w[70:], w[:80] + rand_bases(rng, 9) + w[80:], rand_bases(rng, 130), w[:30] + "N" + w[31:]]
     for semi in (False, True):
-        check_batch(g.gfa(), reads, semi, scores=sc, o=-400, e=-30)
+        check_base(g.gfa(), reads, semi, scores=sc, o=-400, e=-30)
 
 
 def test_bad_base_and_cells():
@@ -179,11 +136,11 @@ def test_stream_and_multi_give_the_batch_text():
     from recgraph_amd import api
     g = _haplotype()
     rng = np.random.default_rng(9)
-    reads = [g.path_sequence(i % 4)[: 20 + 9 * i] for i in range(12)] + [_rand(rng, 300)]
+    reads = [g.path_sequence(i % 4)[: 20 + 9 * i] for i in range(12)] + [rand_bases(rng, 300)]
     names = ["r%d" % i for i in range(len(reads))]
     gg = api.Graph.from_gfa_text(g.gfa())
     for mode, semi in ((api.MODE_PATHWISE_GAP, False), (api.MODE_PATHWISE_GAP_SEMI, True)):
-        texts, _ = check_batch(g.gfa(), reads, semi)
+        texts, _ = check_base(g.gfa(), reads, semi)
         st, status = api.align_stream(gg, reads, names, mode=mode, device_ids=[0], handles_per_device=2, tile_reads=5)
         assert st == texts and status == [0] * len(reads)
         mt, status = api.align_batch_multi(gg, reads, names, mode=mode, device_ids=[0])

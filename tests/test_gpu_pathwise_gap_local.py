@@ -1,7 +1,7 @@
 """-m 12 (local pathwise alignment with affine gaps) on the GPU against the rule of tests/pathwise_gap_local_rule.py.
 
-Every read is checked three ways (check_batch): (a) the whole line equals the line built from the rule's record — query start and
-end, path string, path length, start and end — and is empty for a read the rule leaves unaligned; (b) the printed CIGAR, re-scored
+Every read is checked three ways (check_local of tests/pathwise_support.py): (a) the whole line equals the line built from the rule's
+record — query start and end, path string, path length, start and end — and is empty for a read the rule leaves unaligned; (b) the printed CIGAR, re-scored
 against the printed path bases and the read slice [query start, query end] with o, e and the matrix, gives exactly the printed
 score and consumes exactly that slice — true whatever the tie rules; (c) the status is 0, or RG_READ_UNALIGNED where the rule finds
 no local alignment.  Every aligned read also scores > 0 and at least what -m 7 gives the same read."""
@@ -11,63 +11,24 @@ import re
 import numpy as np
 import pytest
 
-import pathwise_gap_local_rule as L
-import pathwise_gap_rule as R
-from test_gpu_pathwise import DIAMOND, TWO_BUBBLES
+from pathwise_support import DIAMOND, NO_G, TWO_BUBBLES, check_local, rand_bases
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NO_G = "S\t1\tA\nS\t2\tC\nS\t3\tT\nS\t4\tA\nL\t1\t+\t2\t+\t0M\nL\t2\t+\t3\t+\t0M\nL\t3\t+\t4\t+\t0M\nP\tp0\t1+,2+,3+,4+\t*\n"
-
-
-def _rand(rng, n, alphabet="ACGT"):
-    return "".join(alphabet[int(x)] for x in rng.integers(0, len(alphabet), size=n))
-
-
-def check_batch(gfa, reads, scores=None, o=-4, e=-2, texts=None, status=None):
-    """Aligns `reads` in -m 12 (or takes `texts` and `status`) and checks every read; returns (texts, status)."""
-    from recgraph_amd import api
-    g = api.Graph.from_gfa_text(gfa)
-    lnz, rows = R.graph_paths(g)
-    node_ids = R.graph_node_ids(g)
-    names = ["r%d" % i for i in range(len(reads))]
-    table = None if scores is None else api._table_from_dict(scores)
-    if texts is None:
-        texts, status = api.align_batch(g, reads, names, mode=api.MODE_PATHWISE_GAP_LOCAL, score_matrix=scores, o=o, e=e)
-    m7, st7 = api.align_batch(g, reads, names, mode=api.MODE_PATHWISE_GAP_SEMI, score_matrix=scores, o=o, e=e)
-    assert st7 == [0] * len(reads)
-    for i, rd in enumerate(reads):
-        n = len(rd)
-        exp = L.line_local(lnz, rows, node_ids, "r%d" % i, rd, table, o, e)
-        assert texts[i] == exp, (i, rd[:60], texts[i].split("\t")[:12], exp.split("\t")[:12], texts[i][-200:], exp[-200:])      # (a)
-        assert status[i] == (0 if exp else api.READ_UNALIGNED), (i, status[i])                                       # (c)
-        if not exp:
-            continue
-        f = texts[i][:-1].split("\t")
-        qs, qe = int(f[2]), int(f[3])
-        assert f[0] == "r%d" % i and f[1] == str(n) and 0 <= qs <= qe <= n - 1 and f[4] == "+" and f[9:12] == ["0", "*", "*"], (i, f[:12])
-        mm = re.fullmatch(r"([0-9MXID]+), best path: (\d+), score: (-?\d+)", f[12])
-        cigar, k, score, pseq = mm.group(1), int(mm.group(2)), int(mm.group(3)), f[13]
-        got, ri, pi = L.rescore(cigar, pseq, rd, qs, qe, table, o, e)                                                 # (b)
-        assert (got, ri, pi) == (score, qe - qs + 1, len(pseq)), (i, got, score, ri, pi, qs, qe)
-        assert pseq in "".join(lnz[r] for r in rows[k])
-        score7 = int(re.search(r"score: (-?\d+)", m7[i]).group(1))
-        assert score > 0 and score >= score7, (i, score, score7)
-    return texts, status
 
 
 def test_hand_checked_lines():
-    t, st = check_batch(DIAMOND, ["CCATGCC", "ATG", "NNN", "G", "TTCGTT"])
+    t, st = check_local(DIAMOND, ["CCATGCC", "ATG", "NNN", "G", "TTCGTT"])
     assert t[0] == "r0\t7\t2\t4\t+\t>1>2>4\t3\t0\t2\t0\t*\t*\t3M, best path: 0, score: 6\tATG\n"
     assert t[1] == "r1\t3\t0\t2\t+\t>1>2>4\t3\t0\t2\t0\t*\t*\t3M, best path: 0, score: 6\tATG\n"
     assert t[2] == "" and t[3].split("\t")[12] == "1M, best path: 0, score: 2"
     assert t[4] == "r4\t6\t2\t3\t+\t>3>4\t2\t0\t1\t0\t*\t*\t2M, best path: 1, score: 4\tCG\n"
     assert st == [0, 0, 16, 0, 0]
-    t, _ = check_batch(TWO_BUBBLES, ["GGATGATCC", "A", "AA"])
+    t, _ = check_local(TWO_BUBBLES, ["GGATGATCC", "A", "AA"])
     assert t[0] == "r0\t9\t2\t6\t+\t>1>2>4>5>7\t5\t0\t4\t0\t*\t*\t5M, best path: 0, score: 10\tATGAT\n"
     assert t[2].split("\t")[2:4] == ["0", "0"]              # the smallest column of the tie
     sc = _scores(5, -4)
-    t, _ = check_batch(TWO_BUBBLES, ["CCATGGATCC"], scores=sc)
+    t, _ = check_local(TWO_BUBBLES, ["CCATGGATCC"], scores=sc)
     assert t[0].split("\t")[2:4] == ["2", "7"] and t[0].split("\t")[12:] == ["2M1D3M, best path: 0, score: 19", "ATGAT\n"]
 
 
@@ -79,8 +40,8 @@ def _scores(m, x):
 def test_small_graphs():
     rng = np.random.default_rng(3)
     for gfa in (DIAMOND, TWO_BUBBLES):
-        reads = [_rand(rng, int(rng.integers(1, 9))) for _ in range(40)] + ["A", "N", "ANG", "TTTTTTTT", "NNNNN"]
-        check_batch(gfa, reads)
+        reads = [rand_bases(rng, int(rng.integers(1, 9))) for _ in range(40)] + ["A", "N", "ANG", "TTTTTTTT", "NNNNN"]
+        check_local(gfa, reads)
 
 
 def _haplotype():
@@ -93,15 +54,15 @@ def test_overhangs_and_exact_substrings():
     g = _haplotype()
     rng = np.random.default_rng(4)
     w, v = g.path_sequence(1), g.path_sequence(3)
-    reads = [_rand(rng, 50) + w[20:120], w[20:120] + _rand(rng, 50), _rand(rng, 50) + v[10:140] + _rand(rng, 50), _rand(rng, 50) + w + _rand(rng, 50)]
-    t, _ = check_batch(g.gfa(), reads)
+    reads = [rand_bases(rng, 50) + w[20:120], w[20:120] + rand_bases(rng, 50), rand_bases(rng, 50) + v[10:140] + rand_bases(rng, 50), rand_bases(rng, 50) + w + rand_bases(rng, 50)]
+    t, _ = check_local(g.gfa(), reads)
     # the flanks are clipped (a few flank bases may join the alignment by chance: the rule above decides, this only says "clipped")
     q = [(int(x.split("\t")[2]), int(x.split("\t")[3])) for x in t]
     assert q[0][0] >= 40 and q[0][1] == len(reads[0]) - 1 and q[1][0] == 0 and q[1][1] <= 120, q
     assert q[2][0] >= 40 and q[2][1] <= len(reads[2]) - 41 and q[3][0] >= 40 and q[3][1] <= len(reads[3]) - 41, q
     # an exact substring of a path: the -m 7 line, byte for byte
     subs = [w[30:90], v[:40], v[100:], w, w[75:76]]
-    t, st = check_batch(g.gfa(), subs)
+    t, st = check_local(g.gfa(), subs)
     m7, _ = api.align_batch(api.Graph.from_gfa_text(g.gfa()), subs, ["r%d" % i for i in range(len(subs))], mode=api.MODE_PATHWISE_GAP_SEMI)
     assert t == m7 and st == [0] * len(subs)
 
@@ -113,11 +74,11 @@ def test_long_runs_that_cross_lanes():
     big = synth.haplotype_graph(1200, 3, path_len=400, seed=22)
     rng = np.random.default_rng(8)
     v = big.path_sequence(1)
-    reads = [v[:100] + _rand(rng, 200) + v[100:220], v[:100] + v[300:], _rand(rng, 30) + v[50:120] + v[320:390] + _rand(rng, 30)]
-    t, _ = check_batch(big.gfa(), reads, o=-6, e=0)
+    reads = [v[:100] + rand_bases(rng, 200) + v[100:220], v[:100] + v[300:], rand_bases(rng, 30) + v[50:120] + v[320:390] + rand_bases(rng, 30)]
+    t, _ = check_local(big.gfa(), reads, o=-6, e=0)
     assert re.search(r"\d{3}D", t[0].split("\t")[12]) and re.search(r"\d{3}I", t[1].split("\t")[12]), [x.split("\t")[12][:80] for x in t]
     # the default costs drop the gap and keep one flank
-    check_batch(big.gfa(), reads)
+    check_local(big.gfa(), reads)
 
 
 def test_free_gap_opening_and_a_long_inserted_run():
@@ -128,7 +89,7 @@ def test_free_gap_opening_and_a_long_inserted_run():
     for m, e in ((100, -1), (10, -1), (100, 0)):
         sc = _scores(m, -4)
         reads = ["A" + "C" * 99 + "T", "A" + "C" * 9 + "T", "GA" + "C" * 30 + "TG"]
-        t, st = check_batch(AT, reads, scores=sc, o=0, e=e)
+        t, st = check_local(AT, reads, scores=sc, o=0, e=e)
         assert st == [0, 0, 0]
         if m == 100:
             assert t[0].split("\t")[12:] == ["1M99D1M, best path: 0, score: %d" % (200 + 99 * e), "AT\n"], t[0]
@@ -138,7 +99,7 @@ def test_free_gap_opening_and_a_long_inserted_run():
     rng = np.random.default_rng(14)
     w = g.path_sequence(0)
     for n_ins in (200, 900):
-        check_batch(g.gfa(), [w[:60] + _rand(rng, n_ins) + w[60:120], _rand(rng, 20) + w[10:70] + _rand(rng, n_ins) + w[70:140]], scores=_scores(50, -4), o=0, e=-1)
+        check_local(g.gfa(), [w[:60] + rand_bases(rng, n_ins) + w[60:120], rand_bases(rng, 20) + w[10:70] + rand_bases(rng, n_ins) + w[70:140]], scores=_scores(50, -4), o=0, e=-1)
 
 
 def test_both_sides_of_every_column_count():
@@ -147,7 +108,7 @@ def test_both_sides_of_every_column_count():
     g = _haplotype()
     for n in (63, 64, 255, 256, 511, 512, 1023, 1024, 2047):
         k = n % 4
-        check_batch(g.gfa(), [(g.path_sequence(k) * (n // 100 + 1))[:n]])
+        check_local(g.gfa(), [(g.path_sequence(k) * (n // 100 + 1))[:n]])
 
 
 @pytest.mark.parametrize("P", [1, 2, 64, 65, 256])
@@ -164,8 +125,8 @@ def test_path_counts_and_identical_paths(P):
     rng = np.random.default_rng(P)
     picks = sorted({0, P - 1, 3 % P, 40 % P, 17 % P})
     walks = [g.path_sequence(k) for k in picks]
-    reads = [_rand(rng, 9) + w + _rand(rng, 9) for w in walks] + [w[len(w) // 3: len(w) // 3 + 25] for w in walks]
-    texts, _ = check_batch(g.gfa(), reads)
+    reads = [rand_bases(rng, 9) + w + rand_bases(rng, 9) for w in walks] + [w[len(w) // 3: len(w) // 3 + 25] for w in walks]
+    texts, _ = check_local(g.gfa(), reads)
     seqs = [g.path_sequence(q) for q in range(P)]
     for k, t in zip(picks, texts):
         best = int(re.search(r"best path: (\d+)", t).group(1))
@@ -177,9 +138,9 @@ def test_gap_costs(oe):
     g = _haplotype()
     rng = np.random.default_rng(5)
     w = g.path_sequence(1)
-    reads = [w, w[:30] + w[45:], w[:60] + _rand(rng, 12) + w[60:], w[:20] + w[22:90] + "ACG" + w[90:], _rand(rng, 50),
-             _rand(rng, 20) + w[40:100] + _rand(rng, 20)]
-    check_batch(g.gfa(), reads, o=oe[0], e=oe[1])
+    reads = [w, w[:30] + w[45:], w[:60] + rand_bases(rng, 12) + w[60:], w[:20] + w[22:90] + "ACG" + w[90:], rand_bases(rng, 50),
+             rand_bases(rng, 20) + w[40:100] + rand_bases(rng, 20)]
+    check_local(g.gfa(), reads, o=oe[0], e=oe[1])
 
 
 def test_hoxd70():
@@ -188,8 +149,8 @@ def test_hoxd70():
     g = _haplotype()
     rng = np.random.default_rng(6)
     w = g.path_sequence(3)
-    reads = [w, w[:50] + w[70:], w[:80] + _rand(rng, 9) + w[80:], _rand(rng, 130), w[:30] + "N" + w[31:], _rand(rng, 40) + w[30:110] + _rand(rng, 40)]
-    check_batch(g.gfa(), reads, scores=sc, o=-400, e=-30)
+    reads = [w, w[:50] + w[70:], w[:80] + rand_bases(rng, 9) + w[80:], rand_bases(rng, 130), w[:30] + "N" + w[31:], rand_bases(rng, 40) + w[30:110] + rand_bases(rng, 40)]
+    check_local(g.gfa(), reads, scores=sc, o=-400, e=-30)
 
 
 def test_positive_n_entries_do_not_let_padding_columns_win():
@@ -203,13 +164,13 @@ def test_positive_n_entries_do_not_let_padding_columns_win():
     g = _haplotype()
     w = g.path_sequence(2)
     for n in (22, 23, 255, 256):
-        check_batch(g.gfa(), [(w * 3)[5:5 + n], (w * 3)[40:40 + n - 1] + "N"], scores=sc)
+        check_local(g.gfa(), [(w * 3)[5:5 + n], (w * 3)[40:40 + n - 1] + "N"], scores=sc)
 
 
 def test_unaligned_reads_leave_their_neighbours_alone():
     from recgraph_amd import api
     reads = ["ACTA", "GGGG", "CT", "NNNNNN", "G", "TA"]
-    t, st = check_batch(NO_G, reads)
+    t, st = check_local(NO_G, reads)
     assert st == [0, 16, 0, 16, 16, 0] and [bool(x) for x in t] == [True, False, True, False, False, True]
     g = api.Graph.from_gfa_text(NO_G)
     b = api.Batch(g, reads, api.make_params(api.MODE_PATHWISE_GAP_LOCAL))
@@ -227,8 +188,8 @@ def test_mixed_lengths():
     g = _haplotype()
     rng = np.random.default_rng(8)
     w = g.path_sequence(2)
-    reads = [w[:5], (w * 8)[:1000], "A" * 90, "N" * 40, "T", w[:40] + "N" * 10 + w[50:], _rand(rng, 300)]
-    check_batch(g.gfa(), reads)
+    reads = [w[:5], (w * 8)[:1000], "A" * 90, "N" * 40, "T", w[:40] + "N" * 10 + w[50:], rand_bases(rng, 300)]
+    check_local(g.gfa(), reads)
 
 
 def test_bad_base_cells_and_kernel_names():
@@ -250,10 +211,10 @@ def test_stream_and_multi_give_the_batch_text():
     from recgraph_amd import api
     g = _haplotype()
     rng = np.random.default_rng(9)
-    reads = [_rand(rng, 7) + g.path_sequence(i % 4)[5: 25 + 9 * i] + _rand(rng, i) for i in range(12)] + [_rand(rng, 300), "NNNN"]
+    reads = [rand_bases(rng, 7) + g.path_sequence(i % 4)[5: 25 + 9 * i] + rand_bases(rng, i) for i in range(12)] + [rand_bases(rng, 300), "NNNN"]
     names = ["r%d" % i for i in range(len(reads))]
     gg = api.Graph.from_gfa_text(g.gfa())
-    texts, status = check_batch(g.gfa(), reads)
+    texts, status = check_local(g.gfa(), reads)
     assert status[-1] == api.READ_UNALIGNED
     st, sstatus = api.align_stream(gg, reads, names, mode=api.MODE_PATHWISE_GAP_LOCAL, device_ids=[0], handles_per_device=2, tile_reads=5)
     assert [x.decode() if isinstance(x, bytes) else x for x in st] == texts and list(sstatus) == status

@@ -2,13 +2,13 @@
 tests/pathwise_gap_strands_rule.py: which strands are aligned and which record is kept by the rules of RG_AMB_BOTH_STRANDS and
 RG_AMB_STRAND_VOTE, every pass by the numpy rules of the base modes.
 
-Every read is checked the same way (check_strands): (a) the whole line equals the rule's — the forward line, or the line of the
-reverse complement with strand '-' — and is empty for a read without a record; (b) the status; (c) rg_result_fields().strand and
-rg_result_score describe the chosen record; (d) the printed CIGAR, re-scored against the printed path bases and the read ON THE
-STRAND THAT WAS CHOSEN (mode 32: its slice [query start, query end]), gives exactly the printed score.
+Every read is checked the same way (check_strands of tests/pathwise_support.py): (a) the whole line equals the rule's — the forward
+line, or the line of the reverse complement with strand '-' — and is empty for a read without a record; (b) the status; (c)
+rg_result_fields().strand and rg_result_score describe the chosen record; (d) the printed CIGAR, re-scored against the printed path
+bases and the read ON THE STRAND THAT WAS CHOSEN (mode 32: its slice [query start, query end]), gives exactly the printed score.
 
-The graphs are those of tests/test_gpu_pathwise_gap_long.py; the rule's matrices stay under rows * (n + 1) <= 1.2e7 per read."""
-import functools
+The graphs are those of tests/test_gpu_pathwise_gap_long.py (haplotype of tests/pathwise_support.py); the rule's matrices stay under
+rows * (n + 1) <= 1.2e7 per read."""
 import re
 
 import numpy as np
@@ -18,110 +18,10 @@ import pathwise_gap_local_rule as L
 import pathwise_gap_rule as R
 import pathwise_gap_strands_rule as S
 import strand_vote_rule as V
-from test_gpu_pathwise_gap_long import _graph, _noisy, _rand
+from pathwise_support import (NO_A, PALINDROME, check_strands, expect_strands, graph_tuple, haplotype, long_read, mixed_reads, noisy, rand_bases,
+                              run_batch_strands, with_bad_base, wrong_strand_read_that_scores_above_zero)
 
 pytestmark = pytest.mark.gpu
-PALINDROME = "ACGTACGT" * 4
-# no segment holds an A: AAAAAA finds nothing forward, its reverse complement TTTTTT does
-NO_A = ("S\t1\tGCTTTTTTCG\nS\t2\tC\nS\t3\tG\nS\t4\tTTCC\n" + "".join("L\t%d\t+\t%d\t+\t0M\n" % ab for ab in [(1, 2), (1, 3), (2, 4), (3, 4)]) +
-        "P\tp0\t1+,2+,4+\t*\nP\tp1\t1+,3+,4+\t*\n")
-
-
-def run_batch(gg, reads, mode, amb=None, log=False):
-    """One batch through the C accessors: texts, status, scores, strands (None: no record), kernel statistics, cell counters."""
-    from recgraph_amd import api
-    n = len(reads)
-    if log:
-        api.set_option("launch_log", 1)
-    try:
-        b = api.Batch(gg, reads, api.make_params(mode, amb=amb))
-        b.run()
-        b.fetch()
-        stats = b.kernel_stats()
-    finally:
-        if log:
-            api.set_option("launch_log", 0)
-    fields = [b.fields(i) for i in range(n)]
-    return dict(texts=[b.gaf_text(i, "r%d" % i, i + 1) for i in range(n)], status=[b.status(i) for i in range(n)],
-                score=[b.score(i) for i in range(n)], strand=[f.strand if f else None for f in fields],
-                query=[(f.query_start, f.query_end) if f else None for f in fields],
-                stats={k: v[1] for k, v in stats.items() if not k.startswith("inst:") and not k.startswith("mem:")},
-                inst={k[5:]: v[1] for k, v in stats.items() if k.startswith("inst:")}, cells=(b.cell_updates, b.cell_updates_performed))
-
-
-def expect(graph, reads, mode, kmers=None):
-    g, gg, lnz, rows, node_ids = graph
-    out = []
-    for i, rd in enumerate(reads):
-        assert max(len(r) for r in rows) * (len(rd) + 1) <= 12_000_000, "the rule would need more than ~400 MB"
-        out.append(S.expected(mode, rd, S.line_fn(mode, lnz, rows, node_ids, "r%d" % i), kmers))
-    return out
-
-
-def check_strands(graph, reads, mode, res, kmers=None, exp=None):
-    """Checks every read of the batch result `res` (run_batch) against the composed rule; returns the rule's answers."""
-    g, gg, lnz, rows, node_ids = graph
-    exp = exp or expect(graph, reads, mode, kmers)
-    for i, rd in enumerate(reads):
-        text, status, strand, passes = exp[i]
-        got = res["texts"][i]
-        assert got == text, (mode, i, len(rd), got.split("\t")[:12], text.split("\t")[:12], got[-120:], text[-120:])        # (a)
-        assert res["status"][i] == status, (mode, i, res["status"][i], status)                                               # (b)
-        if not text:
-            assert res["strand"][i] is None, (mode, i)
-            if status == S.READ_UNALIGNED:
-                assert res["score"][i] == 0
-            continue
-        f = got[:-1].split("\t")
-        assert res["strand"][i] == strand == f[4] and res["score"][i] == S.score_of(text), (mode, i, res["strand"][i], strand, res["score"][i])     # (c)
-        assert res["query"][i] == (int(f[2]), int(f[3]))
-        mm = re.fullmatch(r"([0-9MXID]+), best path: (\d+), score: (-?\d+)", f[12])
-        cigar, k, score, pseq = mm.group(1), int(mm.group(2)), int(mm.group(3)), f[13]
-        chosen = V.rc(S.canonical(rd)) if strand == "-" else S.canonical(rd)                                                 # (d)
-        n = len(rd)
-        if mode == 32:
-            qs, qe = int(f[2]), int(f[3])
-            assert 0 <= qs <= qe <= n - 1 and score > 0
-            assert L.rescore(cigar, pseq, chosen, qs, qe) == (score, qe - qs + 1, len(pseq)), (mode, i)
-        else:
-            assert f[2:4] == ["0", str(n - 1)]
-            assert R.rescore(cigar, pseq, chosen) == (score, n, len(pseq)), (mode, i)
-        assert pseq in "".join(lnz[r] for r in rows[k])
-    return exp
-
-
-def _bad(rd):
-    return rd[:len(rd) // 2] + "?" + rd[len(rd) // 2 + 1:]
-
-
-@functools.lru_cache(maxsize=None)
-def _wrong_strand_read_that_scores_above_zero():
-    """A 12- to 20-base piece of a path, given on the REVERSE strand, whose forward semiglobal score is >= 0 although its reverse
-    complement scores higher: the exact rule never looks at the other strand.  Searched with a fixed seed; the search must succeed."""
-    g, gg, lnz, rows, node_ids = _graph(300, 3)
-    rng = np.random.default_rng(2027)
-    for _ in range(400):
-        k, n = int(rng.integers(0, 3)), int(rng.integers(12, 21))
-        w = g.path_sequence(k)
-        q = int(rng.integers(0, len(w) - n))
-        rd = V.rc(w[q:q + n])
-        f, r = R.align(lnz, rows, rd, semi=True)[0], R.align(lnz, rows, V.rc(rd), semi=True)[0]
-        if f >= 0 and r > f:
-            return rd, f, r
-    raise AssertionError("no 12- to 20-base reverse-strand read scores >= 0 forward on this graph: the precondition of the case does not hold")
-
-
-@functools.lru_cache(maxsize=None)
-def mixed_reads(mode):
-    """Case 1, shared with the surfaces test."""
-    g = _graph(300, 3)[0]
-    rng = np.random.default_rng(260 + mode)
-    w = [g.path_sequence(k) for k in range(3)]
-    whole, piece = _noisy(rng, w[0]), _noisy(rng, w[1][40:190], every=41)
-    reads = [whole, piece, V.rc(whole), V.rc(piece), "A", "N" * 30, _bad(w[2][20:120]), PALINDROME, _noisy(rng, V.rc(w[2])), w[2][100:250]]
-    if mode == 27:
-        reads.append(_wrong_strand_read_that_scores_above_zero()[0])
-    return tuple(reads)
 
 
 @pytest.mark.parametrize("amb", [0, 4])
@@ -129,17 +29,17 @@ def mixed_reads(mode):
 def test_mixed_batch(mode, amb):
     """Both strands, a 1-base read, N only, a bad base (never in pass B), a reverse palindrome (a tie: '+'); amb_mode 4 is redundant."""
     from recgraph_amd import api
-    graph = _graph(300, 3)
+    graph = haplotype(300, 3)
     reads = list(mixed_reads(mode))
     assert V.rc(PALINDROME) == PALINDROME
-    res = run_batch(graph[1], reads, mode, amb=amb)
+    res = run_batch_strands(graph[1], reads, mode, amb=amb)
     exp = check_strands(graph, reads, mode, res)
     # (the 1-base read: whichever strand the rule says — globally, "T" may well beat "A")
     assert [e[2] for e in exp[:4] + exp[5:10]] == ["+", "+", "-", "-", "+", " ", "+", "-", "+"], [e[2] for e in exp]
     assert res["status"][6] == api.READ_BAD_BASE and res["texts"][6] == "" and exp[6][3] == []
     assert exp[7][3] == ["+", "-"] or mode == 27                  # (global: the palindrome scores below 0 on 300 rows, both ways alike)
     if mode == 27:
-        rd, f, r = _wrong_strand_read_that_scores_above_zero()
+        rd, f, r = wrong_strand_read_that_scores_above_zero()
         assert 12 <= len(rd) <= 20 and f >= 0 and r > f
         # the exact rule keeps the FORWARD record of this read: its reverse complement was never aligned
         assert exp[10][2:] == ("+", ["+"]) and res["strand"][10] == "+" and res["score"][10] == f
@@ -151,21 +51,21 @@ def test_mixed_batch(mode, amb):
 @pytest.mark.parametrize("mode", [26, 27])
 def test_pass_b_empty_and_pass_b_full(mode):
     """No forward score below 0: the bytes, statuses and scores of mode 16 / 17, and no merge.  Every read on the other strand: '-'."""
-    graph = _graph(300, 3)
+    graph = haplotype(300, 3)
     g, gg = graph[0], graph[1]
     rng = np.random.default_rng(mode)
     w = [g.path_sequence(k) for k in range(3)]
-    fwd = [_noisy(rng, w[k]) for k in range(3)] if mode == 26 else [_noisy(rng, w[0]), w[1][30:180], w[2][100:160], w[0][5:60]]
-    exp = expect(graph, fwd, mode)
+    fwd = [noisy(rng, w[k]) for k in range(3)] if mode == 26 else [noisy(rng, w[0]), w[1][30:180], w[2][100:160], w[0][5:60]]
+    exp = expect_strands(graph, fwd, mode)
     assert all(S.score_of(e[0]) >= 0 and e[3] == ["+"] for e in exp)
-    res = run_batch(gg, fwd, mode)
+    res = run_batch_strands(gg, fwd, mode)
     check_strands(graph, fwd, mode, res, exp=exp)
-    base = run_batch(gg, fwd, mode - 10)
+    base = run_batch_strands(gg, fwd, mode - 10)
     assert (res["texts"], res["status"], res["score"]) == (base["texts"], base["status"], base["score"])
     assert "k_strand_merge" not in res["stats"] and res["stats"]["k_strand_gate"] == 1 and res["stats"]["k_gap_score"] == 1
     assert res["cells"] == base["cells"]
     rev = [V.rc(r) for r in fwd]
-    res = run_batch(gg, rev, mode)
+    res = run_batch_strands(gg, rev, mode)
     exp = check_strands(graph, rev, mode, res)
     assert [e[2] for e in exp] == ["-"] * len(rev) and all(t.split("\t")[4] == "-" for t in res["texts"])
     # reported exactly as the reverse complement would be had it been submitted by itself in mode 16 / 17, but for the strand
@@ -177,25 +77,16 @@ def _n_ops(text):
     return sum(int(x) for x in re.findall(r"(\d+)[MXID]", text.split("\t")[12].split(",")[0]))
 
 
-@functools.lru_cache(maxsize=None)
-def _long_read():
-    """A noisy 2100-base prefix of a path of about 2200 rows: it scores above 0 in modes 26 and 27 on its own strand."""
-    g = _graph(2200)[0]
-    rd = _noisy(np.random.default_rng(3), g.path_sequence(1)[:2100], every=53)
-    assert len(rd) == 2100
-    return rd
-
-
 @pytest.mark.parametrize("mode", [26, 27])
 def test_the_passes_run_in_different_length_classes(mode):
-    graph = _graph(2200)
+    graph = haplotype(2200)
     g, gg = graph[0], graph[1]
     rng = np.random.default_rng(40 + mode)
     w = g.path_sequence(0)
-    short = [_noisy(rng, w[300 * k + 20: 300 * k + 170], every=37) for k in range(4)]
+    short = [noisy(rng, w[300 * k + 20: 300 * k + 170], every=37) for k in range(4)]
     # (a) pass A striped (the 2100-base read is on the forward strand and stays there), pass B on the base kernels
-    reads = [V.rc(short[0]), _long_read(), V.rc(short[1]), V.rc(short[2]), short[3]]
-    res = run_batch(gg, reads, mode, log=True)
+    reads = [V.rc(short[0]), long_read(), V.rc(short[1]), V.rc(short[2]), short[3]]
+    res = run_batch_strands(gg, reads, mode, log=True)
     exp = check_strands(graph, reads, mode, res)
     assert exp[1][2:] == ("+", ["+"]) and [e[2] for e in exp] == ["-", "+", "-", "-", "+"]
     assert max(len(reads[i]) for i, e in enumerate(exp) if "-" in e[3]) == 150
@@ -206,8 +97,8 @@ def test_the_passes_run_in_different_length_classes(mode):
     assert res["inst"].get("rg::k_strand_gate") == 1 and res["inst"].get("rg::k_strand_merge") == 1 and "rg::k_gap_strands_gate" not in res["inst"]
     # (b) the 2100-base read on the reverse strand: striped kernels in both passes, and a merge of more than 1024 op bytes that ends on
     # a partial 16-byte piece (more than one round per lane of k_strand_merge's copy loop)
-    reads = [short[0], V.rc(_long_read()), short[1]]
-    res = run_batch(gg, reads, mode, log=True)
+    reads = [short[0], V.rc(long_read()), short[1]]
+    res = run_batch_strands(gg, reads, mode, log=True)
     exp = check_strands(graph, reads, mode, res)
     assert exp[1][2:] == ("-", ["+", "-"])
     n_ops = _n_ops(exp[1][0])
@@ -218,13 +109,13 @@ def test_the_passes_run_in_different_length_classes(mode):
 
 def test_local_both_strands():
     from recgraph_amd import api
-    graph = _graph(300, 3)
+    graph = haplotype(300, 3)
     g, gg = graph[0], graph[1]
     rng = np.random.default_rng(32)
     w = [g.path_sequence(k) for k in range(3)]
-    flanked = [_rand(rng, 15) + _noisy(rng, w[k][40 + 10 * k: 190 + 10 * k], every=31) + _rand(rng, 15) for k in range(3)]
-    reads = [flanked[0], V.rc(flanked[1]), V.rc(flanked[2]), PALINDROME, "N" * 30, _bad(w[0][10:90]), "A", w[1][100:130]]
-    res = run_batch(gg, reads, 32, log=True)
+    flanked = [rand_bases(rng, 15) + noisy(rng, w[k][40 + 10 * k: 190 + 10 * k], every=31) + rand_bases(rng, 15) for k in range(3)]
+    reads = [flanked[0], V.rc(flanked[1]), V.rc(flanked[2]), PALINDROME, "N" * 30, with_bad_base(w[0][10:90]), "A", w[1][100:130]]
+    res = run_batch_strands(gg, reads, 32, log=True)
     exp = check_strands(graph, reads, 32, res)
     assert [e[2] for e in exp[:3]] == ["+", "-", "-"] and exp[3][2] in "+ " and exp[7][2] == "+"
     for i in range(3):
@@ -238,19 +129,17 @@ def test_local_both_strands():
     assert res["stats"]["k_gap_strands_gate"] == 1 and res["stats"]["k_gap_score_local"] == 2 and res["stats"]["k_strand_merge"] == 1
     assert res["inst"].get("rg::k_revcomp") == 1 and res["inst"].get("rg::k_strand_merge") == 1
     # amb_mode 4 is redundant
-    again = run_batch(gg, reads, 32, amb=4)
+    again = run_batch_strands(gg, reads, 32, amb=4)
     assert (again["texts"], again["status"], again["score"], again["strand"]) == (res["texts"], res["status"], res["score"], res["strand"])
 
 
 def test_local_forward_unaligned_and_reverse_aligned():
-    from recgraph_amd import api
-    gg = api.Graph.from_gfa_text(NO_A)
-    lnz, rows = R.graph_paths(gg)
+    graph = graph_tuple(NO_A)
+    gg, lnz, rows = graph[1:4]
     assert "A" not in "".join(lnz[r] for pr in rows for r in pr)
-    graph = (None, gg, lnz, rows, R.graph_node_ids(gg))
     reads = ["AAAAAA", "TTTTTT", "AAAA"]
     assert L.align_local(lnz, rows, "AAAAAA") is None or L.align_local(lnz, rows, "AAAAAA")[0] == 0
-    res = run_batch(gg, reads, 32)
+    res = run_batch_strands(gg, reads, 32)
     exp = check_strands(graph, reads, 32, res)
     assert [(e[1], e[2]) for e in exp] == [(0, "-"), (0, "+"), (0, "-")]
     assert res["score"][:2] == [12, 12] and res["strand"] == ["-", "+", "-"] and res["status"] == [0, 0, 0]
@@ -258,14 +147,14 @@ def test_local_forward_unaligned_and_reverse_aligned():
 
 
 def test_local_gate_feeds_the_striped_pass():
-    graph = _graph(300, 3)
+    graph = haplotype(300, 3)
     g, gg = graph[0], graph[1]
     rng = np.random.default_rng(33)
     w = g.path_sequence(2)
-    long_rd = _rand(rng, 1000) + _noisy(rng, w) + _rand(rng, 2100 - 1000 - len(w))
+    long_rd = rand_bases(rng, 1000) + noisy(rng, w) + rand_bases(rng, 2100 - 1000 - len(w))
     assert len(long_rd) == 2100
     reads = [g.path_sequence(0)[30:130], V.rc(long_rd), "N" * 12]
-    res = run_batch(gg, reads, 32, log=True)
+    res = run_batch_strands(gg, reads, 32, log=True)
     exp = check_strands(graph, reads, 32, res)
     assert [e[2] for e in exp] == ["+", "-", " "]
     assert res["inst"].get("rg::k_gap_strands_gate") == 1 and res["inst"].get("rg::k_gap_score_long<2>") == 2 and "rg::k_strand_gate" not in res["inst"]
@@ -288,22 +177,22 @@ def _cells(graph, reads, mode, exp):
 
 @pytest.mark.parametrize("mode", [26, 27])
 def test_strand_vote(mode):
-    graph = _graph(300, 3)
+    graph = haplotype(300, 3)
     g, gg = graph[0], graph[1]
     rng = np.random.default_rng(120 + mode)
     w = [g.path_sequence(k) for k in range(3)]
     kmers = V.kmer_set(w)
     short = w[0][5:12]
-    good_rev = V.rc(_noisy(rng, w[0], every=61)) if mode == 26 else V.rc(w[1][40:190])
+    good_rev = V.rc(noisy(rng, w[0], every=61)) if mode == 26 else V.rc(w[1][40:190])
     chimera = w[0][100:140] + V.rc(w[1][50:200])                       # its forward piece is the shorter one: the vote sends it reverse first
-    hopeless_rev = V.rc(w[2][50:90]) + _rand(rng, 200)                  # reverse first, below 0 there: the forward strand is aligned too
-    reads = [short, good_rev, chimera, hopeless_rev, _noisy(rng, w[2]), V.rc(_noisy(rng, w[1])), "N" * 40, _bad(w[0][:80]), w[1][10:150]]
+    hopeless_rev = V.rc(w[2][50:90]) + rand_bases(rng, 200)                  # reverse first, below 0 there: the forward strand is aligned too
+    reads = [short, good_rev, chimera, hopeless_rev, noisy(rng, w[2]), V.rc(noisy(rng, w[1])), "N" * 40, with_bad_base(w[0][:80]), w[1][10:150]]
     assert V.votes(kmers, short) == (0, 0)
     vf, vr = V.votes(kmers, chimera)
     assert vr > vf > 0, (vf, vr)
     vf, vr = V.votes(kmers, hopeless_rev)
     assert vr > vf == 0
-    res = run_batch(gg, reads, mode, amb=12)
+    res = run_batch_strands(gg, reads, mode, amb=12)
     exp = check_strands(graph, reads, mode, res, kmers=kmers)
     assert exp[0][3][0] == "+"                                         # votes 0 / 0: forward first
     assert exp[1][2:] == ("-", ["-"]) and S.score_of(exp[1][0]) >= 0    # reverse first and >= 0 there: forward never aligned
@@ -313,7 +202,7 @@ def test_strand_vote(mode):
     assert res["stats"]["k_strand_vote"] == 1 and res["stats"]["k_strand_orient"] == 1 and res["stats"]["k_strand_gate"] == 1
     assert res["cells"] == _cells(graph, reads, mode, exp), (res["cells"], _cells(graph, reads, mode, exp))
     # the exact rule on the same reads runs other passes, and counts them
-    exact = run_batch(gg, reads, mode)
+    exact = run_batch_strands(gg, reads, mode)
     exp0 = check_strands(graph, reads, mode, exact)
     assert exact["cells"] == _cells(graph, reads, mode, exp0)
     assert [e[3] for e in exp0] != [e[3] for e in exp]
@@ -322,11 +211,11 @@ def test_strand_vote(mode):
 @pytest.mark.parametrize("mode", [26, 32])
 def test_stream_and_multi_give_the_batch_text(mode):
     from recgraph_amd import api
-    graph = _graph(300, 3)
+    graph = haplotype(300, 3)
     gg = graph[1]
     reads = list(mixed_reads(26))
     names = ["r%d" % i for i in range(len(reads))]
-    res = run_batch(gg, reads, mode)
+    res = run_batch_strands(gg, reads, mode)
     check_strands(graph, reads, mode, res)
     for kw in ({}, {"both_strands": True}):
         assert api.align_batch(gg, reads, names, mode=mode, **kw) == (res["texts"], res["status"])
@@ -346,7 +235,7 @@ def test_stream_and_multi_give_the_batch_text(mode):
         assert one.strand == "-" and one.to_string() == res["texts"][3].replace("r3\t", "Temp\t", 1).rstrip("\n")
         assert api.pathwise_alignment_gap_local_exec(["$"] + list(V.rc(reads[3])), gg, both_strands=True).strand == "+"
     else:
-        vote = run_batch(gg, reads, mode, amb=12)
+        vote = run_batch_strands(gg, reads, mode, amb=12)
         st, sstatus = api.align_stream(gg, reads, names, mode=mode, device_ids=[0], handles_per_device=2, tile_reads=4, strand_vote=True)
         assert list(st) == vote["texts"] and list(sstatus) == vote["status"]
         assert api.align_batch(gg, reads, names, mode=mode, strand_vote=True) == (vote["texts"], vote["status"])
@@ -356,7 +245,7 @@ def test_stream_and_multi_give_the_batch_text(mode):
 
 def test_the_cli_runs_the_modes(tmp_path, capsys):
     from recgraph_amd import api, cli
-    g, gg = _graph(300, 3)[:2]
+    g, gg = haplotype(300, 3)[:2]
     reads = [g.path_sequence(0)[20:170], V.rc(g.path_sequence(1)[20:170]), "NNNN"]
     (tmp_path / "g.gfa").write_text(g.gfa())
     (tmp_path / "r.fa").write_text("".join(">s%d\n%s\n" % (i, r) for i, r in enumerate(reads)))

@@ -9,6 +9,8 @@ import random
 
 import pytest
 
+from pathwise_support import ODD_LINKS as LINKS, ODD_SEGMENTS as S, odd_gfa, renumbered
+
 
 @pytest.fixture(scope="module")
 def rg():
@@ -16,19 +18,6 @@ def rg():
     _lib.build_library()
     import recgraph_amd
     return recgraph_amd
-
-
-S = {10: "AC", 3: "G", 7: "T", 20: "CA", 15: "TT"}
-LINKS = [(7, 20), (7, 15), (3, 10), (10, 15), (3, 7)]
-PATHS = [("p0", [3, 10, 15]), ("p1", [3, 7, 20]), ("p2", [3, 7, 15])]
-
-
-def odd_gfa(links=LINKS, seg_order=(10, 3, 7, 20, 15)):
-    out = ["H\tVN:Z:1.0"]
-    out += ["S\t%d\t%s" % (i, S[i]) for i in seg_order]
-    out += ["L\t%d\t+\t%d\t+\t0M" % l for l in links]
-    out += ["P\t%s\t%s\t*" % (n, ",".join("%d+" % i for i in st)) for n, st in PATHS]
-    return "\n".join(out) + "\n"
 
 
 def test_hand_derived_arrays(rg, oracle):
@@ -66,20 +55,6 @@ def test_line_order_rules(rg, oracle):
         want5 = [2 if a == 7 else 4 for a, b in lk if b == 15]
         assert g.dump(2) == "1:0;2:1;3:1;5:%d,%d;7:2;9:6,8;" % tuple(want5)
         assert g.dump(2) == og.dump(2) and g.dump(12) == ref.dump(12)       # PredHash does not depend on L lines at all
-
-
-def renumbered(sg, rnd):
-    """A synthetic graph with ids mapped to a random increasing sequence (gaps, still topological) and shuffled lines."""
-    ids = sorted(rnd.sample(range(1, 5 * len(sg.segments)), len(sg.segments)))
-    mp = {i: ids[k] for k, (i, _) in enumerate(sg.segments)}
-    segs = ["S\t%d\t%s" % (mp[i], s) for i, s in sg.segments]
-    links = ["L\t%d\t+\t%d\t+\t0M" % (mp[a], mp[b]) for a, b in sorted(set(sg.links))]
-    rnd.shuffle(segs)
-    rnd.shuffle(links)
-    paths = ["P\tp%d\t%s\t*" % (k, ",".join("%d+" % mp[i] for i in p)) for k, p in enumerate(sg.paths)]
-    lines = segs + links
-    rnd.shuffle(lines)                     # S and L lines interleaved
-    return "\n".join(["H\tVN:Z:1.0"] + lines + paths) + "\n"
 
 
 def test_renumbered_shuffled_graphs_match_the_oracle(rg, oracle):

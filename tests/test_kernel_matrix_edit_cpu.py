@@ -3,27 +3,16 @@
 The key set of the matrix must equal the set of `__global__` instantiations hipcc compiles from
 recgraph_amd/csrc/edit/rg_path_edit.hip (tools/kernel_resources.py report(): cross-compiled for gfx950, no GPU), and no other file of
 that directory may hold a kernel without a matrix."""
-import os
-import sys
 import time
 
 import kernel_matrix_edit as KE
 import kernel_matrix_gap_long as KG
 import pathwise_gap_rule as R
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EDIT_DIR = os.path.join(ROOT, "recgraph_amd", "csrc", "edit")
+from kernel_matrix_checks import assert_matrix_is_complete
 
 
 def test_the_matrix_has_exactly_the_compiled_instantiations():
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import kernel_resources
-    assert sorted(f for f in os.listdir(EDIT_DIR) if f.endswith(".hip")) == ["rg_path_edit.hip"]
-    names = [k["name"] for k in kernel_resources.report("edit/rg_path_edit.hip")]
-    assert len(names) == len(set(names))
-    compiled, keys = set(names), set(KE.MATRIX)
-    assert compiled == keys, {"compiled without an entry": sorted(compiled - keys), "entries without a kernel": sorted(keys - compiled)}
-    assert len(compiled) == 17
+    assert_matrix_is_complete(KE, "edit/rg_path_edit.hip", 17)
 
 
 def test_every_entry_names_a_case_and_every_width_is_reached_from_both_sides():

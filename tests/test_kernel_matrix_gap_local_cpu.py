@@ -3,26 +3,15 @@
 The key set of the matrix must equal the set of `__global__` instantiations hipcc compiles from
 recgraph_amd/csrc/gap_local/rg_path_gap_local.hip (tools/kernel_resources.py report(): cross-compiled for gfx950, no GPU), and no other
 file of that directory may hold a kernel without a matrix."""
-import os
-import sys
 import time
 
 import kernel_matrix_gap_local as KL
 import pathwise_gap_local_rule as L
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GAP_LOCAL = os.path.join(ROOT, "recgraph_amd", "csrc", "gap_local")
+from kernel_matrix_checks import assert_matrix_is_complete
 
 
 def test_the_matrix_has_exactly_the_compiled_instantiations():
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import kernel_resources
-    assert sorted(f for f in os.listdir(GAP_LOCAL) if f.endswith(".hip")) == ["rg_path_gap_local.hip"]
-    names = [k["name"] for k in kernel_resources.report("gap_local/rg_path_gap_local.hip")]
-    assert len(names) == len(set(names))
-    compiled, keys = set(names), set(KL.MATRIX)
-    assert compiled == keys, {"compiled without an entry": sorted(compiled - keys), "entries without a kernel": sorted(keys - compiled)}
-    assert len(compiled) == 10
+    assert_matrix_is_complete(KL, "gap_local/rg_path_gap_local.hip", 10)
 
 
 def test_every_entry_names_a_case():

@@ -3,27 +3,16 @@
 The key set of the matrix must equal the set of `__global__` instantiations hipcc compiles from
 recgraph_amd/csrc/gap_strands/rg_gap_strands.hip (tools/kernel_resources.py report(): cross-compiled for gfx950, no GPU), and no
 other file of that directory may hold a kernel without a matrix."""
-import os
-import sys
 import time
 
 import kernel_matrix_gap_strands as KS
 import pathwise_gap_rule as R
 import pathwise_gap_strands_rule as S
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GAP_STRANDS = os.path.join(ROOT, "recgraph_amd", "csrc", "gap_strands")
+from kernel_matrix_checks import assert_matrix_is_complete
 
 
 def test_the_matrix_has_exactly_the_compiled_instantiations():
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import kernel_resources
-    assert sorted(f for f in os.listdir(GAP_STRANDS) if f.endswith(".hip")) == ["rg_gap_strands.hip"]
-    names = [k["name"] for k in kernel_resources.report("gap_strands/rg_gap_strands.hip")]
-    assert len(names) == len(set(names))
-    compiled, keys = set(names), set(KS.MATRIX)
-    assert compiled == keys, {"compiled without an entry": sorted(compiled - keys), "entries without a kernel": sorted(keys - compiled)}
-    assert len(compiled) == 1
+    assert_matrix_is_complete(KS, "gap_strands/rg_gap_strands.hip", 1)
 
 
 def test_every_entry_names_a_case():

@@ -14,7 +14,7 @@ import pathwise_edit_rule as E
 import pathwise_gap_rule as R
 import plan_check_build
 
-from test_pathwise_gap_cpu import TWO_BUBBLES, _no_device
+from pathwise_support import TWO_BUBBLES, assert_rows_in_registers, no_device
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EDIT = (44, 45)
@@ -40,7 +40,7 @@ def _create(reads, mode, match=0, mismatch=-1, o=0, e=-1, amb=0, entries=()):
 
 @pytest.mark.parametrize("mode", EDIT)
 def test_the_edit_modes_are_admitted_before_a_device_is_needed(mode):
-    ok = -3 if _no_device() else 0
+    ok = -3 if no_device() else 0
     for n in (1, 2048, 2049, 16383):
         rc, msg = _create(["A" * n], mode)
         # (on the parent commit: RG_ERR_ARG "unsupported mode")
@@ -69,7 +69,7 @@ def test_every_refusal_comes_before_a_device_is_needed(mode, n):
     if n > 16383:
         rc, msg = _create(reads, mode)
         assert rc == -1 and "16383" in msg, (rc, msg)
-        assert _create(["ATG", "A" * 16383], mode)[0] == (-3 if _no_device() else 0)
+        assert _create(["ATG", "A" * 16383], mode)[0] == (-3 if no_device() else 0)
 
 
 def test_the_neighbours_stay_unsupported_and_the_modes_are_no_rows_of_the_gap_table():
@@ -195,14 +195,9 @@ def test_the_cli_wants_the_unit_costs_spelled_out(tmp_path):
 
 def test_the_kernels_keep_their_rows_in_registers():
     """No scratch, no spilled VGPR and no AGPR in the 17 instantiations of edit/rg_path_edit.hip; LDS: the 32 bytes of the match table."""
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import kernel_resources
-    ks = kernel_resources.report("edit/rg_path_edit.hip")
+    # the state of a lane is 7 W words (Peq of five bases, Pv, Mv) and a row step holds a handful of W more
+    cap = lambda name: 16 * (int(re.search(r"<(\d)", name).group(1)) if "<" in name else 1) + 24
+    ks = assert_rows_in_registers("edit/rg_path_edit.hip", 17, vgprs=cap, lds=32)
     want = ["rg::k_edit_%s<%d, %s>" % (k, w, s) for k in ("score", "dirs") for w in (1, 2, 4, 8) for s in ("false", "true")] + ["rg::k_edit_trace"]
     assert sorted(k["name"] for k in ks) == sorted(want) and len(ks) == 17
-    for k in ks:
-        assert k["ScratchSize [bytes/lane]"] == 0 and k["VGPRs Spill"] == 0 and k["SGPRs Spill"] == 0 and k["AGPRs"] == 0, (k["name"], k)
-        assert k["LDS Size [bytes/block]"] <= 32, (k["name"], k)
-        # the state of a lane is 7 W words (Peq of five bases, Pv, Mv) and a row step holds a handful of W more
-        w = int(re.search(r"<(\d)", k["name"]).group(1)) if "<" in k["name"] else 1
-        assert k["VGPRs"] <= 16 * w + 24, (k["name"], k["VGPRs"])
+    assert all(k["SGPRs Spill"] == 0 for k in ks), [(k["name"], k["SGPRs Spill"]) for k in ks]

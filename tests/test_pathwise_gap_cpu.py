@@ -1,23 +1,13 @@
 """CPU: the rule of -m 6 / -m 7 (tests/pathwise_gap_rule.py) against the hand-checked results and a plain scalar Gotoh, the refusals
 of rg_batch_create (answered before a device is needed), the plan's routes (tests/c/gap_plan_check.cpp), the CLI's parser and the
 registers of the new kernels."""
-import ctypes as C
-import os
-import sys
-
 import numpy as np
 import pytest
 
 import plan_check_build
 
 import pathwise_gap_rule as R
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DIAMOND = ("H\tVN:Z:1.0\nS\t1\tA\nS\t2\tT\nS\t3\tC\nS\t4\tG\nL\t1\t+\t2\t+\t0M\nL\t1\t+\t3\t+\t0M\nL\t2\t+\t4\t+\t0M\n"
-           "L\t3\t+\t4\t+\t0M\nP\tp0\t1+,2+,4+\t*\nP\tp1\t1+,3+,4+\t*\n")
-TWO_BUBBLES = ("S\t1\tA\nS\t2\tT\nS\t3\tC\nS\t4\tG\nS\t5\tA\nS\t6\tC\nS\t7\tT\n" +
-               "".join(f"L\t{a}\t+\t{b}\t+\t0M\n" for a, b in [(1, 2), (1, 3), (2, 4), (3, 4), (4, 5), (4, 6), (5, 7), (6, 7)]) +
-               "P\tp0\t1+,2+,4+,5+,7+\t*\nP\tp1\t1+,3+,4+,6+,7+\t*\n")
+from pathwise_support import DIAMOND, TWO_BUBBLES, assert_rows_in_registers, create_rc, no_device
 
 
 def _graph(gfa):
@@ -80,43 +70,23 @@ def test_linear_gaps_on_one_path_equal_the_oracle_m4(oracle):
             assert R.line(lnz, rows, ids, "r", rd, sc, 0, -8, semi) == text, (semi, rd, text[-120:])
 
 
-def _create(gfa, reads, mode, o=-4, e=-2, amb=0, match=2):
-    from recgraph_amd import api
-    lib = api._lib.load()
-    g = api.Graph.from_gfa_text(gfa)
-    p = api.make_params(mode, o=o, e=e, amb=amb)
-    p.scores[0] = match
-    blob = "".join(reads).encode()
-    off = (C.c_int64 * (len(reads) + 1))(*np.concatenate([[0], np.cumsum([len(r) for r in reads])]).tolist())
-    out = C.c_void_p()
-    rc = lib.rg_batch_create(g._h, C.byref(p), blob, off, len(reads), C.byref(out))
-    if rc == 0:
-        lib.rg_batch_destroy(out)
-    return rc, lib.rg_last_error().decode()
-
-
-def _no_device():
-    from recgraph_amd import api
-    return api._lib.load().rg_device_count() == 0
-
-
 def test_modes_6_and_7_are_supported_and_refuse_before_a_device_is_needed():
     from recgraph_amd import api
     for mode in (api.MODE_PATHWISE_GAP, api.MODE_PATHWISE_GAP_SEMI):
-        rc, msg = _create(TWO_BUBBLES, ["ATGCT"], mode)
+        rc, msg = create_rc(TWO_BUBBLES, ["ATGCT"], mode)
         # (on the parent commit: RG_ERR_ARG "unsupported mode")
-        assert rc == (-3 if _no_device() else 0), (rc, msg)
-        assert _create(TWO_BUBBLES, ["ATGCT"], mode, o=1)[0] == -1
-        assert _create(TWO_BUBBLES, ["ATGCT"], mode, e=1)[0] == -1
+        assert rc == (-3 if no_device() else 0), (rc, msg)
+        assert create_rc(TWO_BUBBLES, ["ATGCT"], mode, o=1)[0] == -1
+        assert create_rc(TWO_BUBBLES, ["ATGCT"], mode, e=1)[0] == -1
         for amb in (1, 2, 4, 8, 12):
-            assert _create(TWO_BUBBLES, ["ATGCT"], mode, amb=amb)[0] == -1, amb
-        rc, msg = _create(TWO_BUBBLES, ["A" * 2048], mode)
+            assert create_rc(TWO_BUBBLES, ["ATGCT"], mode, amb=amb)[0] == -1, amb
+        rc, msg = create_rc(TWO_BUBBLES, ["A" * 2048], mode)
         assert rc == -1 and "2047" in msg, (rc, msg)
-        assert _create(TWO_BUBBLES, ["A" * 2047], mode)[0] == (-3 if _no_device() else 0)
+        assert create_rc(TWO_BUBBLES, ["A" * 2047], mode)[0] == (-3 if no_device() else 0)
         # (5 rows + 5 bases) * 2^25 >= 2^28
-        rc, msg = _create(TWO_BUBBLES, ["ATGCT"], mode, match=1 << 25)
+        rc, msg = create_rc(TWO_BUBBLES, ["ATGCT"], mode, match=1 << 25)
         assert rc == -5, (rc, msg)
-        rc, msg = _create(TWO_BUBBLES, ["ATGCT"], mode, o=-(1 << 25))
+        rc, msg = create_rc(TWO_BUBBLES, ["ATGCT"], mode, o=-(1 << 25))
         assert rc == -5, (rc, msg)
 
 
@@ -148,11 +118,5 @@ def test_gap_plan_routes(tmp_path):
 def test_the_kernels_keep_their_rows_in_registers():
     """No scratch, no spilled VGPRs and no AGPRs (a kernel without MFMA that holds AGPRs has had VGPRs moved there: a spill in all but
     name) in any instantiation: H and Y of a row live in registers (DESIGN 4.8 lists the counts)."""
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import kernel_resources
-    ks = kernel_resources.report("gap/rg_path_gap.hip")
-    assert len(ks) == 18
-    for k in ks:
-        assert k["ScratchSize [bytes/lane]"] == 0 and k["VGPRs Spill"] == 0 and k["AGPRs"] == 0, (k["name"], k)
-        assert k["VGPRs"] <= 200, (k["name"], k)         # (two waves per SIMD at the least, C = 32 included)
-        assert k["LDS Size [bytes/block]"] <= 160, (k["name"], k)      # the score table only: no row was moved to LDS
+    # 200 VGPRs: two waves per SIMD at the least, C = 32 included; 160 B of LDS: the score table only, no row was moved to LDS
+    assert_rows_in_registers("gap/rg_path_gap.hip", 18, vgprs=200, lds=160)

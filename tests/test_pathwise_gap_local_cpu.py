@@ -1,9 +1,6 @@
 """CPU: the rule of -m 12 (tests/pathwise_gap_local_rule.py) against hand-checked lines and a plain scalar Smith-Waterman-Gotoh, the
 admission and the refusals of rg_batch_create (answered before a device is needed), the plan's routes
 (tests/c/gap_local_plan_check.cpp), the CLI's parser and the registers of the new kernels."""
-import os
-import sys
-
 import numpy as np
 import pytest
 
@@ -11,9 +8,8 @@ import plan_check_build
 
 import pathwise_gap_local_rule as L
 import pathwise_gap_rule as R
-from test_pathwise_gap_cpu import DIAMOND, TWO_BUBBLES, _create, _no_device
+from pathwise_support import DIAMOND, TWO_BUBBLES, assert_rows_in_registers, create_rc, no_device
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 COSTS = [(-4, -2), (0, -2), (-6, 0), (-40, -1), (0, 0)]
 
 
@@ -66,34 +62,34 @@ def test_mode_12_is_admitted_and_refuses_before_a_device_is_needed():
     from recgraph_amd import api
     mode = api.MODE_PATHWISE_GAP_LOCAL
     assert mode == 12 == api._lib.MODE_PATHWISE_GAP_LOCAL and api.READ_UNALIGNED == 16 == api._lib.READ_UNALIGNED
-    rc, msg = _create(TWO_BUBBLES, ["ATGCT"], mode)
+    rc, msg = create_rc(TWO_BUBBLES, ["ATGCT"], mode)
     # (on the parent commit: RG_ERR_ARG "unsupported mode")
-    assert rc == (-3 if _no_device() else 0), (rc, msg)
-    assert _create(TWO_BUBBLES, ["ATGCT"], mode, o=1)[0] == -1
-    assert _create(TWO_BUBBLES, ["ATGCT"], mode, e=1)[0] == -1
+    assert rc == (-3 if no_device() else 0), (rc, msg)
+    assert create_rc(TWO_BUBBLES, ["ATGCT"], mode, o=1)[0] == -1
+    assert create_rc(TWO_BUBBLES, ["ATGCT"], mode, e=1)[0] == -1
     for amb in (1, 2, 4, 8, 12):
-        assert _create(TWO_BUBBLES, ["ATGCT"], mode, amb=amb)[0] == -1, amb
-    rc, msg = _create(TWO_BUBBLES, ["A" * 2048], mode)
+        assert create_rc(TWO_BUBBLES, ["ATGCT"], mode, amb=amb)[0] == -1, amb
+    rc, msg = create_rc(TWO_BUBBLES, ["A" * 2048], mode)
     assert rc == -1 and "2047" in msg, (rc, msg)
-    assert _create(TWO_BUBBLES, ["A" * 2047], mode)[0] == (-3 if _no_device() else 0)
+    assert create_rc(TWO_BUBBLES, ["A" * 2047], mode)[0] == (-3 if no_device() else 0)
     # (5 rows + 5 bases) * 2^25 >= 2^28
-    assert _create(TWO_BUBBLES, ["ATGCT"], mode, match=1 << 25)[0] == -5
-    assert _create(TWO_BUBBLES, ["ATGCT"], mode, o=-(1 << 25))[0] == -5
+    assert create_rc(TWO_BUBBLES, ["ATGCT"], mode, match=1 << 25)[0] == -5
+    assert create_rc(TWO_BUBBLES, ["ATGCT"], mode, o=-(1 << 25))[0] == -5
     # no mode between the families was admitted by accident
     for other in (13, 14, -1):
-        rc, msg = _create(TWO_BUBBLES, ["ATGCT"], other)
+        rc, msg = create_rc(TWO_BUBBLES, ["ATGCT"], other)
         assert rc == -1 and "unsupported mode" in msg
 
 
 def test_modes_6_and_7_refuse_what_they_refused():
     from recgraph_amd import api
     for mode in (api.MODE_PATHWISE_GAP, api.MODE_PATHWISE_GAP_SEMI):
-        rc, msg = _create(TWO_BUBBLES, ["A" * 2048], mode)
+        rc, msg = create_rc(TWO_BUBBLES, ["A" * 2048], mode)
         assert rc == -1 and "(-m 6 / -m 7)" in msg, (rc, msg)
-        rc, msg = _create(TWO_BUBBLES, ["ATGCT"], mode, amb=4)
+        rc, msg = create_rc(TWO_BUBBLES, ["ATGCT"], mode, amb=4)
         assert rc == -1 and "(-m 6 / -m 7)" in msg, (rc, msg)
-        assert _create(TWO_BUBBLES, ["ATGCT"], mode, o=1)[0] == -1
-        assert _create(TWO_BUBBLES, ["ATGCT"], mode, match=1 << 25)[0] == -5
+        assert create_rc(TWO_BUBBLES, ["ATGCT"], mode, o=1)[0] == -1
+        assert create_rc(TWO_BUBBLES, ["ATGCT"], mode, match=1 << 25)[0] == -5
 
 
 def test_no_new_entry_point():
@@ -136,11 +132,4 @@ def test_gap_local_plan_routes(tmp_path):
 def test_the_kernels_keep_their_rows_in_registers():
     """The bar of -m 6 / -m 7: no scratch, no spilled VGPR, no AGPR, at most 200 VGPRs and the score table's 160 B of LDS in every
     instantiation of gap_local/rg_path_gap_local.hip."""
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import kernel_resources
-    ks = kernel_resources.report("gap_local/rg_path_gap_local.hip")
-    assert len(ks) == 10
-    for k in ks:
-        assert k["ScratchSize [bytes/lane]"] == 0 and k["VGPRs Spill"] == 0 and k["AGPRs"] == 0, (k["name"], k)
-        assert k["VGPRs"] <= 200, (k["name"], k)
-        assert k["LDS Size [bytes/block]"] <= 160, (k["name"], k)
+    assert_rows_in_registers("gap_local/rg_path_gap_local.hip", 10, vgprs=200, lds=160)

@@ -2,13 +2,12 @@
 bases): admission and refusals of rg_batch_create (answered before a device is needed), the plan's routes
 (tests/c/gap_long_plan_check.cpp), the API and CLI surface and the registers of the new kernels."""
 import os
-import sys
 
 import pytest
 
 import plan_check_build
 
-from test_pathwise_gap_cpu import TWO_BUBBLES, _create, _no_device
+from pathwise_support import TWO_BUBBLES, assert_rows_in_registers, create_rc, no_device
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LONG = {16: 6, 17: 7, 22: 12}
@@ -16,35 +15,35 @@ LONG = {16: 6, 17: 7, 22: 12}
 
 @pytest.mark.parametrize("mode", sorted(LONG))
 def test_the_long_modes_are_admitted_and_refuse_before_a_device_is_needed(mode):
-    ok = -3 if _no_device() else 0
-    rc, msg = _create(TWO_BUBBLES, ["ATGCT"], mode)
+    ok = -3 if no_device() else 0
+    rc, msg = create_rc(TWO_BUBBLES, ["ATGCT"], mode)
     # (on the parent commit: RG_ERR_ARG "unsupported mode")
     assert rc == ok, (rc, msg)
     # what the base modes refuse at 2048 bases is admitted up to 16383
     for n in (2047, 2048, 16383):
-        rc, msg = _create(TWO_BUBBLES, ["A" * n], mode)
+        rc, msg = create_rc(TWO_BUBBLES, ["A" * n], mode)
         assert rc == ok, (n, rc, msg)
-    rc, msg = _create(TWO_BUBBLES, ["ATG", "A" * 16384], mode)
+    rc, msg = create_rc(TWO_BUBBLES, ["ATG", "A" * 16384], mode)
     assert rc == -1 and "16383" in msg, (rc, msg)
-    assert _create(TWO_BUBBLES, ["ATGCT"], mode, o=1)[0] == -1
-    assert _create(TWO_BUBBLES, ["ATGCT"], mode, e=1)[0] == -1
-    assert _create(TWO_BUBBLES, ["A" * 5000], mode, o=1)[0] == -1
+    assert create_rc(TWO_BUBBLES, ["ATGCT"], mode, o=1)[0] == -1
+    assert create_rc(TWO_BUBBLES, ["ATGCT"], mode, e=1)[0] == -1
+    assert create_rc(TWO_BUBBLES, ["A" * 5000], mode, o=1)[0] == -1
     for amb in (1, 2, 4, 8, 12):
-        assert _create(TWO_BUBBLES, ["ATGCT"], mode, amb=amb)[0] == -1, amb
-        assert _create(TWO_BUBBLES, ["A" * 3000], mode, amb=amb)[0] == -1, amb
+        assert create_rc(TWO_BUBBLES, ["ATGCT"], mode, amb=amb)[0] == -1, amb
+        assert create_rc(TWO_BUBBLES, ["A" * 3000], mode, amb=amb)[0] == -1, amb
     # (5 rows + 5 bases) * 2^25 >= 2^28, and (5 rows + 16379 bases) * 2^14 = 2^28
-    assert _create(TWO_BUBBLES, ["ATGCT"], mode, match=1 << 25)[0] == -5
-    assert _create(TWO_BUBBLES, ["ATGCT"], mode, o=-(1 << 25))[0] == -5
-    assert _create(TWO_BUBBLES, ["A" * 16379], mode, match=1 << 14)[0] == -5
-    assert _create(TWO_BUBBLES, ["A" * 16378], mode, match=1 << 14)[0] == ok
+    assert create_rc(TWO_BUBBLES, ["ATGCT"], mode, match=1 << 25)[0] == -5
+    assert create_rc(TWO_BUBBLES, ["ATGCT"], mode, o=-(1 << 25))[0] == -5
+    assert create_rc(TWO_BUBBLES, ["A" * 16379], mode, match=1 << 14)[0] == -5
+    assert create_rc(TWO_BUBBLES, ["A" * 16378], mode, match=1 << 14)[0] == ok
 
 
 def test_the_base_modes_keep_their_limit_and_the_gaps_between_the_modes_stay_closed():
     for mode in (6, 7, 12):
-        rc, msg = _create(TWO_BUBBLES, ["A" * 2048], mode)
+        rc, msg = create_rc(TWO_BUBBLES, ["A" * 2048], mode)
         assert rc == -1 and "2047" in msg, (mode, rc, msg)
     for other in (13, 14, 15, 18, 19, 20, 21, 23, -1):
-        rc, msg = _create(TWO_BUBBLES, ["ATGCT"], other)
+        rc, msg = create_rc(TWO_BUBBLES, ["ATGCT"], other)
         assert rc == -1 and "unsupported mode" in msg, (other, rc, msg)
 
 
@@ -92,12 +91,6 @@ def test_gap_long_plan_routes(tmp_path):
 def test_the_kernels_keep_their_rows_in_registers():
     """The family's bar: no scratch, no spilled VGPR, no AGPR, at most 200 VGPRs and no LDS beyond the score table's 160 B in every
     instantiation of gap_long/rg_path_gap_long.hip (DESIGN 4.10 lists the counts)."""
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import kernel_resources
-    ks = kernel_resources.report("gap_long/rg_path_gap_long.hip")
+    ks = assert_rows_in_registers("gap_long/rg_path_gap_long.hip", 8, vgprs=200, lds=160)
     assert sorted(k["name"] for k in ks) == sorted(["rg::k_gap_score_long<%d>" % k for k in range(3)] + ["rg::k_gap_dirs_long<%d>" % k for k in range(3)] +
                                                   ["rg::k_gap_trace_long", "rg::k_gap_trace_local_long"])
-    for k in ks:
-        assert k["ScratchSize [bytes/lane]"] == 0 and k["VGPRs Spill"] == 0 and k["AGPRs"] == 0, (k["name"], k)
-        assert k["VGPRs"] <= 200, (k["name"], k)
-        assert k["LDS Size [bytes/block]"] <= 160, (k["name"], k)

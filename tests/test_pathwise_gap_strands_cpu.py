@@ -5,7 +5,6 @@ tests/pathwise_gap_strands_rule.py on hand cases and in the score regimes the GP
 import functools
 import inspect
 import os
-import sys
 
 import pytest
 
@@ -15,7 +14,7 @@ import pathwise_gap_local_rule as L
 import pathwise_gap_rule as R
 import pathwise_gap_strands_rule as S
 import strand_vote_rule as V
-from test_pathwise_gap_cpu import TWO_BUBBLES, _create, _no_device
+from pathwise_support import TWO_BUBBLES, assert_rows_in_registers, create_rc, kernel_resources, no_device
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STRANDS = {26: 6, 27: 7, 32: 12}
@@ -23,50 +22,50 @@ STRANDS = {26: 6, 27: 7, 32: 12}
 
 @pytest.mark.parametrize("mode", sorted(STRANDS))
 def test_the_modes_are_admitted_and_refuse_before_a_device_is_needed(mode):
-    ok = -3 if _no_device() else 0
-    rc, msg = _create(TWO_BUBBLES, ["ATGCT"], mode)
+    ok = -3 if no_device() else 0
+    rc, msg = create_rc(TWO_BUBBLES, ["ATGCT"], mode)
     # (on the parent commit: RG_ERR_ARG "unsupported mode")
     assert rc == ok, (rc, msg)
     for n in (2047, 2048, 16383):
-        rc, msg = _create(TWO_BUBBLES, ["A" * n], mode)
+        rc, msg = create_rc(TWO_BUBBLES, ["A" * n], mode)
         assert rc == ok, (n, rc, msg)
-    rc, msg = _create(TWO_BUBBLES, ["ATG", "A" * 16384], mode)
+    rc, msg = create_rc(TWO_BUBBLES, ["ATG", "A" * 16384], mode)
     assert rc == -1 and "16383" in msg, (rc, msg)
-    assert _create(TWO_BUBBLES, ["ATGCT"], mode, o=1)[0] == -1
-    assert _create(TWO_BUBBLES, ["ATGCT"], mode, e=1)[0] == -1
-    assert _create(TWO_BUBBLES, ["A" * 5000], mode, o=1, amb=4)[0] == -1
+    assert create_rc(TWO_BUBBLES, ["ATGCT"], mode, o=1)[0] == -1
+    assert create_rc(TWO_BUBBLES, ["ATGCT"], mode, e=1)[0] == -1
+    assert create_rc(TWO_BUBBLES, ["A" * 5000], mode, o=1, amb=4)[0] == -1
     # the two capacity cases of the long modes: (5 rows + 5 bases) * 2^25 >= 2^28, and (5 rows + 16379 bases) * 2^14 = 2^28
-    assert _create(TWO_BUBBLES, ["ATGCT"], mode, match=1 << 25)[0] == -5
-    assert _create(TWO_BUBBLES, ["ATGCT"], mode, o=-(1 << 25))[0] == -5
-    assert _create(TWO_BUBBLES, ["A" * 16379], mode, match=1 << 14)[0] == -5
-    assert _create(TWO_BUBBLES, ["A" * 16378], mode, match=1 << 14)[0] == ok
+    assert create_rc(TWO_BUBBLES, ["ATGCT"], mode, match=1 << 25)[0] == -5
+    assert create_rc(TWO_BUBBLES, ["ATGCT"], mode, o=-(1 << 25))[0] == -5
+    assert create_rc(TWO_BUBBLES, ["A" * 16379], mode, match=1 << 14)[0] == -5
+    assert create_rc(TWO_BUBBLES, ["A" * 16378], mode, match=1 << 14)[0] == ok
 
 
 @pytest.mark.parametrize("mode", sorted(STRANDS))
 def test_amb_mode_admission(mode):
-    ok = -3 if _no_device() else 0
+    ok = -3 if no_device() else 0
     for amb in (0, 4):
         for rd in ("ATGCT", "A" * 3000):
-            rc, msg = _create(TWO_BUBBLES, [rd], mode, amb=amb)
+            rc, msg = create_rc(TWO_BUBBLES, [rd], mode, amb=amb)
             assert rc == ok, (amb, rc, msg)
-    rc, msg = _create(TWO_BUBBLES, ["ATGCT"], mode, amb=12)
+    rc, msg = create_rc(TWO_BUBBLES, ["ATGCT"], mode, amb=12)
     if mode == 32:
         # the message says why: a vote needs a score that says "hopeless"
         assert rc == -1 and "hopeless" in msg and "32" in msg, (rc, msg)
     else:
         assert rc == ok, (rc, msg)
     for amb in (1, 2, 8, 16, 3, 5, 13, 20, 28):
-        assert _create(TWO_BUBBLES, ["ATGCT"], mode, amb=amb)[0] == -1, amb
-        assert _create(TWO_BUBBLES, ["A" * 3000], mode, amb=amb)[0] == -1, amb
+        assert create_rc(TWO_BUBBLES, ["ATGCT"], mode, amb=amb)[0] == -1, amb
+        assert create_rc(TWO_BUBBLES, ["A" * 3000], mode, amb=amb)[0] == -1, amb
 
 
 def test_the_gaps_between_the_modes_stay_closed_and_the_other_modes_keep_refusing():
     for other in (24, 25, 28, 29, 30, 31, 33, 34, 36, 42, 46):
-        rc, msg = _create(TWO_BUBBLES, ["ATGCT"], other)
+        rc, msg = create_rc(TWO_BUBBLES, ["ATGCT"], other)
         assert rc == -1 and "unsupported mode" in msg, (other, rc, msg)
     for mode in (6, 7, 12, 16, 17, 22):
         for amb in (4, 12):
-            rc, msg = _create(TWO_BUBBLES, ["ATGCT"], mode, amb=amb)
+            rc, msg = create_rc(TWO_BUBBLES, ["ATGCT"], mode, amb=amb)
             assert rc == -1 and "as given" in msg, (mode, amb, rc, msg)
 
 
@@ -134,16 +133,11 @@ def test_gap_strands_plan_routes(tmp_path):
 def test_the_gate_kernel_is_small():
     """Like the three kernels of rg_strand.hip it runs beside other handles' Gotoh waves: at most 64 VGPRs, no scratch, no spill, no
     AGPR, and no store whose source register is overwritten too early.  It is the only kernel of its directory."""
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import kernel_resources
     d = os.path.join(ROOT, "recgraph_amd", "csrc", "gap_strands")
     assert sorted(os.listdir(d)) == ["rg_gap_strands.hip", "rg_gap_strands.hpp"]
-    ks = {k["name"].split("(")[0]: k for k in kernel_resources.report("gap_strands/rg_gap_strands.hip")}
-    assert set(ks) == {"rg::k_gap_strands_gate"}, sorted(ks)
-    for name, k in ks.items():
-        assert k["ScratchSize [bytes/lane]"] == 0 and k["VGPRs Spill"] == 0 and k["AGPRs"] == 0, (name, k)
-        assert k["VGPRs"] <= 64, (name, k)
-    hits, stores = kernel_resources.store_hazards("gap_strands/rg_gap_strands.hip")
+    ks = assert_rows_in_registers("gap_strands/rg_gap_strands.hip", 1, vgprs=64)
+    assert {k["name"].split("(")[0] for k in ks} == {"rg::k_gap_strands_gate"}, ks
+    hits, stores = kernel_resources().store_hazards("gap_strands/rg_gap_strands.hip")
     assert not hits, hits[:4]
 
 

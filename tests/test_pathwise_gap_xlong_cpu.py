@@ -3,13 +3,12 @@ and refusals of rg_batch_create (answered before a device is needed), the plan's
 and CLI surface and the registers of the new kernels."""
 import inspect
 import os
-import sys
 
 import pytest
 
 import plan_check_build
 
-from test_pathwise_gap_cpu import TWO_BUBBLES, _create, _no_device
+from pathwise_support import TWO_BUBBLES, assert_rows_in_registers, create_rc, no_device
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 XLONG = {56: 6, 57: 7, 62: 12}
@@ -19,39 +18,39 @@ KERNELS = (["rg::k_gap_ckpt_long<%d>" % k for k in range(3)] + ["rg::k_gap_redo_
 
 @pytest.mark.parametrize("mode", sorted(XLONG))
 def test_the_modes_are_admitted_and_refuse_before_a_device_is_needed(mode):
-    ok = -3 if _no_device() else 0
-    rc, msg = _create(TWO_BUBBLES, ["ATGCT"], mode)
+    ok = -3 if no_device() else 0
+    rc, msg = create_rc(TWO_BUBBLES, ["ATGCT"], mode)
     # (on the parent commit: RG_ERR_ARG "unsupported mode")
     assert rc == ok, (rc, msg)
     # both sides of the limits of the base modes and of the long modes, and the new limit itself
     for n in (2047, 2048, 16383, 16384, 131071):
-        rc, msg = _create(TWO_BUBBLES, ["A" * n], mode)
+        rc, msg = create_rc(TWO_BUBBLES, ["A" * n], mode)
         assert rc == ok, (n, rc, msg)
-    rc, msg = _create(TWO_BUBBLES, ["ATG", "A" * 131072], mode)
+    rc, msg = create_rc(TWO_BUBBLES, ["ATG", "A" * 131072], mode)
     assert rc == -1 and "131071" in msg, (rc, msg)
-    assert _create(TWO_BUBBLES, ["ATGCT"], mode, o=1)[0] == -1
-    assert _create(TWO_BUBBLES, ["ATGCT"], mode, e=1)[0] == -1
-    assert _create(TWO_BUBBLES, ["A" * 50000], mode, o=1)[0] == -1
-    assert _create(TWO_BUBBLES, ["A" * 50000], mode, e=1)[0] == -1
+    assert create_rc(TWO_BUBBLES, ["ATGCT"], mode, o=1)[0] == -1
+    assert create_rc(TWO_BUBBLES, ["ATGCT"], mode, e=1)[0] == -1
+    assert create_rc(TWO_BUBBLES, ["A" * 50000], mode, o=1)[0] == -1
+    assert create_rc(TWO_BUBBLES, ["A" * 50000], mode, e=1)[0] == -1
     for amb in (1, 2, 4, 8, 12):
-        assert _create(TWO_BUBBLES, ["ATGCT"], mode, amb=amb)[0] == -1, amb
-        assert _create(TWO_BUBBLES, ["A" * 30000], mode, amb=amb)[0] == -1, amb
+        assert create_rc(TWO_BUBBLES, ["ATGCT"], mode, amb=amb)[0] == -1, amb
+        assert create_rc(TWO_BUBBLES, ["A" * 30000], mode, amb=amb)[0] == -1, amb
     # the two capacity edges: (5 rows + 5 bases) * 2^25 >= 2^28, and (5 rows + 131067 bases) * 2^11 = 2^28
-    assert _create(TWO_BUBBLES, ["ATGCT"], mode, match=1 << 25)[0] == -5
-    assert _create(TWO_BUBBLES, ["ATGCT"], mode, o=-(1 << 25))[0] == -5
-    assert _create(TWO_BUBBLES, ["A" * 131067], mode, match=1 << 11)[0] == -5
-    assert _create(TWO_BUBBLES, ["A" * 131066], mode, match=1 << 11)[0] == ok
+    assert create_rc(TWO_BUBBLES, ["ATGCT"], mode, match=1 << 25)[0] == -5
+    assert create_rc(TWO_BUBBLES, ["ATGCT"], mode, o=-(1 << 25))[0] == -5
+    assert create_rc(TWO_BUBBLES, ["A" * 131067], mode, match=1 << 11)[0] == -5
+    assert create_rc(TWO_BUBBLES, ["A" * 131066], mode, match=1 << 11)[0] == ok
 
 
 def test_the_earlier_modes_keep_their_limits_and_the_gaps_between_the_modes_stay_closed():
     for mode in (6, 7, 12):
-        rc, msg = _create(TWO_BUBBLES, ["A" * 2048], mode)
+        rc, msg = create_rc(TWO_BUBBLES, ["A" * 2048], mode)
         assert rc == -1 and "2047" in msg, (mode, rc, msg)
     for mode in (16, 17, 22, 26, 27, 32):
-        rc, msg = _create(TWO_BUBBLES, ["A" * 16384], mode)
+        rc, msg = create_rc(TWO_BUBBLES, ["A" * 16384], mode)
         assert rc == -1 and "16383" in msg, (mode, rc, msg)
     for other in (36, 37, 42, 46, 47, 52, 50, 51, 53, 54, 55, 58, 59, 60, 61, 63, 66, 67, 72):
-        rc, msg = _create(TWO_BUBBLES, ["ATGCT"], other)
+        rc, msg = create_rc(TWO_BUBBLES, ["ATGCT"], other)
         assert rc == -1 and "unsupported mode" in msg, (other, rc, msg)
 
 
@@ -116,14 +115,8 @@ def test_gap_xlong_plan_routes(tmp_path):
 def test_the_kernels_keep_their_rows_in_registers():
     """The family's bar: no scratch, no spilled VGPR, no AGPR, at most 200 VGPRs and no LDS beyond the score table's 160 B in every
     instantiation of gap_xlong/rg_path_gap_xlong.hip (DESIGN 4.12 lists the counts)."""
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import kernel_resources
-    ks = kernel_resources.report("gap_xlong/rg_path_gap_xlong.hip")
+    ks = assert_rows_in_registers("gap_xlong/rg_path_gap_xlong.hip", len(KERNELS), vgprs=200, lds=160)
     assert sorted(k["name"] for k in ks) == sorted(KERNELS)
-    for k in ks:
-        assert k["ScratchSize [bytes/lane]"] == 0 and k["VGPRs Spill"] == 0 and k["AGPRs"] == 0, (k["name"], k)
-        assert k["VGPRs"] <= 200, (k["name"], k)
-        assert k["LDS Size [bytes/block]"] <= 160, (k["name"], k)
 
 
 def test_the_shared_row_step_left_the_long_kernels_as_they_were():

@@ -4,7 +4,6 @@
 tests/pathwise_gap_xstrands_rule.py on hand cases."""
 import inspect
 import os
-import sys
 
 import pytest
 
@@ -13,7 +12,7 @@ import plan_check_build
 import pathwise_gap_rule as R
 import pathwise_gap_xstrands_rule as X
 import strand_vote_rule as V
-from test_pathwise_gap_cpu import TWO_BUBBLES, _create, _no_device
+from pathwise_support import TWO_BUBBLES, assert_rows_in_registers, create_rc, kernel_resources, no_device
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 XSTRANDS = {76: 6, 77: 7, 82: 12}
@@ -24,15 +23,15 @@ LENGTHS = (5, 30000, 131072)
 @pytest.mark.parametrize("mode", sorted(XSTRANDS))
 def test_the_modes_are_admitted_before_a_device_is_needed(mode):
     """The test that fails without the feature: on the parent commit rg_batch_create answers RG_ERR_ARG "unsupported mode"."""
-    ok = -3 if _no_device() else 0
-    rc, msg = _create(TWO_BUBBLES, ["ATGCT"], mode)
+    ok = -3 if no_device() else 0
+    rc, msg = create_rc(TWO_BUBBLES, ["ATGCT"], mode)
     assert rc == ok, (rc, msg)
     for n in (2047, 2048, 16383, 16384, 30000, 131071):
-        rc, msg = _create(TWO_BUBBLES, ["A" * n], mode)
+        rc, msg = create_rc(TWO_BUBBLES, ["A" * n], mode)
         assert rc == ok, (n, rc, msg)
     for amb in (0, 4) + ((12,) if mode != 82 else ()):
         for n in (5, 30000):
-            rc, msg = _create(TWO_BUBBLES, ["A" * n], mode, amb=amb)
+            rc, msg = create_rc(TWO_BUBBLES, ["A" * n], mode, amb=amb)
             assert rc == ok, (amb, n, rc, msg)
 
 
@@ -43,48 +42,48 @@ def test_every_refusal_at_every_length(mode):
     for n in LENGTHS:
         reads = ["ATG", "A" * n]
         for amb in (1, 2, 3, 5, 6, 8, 9, 13, 16, 20, 28, 32, 36, 44):
-            assert _create(TWO_BUBBLES, reads, mode, amb=amb)[0] == -1, (n, amb)
-        assert _create(TWO_BUBBLES, reads, mode, o=1)[0] == -1, n
-        assert _create(TWO_BUBBLES, reads, mode, e=1)[0] == -1, n
-        assert _create(TWO_BUBBLES, reads, mode, o=1, amb=4)[0] == -1, n
-        rc, msg = _create(TWO_BUBBLES, reads, mode, amb=12)
+            assert create_rc(TWO_BUBBLES, reads, mode, amb=amb)[0] == -1, (n, amb)
+        assert create_rc(TWO_BUBBLES, reads, mode, o=1)[0] == -1, n
+        assert create_rc(TWO_BUBBLES, reads, mode, e=1)[0] == -1, n
+        assert create_rc(TWO_BUBBLES, reads, mode, o=1, amb=4)[0] == -1, n
+        rc, msg = create_rc(TWO_BUBBLES, reads, mode, amb=12)
         if mode == 82:
             # mode 32's message and reason
             assert rc == -1 and (n == 131072 or ("hopeless" in msg and "82" in msg)), (n, rc, msg)
         elif n == 131072:
             assert rc == -1
     for amb in (0, 4):
-        rc, msg = _create(TWO_BUBBLES, ["ATG", "A" * 131072], mode, amb=amb)
+        rc, msg = create_rc(TWO_BUBBLES, ["ATG", "A" * 131072], mode, amb=amb)
         assert rc == -1 and "131071" in msg, (rc, msg)
 
 
 @pytest.mark.parametrize("mode", sorted(XSTRANDS))
 def test_both_capacity_edges(mode):
     """(5 rows + 5 bases) * 2^25 >= 2^28, and (5 rows + 131067 bases) * 2^11 = 2^28: RG_ERR_CAPACITY; one base fewer is admitted."""
-    ok = -3 if _no_device() else 0
-    assert _create(TWO_BUBBLES, ["ATGCT"], mode, match=1 << 25)[0] == -5
-    assert _create(TWO_BUBBLES, ["ATGCT"], mode, o=-(1 << 25))[0] == -5
-    assert _create(TWO_BUBBLES, ["ATGCT"], mode, match=1 << 25, amb=4)[0] == -5
-    assert _create(TWO_BUBBLES, ["A" * 131067], mode, match=1 << 11)[0] == -5
-    assert _create(TWO_BUBBLES, ["A" * 131066], mode, match=1 << 11)[0] == ok
+    ok = -3 if no_device() else 0
+    assert create_rc(TWO_BUBBLES, ["ATGCT"], mode, match=1 << 25)[0] == -5
+    assert create_rc(TWO_BUBBLES, ["ATGCT"], mode, o=-(1 << 25))[0] == -5
+    assert create_rc(TWO_BUBBLES, ["ATGCT"], mode, match=1 << 25, amb=4)[0] == -5
+    assert create_rc(TWO_BUBBLES, ["A" * 131067], mode, match=1 << 11)[0] == -5
+    assert create_rc(TWO_BUBBLES, ["A" * 131066], mode, match=1 << 11)[0] == ok
 
 
 def test_the_neighbours_stay_unsupported_and_the_siblings_keep_their_rules():
     for other in (78, 79, 80, 81, 83, 86, 92, 70, 71, 73, 74, 75, 84, 85, 87, 96, 97, 102):
         for amb in (0, 4):
-            rc, msg = _create(TWO_BUBBLES, ["ATGCT"], other, amb=amb)
+            rc, msg = create_rc(TWO_BUBBLES, ["ATGCT"], other, amb=amb)
             assert rc == -1 and "unsupported mode" in msg, (other, rc, msg)
     for other in (36, 37, 42, 46, 47, 52, 66, 67, 72):
-        rc, msg = _create(TWO_BUBBLES, ["ATGCT"], other)
+        rc, msg = create_rc(TWO_BUBBLES, ["ATGCT"], other)
         assert rc == -1 and "unsupported mode" in msg, (other, rc, msg)
     # modes 56 / 57 / 62 keep refusing every amb_mode bit, modes 26 / 27 / 32 keep their 16383 limit
     for mode in (56, 57, 62):
         for amb in (1, 2, 4, 8, 12):
             for rd in ("ATGCT", "A" * 30000):
-                rc, msg = _create(TWO_BUBBLES, [rd], mode, amb=amb)
+                rc, msg = create_rc(TWO_BUBBLES, [rd], mode, amb=amb)
                 assert rc == -1 and (amb & 3 or amb == 8 or "as given" in msg), (mode, amb, rc, msg)
     for mode in (26, 27, 32):
-        rc, msg = _create(TWO_BUBBLES, ["A" * 16384], mode)
+        rc, msg = create_rc(TWO_BUBBLES, ["A" * 16384], mode)
         assert rc == -1 and "16383" in msg, (mode, rc, msg)
 
 
@@ -165,17 +164,12 @@ def test_gap_xstrands_plan_routes(tmp_path):
 def test_the_new_kernels_are_small():
     """They run beside other handles' Gotoh waves: no scratch, no spill, no AGPR, no LDS, at most 48 VGPRs, and no store whose source
     register is overwritten too early.  The directory holds the two files and nothing else; no inline assembly, no atomics."""
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import kernel_resources
     d = os.path.join(ROOT, "recgraph_amd", "csrc", "gap_xstrands")
     assert sorted(os.listdir(d)) == ["rg_gap_xstrands.hip", "rg_gap_xstrands.hpp"]
-    ks = {k["name"].split("(")[0]: k for k in kernel_resources.report("gap_xstrands/rg_gap_xstrands.hip")}
-    assert sorted(ks) == KERNELS, sorted(ks)
-    for name, k in ks.items():
-        assert k["ScratchSize [bytes/lane]"] == 0 and k["VGPRs Spill"] == 0 and k["SGPRs Spill"] == 0 and k["AGPRs"] == 0, (name, k)
-        assert k["VGPRs"] <= 48, (name, k)
-        assert k["LDS Size [bytes/block]"] == 0, (name, k)
-    hits, stores = kernel_resources.store_hazards("gap_xstrands/rg_gap_xstrands.hip")
+    ks = assert_rows_in_registers("gap_xstrands/rg_gap_xstrands.hip", len(KERNELS), vgprs=48, lds=0)
+    assert sorted(k["name"].split("(")[0] for k in ks) == KERNELS, ks
+    assert all(k["SGPRs Spill"] == 0 for k in ks), [(k["name"], k["SGPRs Spill"]) for k in ks]
+    hits, stores = kernel_resources().store_hazards("gap_xstrands/rg_gap_xstrands.hip")
     assert not hits and stores >= 4, hits[:4]
     src = open(os.path.join(d, "rg_gap_xstrands.hip")).read()
     assert "asm" not in src and "atomic" not in src.replace("no atomics", "")
