@@ -238,6 +238,26 @@ typedef enum rg_status {
  */
 #define RG_MODE_PATHWISE_EDIT 44
 #define RG_MODE_PATHWISE_EDIT_SEMI 45
+/*
+ * RG_MODE_PATHWISE_EDIT_XLONG (94), RG_MODE_PATHWISE_EDIT_SEMI_XLONG (95): modes 44 and 45 for reads of 1 to 131071 bases, numbered
+ * `mode + 50` as the xlong family is.  THERE IS NO NEW RULE: mode 94 is mode 56, and mode 95 is mode 57, RESTRICTED TO UNIT COSTS.
+ * For every batch they admit they return the texts, statuses, scores and rg_batch_cell_updates of mode 56 / 57 under the same
+ * rg_params; for a batch whose longest read has at most 16383 bases they return everything of mode 44 / 45, both counters included,
+ * from that mode's plan and kernels.
+ *   ADMISSION AND REFUSALS.  Those of modes 44 / 45 (unit costs — the message names `-M 0 -X 1 -O 0 -E 1` —, no amb_mode bit, mode 16's
+ *     2^28 budget as RG_ERR_CAPACITY) with the read limit at 131071 bases.  All answered by rg_batch_create before a device is needed.
+ *     Modes 44 and 45 keep their limit of 16383 bases.
+ *   COST.  A batch with a longer read runs S = ceil(longest read / 16384) column stripes of 16384, 2 <= S <= 8 (16384 bases: 2), each in the register
+ *     layout of W = 8, one wave per (read, path) walking them in turn.  What a stripe hands to its right neighbour is the difference
+ *     of its last column between two rows, -1, 0 or +1: two bits per row, kept for every stripe but the last of EVERY path, so the
+ *     traceback needs no checkpoint pass.  It keeps D0 and Ph of ONE stripe per read, (rows of the longest path + 1) * 4 KiB, rebuilt
+ *     from the picked path's boundary bits when the walk enters the stripe, once.  rg_batch_cell_updates_performed counts the score
+ *     pass and the rebuilt cells (rows rebuilt * the stripe's columns that belong to the read; cell (i, j) is of stripe (j - 1) / 16384).
+ * k_edit_score_xlong, k_edit_redo_xlong and k_edit_walk_xlong (edit_xlong/rg_path_edit_xlong.hip) appear in the kernel statistics
+ * under their own names beside k_gap_pick.
+ */
+#define RG_MODE_PATHWISE_EDIT_XLONG 94
+#define RG_MODE_PATHWISE_EDIT_SEMI_XLONG 95
 
 /*
  * Scoring and banding parameters.  Replaces the HashMap<(char,char),i32|f32> score matrix arguments

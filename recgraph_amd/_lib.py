@@ -106,8 +106,22 @@ def edit_mode(mode):
     return {MODE_PATHWISE_EDIT: {"semi": False}, MODE_PATHWISE_EDIT_SEMI: {"semi": True}}.get(mode)
 
 
+# The same two rules for reads of up to 131071 bases (RG_MODE_PATHWISE_EDIT_XLONG / RG_MODE_PATHWISE_EDIT_SEMI_XLONG, edit_xlong_mode of
+# csrc/rg_edit_modes.hpp once more): modes 56 / 57 restricted to unit costs.  A lookup of their own: edit_mode(94) is None.
+MODE_PATHWISE_EDIT_XLONG, MODE_PATHWISE_EDIT_SEMI_XLONG = 94, 95
+EDIT_XLONG_MAX_READ = 131071
+EDIT_XLONG_SCORE_REFUSAL = ("the edit-distance pathwise modes (-m 94 / -m 95) take unit costs only: -M 0 -X 1 -O 0 -E 1, or a -t matrix whose ACGTN x ACGTN "
+                            "entries are all 0 or -1 with -O 0 -E 1; every other scoring is what -m 56 / -m 57 are for")
+EDIT_XLONG_STRANDS_REFUSAL = "%s is not available in the edit-distance pathwise modes for reads of up to 131071 bases (94, 95): they align the reads as given"
+
+
+def edit_xlong_mode(mode):
+    """{"valid": True, "semi": bool} of an edit-distance pathwise mode for long reads, None for every other value."""
+    return {MODE_PATHWISE_EDIT_XLONG: {"valid": True, "semi": False}, MODE_PATHWISE_EDIT_SEMI_XLONG: {"valid": True, "semi": True}}.get(mode)
+
+
 def unit_costs(table, gap_open, gap_ext):
-    """What modes 44 / 45 admit: gap_open 0, gap_ext -1 and a 36-entry score table whose ACGTN x ACGTN block holds 0 and -1 only."""
+    """What modes 44 / 45 (and 94 / 95) admit: gap_open 0, gap_ext -1 and a 36-entry score table whose ACGTN x ACGTN block holds 0 and -1 only."""
     return gap_open == 0 and gap_ext == -1 and all(table[a * 6 + b] in (0, -1) for a in range(5) for b in range(5))
 
 

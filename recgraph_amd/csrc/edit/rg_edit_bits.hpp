@@ -120,4 +120,30 @@ RG_EDIT_HD void edit_finish(const uint32_t (&eq)[W], uint32_t (&pv)[W], uint32_t
     }
 }
 
+// ---- THE STRIPED ROW STEP (edit_xlong/rg_path_edit_xlong.hip; tests/c/edit_xlong_bits_check.cpp) ---------------------------------
+// A row longer than one vector is cut into stripes of 64 * 32 W bits, each a vector of its own: Myers' block step.  Stripe s > 0
+// takes from its left neighbour hin in {-1, 0, +1}: how the stripe's column 0 — the neighbour's last column — changed from the row
+// above, i.e. the neighbour's top bit of the UNSHIFTED Ph (+1) / Mh (-1) of this row (edit_hout).  Stripe 0 takes the border: +1 in
+// the global kind, 0 in the semiglobal kind.  What hin changes, derived from the cell recurrence with v = value[i-1][c0], the
+// stripe's column 0 in the row above (Pv / Mv are differences along the row, so v itself never enters):
+//   * hin = -1: value[i][c0] = v - 1, and column c0 + 1 of this row is at most v (one L from there) and at least v (no value lies
+//     below its diagonal): it EQUALS its diagonal whatever the bases say.  That is what a match at bit 0 gives, and from bit 0 on
+//     the chain "equal to the diagonal, and the row above goes up by one" runs on through the addition exactly as from a match: bit 0
+//     of Eq is set FOR THE Xh TERM.  Xv = Eq | Mv keeps the real Eq: whether column c0 + 1 goes DOWN from its left neighbour in the
+//     new row follows from Ph / Mh shifted, not from this help bit.
+//   * the shift: bit 0 of the shifted Ph / Mh is the vertical change of the column to the LEFT of bit 0, which is column c0: Ph takes
+//     (hin > 0), Mh takes (hin < 0).  The unstriped step hard-wires the latter to 0: column 0 of the read never goes down.
+//   * the wide addition's carry does not cross a stripe: the carry of a block is the chain above running on past its top bit, and
+//     whether it does is exactly what the neighbour's hin = -1 says (a chain that reaches the stripe's last column makes that column
+//     equal to its diagonal with the row above going up: the column goes down by one, Mh's top bit).
+// Ph, Mh and D0 of edit_deltas keep their meaning bit for bit (D0 bit 0 = 1 for hin = -1 is the equality above), so a walk reads a
+// stripe's words as it reads the whole vector's.
+RG_EDIT_HD uint32_t edit_hin_eq0(uint32_t eq0, int hin) { return eq0 | (hin < 0 ? 1u : 0u); }
+RG_EDIT_HD uint32_t edit_hin_pin(int hin) { return hin > 0 ? 1u : 0u; }
+RG_EDIT_HD uint32_t edit_hin_nin(int hin) { return hin < 0 ? 1u : 0u; }
+// the hin of the stripe to the right: the top words of the last chunk's UNSHIFTED Ph and Mh (the two bits exclude each other)
+RG_EDIT_HD int edit_hout(uint32_t ph_top, uint32_t mh_top) { return (int)(ph_top >> 31) - (int)(mh_top >> 31); }
+// the same out of two masks of 64 rows each (bit u: row u of the block went up / down), as the stripes exchange it
+RG_EDIT_HD int edit_hin_of_masks(uint64_t up, uint64_t down, int u) { return (int)((up >> u) & 1u) - (int)((down >> u) & 1u); }
+
 }  // namespace rg

@@ -36,70 +36,7 @@ namespace {
 
 #include "../gap/rg_path_gap_common.hpp"           // GNEG, row_index, no_record, write_record, RG_SWITCH_C
 
-// code of a read base -> bit b: the table scores path base b against it with 0 (codes 5 .. 7: nothing matches), in LDS
-__device__ __forceinline__ void load_match_bits(const GapArgs& a, int lane, int* mbits) {
-    if (lane < 8) {
-        int m = 0;
-#pragma unroll
-        for (int b = 0; b < 5; ++b) m |= (lane < 5 && a.sc.t[b * 6 + (lane < 5 ? lane : 0)] == 0) ? 1 << b : 0;
-        mbits[lane] = m;
-    }
-    __syncthreads();
-}
-
-// the lane's chunk of the row state, and the pieces of the row step around their cross-lane exchanges
-template <int W>
-struct EditLane {
-    uint32_t peq[5][W], pv[W], mv[W];
-
-    __device__ __forceinline__ void load(const uint8_t* read /* read[0 .. n) */, int n, int lane, const int* mbits) {
-#pragma unroll
-        for (int k = 0; k < W; ++k) {
-            uint32_t e0 = 0, e1 = 0, e2 = 0, e3 = 0, e4 = 0;
-            const int c0 = (lane * W + k) * 32;
-#pragma unroll 8
-            for (int t = 0; t < 32; ++t) {
-                const int m = c0 + t < n ? mbits[read[c0 + t] & 7] : 0;
-                e0 |= (uint32_t)(m & 1) << t;
-                e1 |= (uint32_t)((m >> 1) & 1) << t;
-                e2 |= (uint32_t)((m >> 2) & 1) << t;
-                e3 |= (uint32_t)((m >> 3) & 1) << t;
-                e4 |= (uint32_t)((m >> 4) & 1) << t;
-            }
-            peq[0][k] = e0; peq[1][k] = e1; peq[2][k] = e2; peq[3][k] = e3; peq[4][k] = e4;
-            pv[k] = ~0u;
-            mv[k] = 0;
-        }
-    }
-    // Eq of path base b (wave-uniform): Peq[b], as five scalar masks of which one is all ones — an index would move Peq out of the
-    // registers, and a chain of selects on the uniform b is compiled into a tree of scalar branches per word (two dozen scalar
-    // instructions each).  The empty asm hides where a mask comes from, so that the AND stays an AND
-    __device__ __forceinline__ void match(int b, uint32_t (&eq)[W]) const {
-        uint32_t sel[5];
-#pragma unroll
-        for (int x = 0; x < 5; ++x) {
-            int s = ((b ^ x) - 1) >> 31;            // b == x ? -1 : 0 (0 <= b <= 4), in scalar integer arithmetic
-            asm("" : "+s"(s));
-            sel[x] = (uint32_t)s;
-        }
-#pragma unroll
-        for (int k = 0; k < W; ++k) eq[k] = (peq[0][k] & sel[0]) | (peq[1][k] & sel[1]) | (peq[2][k] & sel[2]) | (peq[3][k] & sel[3]) | (peq[4][k] & sel[4]);
-    }
-    // the first two pieces: the chunk's sum, the carries of all lanes, Ph / Mh (unshifted) and D0
-    __device__ __forceinline__ void deltas(const uint32_t (&eq)[W], int lane, uint32_t (&ph)[W], uint32_t (&mh)[W], uint32_t (&d0)[W]) const {
-        uint32_t sum[W];
-        const uint32_t g = edit_sum<W>(eq, pv, sum);
-        const bool p = edit_chunk_all_ones<W>(sum);
-        const uint64_t cm = edit_carry_mask(__ballot(g != 0), __ballot(p));
-        edit_deltas<W>(eq, pv, mv, sum, (uint32_t)(cm >> lane) & 1u, ph, mh, d0);
-    }
-    // the third piece (ph and mh come back shifted)
-    __device__ __forceinline__ void finish(const uint32_t (&eq)[W], uint32_t hin, uint32_t (&ph)[W], uint32_t (&mh)[W]) {
-        const uint32_t pin = (uint32_t)dpp_shr1((int)(ph[W - 1] >> 31), (int)hin);
-        const uint32_t nin = (uint32_t)dpp_shr1((int)(mh[W - 1] >> 31), 0);
-        edit_finish<W>(eq, pv, mv, ph, mh, pin, nin);
-    }
-};
+#include "rg_path_edit_lane.hpp"                    // load_match_bits, EditLane<W>
 
 }  // namespace
 

@@ -334,7 +334,7 @@ struct PathwiseWalk {
 inline char base_at(const uint8_t* codes, int n, int col) { return col == 0 ? '$' : "ACGTN"[codes[(size_t)col - 1]]; }
 
 void walk_pathwise(const HostGraph& g, const uint8_t* codes, int n, const ReadRecord& r, int mode, PathwiseScratch& sc, PathwiseWalk& w) {
-    mode = path_gap_base_mode(edit_base_mode(mode));       // (every family of an affine-gap rule, and -m 44 / -m 45: the record and the line of its base mode)
+    mode = path_gap_base_mode(edit_base_mode(mode));       // (every family of an affine-gap rule, and -m 44 / -m 45 / -m 94 / -m 95: the record and the line of its base mode)
     const size_t cap = (size_t)std::max(r.n_ops, 1);
     if (sc.ops.size() < cap) { sc.ops.resize(cap); sc.pseq.resize(cap); sc.ids.resize(cap); }
     char* ops = sc.ops.data();

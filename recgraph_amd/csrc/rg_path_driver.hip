@@ -13,6 +13,8 @@
 //          strand; TRACE = gap_seed_pick -> the rest of the pipeline, run once (gap_xstrands/rg_gap_xstrands.hip; the stages of a batch:
 //          rg_strand_driver.hip)
 //   -m 44: edit_score(every path) -> gap_pick -> edit_dirs(picked path) -> edit_trace        (edit/rg_path_edit.hip; -m 45 likewise)
+//   -m 94: the same up to 16383 bases; a batch with a longer read: edit_score_xlong -> gap_pick -> (edit_redo_xlong -> edit_walk_xlong)
+//          per stripe, last to first                                                        (edit_xlong/rg_path_edit_xlong.hip; -m 95 likewise)
 //   -m 8:  sweep(F1: column maxima) -> seed -> thr -> sweep(R: dirs, candidates, column maxima)
 //          -> thr -> sweep(F2: dirs, candidates) -> search -> layer(F) -> layer(R) -> trace
 #include <algorithm>
@@ -27,6 +29,7 @@
 #include "gap_xlong/rg_path_gap_xlong.hpp"
 #include "gap_xstrands/rg_gap_xstrands.hpp"
 #include "edit/rg_path_edit.hpp"
+#include "edit_xlong/rg_path_edit_xlong.hpp"
 #include "rg_kernel_timer.hpp"
 #include "rg_path_kernels.hpp"
 #include "rg_path_plan.hpp"
@@ -42,6 +45,8 @@ struct PathWorkImpl {
     DevBuf<int> gbnd, gdbnd;            // the long family: the stripe boundaries of the score pass and of the direction pass
     DevBuf<int> gckpt;                  // the xlong family: per stripe but the last, what it leaves to its right neighbour (picked path)
     DevBuf<GapWalkState> gwalk;         // ... and where each read's walk stands between two rounds
+    DevBuf<unsigned long long> ebnd;    // -m 94 / -m 95: the boundary bits of every path's stripes but the last
+    DevBuf<EditWalkState> ewalk;        // ... and where each read's walk stands between two rounds
     DevBuf<Cand> fcand, rcand;
     DevBuf<unsigned> nf, nr, ridx, nrec, nrrec;
     DevBuf<int> frec, rrec;
@@ -111,6 +116,7 @@ struct Run {
     int enqueue_pathwise(const SweepArgs& sa, const SeedArgs& se);
     int enqueue_pathwise_gap();
     int enqueue_pathwise_edit();
+    int enqueue_pathwise_edit_xlong();
     int read_back();
     int enqueue_recombination(SweepArgs& sa, const SeedArgs& se);
     int enqueue_forward_bounded(SweepArgs& sa, const SeedArgs& se);
@@ -167,6 +173,7 @@ int Run::alloc_chunk(bool* oom) {
     int rc;
     if (plan.edit) {
         if ((rc = w.state.alloc(n, oom)) || (rc = w.gdirs.alloc(n * (size_t)plan.gdirs_stride, oom))) return rc;
+        if (plan.edit_xlong && ((rc = w.ebnd.alloc(n * (size_t)plan.edit_bnd_stride, oom)) || (rc = w.ewalk.alloc(n, oom)))) return rc;
         return RG_OK;
     }
     if (plan.gap) {
@@ -346,6 +353,29 @@ int Run::enqueue_pathwise_edit() {
     RG_TRY(T.run("k_gap_pick", [&] { return launch_gap_pick(ga, chunk, 64 * W, semi, stream); }));
     RG_TRY(T.run("k_edit_dirs", [&] { return launch_edit_dirs(ga, chunk, W, semi, stream); }));
     RG_TRY(T.run("k_edit_trace", [&] { return launch_edit_trace(ga, chunk, W, semi, stream); }));
+    return read_back();
+}
+
+// -m 94 / -m 95 with a read over 16383 bases:  edit_score_xlong(every path) -> gap_pick -> per stripe, last to first, the rebuild and
+// the walk (no read-back in between: a read whose walk is elsewhere returns at once) -> the chunk's one read-back
+int Run::enqueue_pathwise_edit_xlong() {
+    static_assert(sizeof(EditWalkState) == 32, "the plan counts 32 bytes of walk state per read");
+    EditXLongArgs xa;
+    memset(&xa, 0, sizeof xa);
+    GapArgs& ga = xa.g;
+    ga.sc = sc; ga.lnz = gd.lnz; ga.reads = d_reads; ga.read_off = off(); ga.bad = bad(); ga.poff = w.fpoff.p; ga.prow = w.fprow.p;
+    ga.P = h.P; ga.o = p.gap_open; ga.e = p.gap_ext; ga.state = w.state.p; ga.dirs = w.gdirs.p; ga.dirs_stride = plan.gdirs_stride;
+    ga.cells = d_cells; ga.rec = d_rec + done; ga.ops = d_ops ? d_ops + (long long)done * ops_stride : nullptr; ga.ops_stride = ops_stride;
+    xa.S = plan.nwv; xa.rows1 = h.max_path_rows + 1;
+    xa.bnd = w.ebnd.p; xa.bnd_stride = plan.edit_bnd_stride; xa.slot_words = plan.edit_slot_words; xa.walk = w.ewalk.p;
+    const bool semi = plan.semi;
+    RG_TRY(T.run("k_edit_score_xlong", [&] { return launch_edit_score_xlong(xa, chunk, semi, stream); }));
+    // (the pick kernel's width, in 64s: above the 16384 S bases of a lane layout that has no column 0, as in enqueue_pathwise_edit)
+    RG_TRY(T.run("k_gap_pick", [&] { return launch_gap_pick(ga, chunk, 64 * EDIT_MAX_WORDS * plan.nwv, semi, stream); }));
+    for (int round = plan.nwv - 1; round >= 0; --round) {
+        RG_TRY(T.run("k_edit_redo_xlong", [&] { return launch_edit_redo_xlong(xa, chunk, semi, round, stream); }));
+        RG_TRY(T.run("k_edit_walk_xlong", [&] { return launch_edit_walk_xlong(xa, chunk, semi, round, stream); }));
+    }
     return read_back();
 }
 
@@ -529,7 +559,7 @@ int Run::read_back() {
 int Run::enqueue_chunk() {
     HIPCHK(hipMemsetAsync(w.state.p, 0, sizeof(ReadState) * chunk, stream));
     if (plan.gap) return enqueue_pathwise_gap();
-    if (plan.edit) return enqueue_pathwise_edit();
+    if (plan.edit) return plan.edit_xlong ? enqueue_pathwise_edit_xlong() : enqueue_pathwise_edit();
     SweepArgs sa = sweep_args();
     SeedArgs se;
     se.g = gd; se.state = w.state.p; se.nreads = chunk; se.mode = p.mode; se.sc = sc; se.reads = d_reads; se.read_off = off();

@@ -134,20 +134,27 @@ static int plan_pathwise_gap(const rg_params& p, const GapMode& gm, const PathPl
 
 // The edit-distance modes (rg_edit_modes.hpp): the rules of modes 16 / 17 at unit costs, one bit per cell.  One wave per (read, path)
 // keeps the whole read in its registers, 32 W columns per lane; the only HBM work buffer beside ReadState holds D0 and Ph of the picked
-// path's rows, 2 bits per cell.
+// path's rows, 2 bits per cell.  -m 94 / -m 95: the same up to 16383 bases; beyond, stripes of 16384 columns (PathPlan::edit_xlong).
 const char* const kEditScoreRefusal =
     "the edit-distance pathwise modes (-m 44 / -m 45) take unit costs only: gap_open 0, gap_ext -1 and every ACGTN x ACGTN score 0 or -1 "
     "(-M 0 -X 1 -O 0 -E 1, or a 0 / -1 matrix); every other scoring is what -m 16 / -m 17 are for";
+const char* const kEditXLongScoreRefusal =
+    "the edit-distance pathwise modes (-m 94 / -m 95) take unit costs only: gap_open 0, gap_ext -1 and every ACGTN x ACGTN score 0 or -1 "
+    "(-M 0 -X 1 -O 0 -E 1, or a 0 / -1 matrix); every other scoring is what -m 56 / -m 57 are for";
 int plan_pathwise_edit(const rg_params& p, const PathPlanInput& in, PathPlan& o) {
-    const EditMode em = edit_mode(p.mode);
+    const bool xlong = edit_xlong_mode(p.mode).valid;
+    const EditMode em = edit_any_mode(p.mode);
     if (!em.valid) return fail(RG_ERR_ARG, "unsupported mode");
     if (p.gap_open > 0 || p.gap_ext > 0) return fail(RG_ERR_ARG, "gap penalties must be <= 0");
     bool unit = p.gap_open == 0 && p.gap_ext == -1;
     for (int x = 0; x < 5; ++x)
         for (int y = 0; y < 5; ++y) unit = unit && (p.scores[x * 6 + y] == 0 || p.scores[x * 6 + y] == -1);
-    if (!unit) return fail(RG_ERR_ARG, kEditScoreRefusal);
-    if (p.amb_mode != 0) return fail(RG_ERR_ARG, "amb_mode must be 0 in the edit-distance pathwise modes (-m 44 / -m 45): they align the reads as given");
-    if (in.max_n > EDIT_MAX_READ) return fail(RG_ERR_ARG, "reads longer than 16383 bases are not supported by the edit-distance pathwise modes (-m 44 / -m 45)");
+    if (!unit) return fail(RG_ERR_ARG, xlong ? kEditXLongScoreRefusal : kEditScoreRefusal);
+    if (p.amb_mode != 0)
+        return fail(RG_ERR_ARG, xlong ? "amb_mode must be 0 in the edit-distance pathwise modes (-m 94 / -m 95): they align the reads as given"
+                                      : "amb_mode must be 0 in the edit-distance pathwise modes (-m 44 / -m 45): they align the reads as given");
+    if (!xlong && in.max_n > EDIT_MAX_READ) return fail(RG_ERR_ARG, "reads longer than 16383 bases are not supported by the edit-distance pathwise modes (-m 44 / -m 45)");
+    if (in.max_n > EDIT_XLONG_MAX_READ) return fail(RG_ERR_ARG, "reads longer than 131071 bases are not supported by the edit-distance pathwise modes (-m 94 / -m 95)");
     // mode 16's budget, at max(|sc|, |o + e|) = 1: what it refuses is refused here
     if ((long long)in.max_path_rows + in.max_n >= (1ll << 28))
         return fail(RG_ERR_CAPACITY, "scores of this batch can reach 2^28 in magnitude: outside the i32 range of the affine-gap pathwise kernels");
@@ -155,13 +162,25 @@ int plan_pathwise_edit(const rg_params& p, const PathPlanInput& in, PathPlan& o)
     o.mode = RG_MODE_PATHWISE_EDIT;
     o.semi = em.semi;
     int W = 1;
-    while (2048 * W < in.max_n) W *= 2;
+    while (2048 * W < in.max_n && W < EDIT_MAX_WORDS) W *= 2;
     o.edit_words = W;
     o.C = 32 * W;                 // columns per lane
     o.nwv = 1;
     o.wpad = 2048 * W;
     o.gdirs_stride = (long long)(in.max_path_rows + 1) * 2 * W * WAVE;
     o.per_read = (size_t)o.gdirs_stride * 4 + sizeof(ReadState);
+    if (in.max_n > EDIT_MAX_READ) {
+        // edit_xlong/rg_path_edit_xlong.hip: D0 and Ph of ONE stripe (the words above, at W = 8), the boundary slots of every path
+        // and stripe but the last, and the walk state
+        o.edit_xlong = true;
+        // (16384 bases fill one stripe to its last bit: such a batch still runs the striped kernels, its second stripe empty)
+        o.nwv = std::max(2, (in.max_n + EDIT_XLONG_STRIPE - 1) / EDIT_XLONG_STRIPE);
+        o.wpad = o.nwv * EDIT_XLONG_STRIPE;
+        o.edit_slot_words = (2 * ((in.max_path_rows + 63) / 64) + 15) / 16 * 16;
+        o.edit_bnd_stride = (long long)in.P * (o.nwv - 1) * o.edit_slot_words;
+        o.gwalk_bytes = 32;
+        o.per_read += (size_t)o.edit_bnd_stride * 8 + o.gwalk_bytes;
+    }
     return RG_OK;
 }
 
@@ -180,7 +199,7 @@ int plan_pathwise(const rg_params& p, const PathPlanInput& in, const Options& op
     o = PathPlan{};
     const GapMode gm = gap_mode(p.mode);
     if (gm.valid) return plan_pathwise_gap(p, gm, in, o);
-    if (edit_mode(p.mode).valid) return plan_pathwise_edit(p, in, o);
+    if (edit_any_mode(p.mode).valid) return plan_pathwise_edit(p, in, o);
     const int P = in.P, L = in.L, max_n = in.max_n;
     o.semi = p.mode == RG_MODE_PATHWISE_SEMI || p.mode == RG_MODE_RECOMBINATION_SEMI;
     o.mode = p.mode == RG_MODE_PATHWISE_SEMI ? RG_MODE_PATHWISE : p.mode == RG_MODE_RECOMBINATION_SEMI ? RG_MODE_RECOMBINATION : p.mode;

@@ -81,6 +81,14 @@ struct PathPlan {
     // words, the only work buffer beside ReadState.  `gap` stays false: none of the affine-gap kernels but the pick runs
     bool edit;
     int edit_words;
+    // -m 94 / -m 95 (edit_xlong/rg_path_edit_xlong.hip) when the longest read has more than 16383 bases — otherwise the plan IS the one
+    // of -m 44 / -m 45: edit_words = 8, C = 256, nwv = S = max(2, ceil(max_n / 16384)) <= 8 column stripes walked by ONE wave, gdirs_stride =
+    // (rows + 1) * 16 * 64 words (ONE stripe); per (path, stripe but the last) a slot of edit_slot_words u64 that holds two bits per
+    // row as two masks per 64 rows (2 * ceil(rows / 64), rounded up to a 128-byte line so that no two waves share one): edit_bnd_stride
+    // = P * (S - 1) * edit_slot_words u64 per read; gwalk_bytes: the walk state of a read
+    bool edit_xlong;
+    int edit_slot_words;
+    long long edit_bnd_stride;
 
     // ... with candidate lists of fcap / rcap entries and record lists of frec_cap / rrec_cap records
     size_t per_read_all(unsigned fcap_, unsigned rcap_, unsigned frec_cap_, unsigned rrec_cap_) const {
@@ -95,7 +103,8 @@ struct PathPlan {
 int plan_pathwise(const rg_params& p, const PathPlanInput& in, const Options& opt, int spec_level, PathPlan& out);
 // The plan of the edit-distance modes (what plan_pathwise returns for -m 44 / -m 45), with every refusal of theirs: gap costs other than
 // (0, -1) or an ACGTN x ACGTN entry other than 0 / -1, an amb_mode bit, a read over 16383 bases (RG_ERR_ARG), mode 16's 2^28 budget
-// (RG_ERR_CAPACITY).  `out` must be a cleared plan
+// (RG_ERR_CAPACITY).  -m 94 / -m 95: the same refusals with the limit at 131071 bases, the plan of -m 44 / -m 45 up to 16383 bases and
+// the striped one (PathPlan::edit_xlong) beyond.  `out` must be a cleared plan
 int plan_pathwise_edit(const rg_params& p, const PathPlanInput& in, PathPlan& out);
 
 // The stages of an affine-gap pipeline (PathJob::stage, rg_path_args.hpp).  PICK: score pass + pick, and the pick goes out into the

@@ -3,7 +3,7 @@
 engine on other read lengths, score parameters and path counts, with the sweep kernel that ran and a parity check of a
 few reads against the oracle.  One JSON line per case.
 
-    python tools/region_bench.py [case ...]        cases: c5 x6 m3x5 hoxd70 len1500 p128 len600 gap gap_local gap_long gap_strands gap_xlong gap_xstrands edit (default: all but the strand cases, the six `gap` cases and `edit`)
+    python tools/region_bench.py [case ...]        cases: c5 x6 m3x5 hoxd70 len1500 p128 len600 gap gap_local gap_long gap_strands gap_xlong gap_xstrands edit edit_xlong (default: all but the strand cases, the six `gap` cases and the two `edit` cases)
 
 The strand cases (RG_AMB_BOTH_STRANDS, config-5 shape; `reads_per_s` counts SOURCE reads): `both_strands_fwd` — option on, every
 read forward (what the option costs when nothing qualifies: compare with `c5`); `both_strands` — option on, half of the reads
@@ -58,6 +58,12 @@ kernel timer.  (a) -m 44 beside -m 16 on the 512 reads of 4000 bases and the 16-
 (compared), time per batch, time per counted cell update, the time of every kernel, the score pass of -m 44 as a ratio to the other
 mode's per counted cell, and the work bytes per read.  Two reads of each part are checked against the rule
 (tests/pathwise_gap_rule.py at unit costs): the printed score is the rule's and the printed CIGAR re-scores to it.  One JSON line per part.
+
+`edit_xlong` (only when named): -m 94 beside -m 56 OF THE SAME BUILD at unit costs on the shape of `gap_xlong`'s part (b) — 32 reads of
+50 000 bases on 16 paths of about 50 000 rows — by the same protocol: one process, warm-up, alternating rounds, whole rg_batch_run calls,
+the handle's kernel timer.  All texts, statuses and counted cells of the two modes are compared; per mode: time per batch, time per
+counted cell update, performed over counted cells, the time of every kernel, the work bytes per read; and -m 94 as a ratio to -m 56.  One
+JSON line.
 
 Every case: TILES tiles of TILE reads through one rg_stream (3 handles), timed after one warm-up tile per handle."""
 import json
@@ -293,6 +299,51 @@ def edit_case():
         out["same_texts_and_counters"] = bool(same)
         out["rule_checked"] = 2 if ok else "FAILED"
         print(json.dumps(out), flush=True)
+
+
+def edit_xlong_case():
+    from recgraph_amd import api, synth
+    unit = api.create_score_matrix_i32(0, -1)
+    rounds, paths, plen, nreads = 3, 16, 50000, 32
+    g = synth.haplotype_graph(3 * plen, paths, path_len=plen, seed=1234)
+    gg = api.Graph.from_gfa_text(g.gfa())
+    reads = synth.haplotype_reads(g, nreads, length=plen, seed=901, mosaic_frac=0.0)
+    modes = (api.MODE_PATHWISE_EDIT_XLONG, api.MODE_PATHWISE_GAP_XLONG)
+    batch = {m: api.Batch(gg, reads, api.make_params(m, score_matrix=unit, o=0, e=-1)) for m in modes}
+    times = {m: [] for m in modes}
+    ks = {m: {} for m in modes}
+    mem = {}
+    for m in modes:
+        batch[m].run()                           # warm-up: code objects, work buffers
+    for _ in range(rounds):
+        for m in modes:                          # alternating: both modes see the same machine
+            t0 = time.perf_counter()
+            batch[m].run()
+            times[m].append(time.perf_counter() - t0)
+            for k, v in batch[m].kernel_stats().items():
+                if k == "mem:work_bytes_per_read":
+                    mem[m] = v[0] / max(1, v[1])
+                if not k.startswith(("host:", "mem:", "inst:")):
+                    ks[m][k] = ks[m].get(k, 0.0) + v[0] / rounds
+    for m in modes:
+        batch[m].fetch()
+    b, o = batch[modes[0]], batch[modes[1]]
+    same = all(b.gaf_text(i, "r", 1) == o.gaf_text(i, "r", 1) and b.status(i) == o.status(i) == 0 and b.score(i) == o.score(i) for i in range(nreads))
+    same = same and b.cell_updates == o.cell_updates
+    med = {m: sorted(times[m])[rounds // 2] for m in modes}
+    out = {"case": "edit_xlong", "rows": gg.rows, "paths": paths, "reads": nreads, "read_len": plen, "rounds": rounds,
+           "stripes": {"m94": (max(len(r) for r in reads) + 16383) // 16384, "m56": (max(len(r) for r in reads) + 2048) // 2048}}
+    for m in modes:
+        bm = batch[m]
+        out["m%d" % m] = {"ms_per_batch_median": round(med[m] * 1e3, 2), "ms_per_batch_min": round(min(times[m]) * 1e3, 2),
+                          "counted_cell_updates": bm.cell_updates, "ps_per_counted_cell_update": round(med[m] / bm.cell_updates * 1e12, 3),
+                          "performed_over_counted": round(bm.cell_updates_performed / bm.cell_updates, 3),
+                          "kernel_ms_per_batch": {k: round(v, 3) for k, v in ks[m].items()}, "work_bytes_per_read": int(mem.get(m, 0))}
+    out["m94_over_m56_time_per_batch_median"] = round(med[modes[0]] / med[modes[1]], 4)
+    out["m94_over_m56_time_per_batch_min"] = round(min(times[modes[0]]) / min(times[modes[1]]), 4)
+    out["k_edit_score_xlong_over_k_gap_score_long"] = round(ks[modes[0]]["k_edit_score_xlong"] / ks[modes[1]]["k_gap_score_long"], 4)
+    out["same_texts_statuses_scores_and_counted_cells"] = bool(same)
+    print(json.dumps(out), flush=True)
 
 
 def gap_xlong_case():
@@ -545,6 +596,11 @@ def gap_strands_case():
 def main():
     from recgraph_amd import api, synth
     from oracle import oracle as O
+    if "edit_xlong" in sys.argv[1:]:
+        edit_xlong_case()
+        sys.argv = [a for a in sys.argv if a != "edit_xlong"]
+        if len(sys.argv) == 1:
+            return
     if "edit" in sys.argv[1:]:
         edit_case()
         sys.argv = [a for a in sys.argv if a != "edit"]
