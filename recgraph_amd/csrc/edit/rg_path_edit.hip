@@ -36,7 +36,7 @@ namespace {
 
 #include "../gap/rg_path_gap_common.hpp"           // GNEG, row_index, no_record, write_record, RG_SWITCH_C
 
-#include "rg_path_edit_lane.hpp"                    // load_match_bits, EditLane<W>
+#include "rg_path_edit_lane.hpp"                    // load_match_bits, EditLane<W>, store_row
 
 }  // namespace
 
@@ -66,13 +66,13 @@ __global__ __launch_bounds__(64) void k_edit_score(GapArgs a) {
             const int b = __builtin_amdgcn_readlane(myb, u);
             uint32_t eq[W], ph[W], mh[W], d0[W];
             st.match(b, eq);
-            st.deltas(eq, lane, ph, mh, d0);
+            st.deltas(eq, kSemi ? 0 : 1, lane, ph, mh, d0);
             uint32_t up = 0, dn = 0;
 #pragma unroll
             for (int w = 0; w < W; ++w) { up |= ph[w] & nm[w]; dn |= mh[w] & nm[w]; }
             cur += (up != 0 ? 1 : 0) - (dn != 0 ? 1 : 0);
             if (kSemi && -cur > best) { best = -cur; bt = t0 + u; }      // strictly better: the first row that attains the maximum
-            st.finish(eq, kSemi ? 0u : 1u, ph, mh);
+            st.finish(eq, kSemi ? 0 : 1, ph, mh);
         }
     }
     if (lane == (n - 1) / (32 * W)) {
@@ -117,14 +117,9 @@ __global__ __launch_bounds__(64) void k_edit_dirs(GapArgs a) {
             const int b = __builtin_amdgcn_readlane(myb, u);
             uint32_t eq[W], ph[W], mh[W], d0[W];
             st.match(b, eq);
-            st.deltas(eq, lane, ph, mh, d0);
-            uint32_t* row = out + (long long)(t0 + u + 1) * (2 * W * WAVE) + lane;
-#pragma unroll
-            for (int w = 0; w < W; ++w) {
-                row[w * WAVE] = d0[w];
-                row[(W + w) * WAVE] = ph[w];
-            }
-            st.finish(eq, kSemi ? 0u : 1u, ph, mh);
+            st.deltas(eq, kSemi ? 0 : 1, lane, ph, mh, d0);
+            store_row<W>(out, t0 + u + 1, lane, d0, ph);
+            st.finish(eq, kSemi ? 0 : 1, ph, mh);
         }
     }
     if (lane == 0 && m > 0) atomicAdd(a.cells + 1, (unsigned long long)m * (unsigned long long)n);
@@ -181,25 +176,29 @@ __global__ __launch_bounds__(64) void k_edit_trace(GapArgs a, int W, int semi) {
 }
 
 // ---- launchers ---------------------------------------------------------------------------------------------------------------
-static bool geometry_ok(const GapArgs& a, int W) { return a.dirs && a.dirs_stride >= 2ll * W * WAVE && a.dirs_stride % (2 * W * WAVE) == 0; }
+// the word counts that exist, stated once: every launcher checks W through words_ok, and the dispatch of the two templates lists the same
+#define RG_EDIT_WORDS 1, 2, 4, 8
+static bool words_ok(int W) { for (const int w : {RG_EDIT_WORDS}) if (w == W) return true; return false; }
+static bool geometry_ok(const GapArgs& a, int W) { return words_ok(W) && a.dirs && a.dirs_stride >= 2ll * W * WAVE && a.dirs_stride % (2 * W * WAVE) == 0; }
 
 const char* launch_edit_score(const GapArgs& a, int nreads, int W, bool semi, hipStream_t s) {
+    if (!words_ok(W)) return nullptr;
     const dim3 grid(a.P, nreads);
     const int C = W;                                 // (the dispatch macro switches on `C`)
-    if (semi) RG_SWITCH_C((1, 2, 4, 8), k_edit_score, (, true), grid, dim3(WAVE), 0, s, a);
-    else RG_SWITCH_C((1, 2, 4, 8), k_edit_score, (, false), grid, dim3(WAVE), 0, s, a);
+    if (semi) RG_SWITCH_C((RG_EDIT_WORDS), k_edit_score, (, true), grid, dim3(WAVE), 0, s, a);
+    else RG_SWITCH_C((RG_EDIT_WORDS), k_edit_score, (, false), grid, dim3(WAVE), 0, s, a);
     return nullptr;
 }
 const char* launch_edit_dirs(const GapArgs& a, int nreads, int W, bool semi, hipStream_t s) {
     if (!geometry_ok(a, W)) return nullptr;
     const dim3 grid(nreads);
     const int C = W;
-    if (semi) RG_SWITCH_C((1, 2, 4, 8), k_edit_dirs, (, true), grid, dim3(WAVE), 0, s, a);
-    else RG_SWITCH_C((1, 2, 4, 8), k_edit_dirs, (, false), grid, dim3(WAVE), 0, s, a);
+    if (semi) RG_SWITCH_C((RG_EDIT_WORDS), k_edit_dirs, (, true), grid, dim3(WAVE), 0, s, a);
+    else RG_SWITCH_C((RG_EDIT_WORDS), k_edit_dirs, (, false), grid, dim3(WAVE), 0, s, a);
     return nullptr;
 }
 const char* launch_edit_trace(const GapArgs& a, int nreads, int W, bool semi, hipStream_t s) {
-    if ((W != 1 && W != 2 && W != 4 && W != 8) || !geometry_ok(a, W)) return nullptr;
+    if (!geometry_ok(a, W)) return nullptr;
     RG_LAUNCH0(k_edit_trace, dim3(nreads), dim3(WAVE), 0, s, a, W, semi ? 1 : 0);
 }
 

@@ -39,7 +39,7 @@ namespace {
 
 #include "../gap/rg_path_gap_common.hpp"           // GNEG, row_index, no_record, write_record
 
-#include "../edit/rg_path_edit_lane.hpp"           // load_match_bits, EditLane<W>
+#include "../edit/rg_path_edit_lane.hpp"           // load_match_bits, EditLane<W>, store_row
 
 constexpr int XW = EDIT_MAX_WORDS;
 constexpr int XSTRIPE = EDIT_XLONG_STRIPE;
@@ -123,7 +123,7 @@ __global__ __launch_bounds__(64) void k_edit_score_xlong(EditXLongArgs xa) {
                 const int hin = hb.hin(u);
                 uint32_t eq[W], ph[W], mh[W], d0[W];
                 st.match(b, eq);
-                st.deltas_hin(eq, hin, lane, ph, mh, d0);
+                st.deltas(eq, hin, lane, ph, mh, d0);
                 if (last) {
                     uint32_t up = 0, dn = 0;
 #pragma unroll
@@ -134,7 +134,7 @@ __global__ __launch_bounds__(64) void k_edit_score_xlong(EditXLongArgs xa) {
                     upo |= (unsigned long long)(ph[W - 1] >> 31) << u;
                     dno |= (unsigned long long)(mh[W - 1] >> 31) << u;
                 }
-                st.finish_hin(eq, hin, ph, mh);
+                st.finish(eq, hin, ph, mh);
             }
             if (!last && lane == WAVE - 1) {
                 to[2 * (t0 >> 6)] = upo;
@@ -193,14 +193,9 @@ __global__ __launch_bounds__(64) void k_edit_redo_xlong(EditXLongArgs xa, int se
             const int hin = hb.hin(u);
             uint32_t eq[W], ph[W], mh[W], d0[W];
             st.match(b, eq);
-            st.deltas_hin(eq, hin, lane, ph, mh, d0);
-            uint32_t* row = out + (long long)(t0 + u + 1) * (2 * W * WAVE) + lane;
-#pragma unroll
-            for (int w = 0; w < W; ++w) {
-                row[w * WAVE] = d0[w];
-                row[(W + w) * WAVE] = ph[w];
-            }
-            st.finish_hin(eq, hin, ph, mh);
+            st.deltas(eq, hin, lane, ph, mh, d0);
+            store_row<W>(out, t0 + u + 1, lane, d0, ph);
+            st.finish(eq, hin, ph, mh);
         }
     }
     if (lane == 0 && m > 0) {

@@ -112,6 +112,7 @@ struct Run {
     int alloc_chunk(bool* oom);
     int enqueue_chunk();
     SweepArgs sweep_args() const;
+    GapArgs gap_args() const;
     const char* sweep(const SweepArgs& sa);     // (what it launched, like the launchers: rg_launch_log.hpp)
     int enqueue_pathwise(const SweepArgs& sa, const SeedArgs& se);
     int enqueue_pathwise_gap();
@@ -234,6 +235,16 @@ SweepArgs Run::sweep_args() const {
     return sa;
 }
 
+// what the kernels of the affine-gap and edit-distance families take of the chunk (the edit kernels read neither o nor e)
+GapArgs Run::gap_args() const {
+    GapArgs ga;
+    memset(&ga, 0, sizeof ga);
+    ga.sc = sc; ga.lnz = gd.lnz; ga.reads = d_reads; ga.read_off = off(); ga.bad = bad(); ga.poff = w.fpoff.p; ga.prow = w.fprow.p;
+    ga.P = h.P; ga.o = p.gap_open; ga.e = p.gap_ext; ga.state = w.state.p; ga.dirs = w.gdirs.p; ga.dirs_stride = plan.gdirs_stride;
+    ga.cells = d_cells; ga.rec = d_rec + done; ga.ops = d_ops ? d_ops + (long long)done * ops_stride : nullptr; ga.ops_stride = ops_stride;
+    return ga;
+}
+
 const char* Run::sweep(const SweepArgs& sa) {
     // (striped sweeps advance the candidate counter of a read atomically from several waves: start it at zero)
     if (plan.nwv > 1 && sa.cand && sa.ncand_out) {
@@ -267,11 +278,7 @@ int Run::enqueue_pathwise(const SweepArgs& sa, const SeedArgs& se) {
 
 // -m 6 / -m 7 / -m 12:  gap_score(every path) -> gap_pick -> gap_dirs(picked path) -> gap_trace -> the chunk's one read-back
 int Run::enqueue_pathwise_gap() {
-    GapArgs ga;
-    memset(&ga, 0, sizeof ga);
-    ga.sc = sc; ga.lnz = gd.lnz; ga.reads = d_reads; ga.read_off = off(); ga.bad = bad(); ga.poff = w.fpoff.p; ga.prow = w.fprow.p;
-    ga.P = h.P; ga.o = p.gap_open; ga.e = p.gap_ext; ga.state = w.state.p; ga.dirs = w.gdirs.p; ga.dirs_stride = plan.gdirs_stride;
-    ga.cells = d_cells; ga.rec = d_rec + done; ga.ops = d_ops ? d_ops + (long long)done * ops_stride : nullptr; ga.ops_stride = ops_stride;
+    const GapArgs ga = gap_args();
     const int C = plan.C;
     const bool semi = plan.semi, local = plan.local;
     const int kind = local ? GAP_LOCAL : semi ? GAP_SEMI : GAP_GLOBAL;
@@ -340,11 +347,7 @@ int Run::enqueue_pathwise_gap() {
 
 // -m 44 / -m 45:  edit_score(every path) -> gap_pick -> edit_dirs(picked path) -> edit_trace -> the chunk's one read-back
 int Run::enqueue_pathwise_edit() {
-    GapArgs ga;
-    memset(&ga, 0, sizeof ga);
-    ga.sc = sc; ga.lnz = gd.lnz; ga.reads = d_reads; ga.read_off = off(); ga.bad = bad(); ga.poff = w.fpoff.p; ga.prow = w.fprow.p;
-    ga.P = h.P; ga.o = p.gap_open; ga.e = p.gap_ext; ga.state = w.state.p; ga.dirs = w.gdirs.p; ga.dirs_stride = plan.gdirs_stride;
-    ga.cells = d_cells; ga.rec = d_rec + done; ga.ops = d_ops ? d_ops + (long long)done * ops_stride : nullptr; ga.ops_stride = ops_stride;
+    const GapArgs ga = gap_args();
     const int W = plan.edit_words;
     const bool semi = plan.semi;
     RG_TRY(T.run("k_edit_score", [&] { return launch_edit_score(ga, chunk, W, semi, stream); }));
@@ -362,16 +365,12 @@ int Run::enqueue_pathwise_edit_xlong() {
     static_assert(sizeof(EditWalkState) == 32, "the plan counts 32 bytes of walk state per read");
     EditXLongArgs xa;
     memset(&xa, 0, sizeof xa);
-    GapArgs& ga = xa.g;
-    ga.sc = sc; ga.lnz = gd.lnz; ga.reads = d_reads; ga.read_off = off(); ga.bad = bad(); ga.poff = w.fpoff.p; ga.prow = w.fprow.p;
-    ga.P = h.P; ga.o = p.gap_open; ga.e = p.gap_ext; ga.state = w.state.p; ga.dirs = w.gdirs.p; ga.dirs_stride = plan.gdirs_stride;
-    ga.cells = d_cells; ga.rec = d_rec + done; ga.ops = d_ops ? d_ops + (long long)done * ops_stride : nullptr; ga.ops_stride = ops_stride;
-    xa.S = plan.nwv; xa.rows1 = h.max_path_rows + 1;
+    xa.g = gap_args(); xa.S = plan.nwv; xa.rows1 = h.max_path_rows + 1;
     xa.bnd = w.ebnd.p; xa.bnd_stride = plan.edit_bnd_stride; xa.slot_words = plan.edit_slot_words; xa.walk = w.ewalk.p;
     const bool semi = plan.semi;
     RG_TRY(T.run("k_edit_score_xlong", [&] { return launch_edit_score_xlong(xa, chunk, semi, stream); }));
     // (the pick kernel's width, in 64s: above the 16384 S bases of a lane layout that has no column 0, as in enqueue_pathwise_edit)
-    RG_TRY(T.run("k_gap_pick", [&] { return launch_gap_pick(ga, chunk, 64 * EDIT_MAX_WORDS * plan.nwv, semi, stream); }));
+    RG_TRY(T.run("k_gap_pick", [&] { return launch_gap_pick(xa.g, chunk, 64 * EDIT_MAX_WORDS * plan.nwv, semi, stream); }));
     for (int round = plan.nwv - 1; round >= 0; --round) {
         RG_TRY(T.run("k_edit_redo_xlong", [&] { return launch_edit_redo_xlong(xa, chunk, semi, round, stream); }));
         RG_TRY(T.run("k_edit_walk_xlong", [&] { return launch_edit_walk_xlong(xa, chunk, semi, round, stream); }));

@@ -59,7 +59,7 @@ static WideRow wide_step(const Wide& eq, const Wide& pv, const Wide& mv, uint32_
 
 static int seen_hin[3];      // how often a stripe s > 0 took -1, 0, +1
 
-// one stripe as EditLane<8>::deltas_hin and finish_hin take it: words [w0, w0 + SW) of the vectors; returns what the next stripe takes
+// one stripe as EditLane<8>::deltas and finish take it with hin: words [w0, w0 + SW) of the vectors; returns what the next stripe takes
 static int stripe_step(const Wide& eq, const Wide& pv, const Wide& mv, int w0, int hin, WideRow& r) {
     static uint32_t e[L][W], p[L][W], m[L][W], sum[L][W], ph[L][W], mh[L][W], d0[L][W];
     uint64_t G = 0, P = 0;
