@@ -92,36 +92,44 @@ def gap_family_modes(*suffixes):
     return tuple(base + gap_family(s).offset for s in suffixes for _, base in GAP_RULES)
 
 
-# The bit-vector edit-distance pathwise modes (RG_MODE_PATHWISE_EDIT / RG_MODE_PATHWISE_EDIT_SEMI in include/recgraph_hip.h, the lookup of
-# csrc/rg_edit_modes.hpp once more): modes 16 / 17 restricted to unit costs.  No rows of the table above: gap_mode(44) is None.
-MODE_PATHWISE_EDIT, MODE_PATHWISE_EDIT_SEMI = 44, 45
-EDIT_MAX_READ = 16383
-EDIT_SCORE_REFUSAL = ("the edit-distance pathwise modes (-m 44 / -m 45) take unit costs only: -M 0 -X 1 -O 0 -E 1, or a -t matrix whose ACGTN x ACGTN "
-                      "entries are all 0 or -1 with -O 0 -E 1; every other scoring is what -m 16 / -m 17 are for")
-EDIT_STRANDS_REFUSAL = "%s is not available in the edit-distance pathwise modes (44, 45): they align the reads as given"
+# The bit-vector edit-distance pathwise modes (values of Params.mode, no entry points of their own): a rule in a family, `mode = the
+# rule's base mode + the family's offset`, each family a family of the table above restricted to unit costs.  The rows of
+# csrc/rg_edit_modes.hpp once more, with the fixed text of the Python side's refusals; DESIGN 4.14 has the table in words.  From it come
+# the MODE_PATHWISE_EDIT* names here and in api, api's tuples and flag rule, and the CLI's.  No rows of the table above: gap_mode(44) is None.
+EDIT_RULES = (("", 44), ("_SEMI", 45))      # (infix of the name, base mode): global, semiglobal
+EditFamily = collections.namedtuple("EditFamily", "suffix offset max_read gap_suffix score_refusal api_refusal cli_refusal cli_help")
+# max_read: the longest read, in bases; gap_suffix: the family of GAP_FAMILIES whose rule, bytes and read limit these are at unit costs;
+# score_refusal: what the CLI says to any other scoring; api_refusal (%s: the flag), cli_refusal: the reads are aligned as given
+_EDIT_SCORES = ("the edit-distance pathwise modes (%s) take unit costs only: -M 0 -X 1 -O 0 -E 1, or a -t matrix whose ACGTN x ACGTN "
+                "entries are all 0 or -1 with -O 0 -E 1; every other scoring is what %s are for")
+EDIT_FAMILIES = (
+    EditFamily("", 0, 16383, "_LONG", _EDIT_SCORES % ("-m 44 / -m 45", "-m 16 / -m 17"),
+               "%s is not available in the edit-distance pathwise modes (44, 45): they align the reads as given",
+               _CLI_AS_GIVEN % ("s 44 and 45", "they align"),
+               "44, 45: modes 16, 17 at unit costs (-M 0 -X 1 -O 0 -E 1 must be given) on the bit-vector kernels"),
+    EditFamily("_XLONG", 50, 131071, "_XLONG", _EDIT_SCORES % ("-m 94 / -m 95", "-m 56 / -m 57"),
+               "%s is not available in the edit-distance pathwise modes for reads of up to 131071 bases (94, 95): they align the reads as given",
+               _CLI_AS_GIVEN % ("s 94 and 95", "they align"),
+               "94, 95: those for reads of up to 131071 bases (modes 56, 57 at unit costs)"),
+)
+EditMode = collections.namedtuple("EditMode", "semi family")
+_EDIT_MODES = {base + f.offset: EditMode(bool(r), f) for f in EDIT_FAMILIES for r, (_, base) in enumerate(EDIT_RULES)}
+EDIT_MODE_NAMES = {"MODE_PATHWISE_EDIT%s%s" % (EDIT_RULES[m.semi][0], m.family.suffix): mode for mode, m in _EDIT_MODES.items()}
+globals().update(EDIT_MODE_NAMES)      # MODE_PATHWISE_EDIT = 44 ... MODE_PATHWISE_EDIT_SEMI_XLONG = 95 (RG_MODE_* in include/recgraph_hip.h)
 
 
 def edit_mode(mode):
-    """{"semi": bool} of an edit-distance pathwise mode, None for every other value."""
-    return {MODE_PATHWISE_EDIT: {"semi": False}, MODE_PATHWISE_EDIT_SEMI: {"semi": True}}.get(mode)
+    """EditMode(semi, family) of an edit-distance pathwise mode, None for every other value."""
+    return _EDIT_MODES.get(mode)
 
 
-# The same two rules for reads of up to 131071 bases (RG_MODE_PATHWISE_EDIT_XLONG / RG_MODE_PATHWISE_EDIT_SEMI_XLONG, edit_xlong_mode of
-# csrc/rg_edit_modes.hpp once more): modes 56 / 57 restricted to unit costs.  A lookup of their own: edit_mode(94) is None.
-MODE_PATHWISE_EDIT_XLONG, MODE_PATHWISE_EDIT_SEMI_XLONG = 94, 95
-EDIT_XLONG_MAX_READ = 131071
-EDIT_XLONG_SCORE_REFUSAL = ("the edit-distance pathwise modes (-m 94 / -m 95) take unit costs only: -M 0 -X 1 -O 0 -E 1, or a -t matrix whose ACGTN x ACGTN "
-                            "entries are all 0 or -1 with -O 0 -E 1; every other scoring is what -m 56 / -m 57 are for")
-EDIT_XLONG_STRANDS_REFUSAL = "%s is not available in the edit-distance pathwise modes for reads of up to 131071 bases (94, 95): they align the reads as given"
-
-
-def edit_xlong_mode(mode):
-    """{"valid": True, "semi": bool} of an edit-distance pathwise mode for long reads, None for every other value."""
-    return {MODE_PATHWISE_EDIT_XLONG: {"valid": True, "semi": False}, MODE_PATHWISE_EDIT_SEMI_XLONG: {"valid": True, "semi": True}}.get(mode)
+def edit_family_modes(suffix):
+    """The modes of the named family: global, semiglobal."""
+    return tuple(mode for mode, m in _EDIT_MODES.items() if m.family.suffix == suffix)
 
 
 def unit_costs(table, gap_open, gap_ext):
-    """What modes 44 / 45 (and 94 / 95) admit: gap_open 0, gap_ext -1 and a 36-entry score table whose ACGTN x ACGTN block holds 0 and -1 only."""
+    """What every edit-distance mode admits: gap_open 0, gap_ext -1 and a 36-entry score table whose ACGTN x ACGTN block holds 0 and -1 only."""
     return gap_open == 0 and gap_ext == -1 and all(table[a * 6 + b] in (0, -1) for a in range(5) for b in range(5))
 
 

@@ -49,13 +49,10 @@ MODE_GAP_LOCAL_POA = 3
 # _XSTRANDS
 globals().update(_lib.GAP_MODE_NAMES)
 
-# pathwise alignment at unit costs by Myers' bit-vector recurrence (RG_MODE_PATHWISE_EDIT / RG_MODE_PATHWISE_EDIT_SEMI): the bytes of
-# MODE_PATHWISE_GAP_LONG / MODE_PATHWISE_GAP_SEMI_LONG for gap costs (0, -1) and a 0 / -1 matrix, anything else is refused
-MODE_PATHWISE_EDIT = _lib.MODE_PATHWISE_EDIT
-MODE_PATHWISE_EDIT_SEMI = _lib.MODE_PATHWISE_EDIT_SEMI
-# ... and for reads of up to 131071 bases: the bytes of MODE_PATHWISE_GAP_XLONG / MODE_PATHWISE_GAP_SEMI_XLONG at those costs
-MODE_PATHWISE_EDIT_XLONG = _lib.MODE_PATHWISE_EDIT_XLONG
-MODE_PATHWISE_EDIT_SEMI_XLONG = _lib.MODE_PATHWISE_EDIT_SEMI_XLONG
+# pathwise alignment at unit costs by Myers' bit-vector recurrence (RG_MODE_PATHWISE_EDIT ... in include/recgraph_hip.h): for gap costs
+# (0, -1) and a 0 / -1 matrix the bytes of the gap family each row of _lib.EDIT_FAMILIES names, anything else is refused.
+# MODE_PATHWISE_EDIT, MODE_PATHWISE_EDIT_SEMI (those of _LONG), and the two again as _XLONG
+globals().update(_lib.EDIT_MODE_NAMES)
 
 READ_BAND_WARNING, READ_BAND_NOT_ENOUGH, READ_WOULD_PANIC, READ_BAD_BASE = 1, 2, 4, 8
 READ_UNALIGNED = _lib.READ_UNALIGNED
@@ -74,9 +71,9 @@ PATHWISE_GAP_XLONG_MODES = _lib.gap_family_modes("_XLONG")
 # ... except through these: both strands is the mode itself again, so ``both_strands=True`` is redundant there
 PATHWISE_GAP_XSTRANDS_MODES = _lib.gap_family_modes("_XSTRANDS")
 # unit costs, the reads as given, up to 16383 bases
-PATHWISE_EDIT_MODES = (MODE_PATHWISE_EDIT, MODE_PATHWISE_EDIT_SEMI)
+PATHWISE_EDIT_MODES = _lib.edit_family_modes("")
 # ... up to 131071 bases
-PATHWISE_EDIT_XLONG_MODES = (MODE_PATHWISE_EDIT_XLONG, MODE_PATHWISE_EDIT_SEMI_XLONG)
+PATHWISE_EDIT_XLONG_MODES = _lib.edit_family_modes("_XLONG")
 
 
 def _both_strands_kw(mode, both_strands, kw, strand_vote=False):
@@ -86,11 +83,9 @@ def _both_strands_kw(mode, both_strands, kw, strand_vote=False):
     if not both_strands and not strand_vote:
         return kw
     flag = "strand_vote" if strand_vote else "both_strands"
-    if _lib.edit_mode(mode):
-        raise _lib.RecGraphError(-1, _lib.EDIT_STRANDS_REFUSAL % flag)
-    if _lib.edit_xlong_mode(mode):
-        raise _lib.RecGraphError(-1, _lib.EDIT_XLONG_STRANDS_REFUSAL % flag)
-    gm = _lib.gap_mode(mode)
+    em, gm = _lib.edit_mode(mode), _lib.gap_mode(mode)
+    if em:
+        raise _lib.RecGraphError(-1, em.family.api_refusal % flag)
     if gm and not gm.family.both_strands:
         raise _lib.RecGraphError(-1, gm.family.api_refusal % flag)
     if gm and strand_vote and gm.rule == _lib.GAP_LOCAL:
@@ -914,22 +909,24 @@ def pathwise_alignment_gap_local_exec(sequence, graph, score_matrix=None, o=-4, 
     return GAFStruct.from_line(text.rstrip("\n"))
 
 
+def _edit_exec(suffix, sequence, graph, semi, score_matrix):
+    sm = score_matrix if score_matrix is not None else create_score_matrix_i32(0, -1)
+    _, text = _single(graph, "".join(sequence[1:]), "Temp", _lib.edit_family_modes(suffix)[bool(semi)], 1, score_matrix=sm, o=0, e=-1)
+    return GAFStruct.from_line(text.rstrip("\n"))
+
+
 def pathwise_alignment_edit_exec(sequence, graph, semi=False, score_matrix=None):
     """-m 44 (``semi=True``: -m 45): ``pathwise_alignment_gap_exec(..., o=0, e=-1, long_reads=True)`` (``..._semi_exec``) for a 0 / -1
     matrix, computed by the bit-vector kernels: one cell per bit, reads of up to 16383 bases.  The default matrix is match 0, mismatch -1;
     any matrix whose ACGTN x ACGTN entries are 0 or -1 is taken (an N that matches N, for one), every other one is refused."""
-    sm = score_matrix if score_matrix is not None else create_score_matrix_i32(0, -1)
-    _, text = _single(graph, "".join(sequence[1:]), "Temp", MODE_PATHWISE_EDIT_SEMI if semi else MODE_PATHWISE_EDIT, 1, score_matrix=sm, o=0, e=-1)
-    return GAFStruct.from_line(text.rstrip("\n"))
+    return _edit_exec("", sequence, graph, semi, score_matrix)
 
 
 def pathwise_alignment_edit_xlong_exec(sequence, graph, semi=False, score_matrix=None):
     """-m 94 (``semi=True``: -m 95): ``pathwise_alignment_edit_exec`` for reads of up to 131071 bases, which is
     ``pathwise_alignment_gap_exec(..., o=0, e=-1, very_long_reads=True)`` (``..._semi_exec``) for a 0 / -1 matrix.  A read of at most
     16383 bases runs exactly as in -m 44 / -m 45; a longer one in column stripes of 16384 on the same bit-vector row step."""
-    sm = score_matrix if score_matrix is not None else create_score_matrix_i32(0, -1)
-    _, text = _single(graph, "".join(sequence[1:]), "Temp", MODE_PATHWISE_EDIT_SEMI_XLONG if semi else MODE_PATHWISE_EDIT_XLONG, 1, score_matrix=sm, o=0, e=-1)
-    return GAFStruct.from_line(text.rstrip("\n"))
+    return _edit_exec("_XLONG", sequence, graph, semi, score_matrix)
 
 
 def pathwise_alignment_recombination_exec(aln_mode, sequence, graph, score_matrix=None, base_rec_cost=4,

@@ -49,16 +49,13 @@ _STRAND_MODES = [m for m in sorted(_lib.GAP_MODE_NAMES.values()) if _lib.gap_mod
 
 
 def check_mode_flags(alignment_mode, both_strands, strand_vote, amb_strand):
-    """What main refuses before it opens a file: a mode that is neither 0 to 9 nor an affine-gap pathwise mode (_lib.GAP_FAMILIES), and
+    """What main refuses before it opens a file: a mode that is neither 0 to 9 nor a row of _lib.GAP_FAMILIES or _lib.EDIT_FAMILIES, and
     --both-strands / --strand-vote where the mode has no such rule.  Returns whether ``-s true`` counts."""
     gm = _lib.gap_mode(alignment_mode)
-    if _lib.edit_mode(alignment_mode):
+    em = _lib.edit_mode(alignment_mode)
+    if em:
         if both_strands or strand_vote:
-            raise SystemExit("--both-strands / --strand-vote are not available in modes 44 and 45: they align the reads as given")
-        return False
-    if _lib.edit_xlong_mode(alignment_mode):
-        if both_strands or strand_vote:
-            raise SystemExit("--both-strands / --strand-vote are not available in modes 94 and 95: they align the reads as given")
+            raise SystemExit(em.family.cli_refusal)
         return False
     if alignment_mode not in range(10) and not gm:
         raise SystemExit("Alignment mode must be in [0..9], or 12")   # main.rs:315-317; 12: local affine-gap pathwise, this project's own
@@ -77,14 +74,14 @@ def check_mode_flags(alignment_mode, both_strands, strand_vote, amb_strand):
 
 
 def check_edit_scores(alignment_mode, scores, gap_open, gap_extension):
-    """Modes 44 and 45, and 94 and 95, take unit costs only: what main refuses once the score matrix is built, before it opens the graph.
-    ``scores``: the matrix as a dict; ``gap_open`` / ``gap_extension``: -O / -E as given (positive)."""
-    xlong = bool(_lib.edit_xlong_mode(alignment_mode))
-    if not _lib.edit_mode(alignment_mode) and not xlong:
+    """The edit-distance modes (_lib.EDIT_FAMILIES) take unit costs only: what main refuses once the score matrix is built, before it opens
+    the graph.  ``scores``: the matrix as a dict; ``gap_open`` / ``gap_extension``: -O / -E as given (positive)."""
+    em = _lib.edit_mode(alignment_mode)
+    if not em:
         return
     table = [scores.get((a, b), 0) for a in "ACGTN-" for b in "ACGTN-"]
     if not _lib.unit_costs(table, -gap_open, -gap_extension):
-        raise SystemExit(_lib.EDIT_XLONG_SCORE_REFUSAL if xlong else _lib.EDIT_SCORE_REFUSAL)
+        raise SystemExit(em.family.score_refusal)
 
 
 def build_parser():
@@ -93,9 +90,7 @@ def build_parser():
     p.add_argument("graph_path")
     p.add_argument("-o", "--out_file", default="standard output")
     p.add_argument("-m", "--aln-mode", type=int, default=0, dest="alignment_mode",
-                   help="0 to 9 as in the reference; " + "; ".join(f.cli_help for f in _lib.GAP_FAMILIES) +
-                        "; 44, 45: modes 16, 17 at unit costs (-M 0 -X 1 -O 0 -E 1 must be given) on the bit-vector kernels"
-                        "; 94, 95: those for reads of up to 131071 bases (modes 56, 57 at unit costs)")
+                   help="0 to 9 as in the reference; " + "; ".join(f.cli_help for f in _lib.GAP_FAMILIES + _lib.EDIT_FAMILIES))
     p.add_argument("-M", "--match", type=int, default=2, dest="match_score")
     p.add_argument("-X", "--mismatch", type=int, default=4, dest="mismatch_score")
     p.add_argument("-t", "--matrix", default="none")

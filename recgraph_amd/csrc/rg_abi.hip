@@ -361,7 +361,7 @@ int32_t rg_batch_create(const rg_graph* gc, const rg_params* p, const char* read
     const rg_graph* g = gc;
     const int mode = p->mode;
     const bool path_gap = gap_mode(mode).valid;       // (every rule in every family of rg_gap_modes.hpp)
-    const bool path_edit = edit_any_mode(mode).valid; // (-m 44 / -m 45 and -m 94 / -m 95: rg_edit_modes.hpp)
+    const bool path_edit = edit_mode(mode).valid;     // (every rule in every family of rg_edit_modes.hpp)
     if (!(is_poa(mode) || mode == RG_MODE_PATHWISE || mode == RG_MODE_RECOMBINATION || mode == RG_MODE_PATHWISE_SEMI ||
           mode == RG_MODE_RECOMBINATION_SEMI || path_gap || path_edit))
         return fail(RG_ERR_ARG, "unsupported mode");

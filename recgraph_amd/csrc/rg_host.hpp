@@ -15,7 +15,7 @@
 
 #include "../../include/recgraph_hip.h"
 #include "rg_gap_modes.hpp"      // gap_mode(): rule and family of an affine-gap pathwise mode
-#include "rg_edit_modes.hpp"     // edit_mode(): the two bit-vector edit-distance pathwise modes
+#include "rg_edit_modes.hpp"     // edit_mode(): rule and family of a bit-vector edit-distance pathwise mode
 
 namespace rg {
 

@@ -132,29 +132,20 @@ static int plan_pathwise_gap(const rg_params& p, const GapMode& gm, const PathPl
     return RG_OK;
 }
 
-// The edit-distance modes (rg_edit_modes.hpp): the rules of modes 16 / 17 at unit costs, one bit per cell.  One wave per (read, path)
-// keeps the whole read in its registers, 32 W columns per lane; the only HBM work buffer beside ReadState holds D0 and Ph of the picked
-// path's rows, 2 bits per cell.  -m 94 / -m 95: the same up to 16383 bases; beyond, stripes of 16384 columns (PathPlan::edit_xlong).
-const char* const kEditScoreRefusal =
-    "the edit-distance pathwise modes (-m 44 / -m 45) take unit costs only: gap_open 0, gap_ext -1 and every ACGTN x ACGTN score 0 or -1 "
-    "(-M 0 -X 1 -O 0 -E 1, or a 0 / -1 matrix); every other scoring is what -m 16 / -m 17 are for";
-const char* const kEditXLongScoreRefusal =
-    "the edit-distance pathwise modes (-m 94 / -m 95) take unit costs only: gap_open 0, gap_ext -1 and every ACGTN x ACGTN score 0 or -1 "
-    "(-M 0 -X 1 -O 0 -E 1, or a 0 / -1 matrix); every other scoring is what -m 56 / -m 57 are for";
+// The edit-distance modes (the table: rg_edit_modes.hpp): the rules of modes 6 / 7 at unit costs, one bit per cell.  One wave per (read,
+// path) keeps the whole read in its registers, 32 W columns per lane; the only HBM work buffer beside ReadState holds D0 and Ph of the
+// picked path's rows, 2 bits per cell.  That up to 16383 bases in every family; beyond, stripes of 16384 columns (PathPlan::edit_xlong).
 int plan_pathwise_edit(const rg_params& p, const PathPlanInput& in, PathPlan& o) {
-    const bool xlong = edit_xlong_mode(p.mode).valid;
-    const EditMode em = edit_any_mode(p.mode);
+    const EditMode em = edit_mode(p.mode);
     if (!em.valid) return fail(RG_ERR_ARG, "unsupported mode");
+    const EditFamily& f = *em.family;
     if (p.gap_open > 0 || p.gap_ext > 0) return fail(RG_ERR_ARG, "gap penalties must be <= 0");
     bool unit = p.gap_open == 0 && p.gap_ext == -1;
     for (int x = 0; x < 5; ++x)
         for (int y = 0; y < 5; ++y) unit = unit && (p.scores[x * 6 + y] == 0 || p.scores[x * 6 + y] == -1);
-    if (!unit) return fail(RG_ERR_ARG, xlong ? kEditXLongScoreRefusal : kEditScoreRefusal);
-    if (p.amb_mode != 0)
-        return fail(RG_ERR_ARG, xlong ? "amb_mode must be 0 in the edit-distance pathwise modes (-m 94 / -m 95): they align the reads as given"
-                                      : "amb_mode must be 0 in the edit-distance pathwise modes (-m 44 / -m 45): they align the reads as given");
-    if (!xlong && in.max_n > EDIT_MAX_READ) return fail(RG_ERR_ARG, "reads longer than 16383 bases are not supported by the edit-distance pathwise modes (-m 44 / -m 45)");
-    if (in.max_n > EDIT_XLONG_MAX_READ) return fail(RG_ERR_ARG, "reads longer than 131071 bases are not supported by the edit-distance pathwise modes (-m 94 / -m 95)");
+    if (!unit) return fail(RG_ERR_ARG, f.score_refusal);
+    if (p.amb_mode != 0) return fail(RG_ERR_ARG, f.amb_refusal);
+    if (in.max_n > f.max_read) return fail(RG_ERR_ARG, f.len_refusal);
     // mode 16's budget, at max(|sc|, |o + e|) = 1: what it refuses is refused here
     if ((long long)in.max_path_rows + in.max_n >= (1ll << 28))
         return fail(RG_ERR_CAPACITY, "scores of this batch can reach 2^28 in magnitude: outside the i32 range of the affine-gap pathwise kernels");
@@ -199,7 +190,7 @@ int plan_pathwise(const rg_params& p, const PathPlanInput& in, const Options& op
     o = PathPlan{};
     const GapMode gm = gap_mode(p.mode);
     if (gm.valid) return plan_pathwise_gap(p, gm, in, o);
-    if (edit_any_mode(p.mode).valid) return plan_pathwise_edit(p, in, o);
+    if (edit_mode(p.mode).valid) return plan_pathwise_edit(p, in, o);
     const int P = in.P, L = in.L, max_n = in.max_n;
     o.semi = p.mode == RG_MODE_PATHWISE_SEMI || p.mode == RG_MODE_RECOMBINATION_SEMI;
     o.mode = p.mode == RG_MODE_PATHWISE_SEMI ? RG_MODE_PATHWISE : p.mode == RG_MODE_RECOMBINATION_SEMI ? RG_MODE_RECOMBINATION : p.mode;

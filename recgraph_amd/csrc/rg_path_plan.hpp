@@ -101,10 +101,10 @@ struct PathPlan {
 // spec_level: 0 = the batch itself; 1 = the reads whose speculation failed, once more with a generous margin; 2 = what fails
 // even that, with the provable bound.  RG_ERR_ARG / RG_ERR_CAPACITY (through fail()) for batches the kernels cannot take.
 int plan_pathwise(const rg_params& p, const PathPlanInput& in, const Options& opt, int spec_level, PathPlan& out);
-// The plan of the edit-distance modes (what plan_pathwise returns for -m 44 / -m 45), with every refusal of theirs: gap costs other than
-// (0, -1) or an ACGTN x ACGTN entry other than 0 / -1, an amb_mode bit, a read over 16383 bases (RG_ERR_ARG), mode 16's 2^28 budget
-// (RG_ERR_CAPACITY).  -m 94 / -m 95: the same refusals with the limit at 131071 bases, the plan of -m 44 / -m 45 up to 16383 bases and
-// the striped one (PathPlan::edit_xlong) beyond.  `out` must be a cleared plan
+// The plan of the edit-distance modes (what plan_pathwise returns for a mode of rg_edit_modes.hpp), with every refusal of theirs, in the
+// words of the mode's family: gap costs other than (0, -1) or an ACGTN x ACGTN entry other than 0 / -1, an amb_mode bit, a read over the
+// family's limit (RG_ERR_ARG), mode 16's 2^28 budget (RG_ERR_CAPACITY).  In every family the plan of -m 44 / -m 45 up to 16383 bases, the
+// striped one (PathPlan::edit_xlong) beyond.  `out` must be a cleared plan
 int plan_pathwise_edit(const rg_params& p, const PathPlanInput& in, PathPlan& out);
 
 // The stages of an affine-gap pipeline (PathJob::stage, rg_path_args.hpp).  PICK: score pass + pick, and the pick goes out into the

@@ -16,9 +16,10 @@ static rg_params unit(int mode, int m = 0, int x = -1, int o = 0, int e = -1, in
 int main() {
     CHECK(RG_MODE_PATHWISE_EDIT == 44 && RG_MODE_PATHWISE_EDIT_SEMI == 45);
     CHECK(edit_mode(44).valid && !edit_mode(44).semi && edit_mode(45).valid && edit_mode(45).semi);
+    CHECK(edit_mode(44).family == edit_mode(45).family && edit_mode(44).family->max_read == 16383 && edit_mode(44).family->gap_family == GAP_FAM_LONG);
     CHECK(edit_base_mode(44) == RG_MODE_PATHWISE_GAP && edit_base_mode(45) == RG_MODE_PATHWISE_GAP_SEMI && edit_base_mode(16) == 16 && edit_base_mode(4) == 4);
     for (int m = -2; m < 200; ++m) {
-        CHECK(edit_mode(m).valid == (m == 44 || m == 45));
+        CHECK(edit_mode(m).valid == (m == 44 || m == 45 || m == 94 || m == 95));
         if (m == 44 || m == 45) CHECK(!gap_mode(m).valid && path_gap_base_mode(m) == m);
     }
     for (int M : {RG_MODE_PATHWISE_EDIT, RG_MODE_PATHWISE_EDIT_SEMI}) {

@@ -1,6 +1,6 @@
 // CPU check of the plan of the edit-distance pathwise modes for long reads (-m 94 / -m 95; recgraph_amd/csrc/rg_path_plan.cpp:
 // plan_pathwise_edit): up to 16383 bases the plan IS the one of -m 44 / -m 45, field for field; beyond, S, the strides and per_read at
-// 16384, 16385, 32768, 32769 and 131071 bases; every refusal; and that the modes are rows of neither lookup of their neighbours.
+// 16384, 16385, 32768, 32769 and 131071 bases; every refusal; and that the modes are rows of the edit family table alone.
 // Built and run by tests/test_pathwise_edit_xlong_cpu.py.
 #include "gap_mode_check.hpp"
 
@@ -17,12 +17,13 @@ static rg_params unit(int mode, int m = 0, int x = -1, int o = 0, int e = -1, in
 int main() {
     CHECK(RG_MODE_PATHWISE_EDIT_XLONG == 94 && RG_MODE_PATHWISE_EDIT_SEMI_XLONG == 95);
     CHECK(EDIT_XLONG_MAX_READ == 131071 && EDIT_XLONG_STRIPE == 16384 && EDIT_XLONG_MAX_STRIPES == 8 && EDIT_MAX_READ == 16383);
-    CHECK(edit_xlong_mode(94).valid && !edit_xlong_mode(94).semi && edit_xlong_mode(95).valid && edit_xlong_mode(95).semi);
+    CHECK(edit_mode(94).valid && !edit_mode(94).semi && edit_mode(95).valid && edit_mode(95).semi);
+    CHECK(edit_mode(94).family == edit_mode(95).family && edit_mode(94).family->max_read == 131071 && edit_mode(94).family->gap_family == GAP_FAM_XLONG);
+    CHECK(edit_mode(94).family != edit_mode(44).family && edit_mode(44).family->max_read == 16383);
     CHECK(edit_base_mode(94) == RG_MODE_PATHWISE_GAP && edit_base_mode(95) == RG_MODE_PATHWISE_GAP_SEMI && edit_base_mode(93) == 93 && edit_base_mode(56) == 56);
     for (int m = -2; m < 200; ++m) {
-        CHECK(edit_xlong_mode(m).valid == (m == 94 || m == 95));
-        CHECK(edit_mode(m).valid == (m == 44 || m == 45));
-        CHECK(edit_any_mode(m).valid == (m == 44 || m == 45 || m == 94 || m == 95));
+        CHECK(edit_mode(m).valid == (m == 44 || m == 45 || m == 94 || m == 95));
+        CHECK(edit_mode(m).family->offset == (m == 94 || m == 95 ? 50 : 0) && edit_mode(m).semi == (m == 45 || m == 95));
         if (m == 94 || m == 95) CHECK(!gap_mode(m).valid && path_gap_base_mode(m) == m);
     }
     for (int M : {RG_MODE_PATHWISE_EDIT_XLONG, RG_MODE_PATHWISE_EDIT_SEMI_XLONG}) {

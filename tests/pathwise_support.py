@@ -136,13 +136,17 @@ def align(gg, reads, mode, scores=None, o=-4, e=-2):
     return api.align_batch(gg, reads, ["r%d" % i for i in range(len(reads))], mode=mode, score_matrix=scores, o=o, e=e)
 
 
-def create_rc(gfa, reads, mode, o=-4, e=-2, amb=0, match=2):
-    """(return code, message) of rg_batch_create, which answers its refusals before a device is needed."""
+def create_rc(gfa, reads, mode, o=-4, e=-2, amb=0, match=2, mismatch=None, entries=()):
+    """(return code, message) of rg_batch_create, which answers its refusals before a device is needed.  The scores: the default matrix
+    with its A / A entry set to `match`, or, given `mismatch`, the match / mismatch matrix; entries ((a, b, value), ...) are written over it."""
     from recgraph_amd import api
     lib = api._lib.load()
     g = api.Graph.from_gfa_text(gfa)
-    p = api.make_params(mode, o=o, e=e, amb=amb)
-    p.scores[0] = match
+    p = api.make_params(mode, score_matrix=None if mismatch is None else api.create_score_matrix_i32(match, mismatch), o=o, e=e, amb=amb)
+    if mismatch is None:
+        p.scores[0] = match
+    for a, b, v in entries:
+        p.scores[a * 6 + b] = v
     blob = "".join(reads).encode()
     off = (C.c_int64 * (len(reads) + 1))(*np.concatenate([[0], np.cumsum([len(r) for r in reads])]).tolist())
     out = C.c_void_p()

@@ -2,7 +2,7 @@
 rg_batch_create (answered before a device is needed), the two constants on every side, the bit-vector rule of tests/pathwise_edit_rule.py
 against the numpy rule of modes 6 / 7, the bit arithmetic of the kernels on the host (tests/c/edit_bits_check.cpp), the plan
 (tests/c/edit_plan_check.cpp), the API and CLI surface and the registers of the new kernels."""
-import ctypes as C
+import functools
 import os
 import re
 import sys
@@ -14,28 +14,15 @@ import pathwise_edit_rule as E
 import pathwise_gap_rule as R
 import plan_check_build
 
-from pathwise_support import TWO_BUBBLES, assert_rows_in_registers, no_device
+from pathwise_support import TWO_BUBBLES, assert_rows_in_registers, create_rc, no_device
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EDIT = (44, 45)
 FLAGS = "-M 0 -X 1 -O 0 -E 1"
 
 
-def _create(reads, mode, match=0, mismatch=-1, o=0, e=-1, amb=0, entries=()):
-    """(return code, message) of rg_batch_create on TWO_BUBBLES; entries: ((a, b, value), ...) written over the match / mismatch matrix."""
-    from recgraph_amd import api
-    lib = api._lib.load()
-    g = api.Graph.from_gfa_text(TWO_BUBBLES)
-    p = api.make_params(mode, score_matrix=api.create_score_matrix_i32(match, mismatch), o=o, e=e, amb=amb)
-    for a, b, v in entries:
-        p.scores[a * 6 + b] = v
-    blob = "".join(reads).encode()
-    off = (C.c_int64 * (len(reads) + 1))(*np.concatenate([[0], np.cumsum([len(r) for r in reads])]).tolist())
-    out = C.c_void_p()
-    rc = lib.rg_batch_create(g._h, C.byref(p), blob, off, len(reads), C.byref(out))
-    if rc == 0:
-        lib.rg_batch_destroy(out)
-    return rc, lib.rg_last_error().decode()
+# (return code, message) of rg_batch_create on TWO_BUBBLES at unit costs, each of them a keyword
+_create = functools.partial(create_rc, TWO_BUBBLES, match=0, mismatch=-1, o=0, e=-1)
 
 
 @pytest.mark.parametrize("mode", EDIT)
@@ -79,8 +66,8 @@ def test_the_neighbours_stay_unsupported_and_the_modes_are_no_rows_of_the_gap_ta
         assert rc == -1 and "unsupported mode" in msg, (other, rc, msg)
     assert _lib.gap_mode(44) is None and _lib.gap_mode(45) is None
     assert 44 not in _lib.GAP_MODE_NAMES.values() and 45 not in _lib.GAP_MODE_NAMES.values()
-    assert _lib.edit_mode(44) == {"semi": False} and _lib.edit_mode(45) == {"semi": True}
-    assert [m for m in range(-2, 200) if _lib.edit_mode(m)] == [44, 45]
+    assert [(m, _lib.edit_mode(m).semi, _lib.edit_mode(m).family.max_read) for m in range(-2, 200) if _lib.edit_mode(m)] == \
+        [(44, False, 16383), (45, True, 16383), (94, False, 131071), (95, True, 131071)]
 
 
 def test_no_new_entry_point():
@@ -100,7 +87,7 @@ def test_the_constants_agree_on_every_side():
         assert re.search(r"^pub const RG_MODE_%s: i32 = %d;$" % (name, value), rust, re.M)
         assert getattr(_lib, "MODE_" + name) == getattr(api, "MODE_" + name) == value
         assert "RG_MODE_%s" % name in modes_hpp
-    assert api.PATHWISE_EDIT_MODES == (44, 45) and _lib.EDIT_MAX_READ == 16383 and "EDIT_MAX_READ == 16383" in modes_hpp
+    assert api.PATHWISE_EDIT_MODES == (44, 45) and _lib.edit_mode(44).family.max_read == 16383 and "EDIT_MAX_READ == 16383" in modes_hpp
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import gen_rust_ffi
     assert gen_rust_ffi.generate() == rust

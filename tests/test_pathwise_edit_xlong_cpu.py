@@ -3,7 +3,7 @@ costs): admission and refusals of rg_batch_create (answered before a device is n
 of tests/pathwise_edit_xlong_rule.py against the whole-vector rule of tests/pathwise_edit_rule.py, the striped bit arithmetic of the
 kernels on the host (tests/c/edit_xlong_bits_check.cpp), the plan (tests/c/edit_xlong_plan_check.cpp), the API and CLI surface and the
 registers of the new kernels."""
-import ctypes as C
+import functools
 import inspect
 import os
 import re
@@ -17,28 +17,15 @@ import pathwise_edit_xlong_rule as X
 import pathwise_gap_rule as R
 import plan_check_build
 
-from pathwise_support import TWO_BUBBLES, assert_rows_in_registers, no_device
+from pathwise_support import TWO_BUBBLES, assert_rows_in_registers, create_rc, no_device
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 XLONG = (94, 95)
 FLAGS = "-M 0 -X 1 -O 0 -E 1"
 
 
-def _create(reads, mode, match=0, mismatch=-1, o=0, e=-1, amb=0, entries=()):
-    """(return code, message) of rg_batch_create on TWO_BUBBLES; entries: ((a, b, value), ...) written over the match / mismatch matrix."""
-    from recgraph_amd import api
-    lib = api._lib.load()
-    g = api.Graph.from_gfa_text(TWO_BUBBLES)
-    p = api.make_params(mode, score_matrix=api.create_score_matrix_i32(match, mismatch), o=o, e=e, amb=amb)
-    for a, b, v in entries:
-        p.scores[a * 6 + b] = v
-    blob = "".join(reads).encode()
-    off = (C.c_int64 * (len(reads) + 1))(*np.concatenate([[0], np.cumsum([len(r) for r in reads])]).tolist())
-    out = C.c_void_p()
-    rc = lib.rg_batch_create(g._h, C.byref(p), blob, off, len(reads), C.byref(out))
-    if rc == 0:
-        lib.rg_batch_destroy(out)
-    return rc, lib.rg_last_error().decode()
+# (return code, message) of rg_batch_create on TWO_BUBBLES at unit costs, each of them a keyword
+_create = functools.partial(create_rc, TWO_BUBBLES, match=0, mismatch=-1, o=0, e=-1)
 
 
 @pytest.mark.parametrize("mode", XLONG)
@@ -83,10 +70,11 @@ def test_the_neighbours_stay_unsupported_and_modes_44_and_45_keep_their_limit():
     for mode in (44, 45):
         rc, msg = _create(["ATG", "A" * 16384], mode)
         assert rc == -1 and "16383" in msg and "-m 44 / -m 45" in msg, (mode, rc, msg)
-    assert all(_lib.gap_mode(m) is None and _lib.edit_mode(m) is None for m in XLONG)
-    assert _lib.edit_xlong_mode(94) == {"valid": True, "semi": False} and _lib.edit_xlong_mode(95) == {"valid": True, "semi": True}
-    assert [m for m in range(-2, 200) if _lib.edit_xlong_mode(m)] == [94, 95]
-    assert [m for m in range(-2, 200) if _lib.edit_mode(m)] == [44, 45]
+    assert all(_lib.gap_mode(m) is None for m in XLONG)
+    # one lookup: the same four modes, each with its rule, and modes 94 / 95 in a family of their own with its own reach
+    assert [(m, _lib.edit_mode(m).semi, _lib.edit_mode(m).family.max_read) for m in range(-2, 200) if _lib.edit_mode(m)] == \
+        [(44, False, 16383), (45, True, 16383), (94, False, 131071), (95, True, 131071)]
+    assert _lib.edit_mode(94).family is _lib.edit_mode(95).family is not _lib.edit_mode(44).family and _lib.edit_mode(44).family is _lib.edit_mode(45).family
 
 
 def test_no_new_entry_point():
@@ -107,8 +95,8 @@ def test_the_constants_agree_on_every_side():
         assert getattr(_lib, "MODE_" + name) == getattr(api, "MODE_" + name) == value
         assert "RG_MODE_%s" % name in modes_hpp
     assert api.PATHWISE_EDIT_XLONG_MODES == (94, 95) and api.PATHWISE_EDIT_MODES == (44, 45)
-    assert _lib.EDIT_XLONG_MAX_READ == 131071 and "EDIT_XLONG_MAX_READ == 131071" in modes_hpp and _lib.EDIT_MAX_READ == 16383
-    assert "constexpr EditMode edit_xlong_mode(int mode)" in modes_hpp
+    assert _lib.edit_mode(94).family.max_read == 131071 and "EDIT_XLONG_MAX_READ == 131071" in modes_hpp and _lib.edit_mode(44).family.max_read == 16383
+    assert modes_hpp.count("constexpr EditMode edit_") == 1 and "constexpr EditMode edit_mode(int mode)" in modes_hpp
     assert X.STRIPE == 16384 and "EDIT_XLONG_STRIPE = 32 * EDIT_MAX_WORDS * WAVE" in modes_hpp
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import gen_rust_ffi
