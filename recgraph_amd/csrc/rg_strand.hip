@@ -6,8 +6,10 @@
 //
 // A read QUALIFIES for the second pass when its status has neither ST_BAD_BASE nor ST_WOULD_PANIC and the score its record
 // prints is < 0 (the reference's rule for the global POA modes, main.rs:82).  The printed score (rg_gaf.cpp) is the integer
-// `score`, or the f32 `fscore` of a record with a recombination (two different paths, -m 8 / -m 9): compared as f32, every
-// integer involved is below 2^24.  The reverse record replaces the forward one only when its printed score is STRICTLY
+// `score`, or the f32 `fscore` of a record with a recombination (two different paths, -m 8 / -m 9).  Two integer scores are
+// compared as integers: in modes 26 / 27 / 32 they reach 2^28, where an f32 cannot tell neighbours apart.  Only where a
+// record actually prints `fscore` is the comparison one of f32, and there every integer involved is below 2^24.
+// The reverse record replaces the forward one only when its printed score is STRICTLY
 // greater; ties keep the forward record.  With RG_AMB_STRAND_VOTE (rg_strand_vote.hip) the first pass aligned each read on
 // the strand its 12-mers vote for: the gate presets the strand flag from `first_rev`, and the merge keeps the reverse record
 // only when it is strictly greater, whichever pass produced it.
@@ -24,8 +26,15 @@ namespace {
 constexpr int GATE_THREADS = 256;
 constexpr int GATE_WAVES = GATE_THREADS / WAVE;
 
-__device__ __forceinline__ float printed_score(const DevRecord& r, int recomb) {
-    return recomb && r.best_path != r.rev_path ? r.fscore : (float)r.score;
+__device__ __forceinline__ bool prints_fscore(const DevRecord& r, int recomb) { return recomb && r.best_path != r.rev_path; }
+__device__ __forceinline__ bool printed_negative(const DevRecord& r, int recomb) {
+    return prints_fscore(r, recomb) ? r.fscore < 0.0f : r.score < 0;
+}
+// printed score of x STRICTLY greater than that of y
+__device__ __forceinline__ bool printed_greater(const DevRecord& x, const DevRecord& y, int recomb) {
+    const bool fx = prints_fscore(x, recomb), fy = prints_fscore(y, recomb);
+    if (!(fx || fy)) return x.score > y.score;
+    return (fx ? x.fscore : (float)x.score) > (fy ? y.fscore : (float)y.score);      // (recomb modes: |score| < 2^24, exact as f32)
 }
 __device__ __forceinline__ bool no_record(uint32_t status) { return (status & (ST_BAD_BASE | ST_WOULD_PANIC)) != 0; }
 
@@ -48,7 +57,7 @@ __global__ __launch_bounds__(GATE_THREADS) void k_strand_gate(StrandGateArgs a) 
         int len = 0;
         if (i < a.nreads) {
             const DevRecord r = a.rec[i];
-            q = !no_record(r.status) && printed_score(r, a.recomb) < 0.0f;
+            q = !no_record(r.status) && printed_negative(r, a.recomb);
             if (q) len = (int)(a.off[i + 1] - a.off[i]);
             a.rec[i].pad = a.first_rev ? (int32_t)a.first_rev[i] : 0;      // (REC_REVERSE_STRAND: the strand of the record so far)
         }
@@ -125,8 +134,7 @@ __global__ __launch_bounds__(WAVE) void k_strand_merge(StrandMergeArgs a) {
     // (RG_AMB_STRAND_VOTE: a read whose first pass was the reverse one, `pad` preset by the gate, has its FORWARD record
     // here: it replaces the reverse one unless that is strictly greater.  Without the vote `pad` is 0 on every read.)
     const bool first_rev = (f.pad & REC_REVERSE_STRAND) != 0;
-    const float sf = printed_score(f, a.recomb), sr = printed_score(r, a.recomb);
-    if (first_rev ? sf > sr : !(sr > sf)) return;
+    if (first_rev ? printed_greater(f, r, a.recomb) : !printed_greater(r, f, a.recomb)) return;
     static_assert(sizeof(DevRecord) == 4 * sizeof(int4), "a record is four 16-byte pieces");
     if (lane < 4) {
         int4 v = reinterpret_cast<const int4*>(a.rec2 + k)[lane];

@@ -280,14 +280,15 @@ def check_edit(graph, reads, mode, scores=None, out=None):
 
 # ---- both strands: modes 26 / 27 / 32 and 76 / 77 / 82 ----
 
-def run_batch_strands(gg, reads, mode, amb=None, log=False):
-    """One batch through the C accessors: texts, status, scores, strands (None: no record), kernel statistics, cell counters."""
+def run_batch_strands(gg, reads, mode, amb=None, log=False, scores=None, o=-4, e=-2):
+    """One batch through the C accessors: texts, status, scores, strands (None: no record), kernel statistics, cell counters.
+    `scores` (a matrix of api.create_score_matrix_i32; None: the default one), `o` and `e` as in `align`."""
     from recgraph_amd import api
     n = len(reads)
     if log:
         api.set_option("launch_log", 1)
     try:
-        b = api.Batch(gg, reads, api.make_params(mode, amb=amb))
+        b = api.Batch(gg, reads, api.make_params(mode, score_matrix=scores, o=o, e=e, amb=amb))
         b.run()
         b.fetch()
         stats = b.kernel_stats()
@@ -302,24 +303,31 @@ def run_batch_strands(gg, reads, mode, amb=None, log=False):
                 inst={k[5:]: v[1] for k, v in stats.items() if k.startswith("inst:")}, cells=(b.cell_updates, b.cell_updates_performed))
 
 
-def expect_strands(graph, reads, mode, kmers=None):
+def _table(scores):
+    from recgraph_amd import api
+    return None if scores is None else api._table_from_dict(scores)
+
+
+def expect_strands(graph, reads, mode, kmers=None, scores=None, o=-4, e=-2):
     """The answers of the composed rule of tests/pathwise_gap_strands_rule.py, read by read."""
     g, gg, lnz, rows, node_ids = graph
+    table = _table(scores)
     out = []
     for i, rd in enumerate(reads):
         assert max(len(r) for r in rows) * (len(rd) + 1) <= 12_000_000, "the rule would need more than ~400 MB"
-        out.append(S.expected(mode, rd, S.line_fn(mode, lnz, rows, node_ids, "r%d" % i), kmers))
+        out.append(S.expected(mode, rd, S.line_fn(mode, lnz, rows, node_ids, "r%d" % i, table, o, e), kmers))
     return out
 
 
-def check_strands(graph, reads, mode, res, kmers=None, exp=None):
+def check_strands(graph, reads, mode, res, kmers=None, exp=None, scores=None, o=-4, e=-2):
     """Checks every read of the batch result `res` (run_batch_strands) against the composed rule of mode 26 / 27 / 32: (a) the whole
-    line, (b) the status, (c) the strand, score and query accessors, (d) the CIGAR re-scored on the strand that was chosen; returns the
-    rule's answers."""
+    line, (b) the status, (c) the strand, score and query accessors, (d) the CIGAR re-scored on the strand that was chosen, with
+    `scores`, `o` and `e` (the ones the batch ran with); returns the rule's answers."""
     from recgraph_amd import api
     g, gg, lnz, rows, node_ids = graph
     rule = api._lib.gap_mode(mode).rule
-    exp = exp or expect_strands(graph, reads, mode, kmers)
+    exp = exp or expect_strands(graph, reads, mode, kmers, scores, o, e)
+    table = _table(scores)
     for i, rd in enumerate(reads):
         text, status, strand, passes = exp[i]
         got = res["texts"][i]
@@ -334,28 +342,29 @@ def check_strands(graph, reads, mode, res, kmers=None, exp=None):
         assert res["strand"][i] == strand == f[4] and res["score"][i] == S.score_of(text), (mode, i, res["strand"][i], strand, res["score"][i])     # (c)
         assert res["query"][i] == (int(f[2]), int(f[3])), (mode, i, res["query"][i], f[2:4])
         chosen = V.rc(S.canonical(rd)) if strand == "-" else S.canonical(rd)
-        _check_record(f, chosen, rule, None, -4, -2, lnz, rows, (mode, i))                                                   # (d)
+        _check_record(f, chosen, rule, table, o, e, lnz, rows, (mode, i))                                                     # (d)
     return exp
 
 
-def expect_xstrands(graph, reads, mode, kmers=None):
+def expect_xstrands(graph, reads, mode, kmers=None, scores=None, o=-4, e=-2):
     """The answers of the composed rule of tests/pathwise_gap_xstrands_rule.py, read by read."""
     g, gg, lnz, rows, node_ids = graph
+    table = _table(scores)
     striped = max(len(r) for r in reads) > 2047
     out = []
     for i, rd in enumerate(reads):
         assert max(len(r) for r in rows) * (len(rd) + 1) <= 12_000_000, "the rule would need more than ~400 MB"
-        out.append(X.expected(mode, rd, lnz, rows, node_ids, "r%d" % i, kmers, striped=striped))
+        out.append(X.expected(mode, rd, lnz, rows, node_ids, "r%d" % i, kmers, table, o, e, striped=striped))
     return out
 
 
-def check_x(graph, reads, mode, res, kmers=None, exp=None):
+def check_x(graph, reads, mode, res, kmers=None, exp=None, scores=None, o=-4, e=-2):
     """Every read of the batch result `res` (run_batch_strands) of mode 76 / 77 / 82 against the composed rule, by check_strands on the
     rule's answer, and the batch's scores and two cell counters against the rule's sums; returns the rule's answers."""
-    exp = exp or expect_xstrands(graph, reads, mode, kmers)
-    check_strands(graph, reads, mode - 50, res, exp=[(e["text"], e["status"], e["strand"], e["picked"]) for e in exp])
-    assert res["score"] == [e["score"] for e in exp], (mode, res["score"], [e["score"] for e in exp])
-    want = (sum(e["cells"] for e in exp), sum(e["performed"] for e in exp))
+    exp = exp or expect_xstrands(graph, reads, mode, kmers, scores, o, e)
+    check_strands(graph, reads, mode - 50, res, exp=[(x["text"], x["status"], x["strand"], x["picked"]) for x in exp], scores=scores, o=o, e=e)
+    assert res["score"] == [x["score"] for x in exp], (mode, res["score"], [x["score"] for x in exp])
+    want = (sum(x["cells"] for x in exp), sum(x["performed"] for x in exp))
     assert res["cells"] == want, (mode, res["cells"], want)
     return exp
 

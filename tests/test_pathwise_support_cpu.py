@@ -1,4 +1,5 @@
-"""CPU: check_reads of tests/pathwise_support.py, the per-read checker of every affine-gap family, can fail.
+"""CPU: check_reads of tests/pathwise_support.py, the per-read checker of every affine-gap family, can fail; so can the both-strands
+checkers check_strands and check_x, at the default scores and at the scores, o and e they are given.
 
 It has only ever been fed right lines.  Here it gets the rules' own lines for a few short reads on TWO_BUBBLES and NO_G (one of them a
 read the local rule leaves unaligned), which it must accept, and then the same lines with one thing wrong at a time, each of which it
@@ -10,7 +11,9 @@ import pytest
 
 import pathwise_gap_local_rule as L
 import pathwise_gap_rule as R
-from pathwise_support import NO_G, TWO_BUBBLES, check_reads, graph_tuple
+import pathwise_gap_strands_rule as S
+import strand_vote_rule as V
+from pathwise_support import NO_G, TWO_BUBBLES, check_reads, check_strands, check_x, expect_strands, expect_xstrands, graph_tuple
 
 GLOBAL, SEMI, LOCAL = 0, 1, 2
 READ_UNALIGNED = 16
@@ -88,3 +91,70 @@ def test_the_rescoring_objects_without_the_line_comparison(rule, what, monkeypat
     monkeypatch.setattr(L, "line_local", lambda *a, **kw: wrong)
     with pytest.raises(AssertionError):
         check_reads(graph, reads, rule, texts=[wrong], status=status)
+
+
+# ---- the both-strands checkers off the default scores ----
+
+STRAND_READS = ["ATGCT", "AGCAT", "ATCAT", "NNN", "AT?AT", "G"]       # (AGCAT is the reverse complement of ATGCT; ATCAT that of ATGAT, path 0)
+OFF_DEFAULT = [((2, -1), 0, -2), ((3, -1), -1, -1), ((0, -1), 0, -1), ((5, -7), -9, 0)]
+
+
+def _scores(mm):
+    from recgraph_amd import api
+    return None if mm is None else api.create_score_matrix_i32(*mm)
+
+
+def _res_of(exp, cells=None):
+    """What run_batch_strands would return for a device that answers as the rule does: exp is [(text, status, strand, passes), ...]."""
+    texts = [x[0] for x in exp]
+    f = [t[:-1].split("\t") if t else None for t in texts]
+    return dict(texts=texts, status=[x[1] for x in exp], score=[S.score_of(t) for t in texts], strand=[x[2] if x[0] else None for x in exp],
+                query=[(int(q[2]), int(q[3])) if q else None for q in f], cells=cells)
+
+
+@pytest.mark.parametrize("mode", [26, 27, 32])
+@pytest.mark.parametrize("mm,o,e", OFF_DEFAULT)
+def test_the_strand_checkers_take_the_scoring(mode, mm, o, e):
+    """expect_strands and check_strands with scores, o, e: the rule's own answers at that scoring are accepted, and they are the rules'
+    lines at that scoring; the answers at the default scoring are rejected, by the line comparison and, where the rule is made to
+    agree with them, by the re-scoring of the CIGAR with the scoring that was passed."""
+    from recgraph_amd import api
+    graph = graph_tuple(TWO_BUBBLES)
+    lnz, rows, ids = graph[2:]
+    scores = _scores(mm)
+    table = None if scores is None else api._table_from_dict(scores)
+    exp = expect_strands(graph, STRAND_READS, mode, scores=scores, o=o, e=e)
+    for i, rd in enumerate(STRAND_READS[:4]):
+        one = lambda s: (L.line_local(lnz, rows, ids, "r%d" % i, s, table, o, e) if mode == 32 else
+                         R.line(lnz, rows, ids, "r%d" % i, s, table, o, e, mode == 27))
+        assert exp[i][0] in ("", one(rd), V.minus(one(V.rc(rd))) if one(V.rc(rd)) else ""), (mode, i, exp[i])
+    assert exp[4][1:] == (S.READ_BAD_BASE, " ", [])
+    assert check_strands(graph, STRAND_READS, mode, _res_of(exp), scores=scores, o=o, e=e) == exp
+    default = expect_strands(graph, STRAND_READS, mode)
+    assert default != exp
+    with pytest.raises(AssertionError):
+        check_strands(graph, STRAND_READS, mode, _res_of(default), scores=scores, o=o, e=e)
+    if mm[0] != 2:                  # (another match score: every record of the default scoring re-scores to another number)
+        with pytest.raises(AssertionError):
+            check_strands(graph, STRAND_READS, mode, _res_of(default), exp=default, scores=scores, o=o, e=e)
+
+
+@pytest.mark.parametrize("mode", [76, 77, 82])
+@pytest.mark.parametrize("mm,o,e", OFF_DEFAULT)
+def test_the_xstrand_checkers_take_the_scoring(mode, mm, o, e):
+    graph = graph_tuple(TWO_BUBBLES)
+    scores = _scores(mm)
+    exp = expect_xstrands(graph, STRAND_READS, mode, scores=scores, o=o, e=e)
+    same = expect_strands(graph, STRAND_READS, mode - 50, scores=scores, o=o, e=e)
+    assert [(x["text"], x["status"], x["strand"], x["picked"]) for x in exp] == same
+    res = _res_of(same, cells=(sum(x["cells"] for x in exp), sum(x["performed"] for x in exp)))
+    assert check_x(graph, STRAND_READS, mode, res, scores=scores, o=o, e=e) == exp
+    default = expect_xstrands(graph, STRAND_READS, mode)
+    assert [x["score"] for x in default] != [x["score"] for x in exp]
+    with pytest.raises(AssertionError):
+        check_x(graph, STRAND_READS, mode, res, scores=scores, o=o, e=e, exp=default)
+    with pytest.raises(AssertionError):
+        check_x(graph, STRAND_READS, mode, res)                     # (the default scoring: another rule answer)
+    res["cells"] = (res["cells"][0], res["cells"][1] + 1)
+    with pytest.raises(AssertionError):
+        check_x(graph, STRAND_READS, mode, res, scores=scores, o=o, e=e)
