@@ -258,6 +258,35 @@ typedef enum rg_status {
  */
 #define RG_MODE_PATHWISE_EDIT_XLONG 94
 #define RG_MODE_PATHWISE_EDIT_SEMI_XLONG 95
+/*
+ * RG_MODE_PATHWISE_EDIT_STRANDS (64), RG_MODE_PATHWISE_EDIT_SEMI_STRANDS (65): modes 44 and 45 on BOTH STRANDS, for reads of 1 to
+ * 16383 bases.  THERE IS NO NEW RULE: for every batch they admit, every read's text, status, score, strand and query coordinates are
+ * those of mode 26 (mode 64) or mode 27 (mode 65) under the same rg_params with amb_mode 0: modes 6 / 7 on both strands at unit costs.
+ *   DECISION.  A read without RG_READ_BAD_BASE is picked on BOTH strands in one pass (the pick of modes 6 / 7 and its tie rules, per
+ *     strand); the reverse strand wins only when its pick has a record and a STRICTLY greater score.  Ties and reverse-palindromic
+ *     reads stay '+'.  WHY THIS IS THE `< 0` GATE OF MODES 26 / 27: at unit costs every score is <= 0.  A read with forward score < 0
+ *     passes the gate there and is picked on both strands here; a read with forward score 0 does not pass the gate there, and here
+ *     no reverse score can be strictly greater than 0, so forward stays.  Both give the same strand for every read.
+ *   REPORTING.  The winning strand ALONE is traced.  The read is reported exactly as that strand's sequence would be had it been
+ *     submitted by itself in mode 44 / 45, with strand column '-' for a reverse winner.  A read with a bad base: its status, no
+ *     line, strand '+'.
+ *   ADMISSION.  Unit costs exactly as modes 44 / 45; reads of at most 16383 bases; mode 16's 2^28 budget (RG_ERR_CAPACITY).  amb_mode 0
+ *     or 4: bit 2 is implied and accepted as redundant.
+ *   REFUSALS (RG_ERR_ARG).  amb_mode 12: a vote saves nothing when both strands are scored in one pass, and would change the rule.
+ *     amb_mode bits 0 and 1, bit 3 alone, any higher bit.  Any other scoring: the message names `-M 0 -X 1 -O 0 -E 1`, and -m 26 /
+ *     -m 27 for every other scoring.  All answered by rg_batch_create before a device is needed.
+ *   COUNTERS.  rg_batch_cell_updates = 2 * n * (rows_k summed over the paths), summed over the reads without a bad base: BOTH strands
+ *     of every read are always scored — the one place these modes differ from modes 26 / 27, which count the reverse strand of the
+ *     gated reads only.  rg_batch_cell_updates_performed adds mode 44 / 45's direction-pass term for the traced strand only.
+ *   NOT OFFERED.  Reads over 16383 bases (the striped kernels of modes 94 / 95 keep the boundary bits of the score pass for the walk:
+ *     two strands would double up to 206 MB per read), the 12-mer vote, a local rule.  Modes 44, 45, 94 and 95 keep refusing every
+ *     amb_mode bit.
+ * k_edit_score_pair (one wave scores both strands of a (read, path): the read in lanes 0 to 31, its reverse complement in lanes 32 to
+ * 63) and k_edit_strands_duel (edit_strands/rg_edit_strands.hip) appear in the kernel statistics under their own names beside
+ * k_gap_pick (twice per chunk), k_strand_orient, k_edit_dirs, k_edit_trace and k_gap_xstrands_mark.
+ */
+#define RG_MODE_PATHWISE_EDIT_STRANDS 64
+#define RG_MODE_PATHWISE_EDIT_SEMI_STRANDS 65
 
 /*
  * Scoring and banding parameters.  Replaces the HashMap<(char,char),i32|f32> score matrix arguments

@@ -128,6 +128,26 @@ def edit_family_modes(suffix):
     return tuple(mode for mode, m in _EDIT_MODES.items() if m.family.suffix == suffix)
 
 
+# The two both-strands edit-distance pathwise modes (csrc/rg_edit_strands_modes.hpp; RG_MODE_PATHWISE_EDIT_STRANDS in
+# include/recgraph_hip.h): modes 44 / 45 with both strands of every read scored in one wave.  Deliberately NO rows of EDIT_FAMILIES or
+# GAP_FAMILIES: edit_mode(64) and gap_mode(64) are None, and EDIT_MODE_NAMES stays as it is — the flag rule (both strands is the mode
+# itself, the vote is refused) is that of no row there.
+EDIT_STRANDS_MODES = (64, 65)               # global, semiglobal: the rules of modes 26 / 27 at unit costs
+EDIT_STRANDS_MAX_READ = 16383
+EDIT_STRANDS_MODE_NAMES = {"MODE_PATHWISE_EDIT_STRANDS": 64, "MODE_PATHWISE_EDIT_SEMI_STRANDS": 65}
+globals().update(EDIT_STRANDS_MODE_NAMES)
+EDIT_STRANDS_SCORE_REFUSAL = ("the both-strands edit-distance pathwise modes (-m 64 / -m 65) take unit costs only: -M 0 -X 1 -O 0 -E 1, or a -t "
+                              "matrix whose ACGTN x ACGTN entries are all 0 or -1 with -O 0 -E 1; every other scoring is what -m 26 / -m 27 are for")
+EDIT_STRANDS_VOTE_REFUSAL = ("%s is not available in the both-strands edit-distance pathwise modes (64, 65): both strands of every read "
+                             "are scored in one pass, so a 12-mer vote would save nothing and would change the rule")
+EDIT_STRANDS_CLI_HELP = "64, 65: modes 44, 45 on both strands, scored in one pass and traced once (modes 26, 27 at unit costs)"
+
+
+def edit_strands_mode(mode):
+    """``semi`` (False / True) of a both-strands edit-distance pathwise mode, None for every other value."""
+    return bool(EDIT_STRANDS_MODES.index(mode)) if mode in EDIT_STRANDS_MODES else None
+
+
 def unit_costs(table, gap_open, gap_ext):
     """What every edit-distance mode admits: gap_open 0, gap_ext -1 and a 36-entry score table whose ACGTN x ACGTN block holds 0 and -1 only."""
     return gap_open == 0 and gap_ext == -1 and all(table[a * 6 + b] in (0, -1) for a in range(5) for b in range(5))

@@ -53,6 +53,9 @@ globals().update(_lib.GAP_MODE_NAMES)
 # (0, -1) and a 0 / -1 matrix the bytes of the gap family each row of _lib.EDIT_FAMILIES names, anything else is refused.
 # MODE_PATHWISE_EDIT, MODE_PATHWISE_EDIT_SEMI (those of _LONG), and the two again as _XLONG
 globals().update(_lib.EDIT_MODE_NAMES)
+# ... and on both strands, scored in one pass and traced once: MODE_PATHWISE_EDIT_STRANDS (64), MODE_PATHWISE_EDIT_SEMI_STRANDS (65) — the
+# texts, statuses, scores and strands of MODE_PATHWISE_GAP_STRANDS / MODE_PATHWISE_GAP_SEMI_STRANDS at unit costs
+globals().update(_lib.EDIT_STRANDS_MODE_NAMES)
 
 READ_BAND_WARNING, READ_BAND_NOT_ENOUGH, READ_WOULD_PANIC, READ_BAD_BASE = 1, 2, 4, 8
 READ_UNALIGNED = _lib.READ_UNALIGNED
@@ -74,6 +77,8 @@ PATHWISE_GAP_XSTRANDS_MODES = _lib.gap_family_modes("_XSTRANDS")
 PATHWISE_EDIT_MODES = _lib.edit_family_modes("")
 # ... up to 131071 bases
 PATHWISE_EDIT_XLONG_MODES = _lib.edit_family_modes("_XLONG")
+# unit costs on both strands, up to 16383 bases: both strands is the mode itself, so ``both_strands=True`` is redundant there
+PATHWISE_EDIT_STRANDS_MODES = _lib.EDIT_STRANDS_MODES
 
 
 def _both_strands_kw(mode, both_strands, kw, strand_vote=False):
@@ -84,6 +89,10 @@ def _both_strands_kw(mode, both_strands, kw, strand_vote=False):
         return kw
     flag = "strand_vote" if strand_vote else "both_strands"
     em, gm = _lib.edit_mode(mode), _lib.gap_mode(mode)
+    if mode in PATHWISE_EDIT_STRANDS_MODES:
+        if strand_vote:
+            raise _lib.RecGraphError(-1, _lib.EDIT_STRANDS_VOTE_REFUSAL % flag)
+        return dict(kw, amb=(kw.get("amb") or 0) | AMB_BOTH_STRANDS)
     if em:
         raise _lib.RecGraphError(-1, em.family.api_refusal % flag)
     if gm and not gm.family.both_strands:
@@ -927,6 +936,15 @@ def pathwise_alignment_edit_xlong_exec(sequence, graph, semi=False, score_matrix
     ``pathwise_alignment_gap_exec(..., o=0, e=-1, very_long_reads=True)`` (``..._semi_exec``) for a 0 / -1 matrix.  A read of at most
     16383 bases runs exactly as in -m 44 / -m 45; a longer one in column stripes of 16384 on the same bit-vector row step."""
     return _edit_exec("_XLONG", sequence, graph, semi, score_matrix)
+
+
+def pathwise_alignment_edit_strands_exec(sequence, graph, semi=False, score_matrix=None):
+    """-m 64 (``semi=True``: -m 65): ``pathwise_alignment_edit_exec`` on both strands, which is ``pathwise_alignment_gap_exec(..., o=0,
+    e=-1, both_strands=True)`` (``..._semi_exec``) for a 0 / -1 matrix: both strands of the read are scored in one pass, the reverse
+    complement wins only with a strictly greater score, and the GAFStruct of a reverse winner has strand ``-``."""
+    sm = score_matrix if score_matrix is not None else create_score_matrix_i32(0, -1)
+    _, text = _single(graph, "".join(sequence[1:]), "Temp", PATHWISE_EDIT_STRANDS_MODES[bool(semi)], 1, score_matrix=sm, o=0, e=-1)
+    return GAFStruct.from_line(text.rstrip("\n"))
 
 
 def pathwise_alignment_recombination_exec(aln_mode, sequence, graph, score_matrix=None, base_rec_cost=4,

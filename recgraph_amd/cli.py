@@ -49,13 +49,21 @@ _STRAND_MODES = [m for m in sorted(_lib.GAP_MODE_NAMES.values()) if _lib.gap_mod
 
 
 def check_mode_flags(alignment_mode, both_strands, strand_vote, amb_strand):
-    """What main refuses before it opens a file: a mode that is neither 0 to 9 nor a row of _lib.GAP_FAMILIES or _lib.EDIT_FAMILIES, and
+    """What main refuses before it opens a file: a mode that is neither 0 to 9 nor a row of _lib.GAP_FAMILIES or _lib.EDIT_FAMILIES nor one of
+    _lib.EDIT_STRANDS_MODES, and
     --both-strands / --strand-vote where the mode has no such rule.  Returns whether ``-s true`` counts."""
     gm = _lib.gap_mode(alignment_mode)
     em = _lib.edit_mode(alignment_mode)
     if em:
         if both_strands or strand_vote:
             raise SystemExit(em.family.cli_refusal)
+        return False
+    if _lib.edit_strands_mode(alignment_mode) is not None:
+        # both strands is the mode itself: --both-strands is redundant; a vote or the reference's retry would be another rule
+        if strand_vote:
+            raise SystemExit(_lib.EDIT_STRANDS_VOTE_REFUSAL % "--strand-vote")
+        if amb_strand == "true":
+            raise SystemExit("-s true is not available in modes 64 and 65: they align both strands of every read themselves, inside the batch")
         return False
     if alignment_mode not in range(10) and not gm:
         raise SystemExit("Alignment mode must be in [0..9], or 12")   # main.rs:315-317; 12: local affine-gap pathwise, this project's own
@@ -77,11 +85,12 @@ def check_edit_scores(alignment_mode, scores, gap_open, gap_extension):
     """The edit-distance modes (_lib.EDIT_FAMILIES) take unit costs only: what main refuses once the score matrix is built, before it opens
     the graph.  ``scores``: the matrix as a dict; ``gap_open`` / ``gap_extension``: -O / -E as given (positive)."""
     em = _lib.edit_mode(alignment_mode)
-    if not em:
+    strands = _lib.edit_strands_mode(alignment_mode) is not None      # (modes 64 / 65: the same admission, their own words)
+    if not em and not strands:
         return
     table = [scores.get((a, b), 0) for a in "ACGTN-" for b in "ACGTN-"]
     if not _lib.unit_costs(table, -gap_open, -gap_extension):
-        raise SystemExit(em.family.score_refusal)
+        raise SystemExit(_lib.EDIT_STRANDS_SCORE_REFUSAL if strands else em.family.score_refusal)
 
 
 def build_parser():
@@ -90,7 +99,7 @@ def build_parser():
     p.add_argument("graph_path")
     p.add_argument("-o", "--out_file", default="standard output")
     p.add_argument("-m", "--aln-mode", type=int, default=0, dest="alignment_mode",
-                   help="0 to 9 as in the reference; " + "; ".join(f.cli_help for f in _lib.GAP_FAMILIES + _lib.EDIT_FAMILIES))
+                   help="0 to 9 as in the reference; " + "; ".join([f.cli_help for f in _lib.GAP_FAMILIES + _lib.EDIT_FAMILIES] + [_lib.EDIT_STRANDS_CLI_HELP]))
     p.add_argument("-M", "--match", type=int, default=2, dest="match_score")
     p.add_argument("-X", "--mismatch", type=int, default=4, dest="mismatch_score")
     p.add_argument("-t", "--matrix", default="none")
@@ -103,7 +112,7 @@ def build_parser():
     p.add_argument("-b", "--extra-b", type=int, default=1)
     p.add_argument("-f", "--extra-f", type=float, default=0.01)
     p.add_argument("--both-strands", action="store_true", dest="both_strands",
-                   help="modes 4, 5, 8, 9 (not a flag of the reference; refused in 6 and 7; redundant in %s): reads that score below 0 are aligned again as their reverse "
+                   help="modes 4, 5, 8, 9 (not a flag of the reference; refused in 6 and 7; redundant in %s, 64, 65): reads that score below 0 are aligned again as their reverse "
                         "complement; a strictly better reverse record is written with strand '-'" % ", ".join(str(m) for m in _STRAND_MODES))
     p.add_argument("--strand-vote", action="store_true", dest="strand_vote",
                    help="modes 4, 5, 8, 9, %s (not a flag of the reference; implies --both-strands): the strand that is aligned first is "

@@ -331,7 +331,9 @@ static int load_reads(rg_batch* b, const char* reads, const int64_t* read_off, i
     // half (forward to the source, reverse to the sink): <= 2 * (rows of the longest path + n)
     b->ops_stride = is_poa(mode) ? (long long)h.L + b->max_n + 8
                                  : std::min<long long>((long long)h.L + b->max_n + 8, 2ll * (h.max_path_rows + b->max_n) + 16);
-    const bool both = !is_poa(mode) && (p->amb_mode & RG_AMB_BOTH_STRANDS);
+    // (-m 64 / -m 65 score both strands in one pass and trace one: the bit is set on their handles, but there is no second pass, no
+    // merge and none of the strand buffers)
+    const bool both = !is_poa(mode) && (p->amb_mode & RG_AMB_BOTH_STRANDS) && !edit_strands_mode(mode).valid;
     // k_strand_merge moves op bytes in 16-byte pieces (a staged family traces the chosen strand alone: no merge, the op area of one pass)
     if (both && !gap_mode(mode).family->staged) b->ops_stride = (b->ops_stride + 15) & ~15ll;
     if ((rc = b->d_ops.alloc((size_t)nreads * b->ops_stride))) return rc;
@@ -361,7 +363,7 @@ int32_t rg_batch_create(const rg_graph* gc, const rg_params* p, const char* read
     const rg_graph* g = gc;
     const int mode = p->mode;
     const bool path_gap = gap_mode(mode).valid;       // (every rule in every family of rg_gap_modes.hpp)
-    const bool path_edit = edit_mode(mode).valid;     // (every rule in every family of rg_edit_modes.hpp)
+    const bool path_edit = edit_mode(mode).valid || edit_strands_mode(mode).valid;     // (every rule in every family of rg_edit_modes.hpp, and -m 64 / -m 65: rg_edit_strands_modes.hpp)
     if (!(is_poa(mode) || mode == RG_MODE_PATHWISE || mode == RG_MODE_RECOMBINATION || mode == RG_MODE_PATHWISE_SEMI ||
           mode == RG_MODE_RECOMBINATION_SEMI || path_gap || path_edit))
         return fail(RG_ERR_ARG, "unsupported mode");
@@ -406,7 +408,7 @@ int32_t rg_batch_create(const rg_graph* gc, const rg_params* p, const char* read
     b->p = *p;
     // a both-strands family aligns both strands whatever the bit says: from here on the handle IS a both-strands handle (the
     // ops_stride, the strand buffers, the strand of a record)
-    if (gap_mode(mode).family->both_strands) b->p.amb_mode |= RG_AMB_BOTH_STRANDS;
+    if (gap_mode(mode).family->both_strands || edit_strands_mode(mode).valid) b->p.amb_mode |= RG_AMB_BOTH_STRANDS;
     HIPCHK(hipGetDevice(&b->dev));
     {
         // the handle's stream at the highest priority: it carries the small kernels; the pathwise sweeps run on a low-priority

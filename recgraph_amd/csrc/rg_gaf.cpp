@@ -334,7 +334,7 @@ struct PathwiseWalk {
 inline char base_at(const uint8_t* codes, int n, int col) { return col == 0 ? '$' : "ACGTN"[codes[(size_t)col - 1]]; }
 
 void walk_pathwise(const HostGraph& g, const uint8_t* codes, int n, const ReadRecord& r, int mode, PathwiseScratch& sc, PathwiseWalk& w) {
-    mode = path_gap_base_mode(edit_base_mode(mode));       // (every family of an affine-gap rule, and -m 44 / -m 45 / -m 94 / -m 95: the record and the line of its base mode)
+    mode = path_gap_base_mode(edit_any_base_mode(mode));       // (every family of an affine-gap rule, and -m 44 / -m 45 / -m 94 / -m 95 / -m 64 / -m 65: the record and the line of its base mode)
     const size_t cap = (size_t)std::max(r.n_ops, 1);
     if (sc.ops.size() < cap) { sc.ops.resize(cap); sc.pseq.resize(cap); sc.ids.resize(cap); }
     char* ops = sc.ops.data();
@@ -469,7 +469,7 @@ thread_local PathwiseScratch t_scratch;
 
 GafFields fields_pathwise(const HostGraph& g, const std::string& read, const std::string& name,
                           const ReadRecord& r, int mode, char strand) {
-    mode = path_gap_base_mode(edit_base_mode(mode));
+    mode = path_gap_base_mode(edit_any_base_mode(mode));
     const int n = (int)read.size();
     std::vector<uint8_t> codes((size_t)n);
     for (int k = 0; k < n; ++k) { const char c = read[(size_t)k]; codes[(size_t)k] = c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : 4; }
@@ -501,7 +501,7 @@ GafFields fields_pathwise(const HostGraph& g, const std::string& read, const std
 // pathwise_alignment_output.rs:161-167, recombination_output.rs:598-612, 759-765)
 void append_pathwise_text(const HostGraph& g, const uint8_t* codes, int n, const char* name, const ReadRecord& r, int mode, std::string& out,
                           char strand) {
-    mode = path_gap_base_mode(edit_base_mode(mode));
+    mode = path_gap_base_mode(edit_any_base_mode(mode));
     PathwiseWalk w;
     walk_pathwise(g, codes, n, r, mode, t_scratch, w);
     const size_t nlen = strlen(name);

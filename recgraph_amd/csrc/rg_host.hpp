@@ -16,6 +16,7 @@
 #include "../../include/recgraph_hip.h"
 #include "rg_gap_modes.hpp"      // gap_mode(): rule and family of an affine-gap pathwise mode
 #include "rg_edit_modes.hpp"     // edit_mode(): rule and family of a bit-vector edit-distance pathwise mode
+#include "rg_edit_strands_modes.hpp"     // edit_strands_mode(): the two both-strands edit-distance modes, rows of neither table
 
 namespace rg {
 

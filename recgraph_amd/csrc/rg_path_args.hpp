@@ -149,6 +149,9 @@ struct PathJob {
     // -m 82 — the PICK stage (score pass + pick: `rec` gets status, score, path and end row, `ops` is not touched and may be null) or
     // the TRACE stage (`rec` holds such picks on entry, and the records and ops of the traceback on return)
     int stage = 0;
+    // the same offsets on the host, or null.  -m 64 / -m 65 need them: a chunk's reads on the winning strand go into a buffer of the
+    // chunk's own, at the input's offsets minus the chunk's first
+    const long long* h_off = nullptr;
 };
 // cells [2]: the job's cell updates, counted | performed, are ADDED
 int path_driver_run(const PathCtx& c, const PathJob& j, unsigned long long* cells);

@@ -15,6 +15,8 @@
 //   -m 44: edit_score(every path) -> gap_pick -> edit_dirs(picked path) -> edit_trace        (edit/rg_path_edit.hip; -m 45 likewise)
 //   -m 94: the same up to 16383 bases; a batch with a longer read: edit_score_xlong -> gap_pick -> (edit_redo_xlong -> edit_walk_xlong)
 //          per stripe, last to first                                                        (edit_xlong/rg_path_edit_xlong.hip; -m 95 likewise)
+//   -m 64: edit_score_pair(every path, both strands in one wave) -> gap_pick(forward) -> gap_pick(reverse) -> edit_strands_duel
+//          -> strand_orient(the strand that won) -> edit_dirs -> edit_trace -> gap_xstrands_mark   (edit_strands/rg_edit_strands.hip; -m 65 likewise)
 //   -m 8:  sweep(F1: column maxima) -> seed -> thr -> sweep(R: dirs, candidates, column maxima)
 //          -> thr -> sweep(F2: dirs, candidates) -> search -> layer(F) -> layer(R) -> trace
 #include <algorithm>
@@ -30,6 +32,7 @@
 #include "gap_xstrands/rg_gap_xstrands.hpp"
 #include "edit/rg_path_edit.hpp"
 #include "edit_xlong/rg_path_edit_xlong.hpp"
+#include "edit_strands/rg_edit_strands.hpp"
 #include "rg_kernel_timer.hpp"
 #include "rg_path_kernels.hpp"
 #include "rg_path_plan.hpp"
@@ -47,6 +50,8 @@ struct PathWorkImpl {
     DevBuf<GapWalkState> gwalk;         // ... and where each read's walk stands between two rounds
     DevBuf<unsigned long long> ebnd;    // -m 94 / -m 95: the boundary bits of every path's stripes but the last
     DevBuf<EditWalkState> ewalk;        // ... and where each read's walk stands between two rounds
+    DevBuf<ReadState> state2;           // -m 64 / -m 65: the picks of the reverse strand
+    DevBuf<uint8_t> oriented, strand;   // ... the chunk's reads on the strand that won, and which strand that is (1 = reverse)
     DevBuf<Cand> fcand, rcand;
     DevBuf<unsigned> nf, nr, ridx, nrec, nrrec;
     DevBuf<int> frec, rrec;
@@ -103,6 +108,7 @@ struct Run {
     int done = 0, chunk = 0;
     hipError_t async_err = hipSuccess;       // of calls inside timed launches: reported once the chunk is through
     DevScores sc{};
+    const long long* h_off = nullptr;        // PathJob::h_off
 
     const long long* off() const { return d_off + done; }
     const uint8_t* bad() const { return d_bad + done; }
@@ -118,6 +124,7 @@ struct Run {
     int enqueue_pathwise_gap();
     int enqueue_pathwise_edit();
     int enqueue_pathwise_edit_xlong();
+    int enqueue_pathwise_edit_strands();
     int read_back();
     int enqueue_recombination(SweepArgs& sa, const SeedArgs& se);
     int enqueue_forward_bounded(SweepArgs& sa, const SeedArgs& se);
@@ -174,6 +181,7 @@ int Run::alloc_chunk(bool* oom) {
     int rc;
     if (plan.edit) {
         if ((rc = w.state.alloc(n, oom)) || (rc = w.gdirs.alloc(n * (size_t)plan.gdirs_stride, oom))) return rc;
+        if (plan.edit_strands && ((rc = w.state2.alloc(n, oom)) || (rc = w.oriented.alloc(n * plan.edit_orient_bytes + 64, oom)) || (rc = w.strand.alloc(n, oom)))) return rc;
         if (plan.edit_xlong && ((rc = w.ebnd.alloc(n * (size_t)plan.edit_bnd_stride, oom)) || (rc = w.ewalk.alloc(n, oom)))) return rc;
         return RG_OK;
     }
@@ -356,6 +364,34 @@ int Run::enqueue_pathwise_edit() {
     RG_TRY(T.run("k_gap_pick", [&] { return launch_gap_pick(ga, chunk, 64 * W, semi, stream); }));
     RG_TRY(T.run("k_edit_dirs", [&] { return launch_edit_dirs(ga, chunk, W, semi, stream); }));
     RG_TRY(T.run("k_edit_trace", [&] { return launch_edit_trace(ga, chunk, W, semi, stream); }));
+    return read_back();
+}
+
+// -m 64 / -m 65:  edit_score_pair(every path, both strands) -> gap_pick x 2 -> duel -> strand_orient -> edit_dirs -> edit_trace -> mark
+// -> the chunk's one read-back.  No host synchronisation in between: the score decides the strand on the device, and the one strand
+// that won is traced, from a buffer that holds the chunk's reads on that strand at the input's offsets minus the chunk's first
+int Run::enqueue_pathwise_edit_strands() {
+    if (!h_off) return fail(RG_ERR_ARG, "the both-strands edit-distance modes need the read offsets on the host");
+    HIPCHK(hipMemsetAsync(w.state2.p, 0, sizeof(ReadState) * chunk, stream));
+    GapArgs ga = gap_args();
+    const int W = plan.edit_words, Wp = plan.edit_pair_words;
+    const bool semi = plan.semi;
+    RG_TRY(T.run("k_edit_score_pair", [&] { return launch_edit_score_pair(ga, w.state2.p, chunk, Wp, semi, stream); }));
+    // (the pick kernel's width as in enqueue_pathwise_edit; the same reads, offsets and bad flags for either strand)
+    GapArgs gr = ga;
+    gr.state = w.state2.p;
+    RG_TRY(T.run("k_gap_pick", [&] { return launch_gap_pick(ga, chunk, 64 * W, semi, stream); }));
+    RG_TRY(T.run("k_gap_pick", [&] { return launch_gap_pick(gr, chunk, 64 * W, semi, stream); }));
+    RG_TRY(T.run("k_edit_strands_duel", [&] { return launch_edit_strands_duel(w.state.p, w.state2.p, w.strand.p, chunk, stream); }));
+    // (k_strand_orient and the edit kernels address a read as base + offset: the base that puts the chunk's first read at the buffer's start)
+    uint8_t* obase = reinterpret_cast<uint8_t*>(reinterpret_cast<uintptr_t>(w.oriented.p) - (uintptr_t)h_off[done]);
+    StrandOrientArgs oa{d_reads, off(), w.strand.p, obase};
+    RG_TRY(T.run("k_strand_orient", [&] { return launch_strand_orient(oa, chunk, stream); }));
+    ga.reads = obase;
+    RG_TRY(T.run("k_edit_dirs", [&] { return launch_edit_dirs(ga, chunk, W, semi, stream); }));
+    RG_TRY(T.run("k_edit_trace", [&] { return launch_edit_trace(ga, chunk, W, semi, stream); }));
+    // (the walk's record writer clears DevRecord.pad)
+    RG_TRY(T.run("k_gap_xstrands_mark", [&] { return launch_gap_xstrands_mark(ga.rec, w.strand.p, chunk, stream); }));
     return read_back();
 }
 
@@ -558,6 +594,7 @@ int Run::read_back() {
 int Run::enqueue_chunk() {
     HIPCHK(hipMemsetAsync(w.state.p, 0, sizeof(ReadState) * chunk, stream));
     if (plan.gap) return enqueue_pathwise_gap();
+    if (plan.edit_strands) return enqueue_pathwise_edit_strands();
     if (plan.edit) return plan.edit_xlong ? enqueue_pathwise_edit_xlong() : enqueue_pathwise_edit();
     SweepArgs sa = sweep_args();
     SeedArgs se;
@@ -713,6 +750,7 @@ int path_driver_run(const PathCtx& c, const PathJob& j, unsigned long long* cell
     if (rc || (rc = plan_gap_stage(plan, j.stage))) return rc;
     Run r{h, c.gd, p, w, plan, j.reads, j.off, j.bad, j.max_n, j.rec, j.ops, j.ops_stride, d_cells, stream, stats, c.spec_level, c.T, opt.debug != 0};
     for (int i = 0; i < 36; ++i) r.sc.t[i] = p.scores[i];
+    r.h_off = j.h_off;
     if (!w.h_sum) HIPCHK(hipHostMalloc((void**)&w.h_sum, 8 * sizeof(unsigned long long), hipHostMallocDefault));
     if ((rc = w.need.alloc(8)) || (rc = ensure_tables(h, w))) return rc;
     if (w.fcap == 0) { w.fcap = plan.fcap; w.rcap = plan.rcap; w.frec_cap = plan.frec_cap; w.rrec_cap = plan.rrec_cap; }

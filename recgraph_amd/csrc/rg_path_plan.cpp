@@ -175,6 +175,42 @@ int plan_pathwise_edit(const rg_params& p, const PathPlanInput& in, PathPlan& o)
     return RG_OK;
 }
 
+// The both-strands edit-distance modes (rg_edit_strands_modes.hpp): the plan of -m 44 / -m 45 for the direction pass and the walk, which
+// run once per read on the strand that won; the score pass holds a strand in half a wave, 32 W' columns per lane.  Beside that plan's
+// buffers: the picks of the reverse strand (a second ReadState), the read on the winning strand and the strand byte.
+int plan_pathwise_edit_strands(const rg_params& p, const PathPlanInput& in, PathPlan& o) {
+    const EditStrandsMode em = edit_strands_mode(p.mode);
+    if (!em.valid) return fail(RG_ERR_ARG, "unsupported mode");
+    if (p.gap_open > 0 || p.gap_ext > 0) return fail(RG_ERR_ARG, "gap penalties must be <= 0");
+    bool unit = p.gap_open == 0 && p.gap_ext == -1;
+    for (int x = 0; x < 5; ++x)
+        for (int y = 0; y < 5; ++y) unit = unit && (p.scores[x * 6 + y] == 0 || p.scores[x * 6 + y] == -1);
+    if (!unit) return fail(RG_ERR_ARG, kEditStrandsScoreRefusal);
+    // both strands is what the modes do (bit 2 is redundant); the vote would change the rule and save nothing
+    if (p.amb_mode != 0 && p.amb_mode != RG_AMB_BOTH_STRANDS) return fail(RG_ERR_ARG, kEditStrandsAmbRefusal);
+    if (in.max_n > EDIT_STRANDS_MAX_READ) return fail(RG_ERR_ARG, kEditStrandsLenRefusal);
+    // mode 16's budget, at max(|sc|, |o + e|) = 1: what it refuses is refused here
+    if ((long long)in.max_path_rows + in.max_n >= (1ll << 28))
+        return fail(RG_ERR_CAPACITY, "scores of this batch can reach 2^28 in magnitude: outside the i32 range of the affine-gap pathwise kernels");
+    o.edit = true;
+    o.edit_strands = true;
+    o.mode = RG_MODE_PATHWISE_EDIT;
+    o.semi = em.semi;
+    int W = 1;
+    while (2048 * W < in.max_n && W < EDIT_MAX_WORDS) W *= 2;
+    o.edit_words = W;
+    int Wp = 1;
+    while (1024 * Wp < in.max_n && Wp < EDIT_STRANDS_MAX_WORDS) Wp *= 2;
+    o.edit_pair_words = Wp;
+    o.C = 32 * W;                 // columns per lane of the direction pass
+    o.nwv = 1;
+    o.wpad = 2048 * W;
+    o.gdirs_stride = (long long)(in.max_path_rows + 1) * 2 * W * WAVE;
+    o.edit_orient_bytes = ((size_t)in.max_n + 15) & ~(size_t)15;
+    o.per_read = (size_t)o.gdirs_stride * 4 + 2 * sizeof(ReadState) + o.edit_orient_bytes + 1;
+    return RG_OK;
+}
+
 int plan_gap_stage(PathPlan& o, int stage) {
     if (stage == PATH_STAGE_ALL) return RG_OK;
     if ((stage != PATH_STAGE_PICK && stage != PATH_STAGE_TRACE) || !o.gap || (o.nwv > 1 && !o.gap_xlong))
@@ -191,6 +227,7 @@ int plan_pathwise(const rg_params& p, const PathPlanInput& in, const Options& op
     const GapMode gm = gap_mode(p.mode);
     if (gm.valid) return plan_pathwise_gap(p, gm, in, o);
     if (edit_mode(p.mode).valid) return plan_pathwise_edit(p, in, o);
+    if (edit_strands_mode(p.mode).valid) return plan_pathwise_edit_strands(p, in, o);
     const int P = in.P, L = in.L, max_n = in.max_n;
     o.semi = p.mode == RG_MODE_PATHWISE_SEMI || p.mode == RG_MODE_RECOMBINATION_SEMI;
     o.mode = p.mode == RG_MODE_PATHWISE_SEMI ? RG_MODE_PATHWISE : p.mode == RG_MODE_RECOMBINATION_SEMI ? RG_MODE_RECOMBINATION : p.mode;

@@ -89,6 +89,13 @@ struct PathPlan {
     bool edit_xlong;
     int edit_slot_words;
     long long edit_bnd_stride;
+    // -m 64 / -m 65 (both strands in one wave, edit_strands/rg_edit_strands.hip): `edit` is set and the direction pass, the walk and
+    // gdirs_stride are those of -m 44 / -m 45 at edit_words (the smallest with max_n <= 2048 W); the score pass runs at edit_pair_words
+    // (1, 2, 4, 8, 16: the smallest with max_n <= 1024 W, a strand takes 32 lanes).  per_read counts a second ReadState (the reverse
+    // strand's picks), the read on the strand that won (edit_orient_bytes: max_n rounded up to 16) and the strand byte
+    bool edit_strands;
+    int edit_pair_words;
+    size_t edit_orient_bytes;
 
     // ... with candidate lists of fcap / rcap entries and record lists of frec_cap / rrec_cap records
     size_t per_read_all(unsigned fcap_, unsigned rcap_, unsigned frec_cap_, unsigned rrec_cap_) const {
@@ -106,6 +113,9 @@ int plan_pathwise(const rg_params& p, const PathPlanInput& in, const Options& op
 // family's limit (RG_ERR_ARG), mode 16's 2^28 budget (RG_ERR_CAPACITY).  In every family the plan of -m 44 / -m 45 up to 16383 bases, the
 // striped one (PathPlan::edit_xlong) beyond.  `out` must be a cleared plan
 int plan_pathwise_edit(const rg_params& p, const PathPlanInput& in, PathPlan& out);
+// The plan of the both-strands edit-distance modes (rg_edit_strands_modes.hpp; what plan_pathwise returns for -m 64 / -m 65): the
+// admission of -m 44 / -m 45 with amb_mode 0 or 4 admitted and every other value refused in the modes' own words (PathPlan::edit_strands)
+int plan_pathwise_edit_strands(const rg_params& p, const PathPlanInput& in, PathPlan& out);
 
 // The stages of an affine-gap pipeline (PathJob::stage, rg_path_args.hpp).  PICK: score pass + pick, and the pick goes out into the
 // job's records (status, score, path, end row; no ops).  TRACE: the picks come back in from the job's records, then the direction

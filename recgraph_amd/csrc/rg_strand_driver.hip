@@ -12,6 +12,8 @@
 // PathWork, the strand buffers by the handle (size_strand_buffers).
 //
 // A staged family (both strands at up to 131071 bases) is not two passes but two PICK stages and one TRACE stage: run_gap_xstrands below.
+// The both-strands edit-distance modes (-m 64 / -m 65) are ONE pass: its score kernel holds both strands in one wave, and none of the
+// strand buffers here exists on their handles.
 #include "gap_strands/rg_gap_strands.hpp"
 #include "gap_xstrands/rg_gap_xstrands.hpp"
 #include "rg_batch_impl.hpp"
@@ -139,11 +141,15 @@ int rg_run_pathwise(rg_batch* b) {
     unsigned long long cells[2] = {0, 0};      // counted | performed, summed over the passes (the workload grows with pass B)
     // pass A: the reads as given, or (RG_AMB_STRAND_VOTE) each on the strand its 12-mers vote for, at the same offsets
     PathJob a{b->in.reads, b->in.off, b->in.bad, n, b->max_n, b->d_rec.p, b->d_ops.p, b->ops_stride};
-    RG_TRY(first_strand(b, false, a));
+    // -m 64 / -m 65: both strands are scored inside that one pass, which decides and marks the strand itself (rg_path_driver.hip:
+    // enqueue_pathwise_edit_strands); it needs the offsets on the host as well
+    const bool one_pass = edit_strands_mode(b->p.mode).valid;
+    if (one_pass) a.h_off = b->off.data();
+    else RG_TRY(first_strand(b, false, a));
     const int rc_a = path_driver_run(cx, a, cells);
     b->cells = cells[0];
     b->cells_performed = cells[1];
-    if (rc_a || !(b->p.amb_mode & RG_AMB_BOTH_STRANDS)) return rc_a;
+    if (rc_a || one_pass || !(b->p.amb_mode & RG_AMB_BOTH_STRANDS)) return rc_a;
     // the qualifying reads once more, on the other strand, in the same work buffers
     const int recomb = b->p.mode == RG_MODE_RECOMBINATION || b->p.mode == RG_MODE_RECOMBINATION_SEMI ? 1 : 0;
     int count = 0, max_len = 0;

@@ -102,7 +102,7 @@ int usable_cpus() {
 
 bool mode_is_pathwise(int mode) {
     return mode == RG_MODE_PATHWISE || mode == RG_MODE_RECOMBINATION || mode == RG_MODE_PATHWISE_SEMI || mode == RG_MODE_RECOMBINATION_SEMI ||
-           gap_mode(mode).valid || edit_mode(mode).valid;
+           gap_mode(mode).valid || edit_mode(mode).valid || edit_strands_mode(mode).valid;
 }
 bool mode_is_local(int mode) { return mode == RG_MODE_LOCAL_POA || mode == RG_MODE_LOCAL_POA_SCALAR || mode == RG_MODE_GAP_LOCAL_POA; }
 

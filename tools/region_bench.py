@@ -3,7 +3,7 @@
 engine on other read lengths, score parameters and path counts, with the sweep kernel that ran and a parity check of a
 few reads against the oracle.  One JSON line per case.
 
-    python tools/region_bench.py [case ...]        cases: c5 x6 m3x5 hoxd70 len1500 p128 len600 gap gap_local gap_long gap_strands gap_xlong gap_xstrands edit edit_xlong (default: all but the strand cases, the six `gap` cases and the two `edit` cases)
+    python tools/region_bench.py [case ...]        cases: c5 x6 m3x5 hoxd70 len1500 p128 len600 gap gap_local gap_long gap_strands gap_xlong gap_xstrands edit edit_xlong edit_strands (default: all but the strand cases, the six `gap` cases and the three `edit` cases)
 
 The strand cases (RG_AMB_BOTH_STRANDS, config-5 shape; `reads_per_s` counts SOURCE reads): `both_strands_fwd` — option on, every
 read forward (what the option costs when nothing qualifies: compare with `c5`); `both_strands` — option on, half of the reads
@@ -64,6 +64,13 @@ mode's per counted cell, and the work bytes per read.  Two reads of each part ar
 the handle's kernel timer.  All texts, statuses and counted cells of the two modes are compared; per mode: time per batch, time per
 counted cell update, performed over counted cells, the time of every kernel, the work bytes per read; and -m 94 as a ratio to -m 56.  One
 JSON line.
+
+`edit_strands` (only when named): -m 64 beside -m 26 OF THE SAME BUILD (the only other way to these bytes) and beside TWO -m 44 batches — the
+reads as given, and the same reads reverse-complemented on the host: what a caller without the mode submits — at unit costs, by the same
+protocol: one process, warm-up, alternating rounds, whole rg_batch_run calls, the handle's kernel timer.  Shapes (a) and (b) of `edit`;
+half of the reads are reverse-complemented (synth.reverse_complement_share, seed 5678).  Texts, statuses and strands of -m 64 and -m 26
+are compared; per mode: time per batch, the time of every kernel, the work bytes per read; and the ratios -m 64 / -m 26, k_edit_score_pair /
+(the two k_edit_score), -m 64 / (the two -m 44 batches).  One JSON line per part; RG_REGION_PART=a or b runs one part.
 
 Every case: TILES tiles of TILE reads through one rg_stream (3 handles), timed after one warm-up tile per handle."""
 import json
@@ -346,6 +353,67 @@ def edit_xlong_case():
     print(json.dumps(out), flush=True)
 
 
+def edit_strands_case():
+    from recgraph_amd import api, synth
+    unit = api.create_score_matrix_i32(0, -1)
+    comp = {"A": "T", "C": "G", "G": "C", "T": "A", "N": "N"}
+    rc = lambda r: "".join(comp[c] for c in reversed(r))
+    # (part, rows of the graph, paths, rows of a path = read length, reads, rounds)
+    parts = (("a", 12000, 16, 4000, 512, 3), ("b", 5000, 16, 1000, 2048, 5))
+    for part, grows, paths, plen, nreads, rounds in parts:
+        if os.environ.get("RG_REGION_PART", part) != part:
+            continue
+        g = synth.haplotype_graph(grows, paths, path_len=plen, seed=1234)
+        gg = api.Graph.from_gfa_text(g.gfa())
+        reads, _ = synth.reverse_complement_share(synth.haplotype_reads(g, nreads, length=plen, seed=900, mosaic_frac=0.0), 0.5, seed=5678)
+        M64, M26, M44 = api.MODE_PATHWISE_EDIT_STRANDS, api.MODE_PATHWISE_GAP_STRANDS, api.MODE_PATHWISE_EDIT
+        make = lambda m, rs: api.Batch(gg, rs, api.make_params(m, score_matrix=unit, o=0, e=-1))
+        # the runs of a round: -m 64, -m 26, and the two -m 44 batches a caller without the mode submits
+        batch = {"m64": make(M64, reads), "m26": make(M26, reads), "m44_given": make(M44, reads), "m44_revcomp": make(M44, [rc(r) for r in reads])}
+        times = {k: [] for k in batch}
+        ks = {k: {} for k in batch}
+        mem = {}
+        for k in batch:
+            batch[k].run()                       # warm-up: code objects, work buffers
+        for _ in range(rounds):
+            for k in batch:                      # alternating: every run sees the same machine
+                t0 = time.perf_counter()
+                batch[k].run()
+                times[k].append(time.perf_counter() - t0)
+                for name, v in batch[k].kernel_stats().items():
+                    if name == "mem:work_bytes_per_read":
+                        mem[k] = v[0] / max(1, v[1])
+                    if not name.startswith(("host:", "mem:", "inst:")):
+                        ks[k][name] = ks[k].get(name, 0.0) + v[0] / rounds
+        for k in batch:
+            batch[k].fetch()
+        a, b = batch["m64"], batch["m26"]
+        strand = lambda bt, i: (bt.fields(i).strand if bt.fields(i) else None)
+        same = all(a.gaf_text(i, "r", 1) == b.gaf_text(i, "r", 1) and a.status(i) == b.status(i) and a.score(i) == b.score(i) and strand(a, i) == strand(b, i)
+                   for i in range(nreads))
+        minus = sum(1 for i in range(nreads) if strand(a, i) == "-")
+        # ... and the better of the two -m 44 records is the -m 64 record (reverse only when strictly greater)
+        f, r = batch["m44_given"], batch["m44_revcomp"]
+        agree = all(a.score(i) == max(f.score(i), r.score(i)) and (strand(a, i) == "-") == (r.score(i) > f.score(i)) for i in range(nreads))
+        med = {k: sorted(times[k])[rounds // 2] for k in batch}
+        out = {"case": "edit_strands", "part": part, "rows": gg.rows, "paths": paths, "reads": nreads, "read_len": plen, "rounds": rounds,
+               "reverse_winners": minus}
+        for k in batch:
+            bm = batch[k]
+            out[k] = {"ms_per_batch_median": round(med[k] * 1e3, 2), "ms_per_batch_min": round(min(times[k]) * 1e3, 2),
+                      "counted_cell_updates": bm.cell_updates, "performed_cell_updates": bm.cell_updates_performed,
+                      "kernel_ms_per_batch": {name: round(v, 3) for name, v in ks[k].items()}, "work_bytes_per_read": int(mem.get(k, 0))}
+        two44 = med["m44_given"] + med["m44_revcomp"]
+        two_scores = ks["m44_given"]["k_edit_score"] + ks["m44_revcomp"]["k_edit_score"]
+        out["m64_over_m26_time_per_batch_median"] = round(med["m64"] / med["m26"], 4)
+        out["m64_over_two_m44_batches_time_median"] = round(med["m64"] / two44, 4)
+        out["k_edit_score_pair_over_two_k_edit_score"] = round(ks["m64"]["k_edit_score_pair"] / two_scores, 4)
+        out["m64_kernel_sum_over_two_m44_kernel_sums"] = round(sum(ks["m64"].values()) / (sum(ks["m44_given"].values()) + sum(ks["m44_revcomp"].values())), 4)
+        out["same_texts_statuses_scores_and_strands_as_m26"] = bool(same)
+        out["agrees_with_the_better_of_the_two_m44_records"] = bool(agree)
+        print(json.dumps(out), flush=True)
+
+
 def gap_xlong_case():
     from recgraph_amd import api, synth
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -596,6 +664,11 @@ def gap_strands_case():
 def main():
     from recgraph_amd import api, synth
     from oracle import oracle as O
+    if "edit_strands" in sys.argv[1:]:
+        edit_strands_case()
+        sys.argv = [a for a in sys.argv if a != "edit_strands"]
+        if len(sys.argv) == 1:
+            return
     if "edit_xlong" in sys.argv[1:]:
         edit_xlong_case()
         sys.argv = [a for a in sys.argv if a != "edit_xlong"]
