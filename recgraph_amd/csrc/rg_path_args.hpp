@@ -94,6 +94,10 @@ struct DevBuf {
 //                                        (a count, not a time); `launches` the chunks
 //   "mem:silent_rows" / "mem:run_rows"   of the record pipelines: `ms` holds the ROWS of the silent register runs / of all register
 //                                        runs of both sweeps, summed over the chunks and passes
+//   "mem:key_folds" / "mem:key_rows" / "mem:key_rows_hit" / "mem:key_folds_saved"
+//                                        of the same sweeps: member folds into best-member keys on tails and general-path records /
+//                                        rows closed there / those that wrote a record / folds left out for silent members; the
+//                                        last is the sum of "mem:key_saved_gather" / "mem:key_saved_general" / "mem:key_saved_tail"
 //   "mem:layer_window:<instantiation>"   the windowed layer kernel that ran: ms 0, launches counted, always on
 //   "inst:<instantiation>"               the launch log (rg_launch_log.hpp)
 struct KernelStat {

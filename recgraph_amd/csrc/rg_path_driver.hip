@@ -64,8 +64,8 @@ struct PathWorkImpl {
     int retire_shift = RG_SWEEP16_RETIRE_SHIFT;              // the evaluation period the lead tables were built for
     unsigned long long fmembers = 0, rmembers = 0;           // member rows of the forward / reverse table (sum of the group sizes)
     unsigned fcap = 0, rcap = 0;
-    DevBuf<unsigned> need;                 // [8] per chunk: largest nf, nr, forward / reverse record count of a read (k_need); [4] reads whose
-                                        // speculative bound failed (k_verify); [5] NEED_LAYER_FULL; [6], [7] NEED_SILENT_ROWS, NEED_RUN_ROWS
+    DevBuf<unsigned> need;                 // [NEED_WORDS] per chunk: largest nf, nr, forward / reverse record count of a read (k_need); [4] reads whose
+                                        // speculative bound failed (k_verify); [5] NEED_LAYER_FULL; [6], [7] NEED_SILENT_ROWS, NEED_RUN_ROWS; [8] .. [13] NEED_KEY_FOLDS .. NEED_KEY_SAVED_TAIL
     // speculative bound (PickArgs): 12-mer table of the paths, per-read pick, and what aligning the failed reads again needs
     DevBuf<uint32_t> kmer_keys;
     DevBuf<unsigned long long> kmer_masks;
@@ -76,7 +76,7 @@ struct PathWorkImpl {
     DevBuf<DevRecord> rt_rec;
     DevBuf<unsigned long long> rt_cells;
     PathWork retry;                     // work buffers of that second pass (a handful of reads)
-    unsigned long long* h_sum = nullptr;  // pinned: {cell updates of the chunk, need[0..3]} read back once per chunk
+    unsigned long long* h_sum = nullptr;  // pinned: {cell updates of the chunk, need[0 .. NEED_WORDS - 1], cell updates performed} read back once per chunk
     ~PathWorkImpl() { if (h_sum) (void)hipHostFree(h_sum); }
 };
 PathWork::~PathWork() { delete impl; }
@@ -585,8 +585,8 @@ int Run::enqueue_tail() {
 // ONE read-back per chunk: cell updates + overflow summary, through pinned memory on the batch's stream
 int Run::read_back() {
     HIPCHK(hipMemcpyAsync(w.h_sum, d_cells, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipMemcpyAsync(w.h_sum + 5, d_cells + 1, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipMemcpyAsync(w.h_sum + 1, w.need.p, 8 * sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(w.h_sum + 1 + NEED_WORDS / 2, d_cells + 1, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(w.h_sum + 1, w.need.p, NEED_WORDS * sizeof(unsigned), hipMemcpyDeviceToHost, stream));
     return T.collect(stats);
 }
 
@@ -751,8 +751,8 @@ int path_driver_run(const PathCtx& c, const PathJob& j, unsigned long long* cell
     Run r{h, c.gd, p, w, plan, j.reads, j.off, j.bad, j.max_n, j.rec, j.ops, j.ops_stride, d_cells, stream, stats, c.spec_level, c.T, opt.debug != 0};
     for (int i = 0; i < 36; ++i) r.sc.t[i] = p.scores[i];
     r.h_off = j.h_off;
-    if (!w.h_sum) HIPCHK(hipHostMalloc((void**)&w.h_sum, 8 * sizeof(unsigned long long), hipHostMallocDefault));
-    if ((rc = w.need.alloc(8)) || (rc = ensure_tables(h, w))) return rc;
+    if (!w.h_sum) HIPCHK(hipHostMalloc((void**)&w.h_sum, (2 + NEED_WORDS / 2) * sizeof(unsigned long long), hipHostMallocDefault));
+    if ((rc = w.need.alloc(NEED_WORDS)) || (rc = ensure_tables(h, w))) return rc;
     if (w.fcap == 0) { w.fcap = plan.fcap; w.rcap = plan.rcap; w.frec_cap = plan.frec_cap; w.rrec_cap = plan.rrec_cap; }
     // reads per chunk: bounded by a memory budget for the per-read work buffers
     size_t budget = (size_t)96 << 30;
@@ -766,7 +766,7 @@ int path_driver_run(const PathCtx& c, const PathJob& j, unsigned long long* cell
     int oom_shift = 0;      // the budget is halved every time a work-buffer allocation fails (other handles / the retry pass took the memory)
     while (r.done < nreads) {
         HIPCHK(hipMemsetAsync(d_cells, 0, 2 * sizeof(unsigned long long), stream));  // cell updates of this chunk attempt (counted | performed)
-        HIPCHK(hipMemsetAsync(w.need.p, 0, 8 * sizeof(unsigned), stream));
+        HIPCHK(hipMemsetAsync(w.need.p, 0, NEED_WORDS * sizeof(unsigned), stream));
         const size_t per_read_all = plan.per_read_all(w.fcap, w.rcap, w.frec_cap, w.rrec_cap);
         int maxchunk = (int)std::min<size_t>(8192, std::max<size_t>(1, (budget >> oom_shift) / per_read_all));
         if (opt.chunk_reads > 0) maxchunk = std::min<int>(maxchunk, opt.chunk_reads);
@@ -787,7 +787,7 @@ int path_driver_run(const PathCtx& c, const PathJob& j, unsigned long long* cell
         if ((rc = r.regrow_lists(redo))) return rc;
         if (redo) continue;
         const unsigned long long chunk_cells = w.h_sum[0];
-        cells_perf += w.h_sum[5];
+        cells_perf += w.h_sum[1 + NEED_WORDS / 2];
         const unsigned nretry = r.nretry();
         if (r.debug && (plan.spec || plan.spec4)) fprintf(stderr, "[rg] speculative bound (margin %d): %u of %d reads did not reach it\n", plan.spec_margin, nretry, chunk);
         if (r.debug && plan.spec4 && nretry && (rc = r.dump_spec4_retries())) return rc;
@@ -803,6 +803,16 @@ int path_driver_run(const PathCtx& c, const PathJob& j, unsigned long long* cell
             // pseudo-stats: "ms" holds the ROWS, summed over the chunks and the passes
             add_stat(stats, "mem:silent_rows", (double)r.need()[NEED_SILENT_ROWS], 1);
             add_stat(stats, "mem:run_rows", (double)r.need()[NEED_RUN_ROWS], 1);
+            // ... and the key work of their tails and general-path records: eager member folds, rows closed, rows that wrote a record,
+            // member folds left out (k_sweep16, KEY WORK THAT NO RECORD USES)
+            add_stat(stats, "mem:key_folds", (double)r.need()[NEED_KEY_FOLDS], 1);
+            add_stat(stats, "mem:key_rows", (double)r.need()[NEED_KEY_ROWS], 1);
+            add_stat(stats, "mem:key_rows_hit", (double)r.need()[NEED_KEY_ROWS_HIT], 1);
+            const unsigned* kn = r.need();
+            add_stat(stats, "mem:key_folds_saved", (double)kn[NEED_KEY_SAVED_GATHER] + (double)kn[NEED_KEY_SAVED_GENERAL] + (double)kn[NEED_KEY_SAVED_TAIL], 1);
+            add_stat(stats, "mem:key_saved_gather", (double)kn[NEED_KEY_SAVED_GATHER], 1);
+            add_stat(stats, "mem:key_saved_general", (double)kn[NEED_KEY_SAVED_GENERAL], 1);
+            add_stat(stats, "mem:key_saved_tail", (double)kn[NEED_KEY_SAVED_TAIL], 1);
         }
         if (nretry && (rc = r.second_pass(cells_perf))) return rc;
         cells_done += chunk_cells;

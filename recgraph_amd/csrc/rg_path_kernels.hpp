@@ -77,14 +77,26 @@ struct SweepArgs {
     // whatever its members: the reference's search likes to switch to another path for the last few columns of a read (ties
     // among the paths of a shared end segment go to the highest path id), and such a path's layer is only rebuilt over those rows
     int dsel_lo, dsel_hi;
-    // k_sweep16, SILENT RUNS (narrow record variants): [2] rows of the silent register runs | rows of all register runs of the
-    // launch — words NEED_SILENT_ROWS / NEED_RUN_ROWS of the chunk's need[] read-back — or null
+    // k_sweep16, SILENT RUNS (narrow record variants): [8] rows of the silent register runs | rows of all register runs of the
+    // launch | the six key counters (eager member folds | rows closed | rows that wrote a record | members left out of gather
+    // pass (1) | of general-path folds | of silent-run tails) — words NEED_SILENT_ROWS .. NEED_KEY_SAVED_TAIL of the chunk's need[]
+    // read-back — or null
     unsigned* runstat;
 };
 // words of the chunk's need[] read-back that count the rows of the silent runs and of all register runs of the record sweeps
 // (0 .. 3: k_need, 4: k_verify, 5: NEED_LAYER_FULL); reported as "mem:silent_rows" / "mem:run_rows"
 constexpr int NEED_SILENT_ROWS = 6;
 constexpr int NEED_RUN_ROWS = 7;
+// ... and the key work of the tails and general-path records of those sweeps (k_sweep16, KEY WORK THAT NO RECORD USES); reported as
+// "mem:key_folds" / "mem:key_rows" / "mem:key_rows_hit" / "mem:key_folds_saved" (the sum of the three places) and
+// "mem:key_saved_gather" / "mem:key_saved_general" / "mem:key_saved_tail"
+constexpr int NEED_KEY_FOLDS = 8;
+constexpr int NEED_KEY_ROWS = 9;
+constexpr int NEED_KEY_ROWS_HIT = 10;
+constexpr int NEED_KEY_SAVED_GATHER = 11;
+constexpr int NEED_KEY_SAVED_GENERAL = 12;
+constexpr int NEED_KEY_SAVED_TAIL = 13;
+constexpr int NEED_WORDS = 14;      // (even: the read-back packs them into 64-bit words)
 
 // expands the (row, lane) records of the forward sweep into Cand entries, keeping only cells that can still reach
 // the final bound with the best reverse partner of their column

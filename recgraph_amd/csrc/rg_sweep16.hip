@@ -351,7 +351,7 @@ __global__ __launch_bounds__(64, SWEEP16_WAVES) void k_sweep16(SweepArgs a) {
     int* sprof = gT + GTW;               // [4][64][H]
     const int PR_RVL = P, PR_NPROF = P + 1;     // pseudo-rows behind the P rolling rows (same [lane][r] layout)
     if (lane < 36) sct[lane] = a.sc.t[lane];
-    else if (lane < 44) sct[lane] = 0;      // (40 .. 43: the silent set and its counters, see SILENT RUNS)
+    else if (lane < 50) sct[lane] = 0;      // (40 .. 49: the silent set, its counters and the key counters, see SILENT RUNS)
     __syncthreads();
     // uniform gap cost (checked by the driver's plan, sweep16_admissible in rg_path_plan.cpp: score(b, '-') is the same for b = A, C, G, T, N): the
     // z-space slope — and, being the same table column, what a U move adds in EVERY row (g_i below): no per-row lookup
@@ -883,7 +883,34 @@ __global__ __launch_bounds__(64, SWEEP16_WAVES) void k_sweep16(SweepArgs a) {
     // (the set and the two row counters — rows of the silent runs | of all register runs of this read, SweepArgs::runstat — live in
     // four free words behind the score table: read once per run, written once per evaluation / run.  As registers across the run
     // loops they cost the 4-member loop the two VGPRs that take the variant past 224)
-    int* sil = sct + 40;                 // [0], [1]: the set; [2]: silent rows; [3]: run rows
+    int* sil = sct + 40;                 // [0], [1]: the set; [2]: silent rows; [3]: run rows; [4] .. [9]: the key counters below
+    // KEY WORK THAT NO RECORD USES (same variants).  Best-member keys (value << 16 | path) are folded eagerly in three places: tails, the
+    // records of the general path, pass (1) of a gather run.  A member in `silent` is left out of pass (1) of a gather run, out of
+    // the folds of a general-path record into keys that exist already, and the tail of a silent run that lies between the groups of
+    // its row folds nothing: every cell of a hopeless path lies below its threshold, so a
+    // cell that emits has a best member that is not hopeless, and k_expand keeps a record's key only where its cell
+    // reaches the bound.  Keys of cells that do NOT emit, carried along in the record of a lane that has another column at its
+    // threshold, may name a lower member than before.  Row updates, pass (3) and the direction words stay for every member: silent
+    // members still lead.  Every other tail folds as before.
+    // (Packed values instead of keys on tails and on the general path, with the keys rebuilt where a row closes on a hit, were NOT
+    // built: at config 5 the rows that close there write a record 85 % of the time — profiles/lazy_keys_notes.md.)
+    // Counters (SweepArgs::runstat, words 2 .. 7): [4] member folds on tails and on the general path, [5] rows closed there (row_end
+    // called), [6] those that wrote a record (the record count moved), [7] .. [9] members left out: of pass (1) of gather runs, of the
+    // folds of general-path records, of the tails of silent runs.  One LDS read-modify-write each per tail / general record / gather run that has something to add,
+    // six more atomics per read; tests/test_gpu_lazy_keys.py reads all six.
+    enum { KS_GATHER = 7, KS_GENERAL = 8, KS_TAIL = 9 };
+    auto silent_set = [&]() -> unsigned long long {
+        return ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane(sil[1]) << 32) | (unsigned)__builtin_amdgcn_readfirstlane(sil[0]);
+    };
+    // (before: `ncand` in front of the row_end of a row that closed.  Every lane the same words, the same values)
+    auto key_stat = [&](int folds, bool closed, unsigned before, int saved, int place) {
+        if constexpr (kSilent) {
+            if (folds) sil[4] += folds;
+            if (closed) sil[5] += 1;
+            if (closed && ncand != before) sil[6] += 1;
+            if (saved) sil[place] += saved;
+        }
+    };
 #ifdef RG_SWEEP16_RETSTAT
     // (statistics build, tools/sweep_variants.sh RETSTAT: the counters carry evaluations | needed paths << 32 and not-hopeless paths)
     unsigned long long stat_e = 0, stat_n = 0, stat_h = 0;
@@ -1016,7 +1043,9 @@ __global__ __launch_bounds__(64, SWEEP16_WAVES) void k_sweep16(SweepArgs a) {
                 if (track && (flags & F_LAST) && row_open) {
                     int key[C];
                     keys_ld(key);
+                    const unsigned before = ncand;
                     row_end(i, ((w1 >> 20) & 511) - 1, key);
+                    key_stat(0, true, before, 0, KS_GENERAL);
                 }
                 if (flags & F_LAST) row_open = false;
             }
@@ -1105,7 +1134,14 @@ __global__ __launch_bounds__(64, SWEEP16_WAVES) void k_sweep16(SweepArgs a) {
                 int bd[H], bk[H];
 #pragma unroll
                 for (int r = 0; r < H; ++r) { bd[r] = 0; bk[r] = pack16(ka, ka); }
-                MemberIter it{kWide ? wide_gw : PathWords{gm, 0ull, 0ull, 0ull}, 0};
+                // (silent members are left out — KEY WORK THAT NO RECORD USES; the alpha stays as the table's base whatever it is: a
+                // column all of whose other members are silent names the alpha, whose value is a real cell's)
+                unsigned long long pm = gm;
+                if constexpr (kSilent) {
+                    pm = gm & ~silent_set();
+                    key_stat(0, false, 0u, __popcll(gm & ~pm & ~(1ull << ka)), KS_GATHER);
+                }
+                MemberIter it{kWide ? wide_gw : PathWords{pm, 0ull, 0ull, 0ull}, 0};
                 it.w.set(ka >> 6, it.w.get(ka >> 6) & ~(1ull << (ka & 63)));        // (narrow: page 0, path ids below 64)
                 int nx[H];
                 int kn = it.next();
@@ -1202,7 +1238,7 @@ __global__ __launch_bounds__(64, SWEEP16_WAVES) void k_sweep16(SweepArgs a) {
                 fetch(t, nw0, nw1, ngm);
                 ri = nw0 & 0xfffff; rli = (nw0 >> 20) & 7; rslot = nw1 & 0xfffff; rw1 = nw1;
             }
-            done += (unsigned long long)(g_nme - 1) * ((kRec && track) ? 2ull : 1ull);    // passes (1) and (3)
+            done += (unsigned long long)(g_nme - 1) * ((kRec && track) ? 2ull : 1ull);    // passes (1) and (3) (per member of the run, silent or not)
             // (3) every member once: row_k(end)[c] = A(end)[c] - A0[G(c)] + row_k(start)[G(c)]
             {
                 int B[H];
@@ -1378,9 +1414,16 @@ __global__ __launch_bounds__(64, SWEEP16_WAVES) void k_sweep16(SweepArgs a) {
                     for (int kk = 1; kk < KRUN; ++kk)
                         if (kk < RN) RowOps16<C>::member_p2(rr[kk], ML, lmask, zl[kk], vlo[kk]);
                 }
-                if (kRec && kColmax == 0 && tail) {
+                // (the tail of a silent run between the groups of its row — keys parked by an earlier group, another group still to come
+                // — folds nothing: every member is silent, the keys wait in LDS untouched.  KEY WORK THAT NO RECORD USES.  row_open is
+                // only ever set by a tracking sweep, and every variant that has silent runs tracks)
+                bool tail_eager = kRec && kColmax == 0 && tail;
+                if (tail_eager && (rfl & F_FIRST)) row_open = false;
+                if constexpr (kSilent && kLean) {
+                    if (tail_eager && row_open && !(rfl & F_LAST)) { tail_eager = false; key_stat(0, false, 0u, RN, KS_TAIL); }
+                }
+                if (tail_eager) {
                     if (track) {
-                        if (rfl & F_FIRST) row_open = false;
                         int key[C];
                         if (row_open) { keys_ld(key); fold_keys(key, rr[0], mk[0]); } else set_keys(key, rr[0], mk[0]);
 #pragma unroll
@@ -1391,8 +1434,10 @@ __global__ __launch_bounds__(64, SWEEP16_WAVES) void k_sweep16(SweepArgs a) {
                         // thresholds in front of it — nine registers held across every row of the 4-member loop for its one tail)
                         int tri = ri, tw1 = rw1;
                         if constexpr (kLean) asm volatile("" : "+s"(tri), "+s"(tw1));
+                        const unsigned before = ncand;
                         if (rfl & F_LAST) { row_end(tri, ((tw1 >> 20) & 511) - 1, key); row_open = false; }
                         else keys_st(key);
+                        key_stat(RN, (rfl & F_LAST) != 0, before, 0, KS_GENERAL);
                     }
                 } else if constexpr (kLean) {
                     // (a silent row: no column of it reaches a threshold)
@@ -1659,6 +1704,11 @@ __global__ __launch_bounds__(64, SWEEP16_WAVES) void k_sweep16(SweepArgs a) {
             // the compiler has to carry around the record loop because it cannot see that definition and use go together)
             int SEL[H];
             RowOps16<C>::select_steps(SEL, s, MU, g_i, g0, lane);
+            // (silent members are updated and stored like the others; only their fold into keys that exist already — the alpha set
+            // them, or an earlier record of the row — is left out: KEY WORK THAT NO RECORD USES)
+            unsigned long long mute = 0ull;
+            int nfold = cont ? 0 : 1, nmute = 0;
+            if constexpr (kSilent) { if (silent_ok && next_eval != INT32_MAX) mute = silent_set(); }      // (otherwise the set is empty)
             while (knext >= 0) {
                 const int k = knext;
                 int cur[H];
@@ -1671,14 +1721,19 @@ __global__ __launch_bounds__(64, SWEEP16_WAVES) void k_sweep16(SweepArgs a) {
                 } else knext = -1;
                 RowOps16<C>::member(cur, SEL, lane, MU, ML, lmask, src);
                 st_row(k, cur);
-                if (track) fold_keys(key, cur, k);
+                if (track) {
+                    if (kSilent && ((mute >> (k & 63)) & 1ull)) ++nmute;
+                    else { fold_keys(key, cur, k); ++nfold; }
+                }
                 if (semi_end) end_fold(k, i, cur);
             }
             if (track) {
                 // (a continuation entry always follows its group's first entry: have is true by then)
                 row_open = true;
+                const unsigned before = ncand;
                 if (e_flags & F_LAST) row_end(e_i, ((e_w1 >> 20) & 511) - 1, key);
                 else keys_st(key);
+                key_stat(nfold, (e_flags & F_LAST) != 0, before, nmute, KS_GENERAL);
             }
         }
         }
@@ -1713,7 +1768,10 @@ __global__ __launch_bounds__(64, SWEEP16_WAVES) void k_sweep16(SweepArgs a) {
         if (lane == ln_end) { rs->s0 = gbest_val; rs->end_row_best = gbest_row; rs->seed_path = gbest_path; }
     }
     if constexpr (kSilent) {
-        if (lane == 0 && a.runstat) { atomicAdd(a.runstat, (unsigned)sil[2]); atomicAdd(a.runstat + 1, (unsigned)sil[3]); }
+        if (lane == 0 && a.runstat) {
+#pragma unroll
+            for (int w = 0; w < 8; ++w) atomicAdd(a.runstat + w, (unsigned)sil[2 + w]);
+        }
     }
     if (lane == 0 && a.count_cells) {
         // counted: every member row of the table (what the reference updates) — from the table builder when records may have
